@@ -2,6 +2,7 @@
 """bench.py -- Msamples/s through transform -> vumeter on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--workload c2|c2ro|c4|c3|c5] [--gain general|below|off]
+                    [--dump-outputs DIR] [--full]
 
 A step is one pass of the hot path over one batch that is already resident in HBM:
 one fused gain(+channel map) -> VU launch over every stream of the rank's shard, the
@@ -27,8 +28,16 @@ no data-path collective, "weak" scaling):
 Rank 0 prints ONE JSON line.  `value` and `roofline` come from a batch created the library's
 DEFAULT way (two plain allocations; the engine's opt-in placement search is a leg of its own,
 `setup.place_search`, after the benchmarked batch is gone).  `roofline` is for the dominant
-kernel, timed with HIP events on the stream it is launched on; `cpu_baseline` is the CPU oracle
-(the scalar restatement of the reference loops) timed on this host, N=1 only.
+kernel, timed with HIP events on the stream it is launched on; `ms_per_step` is the wall time
+of one timed step.
+
+A plain run does only what that line needs: set up, warm up, time K steps, write the last
+step's outputs (--dump-outputs DIR: DIR/<name>.npy, float32 / float64, the same inputs on
+every run with the same arguments) and print.  --full adds everything else, outside the timed
+region: the parity gate against the oracle, the measured ceilings, small blocks, the VU-only
+lines, the other kernels, the PCIe-inclusive rates, the placement-search leg, `cpu_baseline`
+(the CPU oracle -- the scalar restatement of the reference loops -- timed on this host, N=1
+only) and, at N > 1, the config-4 / config-5 legs on all ranks (`node_vu`).
 
 The process plumbing, the measurement legs beside `value` and the CPU baseline live in benchlib/.
 """
@@ -64,6 +73,48 @@ WORKLOADS = {
 }
 
 
+DUMP_SAMPLE_BYTES = 32 << 20  # --dump-outputs: PCM / float planes of sampled streams (VU results: at most 16 MB more)
+DUMP_VU_BYTES = 16 << 20
+
+
+def dump_outputs(d, b, S, Cn, T, pcm, f32, results, rcs, node_rec):
+    """--dump-outputs: what the last timed step computed, as a caller of the path receives it -- the VU result of
+    every stream's window and, for a fixed, seeded sample of the streams, the int16 PCM (as float32) or the
+    equaliser's float planes; config 5's node-global record when it was exchanged.  The samples depend on the
+    shape only, so that two builds of the project can be compared array for array."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(12345)
+    arrays = {}
+    if pcm or f32:
+        pick = np.sort(rng.choice(S, max(1, min(S, DUMP_SAMPLE_BYTES // (T * Cn * 4))), replace=False))
+        keep = min(T, DUMP_SAMPLE_BYTES // (Cn * 4))          # every frame, unless one stream alone is over the budget
+        arrays["streams"] = pick.astype(np.float64)
+        if pcm:
+            arrays["pcm"] = np.stack([b.download(int(s), T)[:keep * Cn] for s in pick]).astype(np.float32)
+        if f32:
+            arrays["f32_planes"] = np.stack([np.stack([b.download_f32(int(s), c, T)[:keep] for c in range(Cn)])
+                                             for s in pick])
+    if results is not None:
+        per_stream = 8 * (3 + 2 * Cn) + 4
+        vu = np.arange(S)
+        if S * per_stream > DUMP_VU_BYTES:
+            vu = np.sort(rng.choice(S, DUMP_VU_BYTES // per_stream, replace=False))
+            arrays["vu_streams"] = vu.astype(np.float64)
+        rs = [results[int(s)] for s in vu]
+        arrays["vu_rc"] = np.array([rcs[int(s)] for s in vu], dtype=np.float32)
+        arrays["vu_frames"] = np.array([r.frames for r in rs], dtype=np.float64)
+        arrays["vu_global_peak"] = np.array([r.global_peak for r in rs], dtype=np.float32)
+        arrays["vu_global_power"] = np.array([r.global_power for r in rs], dtype=np.float64)
+        arrays["vu_channel_peak"] = np.array([r.channel_peak[:Cn] for r in rs], dtype=np.float32).reshape(len(rs), Cn)
+        arrays["vu_channel_power"] = np.array([r.channel_power[:Cn] for r in rs], dtype=np.float64).reshape(len(rs), Cn)
+    if node_rec is not None:
+        arrays["node_vu_last_block"] = np.array(node_rec, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -83,9 +134,19 @@ def parse_args(argv=None):
                     help="arithmetic form: the workload's own gains (general), every gain below the scale "
                          "(one mulhi per sample in the read-only runs), or the gain disabled as the reference "
                          "creates a transform")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip ceilings / VU-only line / PCIe line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: the parity gate, ceilings, small blocks, "
+                         "VU-only lines, other kernels, PCIe line, placement-search leg, CPU baseline and, at N > 1, "
+                         "the config-4 / config-5 legs (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the parity gate and the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip ceilings / VU-only line / PCIe line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of the streams' PCM or float planes, all VU results)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -287,6 +348,8 @@ def main():
     # eighth launch of the timed region carries them -- every one when the region is short (the driver's --steps 20:
     # SURVEY 8(d) wants the kernel time over at least 20 timed launches).
     time_every = 8 if args.steps >= 64 else 1
+    if eq:
+        b.eq_reset(-1)          # (the filter state the timed steps start from does not depend on how long warm-up took)
     b.timing(time_every)
     b.timing_read()
     barrier()
@@ -363,6 +426,14 @@ def main():
     if node is not None:
         node.close()
 
+    if rank == 0 and args.dump_outputs:
+        nv = out.get("node_vu_last_block")
+        names = dump_outputs(args.dump_outputs, b, S, Cn, T, pcm=not eq and not read_only, f32=eq,
+                             results=results if has_vu else None, rcs=rcs,
+                             node_rec=[nv["frames"], nv["global_peak"], nv["global_power_db"]] if nv else None)
+        print("bench.py: last timed step's outputs -> %s/{%s}.npy" % (args.dump_outputs, ",".join(names)),
+              file=sys.stderr)
+
     # per-GPU efficiency against the committed N=1 line of the same workload (the driver computes
     # its own from its own runs; this is a convenience for a reader of the line)
     if rank == 0 and world > 1:
@@ -376,16 +447,19 @@ def main():
         except Exception:
             pass
 
-    # the parity gate that goes with every benchmark -- one more block of the same batch, outside the
-    # timed region, sampled streams against the oracle (which is here as the checker, as in cpu_baseline)
-    if rank == 0 and not args.no_cpu:
+    # Everything below `value` and `roofline` runs with --full only: a plain run sets up, warms up, times the steps,
+    # writes its outputs and prints the line.
+    full = args.full
+    # the parity gate that goes with every full benchmark -- one more block of the same batch, outside
+    # the timed region, sampled streams against the oracle (which is here as the checker, as in cpu_baseline)
+    if full and rank == 0 and not args.no_cpu:
         out["parity_gate"] = legs.parity_gate(cm, b, args.workload, S, Cn, T, first_global, global_step, gains, swap,
                                               has_pcm=not read_only)
 
-    if rank == 0 and not args.no_extras and not eq and not read_only:
+    if full and rank == 0 and not args.no_extras and not eq and not read_only:
         out["measured_ceilings"] = legs.measured_ceilings(b, achieved)
         out["small_blocks"] = legs.small_blocks(b, S, Cn, T, bps, results, rcs)
-    if rank == 0 and not args.no_extras and read_only:
+    if full and rank == 0 and not args.no_extras and read_only:
         try:
             ceiling = round(b.ceiling(0, 10), 1)
             out["measured_ceilings"] = {"hbm_read_ceiling_GBs": ceiling,
@@ -394,10 +468,10 @@ def main():
             out["measured_ceilings"] = {"ceiling_error": str(e)}
     b.close()
 
-    if rank == 0 and not args.no_extras and not eq and not read_only:
+    if full and rank == 0 and not args.no_extras and not eq and not read_only:
         read_ceiling = out.get("measured_ceilings", {}).get("hbm_read_ceiling_GBs", 0)
         out.update(legs.vu_only_lines(cm, args.workload, S, Cn, T, local_rank, rank, world, read_ceiling))
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "c2":
+    if full and rank == 0 and world == 1 and not args.no_extras and args.workload == "c2":
         out["other_kernels"] = legs.other_kernels(cm, local_rank)
         try:
             out["pcie_inclusive"] = legs.pcie_inclusive(cm, local_rank)
@@ -406,16 +480,19 @@ def main():
         if os.environ.get("COOLMIC_BENCH_PLACE", "1") != "0":
             setup["place_search"] = legs.place_search_leg(cm, make_batch, T)
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args.workload, Cn, gains, swap)
 
-    # Several ranks: configs 4 and 5 at this N, after everything else of the line is known, outside the timed
-    # region and never part of `value` -- the driver's one command passes no --workload, and config 5's
-    # exchange is the only collective of the path.  Guarded: whatever happens in there, rank 0's line goes out.
+    # Several ranks, --full: configs 4 and 5 at this N, after everything else of the line is known, outside the
+    # timed region and never part of `value` -- config 5's exchange is the only collective of the path.  Guarded:
+    # whatever happens in there, rank 0's line goes out.
     printer = launch.LinePrinter(rank, json_fd, out)
-    if world > 1:
+    if world > 1 and full:
         launch.guarded_legs(printer, dist,
                             lambda: legs.node_vu_legs(cm, shard, dist, rank, world, local_rank, rehearsal, NB))
+    elif world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
     sys.stdout.flush()
     printer.emit()
     if out.get("parity_gate", {}).get("ok") is False:

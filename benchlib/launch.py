@@ -292,6 +292,13 @@ def dry_run(args, rank, world, json_fd, shard):
         out["ranks_seen"] = [int(r[0].item()) for r in ranks]
         out["warmup_steps_all_ranks"] = [int(r[1].item()) for r in ranks]
 
+        printer = LinePrinter(rank, json_fd, out)
+        if not args.full:                      # (the real run's legs are --full only, and so are these)
+            dist.barrier()
+            dist.destroy_process_group()
+            printer.emit()
+            return
+
         # the keys the real run's config-4 / config-5 legs report (node_vu_legs), no GPU work behind them here;
         # through the same guard (test hook: a rank that never comes back from its legs)
         def legs():
@@ -302,7 +309,6 @@ def dry_run(args, rank, world, json_fd, shard):
             d = dict.fromkeys(NODE_VU_KEYS)
             d["rccl_ranks"] = 0
             return d
-        printer = LinePrinter(rank, json_fd, out)
         guarded_legs(printer, dist, legs)
         printer.emit()
         return

@@ -24,7 +24,7 @@ def _run(args, extra_env=None, timeout=180):
 
 @pytest.mark.parametrize("n,workload", [(2, "c2"), (2, "c5"), (4, "c4")])
 def test_self_launch_prints_one_line_from_rank0(n, workload):
-    p = _run(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--workload", workload],
+    p = _run(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--workload", workload, "--full"],
              {"COOLMIC_BENCH_DRYRUN": "1"})
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
@@ -41,6 +41,17 @@ def test_self_launch_prints_one_line_from_rank0(n, workload):
     # configs 4 / 5 at this N ride on the driver's one command: the keys of their legs
     for key in ("rccl_ranks", "ms_per_step_c4", "ms_per_step_c5", "matches_host_merge"):
         assert key in out["node_vu"], key
+
+
+def test_plain_multi_rank_run_leaves_the_legs_to_full():
+    """without --full the line is the timed run's alone: the config-4 / config-5 legs are not run"""
+    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "c5"], {"COOLMIC_BENCH_DRYRUN": "1"})
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["ranks_seen"] == [0, 1] and out["node_id_same_on_all_ranks"] is True
+    assert "node_vu" not in out
 
 
 def test_single_rank_needs_no_launcher_and_no_torch():
@@ -69,7 +80,7 @@ def test_a_hang_inside_the_multi_rank_legs_cannot_lose_the_line():
     rank; the launch succeeds, because value and roofline were measured before"""
     import time
     t0 = time.time()
-    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"],
+    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
              {"COOLMIC_BENCH_DRYRUN": "1", "COOLMIC_BENCH_DRYRUN_LEGS_HANG_RANK": "1",
               "COOLMIC_BENCH_LEGS_TIMEOUT_S": "8"}, timeout=120)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
