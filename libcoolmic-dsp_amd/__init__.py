@@ -224,6 +224,10 @@ for _name, (_res, _args) in SIGNATURES.items():
 if hasattr(lib, "cmhip_test_gain_consts"):      # (an older build loaded by tools/ab_two_libs.py has another hook)
     lib.cmhip_test_gain_consts.restype = None
     lib.cmhip_test_gain_consts.argtypes = [C.c_uint16, C.c_uint16, _P(C.c_uint16), _P(C.c_uint32)]
+if hasattr(lib, "cmhip_test_plan_run"):         # (not in builds older than the launcher's plan)
+    lib.cmhip_test_plan_run.restype = None
+    lib.cmhip_test_plan_run.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p]
 lib.cmhip_test_merge_windows.restype = C.c_int
 lib.cmhip_test_merge_windows.argtypes = [_P(C.c_uint64), C.c_uint, C.c_uint, C.c_uint, _P(VuResult)]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
@@ -271,6 +275,28 @@ def gain_consts(gain, scale):
     mi, mf = C.c_uint16(), C.c_uint32()
     lib.cmhip_test_gain_consts(gain, scale, C.byref(mi), C.byref(mf))
     return mi.value, mf.value
+
+
+class RunPlan(C.Structure):
+    """cmhip::RunPlan (csrc/cmhip_internal.h): what the block-kernel launcher launches for a run"""
+    _fields_ = [(name, C.c_int if name == "err" else C.c_uint32)
+                for name in ("err", "family", "channels", "tile_u", "waves", "map", "stage", "grid", "block",
+                             "chunks", "W", "rows_per_tile", "keep_flag")]
+
+
+RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
+
+
+def plan_run(streams, channels, frames, out=False, f32=False, vu=False, identity_maps=True):
+    """Test hook: the block-kernel launcher's plan for a run (plan_run in k_block.hip; host logic, needs no GPU).
+    A dict of the RunPlan's fields, with the family by name; the completion flag is offered to every run, so
+    keep_flag tells the launches of one workgroup."""
+    p = RunPlan()
+    lib.cmhip_test_plan_run(streams, channels, frames, int(bool(out)), int(bool(f32)), int(bool(vu)),
+                            int(bool(identity_maps)), C.byref(p))
+    d = {name: getattr(p, name) for name, _ in RunPlan._fields_}
+    d["family"] = RUN_FAMILIES[d["family"]]
+    return d
 
 
 def merge_windows(windows, channels, rate=48000):

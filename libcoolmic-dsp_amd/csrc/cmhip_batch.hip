@@ -112,23 +112,6 @@ extern "C" int cmhip_device_read(int device, void *dst_host, const void *src_dev
 static RunTune read_tune()
 {
     RunTune t{};
-    if (const char *e = getenv("CMHIP_VU_TILE")) {
-        const int v = atoi(e);
-        if (v == 4 || v == 8 || v == 16)
-            t.vu_tile = (uint32_t)v;
-    }
-    if (getenv("CMHIP_WIDE4_F32"))
-        t.wide4_f32 = 1;
-    if (const char *e = getenv("CMHIP_ROWS_RPT")) {
-        const int v = atoi(e);
-        if (v == 8 || v == 16 || v == 32 || v == 64)      // the tile sizes the kernels are tested with
-            t.rows_rpt = (uint32_t)v;
-    }
-    if (const char *e = getenv("CMHIP_FAST_NW")) {
-        const int v = atoi(e);
-        if (v == 1 || v == 4 || v == 8)
-            t.fast_nw = (uint32_t)v;
-    }
     t.place_env = -1;
     if (const char *e = getenv("CMHIP_PLACE")) {
         const int v = atoi(e);
@@ -1073,7 +1056,7 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
         a.parity = parity;
         a.done_flag = flag;
         a.done_seq = flag_seq;
-        HIP_TRY(launch_run(a, b->tune, b->stream, ev.a, ev.b, &flagged));
+        HIP_TRY(launch_run(a, b->stream, ev.a, ev.b, &flagged));
         b->in_flight = true;
     }
     b->done_flagged = flagged;

@@ -109,7 +109,7 @@ struct cmhip_batch {
     bool timing;
     unsigned int timing_every, timing_count;     // every n-th run carries the events (cmhip_batch_timing)
     std::vector<EventPair> ev_used, ev_free;
-    RunTune tune;                          // launcher knobs, read once at creation
+    RunTune tune;                          // placement and completion settings, read once at creation
     cmhip_placement_t place;               // what the placement search did (cmhip_batch_placement)
     bool vu_off;                           // runs leave the windows alone for now (cmhip_batch_vu_pause)
 };

@@ -83,7 +83,8 @@ struct RunArgs {
     uint32_t       chunks;         // 4 KiB tiles (one wave each) per stream slot
     uint32_t       parity;         // which VuState::samples slot is current
     uint32_t       identity_maps;  // 1 when no stream of the batch has a channel map
-    uint32_t       identity_gains; // 1 when no stream of the batch has a gain (disabled or unity everywhere)
+    uint32_t       identity_gains; // 1 when no stream of the batch has a gain (disabled or unity everywhere); read by
+                                   // no kernel now, kept so that the kernel-argument offsets below stay as they are
     // Completion by flag, for launches of ONE workgroup (the 1 KiB pulls of the per-stream stages): when not
     // null the workgroup, at its very end, makes its stores visible to the host and stores done_seq there
     // (pinned, device-mapped host memory).  The host spins on the word instead of waiting for the stream:
@@ -93,14 +94,9 @@ struct RunArgs {
     uint32_t       done_seq;
 };
 
-// Tuning knobs of the block kernels' launcher, read from the environment ONCE, when a batch is
-// created, and validated there (0 = the built-in choice): $CMHIP_VU_TILE in {4, 8, 16},
-// $CMHIP_WIDE4_F32 set at all, $CMHIP_ROWS_RPT in {8, 16, 32, 64} (tools/ab_tiles.py, bench_generic.py).
+// Placement and completion settings of a batch, read from the environment ONCE, when the batch is created,
+// and validated there.  (Which block kernel serves a run is plan_run's to decide, not the environment's.)
 struct RunTune {
-    uint32_t vu_tile;
-    uint32_t wide4_f32;
-    uint32_t rows_rpt;
-    uint32_t fast_nw;              // CMHIP_FAST_NW in {1, 4, 8}: waves per workgroup of the mono / stereo forms with a window
     int32_t  place_env;            // CMHIP_PLACE: -1 unset (only batches created with CMHIP_PLACE_SEARCH search), 0 never,
                                    // 1 the first large batch of a device also without the flag, 2 every large batch
     uint32_t place_debug;          // CMHIP_PLACE_DEBUG: the probe times of the placement search on stderr
@@ -144,8 +140,23 @@ struct GenArgs {
 // (ev_start / ev_stop: optional events that take the kernel's own start and end -- hipExtLaunchKernelGGL
 // stamps them from the dispatch itself, without the extra packets of hipEventRecord around the launch)
 // (*flagged: the launch was one workgroup and carries the completion flag of RunArgs::done_flag)
-hipError_t launch_run(const RunArgs &a, const RunTune &tune, hipStream_t st, hipEvent_t ev_start = nullptr,
-                      hipEvent_t ev_stop = nullptr, bool *flagged = nullptr);
+// What launch_run launches for a run (plan_run, k_block.hip): the kernel, its grid and its tiles.
+enum RunFamily : uint32_t { RUN_NONE = 0, RUN_FAST, RUN_FAST_RO, RUN_WIDE, RUN_ROWS };
+struct RunPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   family;             // RunFamily; RUN_NONE: nothing to launch (or refused)
+    uint32_t   channels;           // template C of k_run_fast / k_run_fast_ro / k_run_wide (0 for k_run_rows)
+    uint32_t   tile_u;             // 16-byte vectors per lane of a tile (k_run_fast, k_run_fast_ro, k_run_wide)
+    uint32_t   waves;              // waves per workgroup (k_run_fast's NW)
+    uint32_t   map, stage;         // k_run_rows' MAP and STAGE
+    uint32_t   grid, block;        // workgroups, threads per workgroup
+    uint32_t   chunks;             // RunArgs::chunks: tiles per stream
+    uint32_t   W, rows_per_tile;   // k_run_rows' arguments
+    uint32_t   keep_flag;          // the launch is one workgroup and carries RunArgs::done_flag
+};
+RunPlan plan_run(const RunArgs &a);
+hipError_t launch_run(const RunArgs &a, hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                      bool *flagged = nullptr);
 // (the first launch of an EQ kernel variant on a device raises its dynamic-LDS limit there:
 // prepare_eq does that for a batch's device when the batch is created, launch_eq checks it)
 hipError_t prepare_eq(int device);

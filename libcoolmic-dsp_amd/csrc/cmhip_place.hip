@@ -48,12 +48,12 @@ static double place_probe_ms(cmhip_batch_t *b, const void *src, void *dst, hipEv
     a.identity_gains = 1;
     const int n = 6;
     for (int i = 0; i < 2; i++)
-        if (launch_run(a, b->tune, b->stream) != hipSuccess)
+        if (launch_run(a, b->stream) != hipSuccess)
             return -1.;
     if (hipEventRecord(e0, b->stream) != hipSuccess)
         return -1.;
     for (int i = 0; i < n; i++)
-        if (launch_run(a, b->tune, b->stream) != hipSuccess)
+        if (launch_run(a, b->stream) != hipSuccess)
             return -1.;
     float ms = 0.f;
     if (hipEventRecord(e1, b->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||

@@ -22,10 +22,10 @@
 
 namespace cmhip {
 
-// read-only runs take bigger tiles to amortise the epilogue (picked per channel count from
-// interleaved A/B runs, tools/ab_tiles.py); RunTune::vu_tile (4, 8, 16) overrides for tuning
-constexpr u32 TILE_U_VUONLY_MONO = 16;         // (8 until the A/B was repeated at sustained clocks: 6.03 -> 6.51 TB/s)
-constexpr u32 TILE_U_VUONLY_STEREO = 16;
+// read-only mono / stereo runs take bigger tiles to amortise the epilogue: 16 vectors per lane, 16 KiB per wave
+// (picked per channel count from interleaved A/B runs over 4, 8 and 16; 8 until the A/B was repeated at
+// sustained clocks: 6.03 -> 6.51 TB/s)
+constexpr u32 TILE_U_VUONLY = 16;
 
 // One wave = one 4 KiB tile of one stream, one pass: four non-temporal 16-byte loads per
 // lane, arithmetic, four non-temporal stores, then a short epilogue.  Short-lived waves
@@ -396,23 +396,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void k_
 }
 
 // ---------------------------------------------------------------------------
-// Wide path: 4 or 8 channels with the identity channel map (the template also covers 16,
-// which k_run_rows now serves faster).  Same tile scheme and the
-// same packed arithmetic as k_run_fast; a 16-byte vector holds 8/C frames, so every vector
-// position has a fixed channel (for 16 channels: fixed per lane parity) and the per-channel
-// accumulators live in registers.  NS = min(C, 8) accumulator slots per lane: the half h of
-// dword i feeds slot 2*(i % (NS/2)) + h.
+// Wide path: 4 or 8 channels with the identity channel map, runs that write PCM or floats (read-only
+// runs go to k_run_rows).  Same tile scheme and the same packed arithmetic as k_run_fast,
+// over tiles of WIDE_TILE_U vectors per lane (8 KiB; tools/bench_generic.py); a 16-byte vector
+// holds 8/C frames, so every vector position has a fixed channel and the per-channel accumulators
+// live in registers.  NS = C accumulator slots per lane: the half h of dword i feeds slot
+// 2*(i % (NS/2)) + h.
+constexpr u32 WIDE_TILE_U = 8;
 
-// IDENT: no stream of the batch has a gain (the transform as the reference creates it) -- the
-// magnitudes are the samples' own; instantiated for the read-only runs, which the VALU binds.
-template <int C, bool WRITE_PCM, bool WRITE_F32, bool DO_VU, int U, bool IDENT = false>
+template <int C, bool WRITE_PCM, bool WRITE_F32, bool DO_VU>
 __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
 {
-    constexpr u32 TILE_U = U;
+    constexpr u32 TILE_U = WIDE_TILE_U;
     constexpr u32 TILE_VEC = 64 * TILE_U;
-    constexpr u32 NS = C < 8 ? C : 8;            // accumulator slots per lane
+    constexpr u32 NS = C;                        // accumulator slots per lane
     constexpr u32 NG = NS / 2;                   // dword groups
-    constexpr u32 NCLS = C == 16 ? 2 : 1;        // lane classes (vector parity) for 16 channels
     const u32 lane = threadIdx.x;
     const u32 s = blockIdx.x / a.chunks;
     const u32 k = blockIdx.x - s * a.chunks;
@@ -436,14 +434,13 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
     }
 
     const StreamParam *p = a.param + s;
-    const u32 cls = C == 16 ? (lane & 1u) : 0u;  // v0 and 64*u are even: vector parity = lane parity
-    u32 mipk[NG], mf[NS];                        // (per lane class for 16 channels: not uniform)
+    u32 mipk[NG], mf[NS];
 #pragma unroll
     for (u32 i = 0; i < NS; i++)
-        mf[i] = p->mf[i + 8u * cls];
+        mf[i] = p->mf[i];
 #pragma unroll
     for (u32 g = 0; g < NG; g++)
-        mipk[g] = (u32)p->mi[2u * g + 8u * cls] | ((u32)p->mi[2u * g + 1u + 8u * cls] << 16);
+        mipk[g] = (u32)p->mi[2u * g] | ((u32)p->mi[2u * g + 1u] << 16);
 
     const int16_t *ins = a.in + (u64)s * a.stride;
     const u32x4 *src = reinterpret_cast<const u32x4 *>(ins);
@@ -493,10 +490,7 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
             constexpr u32 dummy = 0;
             (void)dummy;
             const u32 g = i % NG;
-            if constexpr (IDENT)
-                qw[u][i] = gain2_identity(x[u][i], o[i]);
-            else
-                qw[u][i] = gain2<C != 16>(x[u][i], mipk[g], mf[2 * g], mf[2 * g + 1], o[i]);
+            qw[u][i] = gain2<true>(x[u][i], mipk[g], mf[2 * g], mf[2 * g + 1], o[i]);
             if constexpr (DO_VU) {
                 vmax[g] = pk_max(vmax[g], qw[u][i]);
                 pw[2 * g].add_lo(qw[u][i]);
@@ -548,48 +542,43 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
         for (u32 i = 0; i < NS; i++)
             pw[i].flush();
 #pragma unroll
-        for (u32 c = 0; c < NCLS; c++) {
-            const bool mine = NCLS == 1 || cls == c;
+        for (u32 sl = 0; sl < NS; sl++) {
+            const u64 sum = wave_add_u40(pw[sl].total);
+            const u32 wkey = wave_max_u32(best[sl]);
+            const u32 mag = wkey >> 16;
+            u64 gkey = 0;
+            if (mag) {
+                const u32 uw = TILE_U - 1u - ((wkey >> 6) & (TILE_U - 1u));
+                const u32 lw = 63u - (wkey & 63u);
+                u32 Q[4], X[4];
 #pragma unroll
-            for (u32 sl = 0; sl < NS; sl++) {
-                const u64 sum = wave_add_u40(mine ? pw[sl].total : 0ull);
-                const u32 wkey = wave_max_u32(mine ? best[sl] : 0u);
-                const u32 ch = sl + 8u * c;
-                const u32 mag = wkey >> 16;
-                u64 gkey = 0;
-                if (mag) {
-                    const u32 uw = TILE_U - 1u - ((wkey >> 6) & (TILE_U - 1u));
-                    const u32 lw = 63u - (wkey & 63u);
-                    u32 Q[4], X[4];
+                for (u32 u = 0; u < TILE_U; u++) {
+                    if (uw == u) {
 #pragma unroll
-                    for (u32 u = 0; u < TILE_U; u++) {
-                        if (uw == u) {
-#pragma unroll
-                            for (u32 i = 0; i < 4; i++) {
-                                Q[i] = (u32)__builtin_amdgcn_readlane((int)qw[u][i], (int)lw);
-                                X[i] = (u32)__builtin_amdgcn_readlane((int)x[u][i], (int)lw);
-                            }
+                        for (u32 i = 0; i < 4; i++) {
+                            Q[i] = (u32)__builtin_amdgcn_readlane((int)qw[u][i], (int)lw);
+                            X[i] = (u32)__builtin_amdgcn_readlane((int)x[u][i], (int)lw);
                         }
                     }
-                    u32 first = 8, neg = 0;
+                }
+                u32 first = 8, neg = 0;
 #pragma unroll
-                    for (u32 j = 0; j < 8; j++) {
-                        if (j % NS != sl)
-                            continue;
-                        const u32 m = (Q[j >> 1] >> (16u * (j & 1u))) & 0xffffu;
-                        if (m == mag && first == 8) {
-                            first = j;
-                            neg = (X[j >> 1] >> (16u * (j & 1u) + 15u)) & 1u;
-                        }
+                for (u32 j = 0; j < 8; j++) {
+                    if (j % NS != sl)
+                        continue;
+                    const u32 m = (Q[j >> 1] >> (16u * (j & 1u))) & 0xffffu;
+                    if (m == mag && first == 8) {
+                        first = j;
+                        neg = (X[j >> 1] >> (16u * (j & 1u) + 15u)) & 1u;
                     }
-                    gkey = make_key(mag, base + 8ull * (v0 + 64u * uw + lw) + first, neg);
                 }
-                if (lane == 0) {
-                    if (sum)
-                        atomicAdd(&vs->power[ch], sum);
-                    if (gkey)
-                        atomicMax(&vs->key[ch], gkey);
-                }
+                gkey = make_key(mag, base + 8ull * (v0 + 64u * uw + lw) + first, neg);
+            }
+            if (lane == 0) {
+                if (sum)
+                    atomicAdd(&vs->power[sl], sum);
+                if (gkey)
+                    atomicMax(&vs->key[sl], gkey);
             }
         }
     }
@@ -977,41 +966,27 @@ __global__ __launch_bounds__(64) void k_run_rows(RunArgs a, u32 W, u32 rows_per_
 }
 
 // ---------------------------------------------------------------------------
-// Launcher of the block kernels: by channel count and by what the batch asks for.
+// Launcher of the block kernels.  plan_run decides, by channel count and by what the batch asks for, which
+// kernel serves a run and how it is cut into tiles; launch_run launches what the plan names.
 
-constexpr u32 FAST_NW = 4;
+constexpr u32 FAST_NW = 4;                       // waves per workgroup of the mono / stereo runs that write PCM and keep a window
 
-hipError_t launch_run(const RunArgs &a, const RunTune &tune, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
-                      bool *flagged)
+RunPlan plan_run(const RunArgs &a)
 {
     const bool pcm = a.out != nullptr, f32 = a.f32 != nullptr, vu = a.vu != nullptr;
-    if (flagged)
-        *flagged = false;
-    if (a.streams == 0 || a.frames == 0)
-        return hipSuccess;
-    // completion by flag only for a launch of one workgroup (RunArgs::done_flag)
-    auto flag_if_single = [&](RunArgs &b, u32 workgroups) {
-        if (workgroups != 1u)
-            b.done_flag = nullptr;
-        if (flagged)
-            *flagged = b.done_flag != nullptr;
-    };
+    RunPlan p{};
+    p.err = hipSuccess;
+    if (a.streams == 0 || a.frames == 0 || !(pcm || f32 || vu))
+        return p;                                // RUN_NONE: nothing to launch
+    const u64 nvec = ((u64)a.frames * a.channels + 7) / 8;   // 16-byte vectors per stream
+    u64 tiles;
+    u32 waves = 1;
     if (a.channels <= 2) {
         // one wave per tile: 4 KiB when PCM or float is written, larger read-only
-        RunArgs b = a;
-        u32 tile_u = TILE_U;
-        if (!pcm && !f32) {
-            tile_u = a.channels == 1 ? TILE_U_VUONLY_MONO : TILE_U_VUONLY_STEREO;
-            if (tune.vu_tile)                    // tuning knob, validated when the batch was made
-                tile_u = tune.vu_tile;
-        }
-        const u64 nvec = ((u64)a.frames * a.channels + 7) / 8;
-        b.chunks = (u32)((nvec + 64ull * tile_u - 1) / (64ull * tile_u));
-        if (b.chunks == 0)
-            b.chunks = 1;
-        if ((u64)b.chunks * a.streams >= (1ull << 31))
-            return hipErrorInvalidValue;
-        const u32 grid = a.streams * b.chunks;
+        p.family = pcm || f32 ? RUN_FAST : RUN_FAST_RO;
+        p.channels = a.channels;
+        p.tile_u = pcm || f32 ? TILE_U : TILE_U_VUONLY;
+        tiles = (nvec + 64ull * p.tile_u - 1) / (64ull * p.tile_u);
         // Waves per workgroup of the runs that write PCM and keep a window (see run_fast).  Over 36 pairs of
         // input and output arrays in one process, three boxes (tools/placement_forms.py): 1 wave 0.356-0.361 ms,
         // 2 0.348-0.357, 4 0.346-0.351, 8 0.344-0.349 on config 2 (no window: 0.327-0.332) -- but only the
@@ -1021,87 +996,23 @@ hipError_t launch_run(const RunArgs &a, const RunTune &tune, hipStream_t st, hip
         // 0.181 / 0.207 ms for 1 / 2 / 4 / 8.
         // (streams of fewer than three tiles -- blocks of a few hundred frames -- take the one-wave form: a
         // workgroup of four waves would leave most of its waves idle there, and it is held to four per SIMD)
-        const u32 nw = tune.fast_nw ? tune.fast_nw : (b.chunks >= 3u ? FAST_NW : 1u);
-        const u32 gridw = a.streams * ((b.chunks + nw - 1u) / nw);
-        if ((u64)a.streams * ((b.chunks + nw - 1u) / nw) >= (1ull << 31))
-            return hipErrorInvalidValue;
-        flag_if_single(b, (pcm && !f32 && vu && nw > 1u) ? gridw : grid);
-#define CMHIP_FAST(C, P, F, V, U)                                                  \
-    hipExtLaunchKernelGGL((k_run_fast<C, P, F, V, U>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b)
-#define CMHIP_FAST_W(C, P, F, V, U)                                                \
-    do {                                                                           \
-        if (nw == 4) hipExtLaunchKernelGGL((k_run_fast<C, P, F, V, U, 4>), dim3(gridw), dim3(256), 0, st, ev_start, ev_stop, 0, b);        \
-        else if (nw == 8) hipExtLaunchKernelGGL((k_run_fast<C, P, F, V, U, 8>), dim3(gridw), dim3(512), 0, st, ev_start, ev_stop, 0, b);   \
-        else CMHIP_FAST(C, P, F, V, U);                                            \
-    } while (0)
-#define CMHIP_FAST_RO(C, U)                                                        \
-    hipExtLaunchKernelGGL((k_run_fast_ro<C, U>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b)
-#define CMHIP_FAST_C(C)                                                            \
-    do {                                                                           \
-        if (pcm && !f32 && vu) CMHIP_FAST_W(C, true, false, true, 4);              \
-        else if (!pcm && !f32 && vu && tile_u == 4) CMHIP_FAST_RO(C, 4);           \
-        else if (!pcm && !f32 && vu && tile_u == 8) CMHIP_FAST_RO(C, 8);           \
-        else if (!pcm && !f32 && vu) CMHIP_FAST_RO(C, 16);                         \
-        else if (pcm && !f32 && !vu) CMHIP_FAST(C, true, false, false, 4);         \
-        else if (pcm && f32 && vu) CMHIP_FAST(C, true, true, true, 4);             \
-        else if (!pcm && f32 && vu) CMHIP_FAST(C, false, true, true, 4);           \
-        else if (pcm && f32 && !vu) CMHIP_FAST(C, true, true, false, 4);           \
-        else if (!pcm && f32 && !vu) CMHIP_FAST(C, false, true, false, 4);         \
-    } while (0)
-        if (a.channels == 1)
-            CMHIP_FAST_C(1);
-        else
-            CMHIP_FAST_C(2);
-#undef CMHIP_FAST_C
-#undef CMHIP_FAST_RO
-#undef CMHIP_FAST_W
-#undef CMHIP_FAST
-    } else if ((a.channels == 4 || a.channels == 8) && a.identity_maps && (pcm || f32) &&
-               !(a.channels == 4 && f32 && !tune.wide4_f32)) {
+        if (pcm && !f32 && vu && tiles >= 3)
+            waves = FAST_NW;
+    } else if ((a.channels == 4 || a.channels == 8) && a.identity_maps && (pcm || f32) && !(a.channels == 4 && f32)) {
         // (4-channel float planes: k_run_wide writes every other float of a line per store;
         // k_run_rows stages the planes through LDS and runs 25 % faster there.  Read-only runs:
-        // k_run_rows 5.9-6.0 TB/s on 8 channels against 4.0-4.7 for k_run_wide, round 2.)
-        RunArgs b = a;
-        // tile size: read-only runs take 16 KiB tiles, the rest 8 KiB (tools/bench_generic.py);
-        // 16 channels run faster on k_run_rows below (5.6 against 4.7 TB/s)
-        const u32 wu = (!pcm && !f32) ? 16u : 8u;
-        const u64 nvec = ((u64)a.frames * a.channels + 7) / 8;
-        b.chunks = (u32)((nvec + 64ull * wu - 1) / (64ull * wu));
-        if (b.chunks == 0)
-            b.chunks = 1;
-        if ((u64)b.chunks * a.streams >= (1ull << 31))
-            return hipErrorInvalidValue;
-        const u32 grid = a.streams * b.chunks;
-        flag_if_single(b, grid);
-#define CMHIP_WIDE(C, P, F, V)                                                     \
-    do {                                                                           \
-        if (wu == 16u)                                                             \
-            hipExtLaunchKernelGGL((k_run_wide<C, P, F, V, 16>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b); \
-        else                                                                       \
-            hipExtLaunchKernelGGL((k_run_wide<C, P, F, V, 8>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b);  \
-    } while (0)
-#define CMHIP_WIDE_C(C)                                                            \
-    do {                                                                           \
-        if (pcm && !f32 && vu) CMHIP_WIDE(C, true, false, true);                   \
-        else if (!pcm && !f32 && vu && a.identity_gains)                           \
-            hipExtLaunchKernelGGL((k_run_wide<C, false, false, true, 16, true>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b); \
-        else if (!pcm && !f32 && vu) CMHIP_WIDE(C, false, false, true);            \
-        else if (pcm && !f32 && !vu) CMHIP_WIDE(C, true, false, false);            \
-        else if (pcm && f32 && vu) CMHIP_WIDE(C, true, true, true);                \
-        else if (!pcm && f32 && vu) CMHIP_WIDE(C, false, true, true);              \
-        else if (pcm && f32 && !vu) CMHIP_WIDE(C, true, true, false);              \
-        else if (!pcm && f32 && !vu) CMHIP_WIDE(C, false, true, false);            \
-    } while (0)
-        if (a.channels == 4)
-            CMHIP_WIDE_C(4);
-        else
-            CMHIP_WIDE_C(8);
-#undef CMHIP_WIDE_C
-#undef CMHIP_WIDE
+        // k_run_rows 5.9-6.0 TB/s on 8 channels against 4.0-4.7 for k_run_wide, round 2.
+        // 16 channels run faster on k_run_rows too: 5.6 against 4.7 TB/s, tools/bench_generic.py)
+        p.family = RUN_WIDE;
+        p.channels = a.channels;
+        p.tile_u = WIDE_TILE_U;
+        tiles = (nvec + 64ull * p.tile_u - 1) / (64ull * p.tile_u);
     } else {
         // any other channel count, or channel maps on more than two channels: rows of W vectors
         // so that every lane position keeps its channel
-        RunArgs b = a;
+        p.family = RUN_ROWS;
+        p.map = a.identity_maps ? 0u : 1u;
+        p.stage = f32 && a.channels != 16 ? 1u : 0u;        // staged float planes unless 16 channels
         u32 g = a.channels, e = 8;
         while (e) {                              // gcd(C, 8)
             const u32 t = g % e;
@@ -1109,54 +1020,124 @@ hipError_t launch_run(const RunArgs &a, const RunTune &tune, hipStream_t st, hip
             e = t;
         }
         const u32 P = a.channels / g;
-        const u32 W = 64u - 64u % P;
+        p.W = 64u - 64u % P;
         // rows per tile (~1 KiB each); with 4 or 8 channels (here only when they carry channel
         // maps) every lane adds to the same few LDS words at the end: bigger tiles, fewer merges
         // (at sustained clocks, tools/bench_generic.py: runs with channel maps gain 3-5 % from 16 rows
         // instead of 8, 16 channels writing PCM 4-16 % from 16 instead of 32)
         const bool ro = !pcm && !f32;
-        // (read-only runs: 64 rows -- the merge at the end of a tile costs as much as two steps of the
-        // loop; 5.2-6.0 TB/s against 4.8-5.6 with 16 or 32 rows, round 2)
-        u32 rpt = ro ? 64u : P == 1 ? (a.channels == 16 ? 16u : 32u) : (a.identity_maps ? 8u : 16u);
-        if (tune.rows_rpt)                                     // tuning knob (tools/bench_generic.py)
-            rpt = tune.rows_rpt;
-        const u64 nvec = ((u64)a.frames * a.channels + 7) / 8;
-        const u64 rows = (nvec + W - 1) / W;
-        if (ro && !tune.rows_rpt) {
+        const u64 rows = (nvec + p.W - 1) / p.W;
+        if (ro) {
+            // (read-only runs: 64 rows -- the merge at the end of a tile costs as much as two steps of the
+            // loop; 5.2-6.0 TB/s against 4.8-5.6 with 16 or 32 rows, round 2)
             // equal tiles: a stream of 98 rows is two tiles of 52, not one of 64 and a ragged one of 34
             // whose merge costs as much as the whole tile's (3 and 6 channels at 16 384 frames: +8 %)
-            const u64 nt = (rows + rpt - 1) / rpt;
-            rpt = (u32)(((rows + nt - 1) / nt + 3u) & ~3ull);
+            const u64 nt = (rows + 63) / 64;
+            p.rows_per_tile = (u32)(((rows + nt - 1) / nt + 3u) & ~3ull);
+        } else {
+            p.rows_per_tile = P == 1 ? (a.channels == 16 ? 16u : 32u) : (a.identity_maps ? 8u : 16u);
         }
-        b.chunks = (u32)((rows + rpt - 1) / rpt);
-        if (b.chunks == 0)
-            b.chunks = 1;
-        if ((u64)b.chunks * a.streams >= (1ull << 31))
-            return hipErrorInvalidValue;
-        const u32 grid = a.streams * b.chunks;
-        flag_if_single(b, grid);
-#define CMHIP_ROWS(P_, F_, V_)                                                                      \
-    do {                                                                                            \
-        constexpr bool S_ = F_;                        /* staged float planes unless 16 channels */ \
-        if (a.identity_maps && (!F_ || a.channels != 16))                                           \
-            hipExtLaunchKernelGGL((k_run_rows<P_, F_, V_, false, S_>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b, W, rpt); \
-        else if (a.identity_maps)                                                                   \
-            hipExtLaunchKernelGGL((k_run_rows<P_, F_, V_, false, false>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b, W, rpt); \
-        else if (!F_ || a.channels != 16)                                                           \
-            hipExtLaunchKernelGGL((k_run_rows<P_, F_, V_, true, S_>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b, W, rpt);  \
-        else                                                                                        \
-            hipExtLaunchKernelGGL((k_run_rows<P_, F_, V_, true, false>), dim3(grid), dim3(64), 0, st, ev_start, ev_stop, 0, b, W, rpt);  \
-    } while (0)
-        if (pcm && !f32 && vu) CMHIP_ROWS(true, false, true);
-        else if (!pcm && !f32 && vu) CMHIP_ROWS(false, false, true);
-        else if (pcm && !f32 && !vu) CMHIP_ROWS(true, false, false);
-        else if (pcm && f32 && vu) CMHIP_ROWS(true, true, true);
-        else if (!pcm && f32 && vu) CMHIP_ROWS(false, true, true);
-        else if (pcm && f32 && !vu) CMHIP_ROWS(true, true, false);
-        else if (!pcm && f32 && !vu) CMHIP_ROWS(false, true, false);
-#undef CMHIP_ROWS
+        tiles = (rows + p.rows_per_tile - 1) / p.rows_per_tile;
+    }
+    if (tiles * a.streams >= (1ull << 31)) {     // (bounds the workgroups of every form)
+        RunPlan refused{};
+        refused.err = hipErrorInvalidValue;
+        return refused;
+    }
+    p.chunks = (u32)tiles;
+    p.waves = waves;
+    p.grid = a.streams * ((p.chunks + waves - 1u) / waves);
+    p.block = 64u * waves;
+    // completion by flag only for a launch of one workgroup (RunArgs::done_flag)
+    p.keep_flag = a.done_flag && p.grid == 1u;
+    return p;
+}
+
+// Every block kernel a plan can name, by what the run writes and keeps (io = IO_PCM | IO_F32 | IO_VU); nothing
+// else is compiled.  k_run_fast's read-only form is k_run_fast_ro, its four-wave form the one for PCM + window.
+constexpr u32 IO_PCM = 1, IO_F32 = 2, IO_VU = 4;
+using RunKernel = void (*)(RunArgs);
+using RowsKernel = void (*)(RunArgs, u32, u32);
+template <int C>
+constexpr RunKernel fast_kernels[8] = {
+    nullptr,
+    k_run_fast<C, true, false, false, TILE_U>,
+    k_run_fast<C, false, true, false, TILE_U>,
+    k_run_fast<C, true, true, false, TILE_U>,
+    nullptr,
+    k_run_fast<C, true, false, true, TILE_U>,
+    k_run_fast<C, false, true, true, TILE_U>,
+    k_run_fast<C, true, true, true, TILE_U>,
+};
+constexpr RunKernel wide_kernels[2][8] = {
+    {nullptr, k_run_wide<4, true, false, false>, nullptr, nullptr,
+     nullptr, k_run_wide<4, true, false, true>, nullptr, nullptr},
+    {nullptr, k_run_wide<8, true, false, false>, k_run_wide<8, false, true, false>, k_run_wide<8, true, true, false>,
+     nullptr, k_run_wide<8, true, false, true>, k_run_wide<8, false, true, true>, k_run_wide<8, true, true, true>},
+};
+template <bool MAP>
+constexpr RowsKernel rows_kernels[2][8] = {     // [STAGE][io]: only float planes are staged
+    {nullptr, k_run_rows<true, false, false, MAP, false>, k_run_rows<false, true, false, MAP, false>,
+     k_run_rows<true, true, false, MAP, false>, k_run_rows<false, false, true, MAP, false>,
+     k_run_rows<true, false, true, MAP, false>, k_run_rows<false, true, true, MAP, false>,
+     k_run_rows<true, true, true, MAP, false>},
+    {nullptr, nullptr, k_run_rows<false, true, false, MAP, true>, k_run_rows<true, true, false, MAP, true>,
+     nullptr, nullptr, k_run_rows<false, true, true, MAP, true>, k_run_rows<true, true, true, MAP, true>},
+};
+
+hipError_t launch_run(const RunArgs &a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, bool *flagged)
+{
+    const RunPlan p = plan_run(a);
+    if (flagged)
+        *flagged = p.keep_flag != 0;
+    if (p.family == RUN_NONE)
+        return p.err;
+    RunArgs b = a;
+    b.chunks = p.chunks;
+    if (!p.keep_flag)
+        b.done_flag = nullptr;
+    auto launch = [&](auto kernel, auto... extra) {
+        hipExtLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), 0, st, ev_start, ev_stop, 0, b, extra...);
+    };
+    const u32 io = (a.out ? IO_PCM : 0u) | (a.f32 ? IO_F32 : 0u) | (a.vu ? IO_VU : 0u);
+    const bool mono = p.channels == 1;
+    switch (p.family) {
+    case RUN_FAST:
+        if (p.waves == FAST_NW)
+            launch(mono ? k_run_fast<1, true, false, true, TILE_U, FAST_NW> : k_run_fast<2, true, false, true, TILE_U, FAST_NW>);
+        else
+            launch((mono ? fast_kernels<1> : fast_kernels<2>)[io]);
+        break;
+    case RUN_FAST_RO:
+        launch(mono ? k_run_fast_ro<1, TILE_U_VUONLY> : k_run_fast_ro<2, TILE_U_VUONLY>);
+        break;
+    case RUN_WIDE:
+        launch(wide_kernels[p.channels == 8][io]);
+        break;
+    case RUN_ROWS:
+        launch((p.map ? rows_kernels<true> : rows_kernels<false>)[p.stage][io], p.W, p.rows_per_tile);
+        break;
     }
     return hipGetLastError();
+}
+
+// test hook: the plan of a run (host logic, needs no GPU).  The pointers only say what the run writes and keeps;
+// the completion flag is offered, so that keep_flag tells the one-workgroup launches.
+extern "C" void cmhip_test_plan_run(uint32_t streams, uint32_t channels, uint32_t frames, int out, int f32, int vu,
+                                    int identity_maps, RunPlan *plan)
+{
+    static uint32_t word;
+    RunArgs a{};
+    a.out = out ? reinterpret_cast<int16_t *>(&word) : nullptr;
+    a.f32 = f32 ? reinterpret_cast<float *>(&word) : nullptr;
+    a.vu = vu ? reinterpret_cast<VuState *>(&word) : nullptr;
+    a.frames = frames;
+    a.streams = streams;
+    a.channels = channels;
+    a.identity_maps = identity_maps ? 1u : 0u;
+    a.done_flag = &word;
+    if (plan)
+        *plan = plan_run(a);
 }
 
 }  // namespace cmhip

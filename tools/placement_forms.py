@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""{window merged by workgroups of 1, 4, 8, 16 waves; no window} x {input and output arrays of the same placement class, of different
-ones}: the config-2 kernel in one process, on the slowest and the fastest of N x N array pairs.
+"""{window (the launcher's form); no window; other builds} x {input and output arrays of the same placement class, of
+different ones}: the config-2 kernel in one process, on the slowest and the fastest of N x N array pairs.
 PF_SNAP=1: a VU window per launch (snapshot + collect every step, as bench.py runs); PF_NOVU=1: the other builds
 named on the command line run without a window (PCM only)."""
 import ctypes as C
@@ -26,12 +26,8 @@ def dmalloc(n):
     return p.value
 
 
-def make(flags, env=None):
-    if env:
-        os.environ[env[0]] = env[1]
+def make(flags):
     b = cm.Batch(S, Cn, T, flags=flags | cm.EXTSLOTS)
-    if env:
-        os.environ.pop(env[0])
     if Cn == 2:
         b.set_gain(-1, 2, 1000, [750, 1250])
         b.set_chmap(-1, [1, 0])
@@ -43,7 +39,7 @@ def make(flags, env=None):
 SNAP = bool(os.environ.get("PF_SNAP"))          # a VU window per launch (snapshot + collect every step), as bench.py runs
 RO = len(sys.argv) > 2 and sys.argv[2] == "ro"          # the read-only runs (VU only): no output array, no pairs
 F32 = cm.OUT_F32 if os.environ.get("PF_F32") else 0            # float planes beside the PCM result
-forms = [("NW=%s" % n, make(cm.VU if RO else cm.OUT_PCM | cm.VU | F32, ("CMHIP_FAST_NW", n))) for n in (("1", "4", "8") if Cn <= 2 else ("1",))]
+forms = [("window", make(cm.VU if RO else cm.OUT_PCM | cm.VU | F32))]
 if not RO:
     forms.insert(1, ("no window", make(cm.OUT_PCM | F32)))
 for extra in sys.argv[3:]:                # other builds of the library (timing-only variants), on the same arrays
