@@ -89,8 +89,7 @@ void           cmhip_batch_free(cmhip_batch_t *b);
  * if it beats the first by 2 % and frees the rest before cmhip_batch_new() returns.  It never asks
  * for more than HALF of the memory hipMemGetInfo reports free (spacers and candidates together;
  * fewer candidates on a fuller card) and stops allocating after 0.3 s.  Without the flag nothing of
- * this happens: two hipMalloc calls, no probe launches.  $CMHIP_PLACE overrides for experiments:
- * 0 never, 1 the first large batch of a device even without the flag, 2 every large batch. */
+ * this happens: two hipMalloc calls, no probe launches. */
 typedef struct cmhip_placement {
     int      searched;          /* 1 when the probes ran */
     int      candidates;        /* arrays probed, the first two included (2..7) */

@@ -109,27 +109,6 @@ extern "C" int cmhip_device_read(int device, void *dst_host, const void *src_dev
 // ---------------------------------------------------------------------------
 // the batch object
 
-static RunTune read_tune()
-{
-    RunTune t{};
-    t.place_env = -1;
-    if (const char *e = getenv("CMHIP_PLACE")) {
-        const int v = atoi(e);
-        t.place_env = v <= 0 ? 0 : (v >= 2 ? 2 : 1);
-    }
-    if (getenv("CMHIP_PLACE_DEBUG"))
-        t.place_debug = 1;
-    if (getenv("CMHIP_NO_DONE_FLAG"))
-        t.no_done_flag = 1;
-    t.done_spin_us = 200;
-    if (const char *e = getenv("CMHIP_DONE_SPIN_US")) {
-        const int v = atoi(e);
-        if (v >= 0 && v <= 20000)
-            t.done_spin_us = (uint32_t)v;
-    }
-    return t;
-}
-
 // The division constants of one gain (StreamParam): gain = mi * scale + r, mf = ceil(r * 2^32 / scale).
 // mf < 2^32 because r <= scale - 1; mi <= 65535.
 static void host_gain_consts(uint16_t gain, uint16_t scale, uint16_t *mi, uint32_t *mf)
@@ -235,7 +214,6 @@ extern "C" void cmhip_batch_free(cmhip_batch_t *b)
     (void)hipFree(b->d_ring);
     if (b->h_ring)
         (void)hipHostFree(b->h_ring);
-    (void)hipFree(b->d_dbg);
     for (int i = 0; i < 3; i++)
         if (b->h_pack[i])
             (void)hipHostFree(b->h_pack[i]);
@@ -276,11 +254,9 @@ static int batch_init(cmhip_batch_t *b)
         HIP_TRY(hipHostMalloc((void **)&b->h_in, pcm_bytes, hipHostMallocMapped));
         memset(b->h_in, 0, pcm_bytes);
         HIP_TRY(hipHostGetDevicePointer((void **)&b->d_in, b->h_in, 0));
-        if (!b->tune.no_done_flag) {                     // (A/B knob: CMHIP_NO_DONE_FLAG)
-            HIP_TRY(hipHostMalloc((void **)&b->h_done, 64, hipHostMallocMapped));
-            memset(b->h_done, 0, 64);
-            HIP_TRY(hipHostGetDevicePointer((void **)&b->d_done, b->h_done, 0));
-        }
+        HIP_TRY(hipHostMalloc((void **)&b->h_done, 64, hipHostMallocMapped));
+        memset(b->h_done, 0, 64);
+        HIP_TRY(hipHostGetDevicePointer((void **)&b->d_done, b->h_done, 0));
         if ((d.flags & CMHIP_OUT_PCM) && !(d.flags & CMHIP_INPLACE)) {
             HIP_TRY(hipHostMalloc((void **)&b->h_out, pcm_bytes, hipHostMallocMapped));
             memset(b->h_out, 0, pcm_bytes);
@@ -318,8 +294,7 @@ static int batch_init(cmhip_batch_t *b)
         // steps the chain snapshot -> collect -> next launch left the card idle for 150 us)
         int least = 0, greatest = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&b->copy_stream, hipStreamNonBlocking,
-                                            getenv("CMHIP_SIDE_PRIORITY_OFF") ? least : greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&b->copy_stream, hipStreamNonBlocking, greatest));
     }
     HIP_TRY(hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&b->ev_node, hipEventDisableTiming));
@@ -328,8 +303,6 @@ static int batch_init(cmhip_batch_t *b)
     HIP_TRY(hipMalloc((void **)&b->d_nframes, S * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&b->d_sink, sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(b->d_sink, 0, sizeof(unsigned long long), b->stream));
-    HIP_TRY(hipMalloc((void **)&b->d_dbg, 64 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(b->d_dbg, 0, 64 * sizeof(unsigned long long), b->stream));
     if (d.flags & CMHIP_EQ) {
         HIP_TRY(prepare_eq(d.device));
         HIP_TRY(hipMalloc((void **)&b->d_eq, S * sizeof(EqParam)));
@@ -422,7 +395,6 @@ extern "C" cmhip_batch_t *cmhip_batch_new(const cmhip_batch_desc_t *desc)
     b->ring_slots = 0;
     b->ring_seq = 0;
     b->ring_fetched = 0;
-    b->d_dbg = nullptr;
     b->h_pack[0] = b->h_pack[1] = b->h_pack[2] = nullptr;
     b->d_pack[0] = b->d_pack[1] = b->d_pack[2] = nullptr;
     b->snap_set2[0] = b->snap_set2[1] = b->snap_set2[2] = 0;
@@ -446,7 +418,6 @@ extern "C" cmhip_batch_t *cmhip_batch_new(const cmhip_batch_desc_t *desc)
     b->timing = false;
     b->timing_every = 1;
     b->timing_count = 0;
-    b->tune = read_tune();
     memset(&b->place, 0, sizeof(b->place));
     b->place.chosen_out = 1;
     b->place.candidates = 2;
@@ -456,17 +427,6 @@ extern "C" cmhip_batch_t *cmhip_batch_new(const cmhip_batch_desc_t *desc)
         return nullptr;
     }
     return b;
-}
-
-// diagnostic hook: the 64 stamp words a -DCMHIP_EQ_STAMPS build of the kernels writes
-extern "C" int cmhip_debug_read(cmhip_batch_t *b, unsigned long long *out)
-{
-    if (!b || !out)
-        return COOLMIC_ERROR_FAULT;
-    if (hipSetDevice(b->d.device) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess ||
-        hipMemcpy(out, b->d_dbg, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
-        return COOLMIC_ERROR_GENERIC;
-    return COOLMIC_ERROR_NONE;
 }
 
 // test hook: runs launched by this process so far (tests count launches per pull with it)
@@ -641,17 +601,20 @@ extern "C" void *cmhip_batch_dev_out(cmhip_batch_t *b) { return b ? b->d_out : n
 extern "C" void *cmhip_batch_dev_f32(cmhip_batch_t *b) { return b ? b->d_f32 : nullptr; }
 extern "C" void *cmhip_batch_hip_stream(cmhip_batch_t *b) { return b ? (void *)b->stream : nullptr; }
 
+// How long the host spins on the completion word of a one-workgroup launch before it waits for the stream:
+// bounded by what such a launch can take -- one workgroup on a block of at most a few KiB: tens of
+// microseconds, 16 384 frames through the equaliser a few hundred -- then the stream after all, which sleeps
+// instead of holding a core (a kernel that faulted never stores; a long one is not worth a core)
+constexpr std::chrono::microseconds DONE_SPIN{200};
+
 // CMHIP_HOSTPCM: the host may touch the slots only while no launch is using them
 static int host_slots_quiet(cmhip_batch_t *b)
 {
     if (b->in_flight) {
         bool done = false;
         if (b->done_flagged) {
-            // the launch's own last act was to store its sequence number here (done_epilogue).  The spin is
-            // bounded by what such a launch can take -- one workgroup on a block of at most a few KiB: tens of
-            // microseconds, 16 384 frames through the equaliser a few hundred -- then the stream after all, which
-            // sleeps instead of holding a core (a kernel that faulted never stores; a long one is not worth a core)
-            const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(b->tune.done_spin_us);
+            // the launch's own last act was to store its sequence number here (done_epilogue)
+            const auto t_end = std::chrono::steady_clock::now() + DONE_SPIN;
             unsigned spins = 0;
             while (!(done = __atomic_load_n(b->h_done, __ATOMIC_ACQUIRE) == b->done_seq)) {
                 if ((++spins & 63u) == 0 && std::chrono::steady_clock::now() > t_end)
@@ -1029,7 +992,6 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
         a.nsec = b->nsec;
         a.whole_streams = (slots_out == slots_in && !b->all_identity) ? 1u : 0u;
         a.parity = parity;
-        a.dbg = b->d_dbg;
         a.stride = b->stride;
         a.plane = b->plane;
         a.done_flag = flag;

@@ -78,7 +78,6 @@ struct cmhip_batch {
     unsigned int ring_slots;
     uint64_t ring_seq;                     // sequence number of the next run
     uint64_t ring_fetched;                 // runs below this sequence number have been fetched: their slots are clear
-    unsigned long long *d_dbg;             // 64 words, written only by diagnostic builds
 
     std::vector<StreamParam> h_param;
     std::vector<uint16_t> h_scale;         // the reference's master_gain_scale per stream
@@ -109,7 +108,6 @@ struct cmhip_batch {
     bool timing;
     unsigned int timing_every, timing_count;     // every n-th run carries the events (cmhip_batch_timing)
     std::vector<EventPair> ev_used, ev_free;
-    RunTune tune;                          // placement and completion settings, read once at creation
     cmhip_placement_t place;               // what the placement search did (cmhip_batch_placement)
     bool vu_off;                           // runs leave the windows alone for now (cmhip_batch_vu_pause)
 };

@@ -94,17 +94,6 @@ struct RunArgs {
     uint32_t       done_seq;
 };
 
-// Placement and completion settings of a batch, read from the environment ONCE, when the batch is created,
-// and validated there.  (Which block kernel serves a run is plan_run's to decide, not the environment's.)
-struct RunTune {
-    int32_t  place_env;            // CMHIP_PLACE: -1 unset (only batches created with CMHIP_PLACE_SEARCH search), 0 never,
-                                   // 1 the first large batch of a device also without the flag, 2 every large batch
-    uint32_t place_debug;          // CMHIP_PLACE_DEBUG: the probe times of the placement search on stderr
-    uint32_t no_done_flag;         // CMHIP_NO_DONE_FLAG: one-workgroup launches are waited for through the stream (A/B)
-    uint32_t done_spin_us;         // CMHIP_DONE_SPIN_US: how long the host spins on the completion word before it
-                                   // waits for the stream instead (default 200; 0 ... 20000)
-};
-
 struct EqArgs {
     const int16_t *in;
     int16_t       *out;            // int16 result or nullptr
@@ -122,7 +111,8 @@ struct EqArgs {
     uint32_t       parity;
     uint64_t       stride;
     uint64_t       plane;
-    unsigned long long *dbg;       // 64 words for in-kernel stamps (diagnostic builds only)
+    unsigned long long *dbg;       // read by no kernel now, kept so that the kernel-argument offsets below stay as
+                                   // they are
     uint32_t      *done_flag;      // as RunArgs::done_flag
     uint32_t       done_seq;
 };
@@ -179,8 +169,6 @@ hipError_t launch_ceiling(int mode, const void *src, void *dst, size_t bytes,
 struct cmhip_batch;
 #define CMHIP_INTERNAL __attribute__((visibility("hidden")))
 CMHIP_INTERNAL int cmhip_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-CMHIP_INTERNAL int cmhip_batch_node_partial_split(struct cmhip_batch *b, long long *dst_sum, long long *dst_key,
-                                                  uint64_t first_global, uint64_t global_step, int clear);
 CMHIP_INTERNAL int cmhip_batch_node_partial_side(struct cmhip_batch *b, long long *dst_sum, long long *dst_key,
                                                  uint64_t first_global, uint64_t global_step);
 CMHIP_INTERNAL void *cmhip_batch_side_stream(struct cmhip_batch *b);

@@ -1,12 +1,10 @@
 // cmhip_place.hip -- the opt-in placement search for a batch's two PCM arrays (CMHIP_PLACE_SEARCH).
 #include "cmhip_engine.h"
 
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <chrono>
-#include <mutex>
 
 // Placement of a batch's two PCM arrays.  On MI355X a kernel that streams one large array in and another
 // out runs 3-5 % faster when the two lie in different stretches of the card's memory (measured:
@@ -63,27 +61,6 @@ static double place_probe_ms(cmhip_batch_t *b, const void *src, void *dst, hipEv
     return (double)ms / n;
 }
 
-// Who searches: a batch created with CMHIP_PLACE_SEARCH, always (the caller asked).  $CMHIP_PLACE, for
-// experiments: 0 nobody, 1 also the first large batch of a device in this process without the flag, 2 every
-// large batch.
-static bool place_search_allowed(const cmhip_batch_t *b)
-{
-    static std::mutex mu;
-    static bool searched[64];
-    if (b->tune.place_env == 0)
-        return false;
-    if ((b->d.flags & CMHIP_PLACE_SEARCH) || b->tune.place_env == 2)
-        return true;
-    if (b->tune.place_env != 1)
-        return false;
-    std::lock_guard<std::mutex> g(mu);
-    const int d = b->d.device;
-    if (d < 0 || d >= 64 || searched[d])
-        return false;
-    searched[d] = true;
-    return true;
-}
-
 // The batch has its two PCM arrays where hipMalloc first put them (candidates 0 and 1).  More candidates
 // follow behind spacers; every pair of candidates is a possible (input, output) -- nothing is in the arrays
 // yet -- and the pair the batch's own run is fastest on is kept if it beats the first by more than 2 %.
@@ -100,7 +77,7 @@ int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes)
     rec.chosen_in = 0;
     rec.chosen_out = 1;
     rec.candidates = 2;
-    if (bytes >= PLACE_MIN_BYTES && place_search_allowed(b) && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+    if (bytes >= PLACE_MIN_BYTES && (b->d.flags & CMHIP_PLACE_SEARCH) && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
         hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
         probed = true;
         rec.searched = 1;
@@ -150,8 +127,6 @@ int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes)
                 if (i == 0 && j == 1)
                     continue;
                 const double t = place_probe_ms(b, cand[i], cand[j], e0, e1);
-                if (b->tune.place_debug)
-                    fprintf(stderr, "cmhip place: %d -> %d: %.4f ms (0 -> 1: %.4f ms)\n", i, j, t, ref);
                 if (t > 0. && (tbest == 0. || t < tbest)) {
                     tbest = t;
                     bi = i;
@@ -173,9 +148,6 @@ int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes)
         rec.chosen_in = in;
         rec.chosen_out = out;
         rec.search_ms = 1e3 * elapsed();
-        if (b->tune.place_debug)
-            fprintf(stderr, "cmhip place: input = candidate %d, output = candidate %d, %.0f ms, %.1f GiB asked of %.1f free\n",
-                    in, out, rec.search_ms, (double)asked / (1ull << 30), (double)free_b / (1ull << 30));
     }
     if (e0)
         (void)hipEventDestroy(e0);

@@ -429,6 +429,25 @@ extern "C" int cmhip_test_merge_windows(const uint64_t *windows, unsigned int co
 // ---------------------------------------------------------------------------
 // node-global VU
 
+// the node record of the batch's windows, its sums and its keys in two places, on the main stream
+static int node_partial_split(cmhip_batch_t *b, long long *dst_sum, long long *dst_key,
+                              uint64_t first_global, uint64_t global_step)
+{
+    if (use(b))
+        return COOLMIC_ERROR_GENERIC;
+    // This kernel reads the windows after the last run, on the same stream: its own end, stamped by
+    // its dispatch, is what the next snapshot has to wait for -- no event packet on the main stream.
+    if (cmhip_engine_settle_node(b))
+        return COOLMIC_ERROR_GENERIC;
+    hipEvent_t done = b->ev_done[b->done_next];
+    b->done_next = (b->done_next + 1u) & 3u;
+    b->last_done = nullptr;
+    HIP_TRY(launch_node_partial(b->d_vu, b->d.streams, b->d.channels, b->parity, first_global, global_step,
+                                dst_sum, dst_key, true, b->stream, done));
+    b->last_done = done;
+    return COOLMIC_ERROR_NONE;
+}
+
 extern "C" int cmhip_batch_vu_node_partial(cmhip_batch_t *b, void *dst_device,
                                            uint64_t first_global, uint64_t global_step)
 {
@@ -439,7 +458,7 @@ extern "C" int cmhip_batch_vu_node_partial(cmhip_batch_t *b, void *dst_device,
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
     long long *dst = (long long *)dst_device;
-    return cmhip_batch_node_partial_split(b, dst, dst + CMHIP_NODE_SUM_WORDS, first_global, global_step, 1);
+    return node_partial_split(b, dst, dst + CMHIP_NODE_SUM_WORDS, first_global, global_step);
 }
 
 extern "C" int cmhip_batch_vu_node_record(cmhip_batch_t *b, int64_t *words_host, uint64_t first_global,
@@ -453,32 +472,13 @@ extern "C" int cmhip_batch_vu_node_record(cmhip_batch_t *b, int64_t *words_host,
         return COOLMIC_ERROR_GENERIC;
     if (!b->d_node_scratch)
         HIP_TRY(hipMalloc((void **)&b->d_node_scratch, CMHIP_NODE_WORDS * sizeof(long long)));
-    const int rc = cmhip_batch_node_partial_split(b, b->d_node_scratch, b->d_node_scratch + CMHIP_NODE_SUM_WORDS,
-                                                  first_global, global_step, 1);
+    const int rc = node_partial_split(b, b->d_node_scratch, b->d_node_scratch + CMHIP_NODE_SUM_WORDS,
+                                      first_global, global_step);
     if (rc != COOLMIC_ERROR_NONE)
         return rc;
     HIP_TRY(hipMemcpyAsync(words_host, b->d_node_scratch, CMHIP_NODE_WORDS * sizeof(long long),
                            hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    return COOLMIC_ERROR_NONE;
-}
-
-// internal (node.hip): the same record with its sums and its keys in two places
-int cmhip_batch_node_partial_split(cmhip_batch_t *b, long long *dst_sum, long long *dst_key,
-                                   uint64_t first_global, uint64_t global_step, int clear)
-{
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    // This kernel reads the windows after the last run, on the same stream: its own end, stamped by
-    // its dispatch, is what the next snapshot has to wait for -- no event packet on the main stream.
-    if (cmhip_engine_settle_node(b))
-        return COOLMIC_ERROR_GENERIC;
-    hipEvent_t done = b->ev_done[b->done_next];
-    b->done_next = (b->done_next + 1u) & 3u;
-    b->last_done = nullptr;
-    HIP_TRY(launch_node_partial(b->d_vu, b->d.streams, b->d.channels, b->parity, first_global, global_step,
-                                dst_sum, dst_key, clear != 0, b->stream, done));
-    b->last_done = done;
     return COOLMIC_ERROR_NONE;
 }
 

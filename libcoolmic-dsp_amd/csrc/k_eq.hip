@@ -1,11 +1,6 @@
 // k_eq.hip -- the pipelined equaliser kernel (BASELINE config 3) and its launcher.
 #include "cmhip_device.h"
 #include <type_traits>
-// 0 never, 1 always, 2 (the product) when the launch has an int16 result: see rec_step
-#ifndef CMHIP_EQ_R_INTERLEAVE
-#define CMHIP_EQ_R_INTERLEAVE 2
-#endif
-
 #include <mutex>
 
 namespace cmhip {
@@ -57,35 +52,6 @@ __device__ __forceinline__ int f32_to_i16(float y)
 // long per step by themselves are the R waves (16 reads, 128 FMAs, 16 writes); everything
 // without a recurrence is spread over T lanes, where a 64-frame row costs 2 reads + 2 writes.
 // Rows are 68 floats (16-byte aligned, lane-per-row b128 access without bank conflicts).
-
-#ifndef CMHIP_EQ_ABL
-#define CMHIP_EQ_ABL 0            // `make abl`: timing-only builds with one part of the pipeline cut out
-#endif
-// Sensitivity builds (`make variant NAME=pad_r DEFS=-DCMHIP_EQ_PAD_R=32`, tools/ab_two_libs.py): N extra
-// VALU instructions per step in the waves of one role.  What the launch time gains per padded
-// instruction says which role the step waits for.  Never defined in the product.
-#ifndef CMHIP_EQ_PAD_R
-#define CMHIP_EQ_PAD_R 0
-#endif
-#ifndef CMHIP_EQ_PAD_TIN
-#define CMHIP_EQ_PAD_TIN 0
-#endif
-#ifndef CMHIP_EQ_PAD_TFF
-#define CMHIP_EQ_PAD_TFF 0
-#endif
-#ifndef CMHIP_EQ_PAD_S
-#define CMHIP_EQ_PAD_S 0
-#endif
-template <int N>
-__device__ __forceinline__ void eq_pad()
-{
-    if constexpr (N > 0) {
-        u32 t = 0;
-#pragma unroll
-        for (int i = 0; i < N; i++)
-            asm volatile("v_add_u32 %0, %0, %0" : "+v"(t));
-    }
-}
 
 // Channels: a "row" is one channel of one stream -- every channel runs its stream's filter
 // with state of its own -- and a workgroup takes G / C whole streams.  CH = 1: mono, the 16-byte
@@ -344,9 +310,7 @@ void k_eq_pipe(EqArgs a)
     auto fetch = [&](u32 b) -> Pcm {
         const u32 f0 = b * EP_TB + l_t8;
         Pcm r = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-        if (CMHIP_EQ_ABL & 2) {
-            r.a = u32x4{f0, f0 * 3u, f0 * 5u, f0 * 7u};
-        } else if constexpr (MONO) {
+        if constexpr (MONO) {
             r.a = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(l_src + min(f0, l_last)));
         } else if constexpr (STEREO) {                    // 8 frames x (L, R): 32 bytes
             const u32x4 *p = reinterpret_cast<const u32x4 *>(l_src + min(2u * f0, l_last));
@@ -404,266 +368,216 @@ void k_eq_pipe(EqArgs a)
             f[j] = __builtin_fmaf(c2, x[j - 2], __builtin_fmaf(c1, x[j - 1], c0 * x[j]));
     };
 
-#ifdef CMHIP_EQ_STAMPS
-    u64 st_busy = 0, st_p[3] = {0, 0, 0};
-    const u64 st_begin = __builtin_readcyclecounter();
-    // which wave reaches the barrier last (sampled every 16th step: the look itself delays wave 0's next
-    // step), and how long the first one waits for it.  One 256-byte block: the tiles in dynamic LDS behind
-    // it keep their 16-byte alignment.
-    struct alignas(256) StampLds { u32 arr[2][16]; u32 last[16]; unsigned long long skew; u32 pad[14]; };
-    static_assert(sizeof(StampLds) == 256, "");
-    __shared__ StampLds st_lds;
-    u32 st_n = 0;
-    if (threadIdx.x < 16)
-        st_lds.last[threadIdx.x] = 0;
-    if (threadIdx.x == 0)
-        st_lds.skew = 0;
-    __syncthreads();
-#endif
     // Schedule: F_k of block b is written in step b+2k, Y_k in step b+2k+1, the block leaves in
     // step b+2*NSEC.  Every buffer is read one step after it was written, so two slots do.
     // (Loading an R wave's next row into registers a step ahead was worth 7 % with eight waves
     // per workgroup; with twelve it needs more registers than three waves per SIMD leave.)
     auto rec_step = [&](const u32 step) {
-        eq_pad<CMHIP_EQ_PAD_R>();
-        if (!(CMHIP_EQ_ABL & 32)) {
-            const u32 first = HOP * sec + HOP - 1u;       // step in which block 0 is worked on
-            const u32 b = step - first;
-            if (has_sec && step >= first && b < nblocks) {
-                float4 *out = reinterpret_cast<float4 *>(
-                    lds + ((2u * sec + 1u) * 2u + (b & 1u)) * EP_TILE + row * EP_ROW);
-                const float4 *in = reinterpret_cast<const float4 *>(
-                    lds + ((2u * sec) * 2u + (b & 1u)) * EP_TILE + row * EP_ROW);
-                float4 v[EP_TB / 4];
+        const u32 first = HOP * sec + HOP - 1u;       // step in which block 0 is worked on
+        const u32 b = step - first;
+        if (has_sec && step >= first && b < nblocks) {
+            float4 *out = reinterpret_cast<float4 *>(
+                lds + ((2u * sec + 1u) * 2u + (b & 1u)) * EP_TILE + row * EP_ROW);
+            const float4 *in = reinterpret_cast<const float4 *>(
+                lds + ((2u * sec) * 2u + (b & 1u)) * EP_TILE + row * EP_ROW);
+            float4 v[EP_TB / 4];
 #pragma unroll
-                for (u32 t = 0; t < EP_TB / 4; t++)      // whole row first: 16 LDS reads in flight
-                    v[t] = in[t];
-                const u32 done = b * EP_TB;
-                const u32 cnt = my_nfr > done ? min(my_nfr - done, EP_TB) : 0u;
-                if (CMHIP_EQ_ABL & 4) {
-#pragma unroll
-                    for (u32 t = 0; t < EP_TB / 4; t++)
-                        out[t] = v[t];
-                } else if (__all(cnt == EP_TB || cnt == 0u)) {
-                    // (every row of the wave has the whole block or nothing of it: rows past the end of the batch,
-                    // streams that ended in an earlier block.  Those run the same instructions on whatever their tile
-                    // holds -- nothing of it is ever stored -- and get their history back afterwards.  Round 3 sent
-                    // the whole wave down the sample-by-sample path below as soon as ONE row was idle: a batch whose
-                    // rows are not a multiple of 32 -- 1365 x 6 -- had one workgroup that took 1.4 x as long as the
-                    // others for the whole launch, and the launch waited for it.)
-                    const float keep_h1 = h1, keep_h2 = h2;
-                    // Where the stores go: left alone the scheduler moves all sixteen to the end of the row.  Kept
-                    // behind their four samples each (a scheduling barrier per store) the runs that produce an
-                    // int16 result take 2.3-3.6 % less and config 3's float planes 0.8 % more (A/B in one process,
-                    // profiles/r03_eq_store_order_ab.txt) -- so the order follows the outputs.  Either way a store
-                    // holds the wave for its 25-50 clk: spacing them does not hide that (NOTES_r03).
-                    auto row = [&](auto spaced) {
-#pragma unroll
-                        for (u32 t = 0; t < EP_TB / 4; t++) {
-                            float4 y = v[t];
-                            if (!(CMHIP_EQ_ABL & 256) || (t & 1u) == 0u) {      // (256: timing only, half the FMAs)
-                                y.x = __builtin_fmaf(d1, h1, __builtin_fmaf(d2, h2, v[t].x));
-                                y.y = __builtin_fmaf(d1, y.x, __builtin_fmaf(d2, h1, v[t].y));
-                                y.z = __builtin_fmaf(d1, y.y, __builtin_fmaf(d2, y.x, v[t].z));
-                                y.w = __builtin_fmaf(d1, y.z, __builtin_fmaf(d2, y.y, v[t].w));
-                                h2 = y.z;
-                                h1 = y.w;
-                            }
-                            if (!(CMHIP_EQ_ABL & 8) || t == 0)
-                                out[t] = y;
-                            if constexpr (decltype(spaced)::value)
-                                __builtin_amdgcn_sched_barrier(0);
-                        }
-                    };
-                    if (CMHIP_EQ_R_INTERLEAVE == 1 || (CMHIP_EQ_R_INTERLEAVE == 2 && a.out != nullptr))
-                        row(std::true_type{});
-                    else
-                        row(std::false_type{});
-                    h1 = cnt ? h1 : keep_h1;
-                    h2 = cnt ? h2 : keep_h2;
-                } else {
-                    // some stream ends inside this block: same arithmetic, but the history of a
-                    // lane moves only on its real samples (what lies beyond is never stored)
+            for (u32 t = 0; t < EP_TB / 4; t++)      // whole row first: 16 LDS reads in flight
+                v[t] = in[t];
+            const u32 done = b * EP_TB;
+            const u32 cnt = my_nfr > done ? min(my_nfr - done, EP_TB) : 0u;
+            if (__all(cnt == EP_TB || cnt == 0u)) {
+                // (every row of the wave has the whole block or nothing of it: rows past the end of the batch,
+                // streams that ended in an earlier block.  Those run the same instructions on whatever their tile
+                // holds -- nothing of it is ever stored -- and get their history back afterwards.  Round 3 sent
+                // the whole wave down the sample-by-sample path below as soon as ONE row was idle: a batch whose
+                // rows are not a multiple of 32 -- 1365 x 6 -- had one workgroup that took 1.4 x as long as the
+                // others for the whole launch, and the launch waited for it.)
+                const float keep_h1 = h1, keep_h2 = h2;
+                // Where the stores go: left alone the scheduler moves all sixteen to the end of the row.  Kept
+                // behind their four samples each (a scheduling barrier per store) the runs that produce an
+                // int16 result take 2.3-3.6 % less and config 3's float planes 0.8 % more (A/B in one process,
+                // profiles/r03_eq_store_order_ab.txt) -- so the order follows the outputs.  Either way a store
+                // holds the wave for its 25-50 clk: spacing them does not hide that (NOTES_r03).
+                auto row = [&](auto spaced) {
 #pragma unroll
                     for (u32 t = 0; t < EP_TB / 4; t++) {
-                        const float xs[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
-                        float rs[4];
-#pragma unroll
-                        for (u32 j = 0; j < 4; j++) {
-                            const float r = __builtin_fmaf(d1, h1, __builtin_fmaf(d2, h2, xs[j]));
-                            const bool real = 4u * t + j < cnt;
-                            h2 = real ? h1 : h2;
-                            h1 = real ? r : h1;
-                            rs[j] = r;
-                        }
-                        out[t] = make_float4(rs[0], rs[1], rs[2], rs[3]);
+                        float4 y = v[t];
+                        y.x = __builtin_fmaf(d1, h1, __builtin_fmaf(d2, h2, v[t].x));
+                        y.y = __builtin_fmaf(d1, y.x, __builtin_fmaf(d2, h1, v[t].y));
+                        y.z = __builtin_fmaf(d1, y.y, __builtin_fmaf(d2, y.x, v[t].z));
+                        y.w = __builtin_fmaf(d1, y.z, __builtin_fmaf(d2, y.y, v[t].w));
+                        h2 = y.z;
+                        h1 = y.w;
+                        out[t] = y;
+                        if constexpr (decltype(spaced)::value)
+                            __builtin_amdgcn_sched_barrier(0);
                     }
+                };
+                if (a.out != nullptr)
+                    row(std::true_type{});
+                else
+                    row(std::false_type{});
+                h1 = cnt ? h1 : keep_h1;
+                h2 = cnt ? h2 : keep_h2;
+            } else {
+                // some stream ends inside this block: same arithmetic, but the history of a
+                // lane moves only on its real samples (what lies beyond is never stored)
+#pragma unroll
+                for (u32 t = 0; t < EP_TB / 4; t++) {
+                    const float xs[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
+                    float rs[4];
+#pragma unroll
+                    for (u32 j = 0; j < 4; j++) {
+                        const float r = __builtin_fmaf(d1, h1, __builtin_fmaf(d2, h2, xs[j]));
+                        const bool real = 4u * t + j < cnt;
+                        h2 = real ? h1 : h2;
+                        h1 = real ? r : h1;
+                        rs[j] = r;
+                    }
+                    out[t] = make_float4(rs[0], rs[1], rs[2], rs[3]);
                 }
             }
         }
     };
     auto tin_step = [&](Pcm &wcur, const u32 step) {
-        eq_pad<CMHIP_EQ_PAD_TIN>();
-        if (!(CMHIP_EQ_ABL & 128)) {
-#ifdef CMHIP_EQ_STAMPS
-            const u64 st_tt = __builtin_readcyclecounter();
-#endif
-            // --- input block `step`: PCM -> gain -> float -> feed-forward of section 0 -> F_0
-            // (also in the drain steps at the end, where it works on zeros: keeping the load
-            // unconditional is what lets the wait above be counted)
-            if (!(CMHIP_EQ_ABL & 64)) {
-                const u32 b = step;
-                const u32 f0 = b * EP_TB + l_t8;
-                const bool have = f0 < l_n;               // beyond the end of the stream: zeros
-                u32 w[4] = {wcur.a.x, wcur.a.y, wcur.a.z, wcur.a.w};
-                if constexpr (STEREO) {                   // this row's channel of the eight frames
-                    w[0] = __builtin_amdgcn_perm(wcur.a.y, wcur.a.x, l_sel);
-                    w[1] = __builtin_amdgcn_perm(wcur.a.w, wcur.a.z, l_sel);
-                    w[2] = __builtin_amdgcn_perm(wcur.b.y, wcur.b.x, l_sel);
-                    w[3] = __builtin_amdgcn_perm(wcur.b.w, wcur.b.z, l_sel);
-                }
-                if constexpr (STAGE_IN) {
-                    // the raw block into this wave's own LDS area, then this lane's eight samples out of it
-                    // (one wave: its LDS operations execute in the order issued, no barrier)
-                    unsigned char *rw = rawin + tw * EQ_RAWIN;
-                    if (lane < tv_n)
-                        *reinterpret_cast<u32x4 *>(rw + lane * 16u) = wcur.a;
-                    if (64u + lane < tv_n)
-                        *reinterpret_cast<u32x4 *>(rw + (64u + lane) * 16u) = wcur.b;
-                    if (128u + lane < tv_n)
-                        *reinterpret_cast<u32x4 *>(rw + (128u + lane) * 16u) = wcur.c;
-                    if (192u + lane < tv_n)
-                        *reinterpret_cast<u32x4 *>(rw + (192u + lane) * 16u) = wcur.d;
-                    const unsigned char *mine = rw + l_raw;
+        // --- input block `step`: PCM -> gain -> float -> feed-forward of section 0 -> F_0
+        // (also in the drain steps at the end, where it works on zeros: keeping the load
+        // unconditional is what lets the wait above be counted)
+        const u32 b = step;
+        const u32 f0 = b * EP_TB + l_t8;
+        const bool have = f0 < l_n;               // beyond the end of the stream: zeros
+        u32 w[4] = {wcur.a.x, wcur.a.y, wcur.a.z, wcur.a.w};
+        if constexpr (STEREO) {                   // this row's channel of the eight frames
+            w[0] = __builtin_amdgcn_perm(wcur.a.y, wcur.a.x, l_sel);
+            w[1] = __builtin_amdgcn_perm(wcur.a.w, wcur.a.z, l_sel);
+            w[2] = __builtin_amdgcn_perm(wcur.b.y, wcur.b.x, l_sel);
+            w[3] = __builtin_amdgcn_perm(wcur.b.w, wcur.b.z, l_sel);
+        }
+        if constexpr (STAGE_IN) {
+            // the raw block into this wave's own LDS area, then this lane's eight samples out of it
+            // (one wave: its LDS operations execute in the order issued, no barrier)
+            unsigned char *rw = rawin + tw * EQ_RAWIN;
+            if (lane < tv_n)
+                *reinterpret_cast<u32x4 *>(rw + lane * 16u) = wcur.a;
+            if (64u + lane < tv_n)
+                *reinterpret_cast<u32x4 *>(rw + (64u + lane) * 16u) = wcur.b;
+            if (128u + lane < tv_n)
+                *reinterpret_cast<u32x4 *>(rw + (128u + lane) * 16u) = wcur.c;
+            if (192u + lane < tv_n)
+                *reinterpret_cast<u32x4 *>(rw + (192u + lane) * 16u) = wcur.d;
+            const unsigned char *mine = rw + l_raw;
 #pragma unroll
-                    for (u32 q = 0; q < 4; q++) {
-                        const u32 lo = *reinterpret_cast<const uint16_t *>(mine + (2u * q) * 2u * C);
-                        const u32 hi = *reinterpret_cast<const uint16_t *>(mine + (2u * q + 1u) * 2u * C);
-                        w[q] = lo | (hi << 16);
-                    }
-                }
-                // (These selects are not needed for the results -- nothing beyond a stream's end is ever
-                // stored -- and the next block's load could be issued before the wait for this one's data or
-                // after the stores below.  Measured, A/B in one process, round 2: without the selects the
-                // compiler issues the load first and the launch takes 6-9 % longer; with the load after the
-                // stores 2-5 % longer.  They stay where round 1 left them.)
-#pragma unroll
-                for (u32 q = 0; q < 4; q++)
-                    w[q] = have ? w[q] : 0u;              // (a chunk the stream ends in keeps what
-                wcur = fetch(b + 2);                      // follows in the row: never stored)
-#ifdef CMHIP_EQ_STAMPS
-                u32 stw = w[0];
-                asm volatile("" : "+v"(stw));
-                st_p[0] += __builtin_readcyclecounter() - st_tt;          // PCM of this block has arrived
-#endif
-                // gain in integers (exact), then straight to float: the magnitude is converted,
-                // the sign bit of the sample is copied in, and one med3 is the int16 saturation
-                float x[8], f[8];
-                if (gain_off) {                           // no master gain on any row of this wave
-#pragma unroll
-                    for (u32 q = 0; q < 4; q++) {
-                        x[2 * q] = (float)(int)(int16_t)(w[q] & 0xffffu);
-                        x[2 * q + 1] = (float)((int)w[q] >> 16);
-                    }
-                } else {
-#pragma unroll
-                    for (u32 q = 0; q < 4; q++) {
-                        const u32 sg = pk_sign(w[q]);
-                        const u32 aw = pk_sub(w[q] ^ sg, sg);
-                        const u32 x0 = aw & 0xffffu, x1 = aw >> 16;
-                        const float m0 = (float)(__umul24(x0, l_mi) + __umulhi(x0, l_mf));
-                        const float m1 = (float)(__umul24(x1, l_mi) + __umulhi(x1, l_mf));
-                        const u32 b0 = (__builtin_bit_cast(u32, m0) & 0x7fffffffu) | ((w[q] << 16) & 0x80000000u);
-                        const u32 b1 = (__builtin_bit_cast(u32, m1) & 0x7fffffffu) | (w[q] & 0x80000000u);
-                        x[2 * q] = __builtin_amdgcn_fmed3f(__builtin_bit_cast(float, b0), -32768.0f, 32767.0f);
-                        x[2 * q + 1] = __builtin_amdgcn_fmed3f(__builtin_bit_cast(float, b1), -32768.0f, 32767.0f);
-                    }
-                }
-                // (Stereo and many-channel rows watch for the end of their stream inside the loop, as in round
-                // 1: the last real samples pass through exactly one lane each.  The mono form fetches them
-                // before the loop -- the same loop without this block ran 1.7 % faster on mono rows and
-                // 4.7 % slower on stereo ones, A/B in one process.)
-                if constexpr (!MONO) {
-                    const u32 bf = b * EP_TB;
-                    if (l_live && l_n > bf && l_n <= bf + EP_TB) {
-                        const u32 e1 = l_n - 1u - bf;                     // last sample, block relative
-                        if ((e1 >> 3) == l_c) {
-                            float val = x[0];
-#pragma unroll
-                            for (u32 j = 1; j < 8; j++)
-                                val = (e1 & 7u) == j ? x[j] : val;
-                            keep1 = val * (1.0f / 32768.0f);
-                            keep_n |= 1u;
-                        }
-                        if (e1 >= 1u) {
-                            const u32 e2 = e1 - 1u;
-                            if ((e2 >> 3) == l_c) {
-                                float val = x[0];
-#pragma unroll
-                                for (u32 j = 1; j < 8; j++)
-                                    val = (e2 & 7u) == j ? x[j] : val;
-                                keep2 = val * (1.0f / 32768.0f);
-                                keep_n |= 2u;
-                            }
-                        } else if (l_c == 7u) {
-                            keep2 = sx1[0][0] * (1.0f / 32768.0f);        // the sample before this block
-                            keep_n |= 2u;
-                        }
-                    }
-                }
-#ifdef CMHIP_EQ_STAMPS
-                asm volatile("" : "+v"(x[7]));
-                st_p[1] += __builtin_readcyclecounter() - st_tt;          // converted
-#endif
-                feed_forward(0, 0, x, f);
-                float4 *dst = reinterpret_cast<float4 *>(lds + (b & 1u) * EP_TILE + l_r * EP_ROW + l_t8);
-                dst[0] = make_float4(f[0], f[1], f[2], f[3]);
-                dst[1] = make_float4(f[4], f[5], f[6], f[7]);
-#ifdef CMHIP_EQ_STAMPS
-                asm volatile("" ::: "memory");
-                st_p[2] += __builtin_readcyclecounter() - st_tt;          // F_0 handed to the LDS queue
-#endif
+            for (u32 q = 0; q < 4; q++) {
+                const u32 lo = *reinterpret_cast<const uint16_t *>(mine + (2u * q) * 2u * C);
+                const u32 hi = *reinterpret_cast<const uint16_t *>(mine + (2u * q + 1u) * 2u * C);
+                w[q] = lo | (hi << 16);
             }
         }
+        // (These selects are not needed for the results -- nothing beyond a stream's end is ever
+        // stored -- and the next block's load could be issued before the wait for this one's data or
+        // after the stores below.  Measured, A/B in one process, round 2: without the selects the
+        // compiler issues the load first and the launch takes 6-9 % longer; with the load after the
+        // stores 2-5 % longer.  They stay where round 1 left them.)
+#pragma unroll
+        for (u32 q = 0; q < 4; q++)
+            w[q] = have ? w[q] : 0u;              // (a chunk the stream ends in keeps what
+        wcur = fetch(b + 2);                      // follows in the row: never stored)
+        // gain in integers (exact), then straight to float: the magnitude is converted,
+        // the sign bit of the sample is copied in, and one med3 is the int16 saturation
+        float x[8], f[8];
+        if (gain_off) {                           // no master gain on any row of this wave
+#pragma unroll
+            for (u32 q = 0; q < 4; q++) {
+                x[2 * q] = (float)(int)(int16_t)(w[q] & 0xffffu);
+                x[2 * q + 1] = (float)((int)w[q] >> 16);
+            }
+        } else {
+#pragma unroll
+            for (u32 q = 0; q < 4; q++) {
+                const u32 sg = pk_sign(w[q]);
+                const u32 aw = pk_sub(w[q] ^ sg, sg);
+                const u32 x0 = aw & 0xffffu, x1 = aw >> 16;
+                const float m0 = (float)(__umul24(x0, l_mi) + __umulhi(x0, l_mf));
+                const float m1 = (float)(__umul24(x1, l_mi) + __umulhi(x1, l_mf));
+                const u32 b0 = (__builtin_bit_cast(u32, m0) & 0x7fffffffu) | ((w[q] << 16) & 0x80000000u);
+                const u32 b1 = (__builtin_bit_cast(u32, m1) & 0x7fffffffu) | (w[q] & 0x80000000u);
+                x[2 * q] = __builtin_amdgcn_fmed3f(__builtin_bit_cast(float, b0), -32768.0f, 32767.0f);
+                x[2 * q + 1] = __builtin_amdgcn_fmed3f(__builtin_bit_cast(float, b1), -32768.0f, 32767.0f);
+            }
+        }
+        // (Stereo and many-channel rows watch for the end of their stream inside the loop, as in round
+        // 1: the last real samples pass through exactly one lane each.  The mono form fetches them
+        // before the loop -- the same loop without this block ran 1.7 % faster on mono rows and
+        // 4.7 % slower on stereo ones, A/B in one process.)
+        if constexpr (!MONO) {
+            const u32 bf = b * EP_TB;
+            if (l_live && l_n > bf && l_n <= bf + EP_TB) {
+                const u32 e1 = l_n - 1u - bf;                     // last sample, block relative
+                if ((e1 >> 3) == l_c) {
+                    float val = x[0];
+#pragma unroll
+                    for (u32 j = 1; j < 8; j++)
+                        val = (e1 & 7u) == j ? x[j] : val;
+                    keep1 = val * (1.0f / 32768.0f);
+                    keep_n |= 1u;
+                }
+                if (e1 >= 1u) {
+                    const u32 e2 = e1 - 1u;
+                    if ((e2 >> 3) == l_c) {
+                        float val = x[0];
+#pragma unroll
+                        for (u32 j = 1; j < 8; j++)
+                            val = (e2 & 7u) == j ? x[j] : val;
+                        keep2 = val * (1.0f / 32768.0f);
+                        keep_n |= 2u;
+                    }
+                } else if (l_c == 7u) {
+                    keep2 = sx1[0][0] * (1.0f / 32768.0f);        // the sample before this block
+                    keep_n |= 2u;
+                }
+            }
+        }
+        feed_forward(0, 0, x, f);
+        float4 *dst = reinterpret_cast<float4 *>(lds + (b & 1u) * EP_TILE + l_r * EP_ROW + l_t8);
+        dst[0] = make_float4(f[0], f[1], f[2], f[3]);
+        dst[1] = make_float4(f[4], f[5], f[6], f[7]);
     };
     // T-ff waves: feed-forward of the later sections, Y_k-1 -> F_k, for G / 2 rows in PASSES of
     // eight (each with the history registers of its own rows)
     auto tff_step = [&](const u32 step) {
-        eq_pad<CMHIP_EQ_PAD_TFF>();
-        if (!(CMHIP_EQ_ABL & (128 | 16))) {
-            // reads of every pass first, then arithmetic: one LDS latency per step
-            constexpr u32 PG = PASSES;
+        // reads of every pass first, then arithmetic: one LDS latency per step
+        constexpr u32 PG = PASSES;
 #pragma unroll
-            for (u32 p0 = 0; p0 < PASSES; p0 += PG) {
-                float4 yin[PG][NSEC][2];
+        for (u32 p0 = 0; p0 < PASSES; p0 += PG) {
+            float4 yin[PG][NSEC][2];
 #pragma unroll
-                for (int k = 1; k < NSEC; k++) {
-                    const u32 b = step - HOP * (u32)k;
-                    if (step >= HOP * (u32)k && b < nblocks) {
+            for (int k = 1; k < NSEC; k++) {
+                const u32 b = step - HOP * (u32)k;
+                if (step >= HOP * (u32)k && b < nblocks) {
 #pragma unroll
-                        for (u32 p = 0; p < PG; p++) {
-                            const float4 *src = reinterpret_cast<const float4 *>(
-                                lds + ((2u * k - 1u) * 2u + (b & 1u)) * EP_TILE + f_r[p0 + p] * EP_ROW + l_t8);
-                            yin[p][k][0] = src[0];
-                            yin[p][k][1] = src[1];
-                        }
+                    for (u32 p = 0; p < PG; p++) {
+                        const float4 *src = reinterpret_cast<const float4 *>(
+                            lds + ((2u * k - 1u) * 2u + (b & 1u)) * EP_TILE + f_r[p0 + p] * EP_ROW + l_t8);
+                        yin[p][k][0] = src[0];
+                        yin[p][k][1] = src[1];
                     }
                 }
+            }
 #pragma unroll
-                for (int k = 1; k < NSEC; k++) {
-                    const u32 b = step - HOP * (u32)k;
-                    if (step >= HOP * (u32)k && b < nblocks) {
+            for (int k = 1; k < NSEC; k++) {
+                const u32 b = step - HOP * (u32)k;
+                if (step >= HOP * (u32)k && b < nblocks) {
 #pragma unroll
-                        for (u32 p = 0; p < PG; p++) {
-                            const float4 v0 = yin[p][k][0], v1 = yin[p][k][1];
-                            const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                            float f[8];
-                            feed_forward(p0 + p, k, x, f);
-                            float4 *dst = reinterpret_cast<float4 *>(
-                                lds + ((2u * k) * 2u + (b & 1u)) * EP_TILE + f_r[p0 + p] * EP_ROW + l_t8);
-                            dst[0] = make_float4(f[0], f[1], f[2], f[3]);
-                            dst[1] = make_float4(f[4], f[5], f[6], f[7]);
-                        }
+                    for (u32 p = 0; p < PG; p++) {
+                        const float4 v0 = yin[p][k][0], v1 = yin[p][k][1];
+                        const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                        float f[8];
+                        feed_forward(p0 + p, k, x, f);
+                        float4 *dst = reinterpret_cast<float4 *>(
+                            lds + ((2u * k) * 2u + (b & 1u)) * EP_TILE + f_r[p0 + p] * EP_ROW + l_t8);
+                        dst[0] = make_float4(f[0], f[1], f[2], f[3]);
+                        dst[1] = make_float4(f[4], f[5], f[6], f[7]);
                     }
                 }
             }
@@ -720,8 +634,7 @@ void k_eq_pipe(EqArgs a)
         }
     }
     auto s_step = [&](const u32 step) {
-        eq_pad<CMHIP_EQ_PAD_S>();
-        if (stage_out && !(CMHIP_EQ_ABL & 2048)) {                       // (2048: timing only, nothing copied out)
+        if (stage_out) {
             // the block the S waves staged in the step before leaves in whole vectors (the barrier between the two
             // steps has made every wave's samples visible; the other slot takes this step's block meanwhile)
             const u32 bo = step - (HOP * NSEC + 1u);
@@ -740,204 +653,180 @@ void k_eq_pipe(EqArgs a)
             }
         }
 
-        if (!(CMHIP_EQ_ABL & 1)) {
-            // --- the finished block of the last section leaves: 256 B (float) / 128 B (int16)
-            // per stream row and instruction, fire and forget (this wave never waits for
-            // global memory); the int16 form is what the VU meter sees
-            const u32 b = step - HOP * NSEC;
-            if (step >= HOP * NSEC && b < nblocks) {
-                const float *Y = lds + ((2u * NSEC - 1u) * 2u + (b & 1u)) * EP_TILE;
-                const u32 t4 = (lane % SPR) * 4u;
-                const u32 f0 = b * EP_TB + t4;
-                float4 vin[NSL];                              // every LDS read of the step up front:
-                u32 nin[NSL];                                 // one latency, not one per row slot
+        // --- the finished block of the last section leaves: 256 B (float) / 128 B (int16)
+        // per stream row and instruction, fire and forget (this wave never waits for
+        // global memory); the int16 form is what the VU meter sees
+        const u32 b = step - HOP * NSEC;
+        if (step >= HOP * NSEC && b < nblocks) {
+            const float *Y = lds + ((2u * NSEC - 1u) * 2u + (b & 1u)) * EP_TILE;
+            const u32 t4 = (lane % SPR) * 4u;
+            const u32 f0 = b * EP_TB + t4;
+            float4 vin[NSL];                              // every LDS read of the step up front:
+            u32 nin[NSL];                                 // one latency, not one per row slot
 #pragma unroll
-                for (u32 i = 0; i < NSL; i++) {
-                    const u32 r = min(s_row(i), (u32)G - 1u);   // (slots past s_cnt are skipped below)
-                    nin[i] = nfr_at(r);
-                    vin[i] = *reinterpret_cast<const float4 *>(Y + r * EP_ROW + t4);
+            for (u32 i = 0; i < NSL; i++) {
+                const u32 r = min(s_row(i), (u32)G - 1u);   // (slots past s_cnt are skipped below)
+                nin[i] = nfr_at(r);
+                vin[i] = *reinterpret_cast<const float4 *>(Y + r * EP_ROW + t4);
+            }
+#pragma unroll
+            for (u32 i = 0; i < NSL; i++) {
+                const u32 n = nin[i];
+                const float4 v = vin[i];
+                const float e[4] = {v.x, v.y, v.z, v.w};
+                const u32 vs_ = v_stream[i], vc_ = v_ch[i];
+                if (vs_ == 0xffffffffu)
+                    continue;
+                if (a.f32) {
+                    float *dstf = a.f32 + ((u64)vs_ * C + vc_) * a.plane + f0;
+                    if (f0 + 4u <= n) {
+                        typedef float f32x4 __attribute__((ext_vector_type(4)));
+                        const f32x4 vv = {v.x, v.y, v.z, v.w};
+                        __builtin_nontemporal_store(vv, reinterpret_cast<f32x4 *>(dstf));
+                    } else if (f0 < n) {
+                        for (u32 j = 0; j < n - f0; j++)
+                            dstf[j] = e[j];
+                    }
                 }
+                if (a.out || a.vu) {
+                    // float -> int16 as oracle_f32_to_i16: y * 32768, round to nearest even, then the
+                    // hardware's saturating conversions do the rest (v_cvt_i32_f32: NaN -> 0, out of
+                    // range -> INT_MIN / INT_MAX; the packing below saturates to int16)
+                    int q[4];
 #pragma unroll
-                for (u32 i = 0; i < NSL; i++) {
-                    const u32 n = nin[i];
-                    const float4 v = vin[i];
-                    const float e[4] = {v.x, v.y, v.z, v.w};
-                    const u32 vs_ = v_stream[i], vc_ = v_ch[i];
-                    if (vs_ == 0xffffffffu)
-                        continue;
-                    if (a.f32) {
-                        float *dstf = a.f32 + ((u64)vs_ * C + vc_) * a.plane + f0;
-                        if (f0 + 4u <= n) {
-                            typedef float f32x4 __attribute__((ext_vector_type(4)));
-                            const f32x4 vv = {v.x, v.y, v.z, v.w};
-                            __builtin_nontemporal_store(vv, reinterpret_cast<f32x4 *>(dstf));
-                        } else if (f0 < n) {
-                            for (u32 j = 0; j < n - f0; j++)
-                                dstf[j] = e[j];
+                    for (u32 j = 0; j < 4; j++) {
+                        const float r = __builtin_rintf(e[j] * 32768.0f);
+                        asm("v_cvt_i32_f32 %0, %1" : "=v"(q[j]) : "v"(r));
+                    }
+                    // (v_cvt_pk_i16_i32 saturates: the clamp and the packing of a sample pair in one)
+                    const u32 p01 = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
+                    const u32 p23 = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
+                    const bool whole = __all(f0 + 4u <= n);     // no stream ends inside these
+                    if (a.out) {
+                        if constexpr (MONO) {
+                            int16_t *d16 = a.out + (u64)vs_ * a.stride + f0;
+                            if (f0 + 4u <= n) {
+                                typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                                const u32x2 pk = {p01, p23};
+                                __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(d16));
+                            } else if (f0 < n) {
+                                for (u32 j = 0; j < n - f0; j++)
+                                    d16[j] = (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
+                            }
+                        } else if constexpr (STEREO) {
+                            // The two rows of a stream are 32 lanes apart (s_row): swap halves with the
+                            // partner (v_permlane32_swap) so that the left row's lanes hold
+                            // frames f0, f0+1 of both channels and the right row's lanes frames
+                            // f0+2, f0+3 -- whole interleaved frames, 8 bytes per lane.
+                            typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                            const u32x2 sw2 = __builtin_amdgcn_permlane32_swap(p01, p23, false, false);
+                            const u32 left = sw2.x, right = sw2.y;   // this frame pair: channel 0, channel 1
+                            const u32 d0 = __builtin_amdgcn_perm(right, left, 0x05040100u);
+                            const u32 d1 = __builtin_amdgcn_perm(right, left, 0x07060302u);
+                            const u32 ff = f0 + 2u * vc_;            // first of this lane's two frames
+                            u32 *d32 = reinterpret_cast<u32 *>(a.out + (u64)vs_ * a.stride) + ff;
+                            if (ff + 2u <= n) {
+                                const u32x2 pk = {d0, d1};
+                                __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(d32));
+                            } else if (ff < n) {
+                                d32[0] = d0;
+                            }
+                        } else if ((C & 1u) == 0u) {
+                            // An even channel count: the rows of a slot's lanes L and L + 32 are channels 2k and
+                            // 2k + 1 of one stream (s_row; rows are dealt out from even numbers), so the two swap
+                            // halves as the stereo form does -- L keeps frames f0, f0 + 1 of both channels, L + 32
+                            // frames f0 + 2, f0 + 3 -- and every sample pair is one aligned dword of a frame:
+                            // two 4-byte stores per lane instead of four 2-byte ones, staged or not.
+                            typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+                            const u32x2 sw2 = __builtin_amdgcn_permlane32_swap(p01, p23, false, false);
+                            const u32 d0 = __builtin_amdgcn_perm(sw2.y, sw2.x, 0x05040100u);
+                            const u32 d1 = __builtin_amdgcn_perm(sw2.y, sw2.x, 0x07060302u);
+                            const u32 hi = lane >> 5;                 // this lane's row is the odd channel of the pair
+                            if (so_base[i] != 0xffffffffu) {
+                                unsigned char *st32 = outstage + (b & 1u) * EQ_STAGE_OUT + so_base[i] - 2u * hi + hi * 4u * C;
+                                *reinterpret_cast<u32 *>(st32) = d0;
+                                *reinterpret_cast<u32 *>(st32 + 2u * C) = d1;
+                            } else {
+                                const u32 ff = f0 + 2u * hi;
+                                int16_t *d16 = a.out + (u64)vs_ * a.stride + (u64)ff * C + (vc_ - hi);
+                                if (ff < n)
+                                    *reinterpret_cast<u32 *>(d16) = d0;
+                                if (ff + 1u < n)
+                                    *reinterpret_cast<u32 *>(d16 + C) = d1;
+                            }
+                        } else if (so_base[i] != 0xffffffffu) {       // interleaved result: into the staged block
+                            unsigned char *st16 = outstage + (b & 1u) * EQ_STAGE_OUT + so_base[i];
+#pragma unroll
+                            for (u32 j = 0; j < 4; j++)
+                                *reinterpret_cast<int16_t *>(st16 + j * 2u * C) =
+                                    (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
+                        } else {                      // ... or, a stream shared with a neighbour, this row's channel
+                            int16_t *d16 = a.out + (u64)vs_ * a.stride + (u64)f0 * C + vc_;
+#pragma unroll
+                            for (u32 j = 0; j < 4; j++)
+                                if (f0 + j < n)
+                                    d16[j * C] = (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
                         }
                     }
-                    if (a.out || a.vu) {
-                        // float -> int16 as oracle_f32_to_i16: y * 32768, round to nearest even, then the
-                        // hardware's saturating conversions do the rest (v_cvt_i32_f32: NaN -> 0, out of
-                        // range -> INT_MIN / INT_MAX; the packing below saturates to int16)
-                        int q[4];
-#pragma unroll
-                        for (u32 j = 0; j < 4; j++) {
-                            const float r = __builtin_rintf(e[j] * 32768.0f);
-                            asm("v_cvt_i32_f32 %0, %1" : "=v"(q[j]) : "v"(r));
+                    if (a.vu) {
+                        // The window of the int16 result on packed pairs (as the block kernels do): the
+                        // magnitudes of four samples in six instructions, their squares in one chain of
+                        // three v_mad_u32_u16 and a fourth, and one comparison of the four's maximum
+                        // with the lane's running peak -- a lane whose peak improves keeps the four
+                        // results and their first frame; which of them came first, and its sign, is
+                        // looked up once, after the loop.  (The samples come in time order, so "strictly
+                        // greater" keeps the first of equals.)
+                        u32 v01 = p01, v23 = p23;     // the results that count: all four, unless a stream ends here
+                        if (!whole) {                 // (uniform branch; what lies beyond a stream's end counts nothing)
+                            v01 &= (f0 + 0u < n ? 0xffffu : 0u) | (f0 + 1u < n ? 0xffff0000u : 0u);
+                            v23 &= (f0 + 2u < n ? 0xffffu : 0u) | (f0 + 3u < n ? 0xffff0000u : 0u);
                         }
-                        // (v_cvt_pk_i16_i32 saturates: the clamp and the packing of a sample pair in one)
-                        const u32 p01 = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
-                        const u32 p23 = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
-                        const bool whole = __all(f0 + 4u <= n);     // no stream ends inside these
-                        if (a.out) {
-                            if constexpr (MONO) {
-                                int16_t *d16 = a.out + (u64)vs_ * a.stride + f0;
-                                if (f0 + 4u <= n) {
-                                    typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-                                    const u32x2 pk = {p01, p23};
-                                    __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(d16));
-                                } else if (f0 < n) {
-                                    for (u32 j = 0; j < n - f0; j++)
-                                        d16[j] = (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
-                                }
-                            } else if constexpr (STEREO) {
-                                // The two rows of a stream are 32 lanes apart (s_row): swap halves with the
-                                // partner (v_permlane32_swap) so that the left row's lanes hold
-                                // frames f0, f0+1 of both channels and the right row's lanes frames
-                                // f0+2, f0+3 -- whole interleaved frames, 8 bytes per lane.
-                                typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-                                const u32x2 sw2 = __builtin_amdgcn_permlane32_swap(p01, p23, false, false);
-                                const u32 left = sw2.x, right = sw2.y;   // this frame pair: channel 0, channel 1
-                                const u32 d0 = __builtin_amdgcn_perm(right, left, 0x05040100u);
-                                const u32 d1 = __builtin_amdgcn_perm(right, left, 0x07060302u);
-                                const u32 ff = f0 + 2u * vc_;            // first of this lane's two frames
-                                u32 *d32 = reinterpret_cast<u32 *>(a.out + (u64)vs_ * a.stride) + ff;
-                                if (ff + 2u <= n) {
-                                    const u32x2 pk = {d0, d1};
-                                    __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(d32));
-                                } else if (ff < n) {
-                                    d32[0] = d0;
-                                }
-                            } else if ((C & 1u) == 0u) {
-                                // An even channel count: the rows of a slot's lanes L and L + 32 are channels 2k and
-                                // 2k + 1 of one stream (s_row; rows are dealt out from even numbers), so the two swap
-                                // halves as the stereo form does -- L keeps frames f0, f0 + 1 of both channels, L + 32
-                                // frames f0 + 2, f0 + 3 -- and every sample pair is one aligned dword of a frame:
-                                // two 4-byte stores per lane instead of four 2-byte ones, staged or not.
-                                typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-                                const u32x2 sw2 = __builtin_amdgcn_permlane32_swap(p01, p23, false, false);
-                                const u32 d0 = __builtin_amdgcn_perm(sw2.y, sw2.x, 0x05040100u);
-                                const u32 d1 = __builtin_amdgcn_perm(sw2.y, sw2.x, 0x07060302u);
-                                const u32 hi = lane >> 5;                 // this lane's row is the odd channel of the pair
-                                if (CMHIP_EQ_ABL & 1024) {                 // (1024: timing only, the result goes nowhere)
-                                } else if (so_base[i] != 0xffffffffu) {
-                                    unsigned char *st32 = outstage + (b & 1u) * EQ_STAGE_OUT + so_base[i] - 2u * hi + hi * 4u * C;
-                                    *reinterpret_cast<u32 *>(st32) = d0;
-                                    *reinterpret_cast<u32 *>(st32 + 2u * C) = d1;
-                                } else {
-                                    const u32 ff = f0 + 2u * hi;
-                                    int16_t *d16 = a.out + (u64)vs_ * a.stride + (u64)ff * C + (vc_ - hi);
-                                    if (ff < n)
-                                        *reinterpret_cast<u32 *>(d16) = d0;
-                                    if (ff + 1u < n)
-                                        *reinterpret_cast<u32 *>(d16 + C) = d1;
-                                }
-                            } else if (so_base[i] != 0xffffffffu) {       // interleaved result: into the staged block
-                                unsigned char *st16 = outstage + (b & 1u) * EQ_STAGE_OUT + so_base[i];
-#pragma unroll
-                                for (u32 j = 0; j < 4; j++)
-                                    *reinterpret_cast<int16_t *>(st16 + j * 2u * C) =
-                                        (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
-                            } else {                      // ... or, a stream shared with a neighbour, this row's channel
-                                int16_t *d16 = a.out + (u64)vs_ * a.stride + (u64)f0 * C + vc_;
-#pragma unroll
-                                for (u32 j = 0; j < 4; j++)
-                                    if (f0 + j < n)
-                                        d16[j * C] = (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
-                            }
-                        }
-                        if (a.vu && !(CMHIP_EQ_ABL & 512)) {            // (512: timing only, no window)
-                            // The window of the int16 result on packed pairs (as the block kernels do): the
-                            // magnitudes of four samples in six instructions, their squares in one chain of
-                            // three v_mad_u32_u16 and a fourth, and one comparison of the four's maximum
-                            // with the lane's running peak -- a lane whose peak improves keeps the four
-                            // results and their first frame; which of them came first, and its sign, is
-                            // looked up once, after the loop.  (The samples come in time order, so "strictly
-                            // greater" keeps the first of equals.)
-                            u32 v01 = p01, v23 = p23;     // the results that count: all four, unless a stream ends here
-                            if (!whole) {                 // (uniform branch; what lies beyond a stream's end counts nothing)
-                                v01 &= (f0 + 0u < n ? 0xffffu : 0u) | (f0 + 1u < n ? 0xffff0000u : 0u);
-                                v23 &= (f0 + 2u < n ? 0xffffu : 0u) | (f0 + 3u < n ? 0xffff0000u : 0u);
-                            }
-                            const u32 s01 = pk_sign(v01), s23 = pk_sign(v23);
-                            const u32 m01 = pk_sub(v01 ^ s01, s01), m23 = pk_sub(v23 ^ s23, s23);
-                            vpw[i] += sq_lo(m23, sq_hi(m01, sq_lo0(m01)));
-                            vpw[i] += sq_hi0(m23);
-                            const u32 mm = pk_max(m01, m23);
-                            const u32 m4 = max(mm & 0xffffu, mm >> 16);
-                            const bool gt = m4 > vmag[i];
-                            vmag[i] = gt ? m4 : vmag[i];
-                            vq01[i] = gt ? v01 : vq01[i];
-                            vq23[i] = gt ? v23 : vq23[i];
-                            vfr[i] = gt ? f0 : vfr[i];
-                        }
+                        const u32 s01 = pk_sign(v01), s23 = pk_sign(v23);
+                        const u32 m01 = pk_sub(v01 ^ s01, s01), m23 = pk_sub(v23 ^ s23, s23);
+                        vpw[i] += sq_lo(m23, sq_hi(m01, sq_lo0(m01)));
+                        vpw[i] += sq_hi0(m23);
+                        const u32 mm = pk_max(m01, m23);
+                        const u32 m4 = max(mm & 0xffffu, mm >> 16);
+                        const bool gt = m4 > vmag[i];
+                        vmag[i] = gt ? m4 : vmag[i];
+                        vq01[i] = gt ? v01 : vq01[i];
+                        vq23[i] = gt ? v23 : vq23[i];
+                        vfr[i] = gt ? f0 : vfr[i];
                     }
                 }
             }
         }
     };
-#ifdef CMHIP_EQ_STAMPS
-#define EQ_STEP(call)                                                   \
-    do {                                                                \
-        const u64 st_t0 = __builtin_readcyclecounter();                 \
-        call;                                                           \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              \
-        const u64 st_t1 = __builtin_readcyclecounter();                 \
-        st_busy += st_t1 - st_t0;                                       \
-        if (lane == 0)                                                  \
-            st_lds.arr[st_n & 1u][wave] = (u32)st_t1;                   \
-        __syncthreads();                                                \
-        if (threadIdx.x == 0 && (st_n & 15u) == 0) {                    \
-            const u32 nw_ = blockDim.x >> 6, ref_ = st_lds.arr[st_n & 1u][0]; \
-            int lo_ = 0, hi_ = 0;                                       \
-            u32 who_ = 0;                                               \
-            for (u32 w_ = 1; w_ < nw_; w_++) {                          \
-                const int d_ = (int)(st_lds.arr[st_n & 1u][w_] - ref_); \
-                if (d_ > hi_) { hi_ = d_; who_ = w_; }                  \
-                if (d_ < lo_) lo_ = d_;                                 \
-            }                                                           \
-            st_lds.last[who_]++;                                        \
-            st_lds.skew += (unsigned long long)(hi_ - lo_);             \
-        }                                                               \
-        st_n++;                                                         \
-    } while (0)
-#else
-#define EQ_STEP(call) do { call; __syncthreads(); } while (0)
-#endif
     // One loop per role (the role never changes, and a loop of its own lets the compiler
     // count a T wave's outstanding loads); every wave passes the same number of barriers.
     const u32 nst2 = (nsteps + 1u) & ~1u;                 // an odd tail step finds nothing to do
     if (is_rec) {
-        for (u32 step = 0; step < nst2; step++)
-            EQ_STEP(rec_step(step));
+        for (u32 step = 0; step < nst2; step++) {
+            rec_step(step);
+            __syncthreads();
+        }
     } else if (is_store) {
-        for (u32 step = 0; step < nst2; step++)
-            EQ_STEP(s_step(step));
+        for (u32 step = 0; step < nst2; step++) {
+            s_step(step);
+            __syncthreads();
+        }
     } else if (is_tff) {
-        for (u32 step = 0; step < nst2; step++)
-            EQ_STEP(tff_step(step));
+        for (u32 step = 0; step < nst2; step++) {
+            tff_step(step);
+            __syncthreads();
+        }
     } else {
         for (u32 step = 0; step < nst2; step += 2) {
-            EQ_STEP(tin_step(wa, step));
-            EQ_STEP(tin_step(wb, step + 1));
+            tin_step(wa, step);
+            __syncthreads();
+            tin_step(wb, step + 1);
+            __syncthreads();
         }
         if (keep_n & 1u)
             a.state[l_sidx].s[0][0] = keep1;
         if (keep_n & 2u)
             a.state[l_sidx].s[0][1] = keep2;
     }
-#undef EQ_STEP
 
     // VU windows of the int16 result: every wave that did store work holds parts of them
     if (is_store && a.vu) {
@@ -975,25 +864,6 @@ void k_eq_pipe(EqArgs a)
             }
         }
     }
-#ifdef CMHIP_EQ_STAMPS
-    if (blockIdx.x == 7 && lane == 0 && a.dbg) {     // per-role busy cycles (tools/eq_stamps.py)
-        a.dbg[2 * wave] = st_busy;
-        a.dbg[2 * wave + 1] = __builtin_readcyclecounter() - st_begin;
-        a.dbg[36 + wave] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_ID
-        a.dbg[48] = nsteps;
-        if (is_tin && tw < 2) {                       // two T-in waves: phases inside a step
-            for (int i = 0; i < 3; i++)
-                a.dbg[50 + 3 * tw + i] = st_p[i];
-        }
-        a.dbg[24 + wave] = role;
-    }
-    __syncthreads();
-    if (blockIdx.x == 7 && threadIdx.x == 0 && a.dbg) {
-        for (u32 w_ = 0; w_ < 12; w_ += 2)
-            a.dbg[56 + w_ / 2] = (u64)st_lds.last[w_] | ((u64)st_lds.last[w_ + 1] << 32);
-        a.dbg[62] = st_lds.skew;
-    }
-#endif
 
     // state for the next launch.  y1/y2 of section k are also the x1/x2 of section k+1
     // (its input is this section's output); section 0's x1/x2 were written by the T lanes.
@@ -1058,13 +928,7 @@ static hipError_t launch_eq_pipe_g(const EqArgs &a, hipStream_t st, hipEvent_t e
 template <int NSEC>
 static hipError_t raise_lds_limit()
 {
-    // (a -DCMHIP_EQ_STAMPS build keeps 256 bytes of static LDS for its stamps: the one variant that fills the
-    // whole 160 KiB, four sections on many channels, cannot be launched in that diagnostic build)
-#ifdef CMHIP_EQ_STAMPS
-    constexpr size_t cap = 160 * 1024 - 256;
-#else
     constexpr size_t cap = 160 * 1024;
-#endif
     auto bytes = [](size_t want) { return (int)(want < cap ? want : cap); };
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_eq_pipe<NSEC, 32, 1>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, bytes(eq_pipe_lds_bytes<NSEC, 32, 1>()));

@@ -136,7 +136,6 @@ struct cmhip_node {
     // the whole set at once, when the first block after an exchange arrives; `filled` marks the
     // slots written since.
     std::vector<bool> filled[NODE_SETS];
-    bool side;                             // records are built beside the batch's next run (its copy stream)
 };
 
 static long long *set_sums(const cmhip_node_t *n, unsigned set)
@@ -190,8 +189,7 @@ static int node_init(cmhip_node_t *n, const Rccl *rc, const void *id128)
     {
         int least = 0, greatest = 0;             // (beside the batches' long kernels: see their copy streams)
         HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&n->stream, hipStreamNonBlocking,
-                                            getenv("CMHIP_SIDE_PRIORITY_OFF") ? least : greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&n->stream, hipStreamNonBlocking, greatest));
     }
     const size_t bytes = (size_t)NODE_SETS * 2u * HALF * n->max_records * sizeof(long long);
     HIP_TRY(hipMalloc((void **)&n->d_words, bytes));
@@ -236,7 +234,6 @@ extern "C" cmhip_node_t *cmhip_node_new(int device, int nranks, int rank, const 
         n->exchanged[i] = false;
         n->filled[i].assign(max_records, false);       // (the buffer starts zeroed)
     }
-    n->side = getenv("CMHIP_NODE_MAIN_STREAM") == nullptr;       // (A/B knob, read once)
     n->device = device;
     n->nranks = nranks;
     n->rank = rank;
@@ -269,7 +266,7 @@ extern "C" int cmhip_node_partial(cmhip_node_t *n, cmhip_batch_t *b, unsigned in
     if (cmhip_batch_device(b) != n->device || !(cmhip_batch_flags(b) & CMHIP_VU))
         return fail(COOLMIC_ERROR_INVAL, "node_partial: the batch must have VU windows on device %d", n->device);
     HIP_TRY(hipSetDevice(n->device));
-    hipStream_t bs = (hipStream_t)(n->side ? cmhip_batch_side_stream(b) : cmhip_batch_hip_stream(b));
+    hipStream_t bs = (hipStream_t)cmhip_batch_side_stream(b);  // records are built beside the batch's next run
     if (n->exchanged[set]) {               // the set's last exchange must be through before it is refilled
         if (hipEventQuery(n->ev_done[set]) != hipSuccess)
             HIP_TRY(hipStreamWaitEvent(bs, n->ev_done[set], 0));
@@ -281,9 +278,6 @@ extern "C" int cmhip_node_partial(cmhip_node_t *n, cmhip_batch_t *b, unsigned in
         HIP_TRY(hipMemsetAsync(set_keys(n, set) + (size_t)slot * HALF, 0, HALF * sizeof(long long), bs));
     }
     n->filled[set][slot] = true;
-    if (!n->side)
-        return cmhip_batch_node_partial_split(b, set_sums(n, set) + (size_t)slot * HALF,
-                                              set_keys(n, set) + (size_t)slot * HALF, first_global, global_step, 0);
     return cmhip_batch_node_partial_side(b, set_sums(n, set) + (size_t)slot * HALF,
                                          set_keys(n, set) + (size_t)slot * HALF, first_global, global_step);
 }
@@ -297,8 +291,7 @@ extern "C" int cmhip_node_allreduce(cmhip_node_t *n, unsigned int set, unsigned 
     const Rccl *rc = rccl();
     HIP_TRY(hipSetDevice(n->device));
     if (after) {
-        HIP_TRY(hipEventRecord(n->ev_filled, (hipStream_t)(n->side ? cmhip_batch_side_stream(after)
-                                                                   : cmhip_batch_hip_stream(after))));
+        HIP_TRY(hipEventRecord(n->ev_filled, (hipStream_t)cmhip_batch_side_stream(after)));
         HIP_TRY(hipStreamWaitEvent(n->stream, n->ev_filled, 0));
     }
     // sums of all slots, then keys of all slots: two collectives, one launch (keys are below 2^63

@@ -5,7 +5,6 @@
 
 #include <atomic>
 #include <chrono>
-#include <stdlib.h>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -31,16 +30,16 @@ struct WorkPool {
     // works too, so a helper that the OS does not schedule in time (busy hosts, CPU quotas) costs
     // nothing: whoever runs takes the chunks.
     // Helpers that have just worked wait for the next job in a short spin before they go to sleep
-    // (default 400 us, $CMHIP_POOL_SPIN_US): jobs that come every few hundred microseconds -- a
-    // bench loop, a busy streaming host -- then never pay a futex wake-up, which on a loaded host
-    // took longer than the job (a step of 0.35 ms grew to 0.40-0.46 ms).
+    // (SPIN_US): jobs that come every few hundred microseconds -- a bench loop, a busy streaming
+    // host -- then never pay a futex wake-up, which on a loaded host took longer than the job (a
+    // step of 0.35 ms grew to 0.40-0.46 ms).
+    static constexpr unsigned SPIN_US = 400;
     unsigned chunk = 64;
     std::vector<std::thread> workers;
     std::mutex m;
     std::condition_variable cv_work, cv_done;
     std::atomic<unsigned> generation{0}, active{0};
     unsigned sleepers = 0;                            // helpers inside cv_work.wait (under m)
-    unsigned spin_us = 400;
     bool stop = false;
     void (*fn)(void *, unsigned, unsigned) = nullptr;
     void *arg = nullptr;
@@ -49,8 +48,6 @@ struct WorkPool {
 
     explicit WorkPool(unsigned n)
     {
-        if (const char *e = getenv("CMHIP_POOL_SPIN_US"))
-            spin_us = (unsigned)atoi(e);
         for (unsigned i = 0; i < n; i++)
             workers.emplace_back([this] { loop(); });
     }
@@ -101,7 +98,7 @@ struct WorkPool {
             void (*f)(void *, unsigned, unsigned);
             void *a;
             unsigned tot;
-            if (!(worked && spin_for(spin_us, [&] { return generation.load(std::memory_order_acquire) != seen; }))) {
+            if (!(worked && spin_for(SPIN_US, [&] { return generation.load(std::memory_order_acquire) != seen; }))) {
                 std::unique_lock<std::mutex> g(m);
                 sleepers++;
                 cv_work.wait(g, [&] { return stop || generation.load(std::memory_order_relaxed) != seen; });

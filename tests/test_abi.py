@@ -97,6 +97,29 @@ def test_no_oracle_in_the_product():
     assert "oracle" not in deps
 
 
+
+def test_no_tuning_knobs_in_the_engine():
+    """the engine reads exactly the environment variables INTEGRATION.md 6 lists, and every kernel source is one
+    build: no preprocessor conditional on a CMHIP_* macro other than an include guard"""
+    csrc = os.path.join(ROOT, "libcoolmic-dsp_amd", "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        read |= set(re.findall(r'getenv\(\s*"(\w+)"', open(os.path.join(csrc, f)).read()))
+    assert read == {"COOLMIC_HIP_DEVICE", "CMHIP_POOL_THREADS", "CMHIP_RCCL_LIB"}, sorted(read)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec6 = re.search(r"^## 6\..*?(?=^## |\Z)", doc, flags=re.M | re.S).group(0)
+    listed = set(re.findall(r"^\| `(\w+)`", sec6, flags=re.M))
+    assert listed == read, sorted(listed ^ read)
+    kernels = sorted(f for f in os.listdir(csrc) if re.fullmatch(r"k_\w+\.hip", f)) + ["cmhip_device.h"]
+    assert len(kernels) >= 4, kernels
+    for f in kernels:
+        text = open(os.path.join(csrc, f)).read()
+        guard = re.match(r"(?:\s*//[^\n]*\n)*\s*#\s*ifndef\s+(\w+)\s*\n\s*#\s*define\s+\1\b", text)
+        for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", text, flags=re.M):
+            names = set(re.findall(r"\bCMHIP_\w+", m.group(1))) - ({guard.group(1)} if guard else set())
+            assert not names, (f, m.group(0).strip())
+
+
 REFERENCE = "/root/reference"
 # the translation units the library replaces inside the reference's own build (INTEGRATION.md 3) and the
 # reference headers that declare what those units define

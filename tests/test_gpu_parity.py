@@ -776,17 +776,14 @@ def test_full_size_config2_properties(gpu, oracle):
     v.close()
 
 
-@pytest.mark.parametrize("place", ["off", "flag", "env2"])
-def test_arrays_placed_apart_hold_the_same_results(gpu, oracle, place, monkeypatch):
+@pytest.mark.parametrize("place", ["off", "flag"])
+def test_arrays_placed_apart_hold_the_same_results(gpu, oracle, place):
     """A batch created with CMHIP_PLACE_SEARCH (PCM arrays of 256 MiB and more) may move both of them at
-    the end of its creation, to where its own run is fastest (`place_arrays_apart`, DESIGN 4.1;
-    $CMHIP_PLACE=2 makes every batch search, 0 none).  Whatever it chose, the probes leave nothing behind:
-    uploads, the input read back, PCM and the windows of the first launch against the oracle; and the
-    search keeps inside its stated budget, half of the memory the card reported free."""
+    the end of its creation, to where its own run is fastest (`place_arrays_apart`).  Whatever
+    it chose, the probes leave nothing behind: uploads, the input read back, PCM and the windows of the
+    first launch against the oracle; and the search keeps inside its stated budget, half of the memory
+    the card reported free."""
     cm = gpu
-    monkeypatch.delenv("CMHIP_PLACE", raising=False)
-    if place == "env2":
-        monkeypatch.setenv("CMHIP_PLACE", "2")
     S, C, T = 1024, 2, 65536                      # 256 MiB per array
     b = cm.Batch(S, C, T, flags=cm.OUT_PCM | cm.VU | (cm.PLACE_SEARCH if place == "flag" else 0))
     rec = b.placement()
@@ -819,12 +816,11 @@ def test_arrays_placed_apart_hold_the_same_results(gpu, oracle, place, monkeypat
     b.close()
 
 
-def test_no_placement_search_unless_asked_for(gpu, monkeypatch):
+def test_no_placement_search_unless_asked_for(gpu):
     """The library's default: creating a large batch is two allocations and no probe launch -- fast, and
     the card's free memory afterwards is down by the batch's own arrays and tables, nothing else."""
     import time
     cm = gpu
-    monkeypatch.delenv("CMHIP_PLACE", raising=False)
     warm = cm.Batch(1, 2, 64, flags=cm.OUT_PCM | cm.VU)       # the device's first batch pays the runtime's start
     warm.close()
     cm.device_synchronize(0)

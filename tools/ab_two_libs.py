@@ -53,16 +53,10 @@ def make(cm, shape):
 shape = sys.argv[1]
 libs = sys.argv[2:]
 items = []
-for i, spec in enumerate(libs):            # "lib.so" or "lib.so+NAME=VALUE" (environment while its batch is made)
-    path, _, env = spec.partition("+")
+for i, path in enumerate(libs):
     cm = load(os.path.abspath(path), str(i))
-    if env:
-        k, _, v = env.partition("=")
-        os.environ[k] = v
     b, T, nbytes = make(cm, shape)
-    if env:
-        os.environ.pop(k, None)
-    items.append((os.path.basename(spec), b, T, nbytes))
+    items.append((os.path.basename(path), b, T, nbytes))
 for _, b, T, _ in items:
     for _ in range(80):
         b.run(T)

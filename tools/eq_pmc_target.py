@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Five launches of the EQ kernel (config 3, or the shape named on the command line: eq3vu1, eq3vu, eq3f6,
-eq3vu6 as in tools/eq_stamps.py): the program rocprofv3 --pmc passes profile (`tools/eq_pmc.sh [SHAPE]`).  Put
+"""Five launches of the EQ kernel (config 3, or the shape named on the command line: one of SHAPES below):
+the program rocprofv3 --pmc passes profile (`tools/eq_pmc.sh [SHAPE]`).  Put
 `python3 tools/eq_pmc_target.py [SHAPE]` directly after `--`."""
 import os
 import sys
