@@ -363,65 +363,6 @@ extern "C" cmhip_batch_t *cmhip_batch_new(const cmhip_batch_desc_t *desc)
     }
     cmhip_batch_t *b = new cmhip_batch();
     b->d = *desc;
-    b->stream = nullptr;
-    b->own_stream = false;
-    b->d_in = b->d_out = nullptr;
-    b->h_in = b->h_out = nullptr;
-    b->in_flight = false;
-    b->h_done = b->d_done = nullptr;
-    b->done_seq = 0;
-    b->done_flagged = false;
-    b->d_f32 = nullptr;
-    b->d_param = nullptr;
-    b->d_vu = nullptr;
-    b->d_vu2[0] = b->d_vu2[1] = b->d_vu2[2] = nullptr;
-    b->cur = 0;
-    b->copy_stream = nullptr;
-    b->ev_main = nullptr;
-    b->ev_node = nullptr;
-    b->node_reading = false;
-    b->ev_done[0] = b->ev_done[1] = b->ev_done[2] = b->ev_done[3] = nullptr;
-    b->last_done = nullptr;
-    b->done_next = 0;
-    b->ev_reset[0] = b->ev_reset[1] = b->ev_reset[2] = nullptr;
-    b->reset_pending[0] = b->reset_pending[1] = b->reset_pending[2] = false;
-    b->pool = nullptr;
-    b->d_nframes = nullptr;
-    b->d_eq = nullptr;
-    b->d_eqstate = nullptr;
-    b->d_sink = nullptr;
-    b->d_node_scratch = nullptr;
-    b->d_ring = b->h_ring = nullptr;
-    b->ring_slots = 0;
-    b->ring_seq = 0;
-    b->ring_fetched = 0;
-    b->h_pack[0] = b->h_pack[1] = b->h_pack[2] = nullptr;
-    b->d_pack[0] = b->d_pack[1] = b->d_pack[2] = nullptr;
-    b->snap_set2[0] = b->snap_set2[1] = b->snap_set2[2] = 0;
-    b->collecting = false;
-    b->job_out = nullptr;
-    b->job_rc = nullptr;
-    b->job_slot = 0;
-    b->snap_head = b->snap_count = 0;
-    b->h_stage = nullptr;
-    for (unsigned i = 0; i < STAGE_SLOTS; i++) {
-        b->stage_ev[i] = nullptr;
-        b->stage_busy[i] = false;
-    }
-    b->stage_next = 0;
-    b->parity = 0;
-    b->param_dirty = true;
-    b->all_identity = true;
-    b->all_gain_identity = true;
-    b->eq_dirty = false;
-    b->nsec = 0;
-    b->timing = false;
-    b->timing_every = 1;
-    b->timing_count = 0;
-    memset(&b->place, 0, sizeof(b->place));
-    b->place.chosen_out = 1;
-    b->place.candidates = 2;
-    b->vu_off = false;
     if (batch_init(b) != COOLMIC_ERROR_NONE) {
         cmhip_batch_free(b);
         return nullptr;
@@ -630,6 +571,25 @@ static int host_slots_quiet(cmhip_batch_t *b)
     return COOLMIC_ERROR_NONE;
 }
 
+// PCM between the caller's memory and a slot array, `at` samples in (h_slots / d_slots: its host view -- nullptr
+// unless the slots live in host memory -- and its device view): slots in host memory take a memcpy once no launch
+// uses them, device slots a copy on the batch's stream, waited for when `wait`
+static int slot_copy(cmhip_batch_t *b, int16_t *h_slots, int16_t *d_slots, size_t at, void *user, size_t bytes,
+                     hipMemcpyKind kind, bool wait)
+{
+    const bool up = kind == hipMemcpyHostToDevice;
+    if (h_slots) {
+        if (host_slots_quiet(b))
+            return COOLMIC_ERROR_GENERIC;
+        memcpy(up ? h_slots + at : user, up ? user : h_slots + at, bytes);
+        return COOLMIC_ERROR_NONE;
+    }
+    HIP_TRY(hipMemcpyAsync(up ? d_slots + at : user, up ? user : d_slots + at, bytes, kind, b->stream));
+    if (wait)
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
 extern "C" int cmhip_batch_upload(cmhip_batch_t *b, unsigned int stream, const int16_t *pcm,
                                   size_t frames)
 {
@@ -640,31 +600,22 @@ extern "C" int cmhip_batch_upload(cmhip_batch_t *b, unsigned int stream, const i
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
     const size_t bytes = frames * b->d.channels * sizeof(int16_t);
-    int16_t *dst = b->d_in + (size_t)stream * b->stride;
+    const size_t at = (size_t)stream * b->stride;
     if (bytes == 0)
         return COOLMIC_ERROR_NONE;
-    if (b->h_in) {
-        if (host_slots_quiet(b))
-            return COOLMIC_ERROR_GENERIC;
-        memcpy(b->h_in + (size_t)stream * b->stride, pcm, bytes);
-        return COOLMIC_ERROR_NONE;
-    }
-    if (bytes <= STAGE_BYTES) {
-        // small blocks (the 1 KiB pulls of the per-stream stages): bounce through pinned
-        // memory so the caller may reuse its buffer as soon as we return
-        const unsigned slot = b->stage_next;
-        b->stage_next = (slot + 1) % STAGE_SLOTS;
-        if (b->stage_busy[slot])
-            HIP_TRY(hipEventSynchronize(b->stage_ev[slot]));
-        unsigned char *bounce = b->h_stage + (size_t)slot * STAGE_BYTES;
-        memcpy(bounce, pcm, bytes);
-        HIP_TRY(hipMemcpyAsync(dst, bounce, bytes, hipMemcpyHostToDevice, b->stream));
-        HIP_TRY(hipEventRecord(b->stage_ev[slot], b->stream));
-        b->stage_busy[slot] = true;
-    } else {
-        HIP_TRY(hipMemcpyAsync(dst, pcm, bytes, hipMemcpyHostToDevice, b->stream));
-        HIP_TRY(hipStreamSynchronize(b->stream));
-    }
+    if (b->h_in || bytes > STAGE_BYTES)
+        return slot_copy(b, b->h_in, b->d_in, at, const_cast<int16_t *>(pcm), bytes, hipMemcpyHostToDevice, true);
+    // small blocks (the 1 KiB pulls of the per-stream stages): bounce through pinned
+    // memory so the caller may reuse its buffer as soon as we return
+    const unsigned slot = b->stage_next;
+    b->stage_next = (slot + 1) % STAGE_SLOTS;
+    if (b->stage_busy[slot])
+        HIP_TRY(hipEventSynchronize(b->stage_ev[slot]));
+    unsigned char *bounce = b->h_stage + (size_t)slot * STAGE_BYTES;
+    memcpy(bounce, pcm, bytes);
+    HIP_TRY(hipMemcpyAsync(b->d_in + at, bounce, bytes, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipEventRecord(b->stage_ev[slot], b->stream));
+    b->stage_busy[slot] = true;
     return COOLMIC_ERROR_NONE;
 }
 
@@ -680,14 +631,7 @@ extern "C" int cmhip_batch_upload_all(cmhip_batch_t *b, const int16_t *host, siz
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
     const size_t span = ((size_t)(b->d.streams - 1) * b->stride + frames * b->d.channels) * sizeof(int16_t);
-    if (b->h_in) {
-        if (host_slots_quiet(b))
-            return COOLMIC_ERROR_GENERIC;
-        memcpy(b->h_in, host, span);
-        return COOLMIC_ERROR_NONE;
-    }
-    HIP_TRY(hipMemcpyAsync(b->d_in, host, span, hipMemcpyHostToDevice, b->stream));
-    return COOLMIC_ERROR_NONE;
+    return slot_copy(b, b->h_in, b->d_in, 0, const_cast<int16_t *>(host), span, hipMemcpyHostToDevice, false);
 }
 
 extern "C" int cmhip_batch_download_all(cmhip_batch_t *b, int16_t *host, size_t frames)
@@ -701,14 +645,7 @@ extern "C" int cmhip_batch_download_all(cmhip_batch_t *b, int16_t *host, size_t 
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
     const size_t span = ((size_t)(b->d.streams - 1) * b->stride + frames * b->d.channels) * sizeof(int16_t);
-    if (b->h_out) {
-        if (host_slots_quiet(b))
-            return COOLMIC_ERROR_GENERIC;
-        memcpy(host, b->h_out, span);
-        return COOLMIC_ERROR_NONE;
-    }
-    HIP_TRY(hipMemcpyAsync(host, b->d_out, span, hipMemcpyDeviceToHost, b->stream));
-    return COOLMIC_ERROR_NONE;
+    return slot_copy(b, b->h_out, b->d_out, 0, host, span, hipMemcpyDeviceToHost, false);
 }
 
 extern "C" void *cmhip_host_alloc(size_t bytes)
@@ -767,17 +704,8 @@ extern "C" int cmhip_batch_download(cmhip_batch_t *b, unsigned int stream, int16
         return fail(COOLMIC_ERROR_INVAL, "download: stream or frames out of range");
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
-    if (b->h_out) {
-        if (host_slots_quiet(b))
-            return COOLMIC_ERROR_GENERIC;
-        memcpy(pcm, b->h_out + (size_t)stream * b->stride, frames * b->d.channels * sizeof(int16_t));
-        return COOLMIC_ERROR_NONE;
-    }
-    HIP_TRY(hipMemcpyAsync(pcm, b->d_out + (size_t)stream * b->stride,
-                           frames * b->d.channels * sizeof(int16_t), hipMemcpyDeviceToHost,
-                           b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return COOLMIC_ERROR_NONE;
+    return slot_copy(b, b->h_out, b->d_out, (size_t)stream * b->stride, pcm, frames * b->d.channels * sizeof(int16_t),
+                     hipMemcpyDeviceToHost, true);
 }
 
 extern "C" int cmhip_batch_download_input(cmhip_batch_t *b, unsigned int stream, int16_t *pcm,
@@ -789,17 +717,8 @@ extern "C" int cmhip_batch_download_input(cmhip_batch_t *b, unsigned int stream,
         return fail(COOLMIC_ERROR_INVAL, "download_input: stream or frames out of range (or a batch without slots of its own)");
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
-    if (b->h_in) {
-        if (host_slots_quiet(b))
-            return COOLMIC_ERROR_GENERIC;
-        memcpy(pcm, b->h_in + (size_t)stream * b->stride, frames * b->d.channels * sizeof(int16_t));
-        return COOLMIC_ERROR_NONE;
-    }
-    HIP_TRY(hipMemcpyAsync(pcm, b->d_in + (size_t)stream * b->stride,
-                           frames * b->d.channels * sizeof(int16_t), hipMemcpyDeviceToHost,
-                           b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return COOLMIC_ERROR_NONE;
+    return slot_copy(b, b->h_in, b->d_in, (size_t)stream * b->stride, pcm, frames * b->d.channels * sizeof(int16_t),
+                     hipMemcpyDeviceToHost, true);
 }
 
 extern "C" int cmhip_batch_download_f32(cmhip_batch_t *b, unsigned int stream, unsigned int channel,
@@ -870,10 +789,6 @@ int cmhip_engine_flush_params(cmhip_batch_t *b)
         for (const auto &p : b->h_param)
             if (!p.map_identity)
                 b->all_identity = false;
-        b->all_gain_identity = true;
-        for (const auto &p : b->h_param)
-            if (p.mode != GAIN_IDENTITY)
-                b->all_gain_identity = false;
         HIP_TRY(hipMemcpyAsync(b->d_param, b->h_param.data(), b->h_param.size() * sizeof(StreamParam),
                                hipMemcpyHostToDevice, b->stream));
         b->param_dirty = false;
@@ -884,6 +799,27 @@ int cmhip_engine_flush_params(cmhip_batch_t *b)
         b->eq_dirty = false;
     }
     return COOLMIC_ERROR_NONE;
+}
+
+RunArgs cmhip_engine_run_args(const cmhip_batch_t *b, const int16_t *in, int16_t *out, size_t frames,
+                              const uint32_t *nframes, VuState *window, uint32_t parity)
+{
+    RunArgs a;
+    memset(&a, 0, sizeof(a));              // (chunks 0: the launcher sizes the tiles per kernel variant)
+    a.in = in;
+    a.out = out;
+    a.f32 = b->d_f32;
+    a.param = b->d_param;
+    a.vu = window;
+    a.nframes = nframes;
+    a.frames = (uint32_t)frames;
+    a.streams = b->d.streams;
+    a.channels = b->d.channels;
+    a.stride = b->stride;
+    a.plane = b->plane;
+    a.identity_maps = b->all_identity ? 1u : 0u;
+    a.parity = parity;
+    return a;
 }
 
 static EventPair take_events(cmhip_batch_t *b)
@@ -999,23 +935,8 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
         HIP_TRY(launch_eq(a, b->stream, ev.a, ev.b, &flagged));
         b->in_flight = true;
     } else {
-        RunArgs a;
-        memset(&a, 0, sizeof(a));
-        a.in = slots_in;
-        a.out = (b->d.flags & CMHIP_OUT_PCM) ? slots_out : nullptr;
-        a.f32 = b->d_f32;
-        a.param = b->d_param;
-            a.vu = vu ? window : nullptr;
-        a.nframes = frames_per_stream ? b->d_nframes : nullptr;
-        a.frames = (uint32_t)frames;
-        a.streams = b->d.streams;
-        a.channels = b->d.channels;
-        a.stride = b->stride;
-        a.plane = b->plane;
-        a.chunks = 0;                      // the launcher sizes the tiles per kernel variant
-        a.identity_maps = b->all_identity ? 1u : 0u;
-        a.identity_gains = b->all_gain_identity ? 1u : 0u;
-        a.parity = parity;
+        RunArgs a = cmhip_engine_run_args(b, slots_in, (b->d.flags & CMHIP_OUT_PCM) ? slots_out : nullptr, frames,
+                                          frames_per_stream ? b->d_nframes : nullptr, vu ? window : nullptr, parity);
         a.done_flag = flag;
         a.done_seq = flag_seq;
         HIP_TRY(launch_run(a, b->stream, ev.a, ev.b, &flagged));

@@ -3,6 +3,7 @@
 //   cmhip_place.hip    the opt-in placement search for a batch's two PCM arrays
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
+//   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
 #pragma once
 
 #include "cmhip_internal.h"
@@ -17,6 +18,8 @@
 
 using namespace cmhip;
 
+#define CMHIP_INTERNAL __attribute__((visibility("hidden")))
+CMHIP_INTERNAL int cmhip_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 #define fail cmhip_fail
 
 #define HIP_TRY(expr)                                                                       \
@@ -82,9 +85,8 @@ struct cmhip_batch {
     std::vector<StreamParam> h_param;
     std::vector<uint16_t> h_scale;         // the reference's master_gain_scale per stream
     std::vector<uint16_t> h_gain;          // [S][16]
-    bool param_dirty;
-    bool all_identity;                     // no stream has a channel map (recomputed on upload)
-    bool all_gain_identity;                // no stream has a gain (same)
+    bool param_dirty = true;
+    bool all_identity = true;              // no stream has a channel map (recomputed on upload)
     std::vector<EqParam> h_eq;
     unsigned int nsec;
     bool eq_dirty;
@@ -106,9 +108,11 @@ struct cmhip_batch {
     unsigned int parity;                   // current slot of VuState::samples
 
     bool timing;
-    unsigned int timing_every, timing_count;     // every n-th run carries the events (cmhip_batch_timing)
+    unsigned int timing_every = 1, timing_count;  // every n-th run carries the events (cmhip_batch_timing)
     std::vector<EventPair> ev_used, ev_free;
-    cmhip_placement_t place;               // what the placement search did (cmhip_batch_placement)
+    // what the placement search did (cmhip_batch_placement); without one, candidates 0 and 1 -- the arrays where
+    // hipMalloc put them -- are the input and the output
+    cmhip_placement_t place = {0, 2, 0, 1, 0, 0, 0, 0, 0, 0};
     bool vu_off;                           // runs leave the windows alone for now (cmhip_batch_vu_pause)
 };
 
@@ -123,5 +127,12 @@ static inline int use(cmhip_batch_t *b)
 CMHIP_INTERNAL int cmhip_engine_settle_node(cmhip_batch_t *b);
 // parameter and equaliser tables to the device, when a setter has run since the last upload
 CMHIP_INTERNAL int cmhip_engine_flush_params(cmhip_batch_t *b);
+// the RunArgs of a run of this batch (nframes: per-stream frame counts on the device, or nullptr; window: the VU
+// windows, or nullptr); the completion flag is left to the caller
+CMHIP_INTERNAL RunArgs cmhip_engine_run_args(const cmhip_batch_t *b, const int16_t *in, int16_t *out, size_t frames,
+                                             const uint32_t *nframes, VuState *window, uint32_t parity);
 // cmhip_place.hip: called once, at the end of a batch's creation, when it has PCM arrays of its own
 CMHIP_INTERNAL int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes);
+// cmhip_vu.hip (for node.hip): the node record of the batch's windows, built on the copy stream
+CMHIP_INTERNAL int cmhip_batch_node_partial_side(cmhip_batch_t *b, long long *dst_sum, long long *dst_key,
+                                                 uint64_t first_global, uint64_t global_step);

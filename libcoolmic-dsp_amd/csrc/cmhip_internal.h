@@ -59,6 +59,7 @@ struct VuState {
 
 constexpr int      KEY_ABS_SHIFT = 47;
 constexpr uint64_t KEY_IDX_MASK  = (1ull << 46) - 1;
+constexpr int      NODE_KEY_ABS_SHIFT = 46;      // |peak| of a node record's key (k_node_partial)
 
 struct EqParam {
     uint32_t nsec;
@@ -83,8 +84,8 @@ struct RunArgs {
     uint32_t       chunks;         // 4 KiB tiles (one wave each) per stream slot
     uint32_t       parity;         // which VuState::samples slot is current
     uint32_t       identity_maps;  // 1 when no stream of the batch has a channel map
-    uint32_t       identity_gains; // 1 when no stream of the batch has a gain (disabled or unity everywhere); read by
-                                   // no kernel now, kept so that the kernel-argument offsets below stay as they are
+    uint32_t       identity_gains; // 0: read by no kernel now, kept so that the kernel-argument offsets below stay as
+                                   // they are
     // Completion by flag, for launches of ONE workgroup (the 1 KiB pulls of the per-stream stages): when not
     // null the workgroup, at its very end, makes its stores visible to the host and stores done_seq there
     // (pinned, device-mapped host memory).  The host spins on the word instead of waiting for the stream:
@@ -164,13 +165,3 @@ hipError_t launch_ceiling(int mode, const void *src, void *dst, size_t bytes,
                           unsigned long long *sink, hipStream_t st);
 
 }  // namespace cmhip
-
-// engine internals shared between cmhip_batch.hip and node.hip (not part of the C ABI)
-struct cmhip_batch;
-#define CMHIP_INTERNAL __attribute__((visibility("hidden")))
-CMHIP_INTERNAL int cmhip_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-CMHIP_INTERNAL int cmhip_batch_node_partial_side(struct cmhip_batch *b, long long *dst_sum, long long *dst_key,
-                                                 uint64_t first_global, uint64_t global_step);
-CMHIP_INTERNAL void *cmhip_batch_side_stream(struct cmhip_batch *b);
-CMHIP_INTERNAL int cmhip_batch_device(const struct cmhip_batch *b);
-CMHIP_INTERNAL unsigned int cmhip_batch_flags(const struct cmhip_batch *b);

@@ -1,8 +1,6 @@
 // cmhip_place.hip -- the opt-in placement search for a batch's two PCM arrays (CMHIP_PLACE_SEARCH).
 #include "cmhip_engine.h"
 
-#include <string.h>
-
 #include <algorithm>
 #include <chrono>
 
@@ -30,20 +28,8 @@ constexpr double PLACE_BUDGET_FRAC = 0.5;
 // a probe: the batch's own run (as created: no gain, no maps), full slots, from one candidate into another
 static double place_probe_ms(cmhip_batch_t *b, const void *src, void *dst, hipEvent_t e0, hipEvent_t e1)
 {
-    RunArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = (const int16_t *)src;
-    a.out = (int16_t *)dst;
-    a.f32 = b->d_f32;
-    a.param = b->d_param;
-    a.vu = (b->d.flags & CMHIP_VU) ? b->d_vu : nullptr;
-    a.frames = (uint32_t)b->d.max_frames;
-    a.streams = b->d.streams;
-    a.channels = b->d.channels;
-    a.stride = b->stride;
-    a.plane = b->plane;
-    a.identity_maps = 1;
-    a.identity_gains = 1;
+    const RunArgs a = cmhip_engine_run_args(b, (const int16_t *)src, (int16_t *)dst, b->d.max_frames, nullptr,
+                                            (b->d.flags & CMHIP_VU) ? b->d_vu : nullptr, 0);
     const int n = 6;
     for (int i = 0; i < 2; i++)
         if (launch_run(a, b->stream) != hipSuccess)
@@ -74,9 +60,6 @@ int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes)
     size_t free_b = 0, total_b = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     cmhip_placement_t &rec = b->place;
-    rec.chosen_in = 0;
-    rec.chosen_out = 1;
-    rec.candidates = 2;
     if (bytes >= PLACE_MIN_BYTES && (b->d.flags & CMHIP_PLACE_SEARCH) && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
         hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
         probed = true;

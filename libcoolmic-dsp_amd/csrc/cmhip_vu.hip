@@ -13,9 +13,10 @@
 // ---------------------------------------------------------------------------
 // VU windows
 
-static int16_t key_peak(unsigned long long key)
+// keys hold |peak| from bit `shift` up and the sign in bit 0: KEY_ABS_SHIFT (a window), NODE_KEY_ABS_SHIFT (a node record)
+static int16_t key_peak(unsigned long long key, int shift)
 {
-    const int mag = (int)(key >> KEY_ABS_SHIFT);
+    const int mag = (int)(key >> shift);
     return (int16_t)((key & 1ull) ? -mag : mag);
 }
 
@@ -27,54 +28,48 @@ static double power_db(unsigned long long sum, unsigned long long count)
     return fmin(p, 0.);
 }
 
-static int finish_window(const cmhip_batch_t *b, const VuState &v, unsigned parity,
-                         coolmic_vumeter_result_t *out)
+// The window's result (ref: src/vumeter.c:189-218): `frames` frames of C channels, the sums and peak keys of channel c
+// at sum[c * stride] / key[c * stride] -- in one of the three spellings of a 64-bit word the windows come in -- and
+// the key of the global peak.  Out is left alone while the window holds no frame.
+template <typename Word>
+static int finish(unsigned long long frames, unsigned C, unsigned rate, const Word *sum, const Word *key, size_t stride,
+                  unsigned long long global_key, int shift, coolmic_vumeter_result_t *out)
 {
-    const unsigned C = b->d.channels;
-    const unsigned long long frames = v.samples[parity] / C;
     if (frames == 0)
         return COOLMIC_ERROR_INVAL;                      // ref: src/vumeter.c:198-199
     memset(out, 0, sizeof(*out));
-    out->rate = b->d.rate;
+    out->rate = rate;
     out->channels = C;
     out->frames = (size_t)frames;
-    unsigned long long all = 0, best = 0;
+    unsigned long long all = 0;
     for (unsigned c = 0; c < C; c++) {
-        all += v.power[c];
-        out->channel_power[c] = power_db(v.power[c], frames);
-        out->channel_peak[c] = key_peak(v.key[c]);
-        if (v.key[c] > best)
-            best = v.key[c];
+        all += (unsigned long long)sum[c * stride];
+        out->channel_power[c] = power_db((unsigned long long)sum[c * stride], frames);
+        out->channel_peak[c] = key_peak((unsigned long long)key[c * stride], shift);
     }
     out->global_power = power_db(all, frames * C);
-    out->global_peak = key_peak(best);       // first max-|x| over all channels
+    out->global_peak = key_peak(global_key, shift);
     return COOLMIC_ERROR_NONE;
 }
 
-// the same from a packed snapshot ([word][stream]: samples, C sums, C keys)
-static int finish_packed(const cmhip_batch_t *b, const unsigned long long *pack, unsigned s,
-                         coolmic_vumeter_result_t *out)
+// a batch window's global peak: the largest key over its channels, the first max-|x| over all of them
+template <typename Word>
+static unsigned long long max_key(const Word *key, size_t stride, unsigned C)
 {
-    const unsigned C = b->d.channels;
-    const size_t S = b->d.streams;
-    const unsigned long long frames = pack[s] / C;
-    if (frames == 0)
-        return COOLMIC_ERROR_INVAL;                      // ref: src/vumeter.c:198-199
-    memset(out, 0, sizeof(*out));
-    out->rate = b->d.rate;
-    out->channels = C;
-    out->frames = (size_t)frames;
-    unsigned long long all = 0, best = 0;
-    for (unsigned c = 0; c < C; c++) {
-        const unsigned long long power = pack[(size_t)(1u + c) * S + s], key = pack[(size_t)(1u + C + c) * S + s];
-        all += power;
-        out->channel_power[c] = power_db(power, frames);
-        out->channel_peak[c] = key_peak(key);
-        if (key > best)
-            best = key;
-    }
-    out->global_power = power_db(all, frames * C);
-    out->global_peak = key_peak(best);
+    unsigned long long best = 0;
+    for (unsigned c = 0; c < C; c++)
+        if (key[c * stride] > best)
+            best = key[c * stride];
+    return best;
+}
+
+// one stream's window to the host, behind what the main stream has queued
+static int read_window(cmhip_batch_t *b, unsigned int stream, VuState *v)
+{
+    if (use(b) || cmhip_engine_settle_node(b))
+        return COOLMIC_ERROR_GENERIC;
+    HIP_TRY(hipMemcpyAsync(v, b->d_vu + stream, sizeof(*v), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
     return COOLMIC_ERROR_NONE;
 }
 
@@ -85,15 +80,13 @@ extern "C" int cmhip_batch_vu_result(cmhip_batch_t *b, unsigned int stream,
         return fail(COOLMIC_ERROR_FAULT, "vu_result: NULL argument");
     if (stream >= b->d.streams || !(b->d.flags & CMHIP_VU))
         return fail(COOLMIC_ERROR_INVAL, "vu_result: stream out of range or batch without VU");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
     b->last_done = nullptr;                  // main-stream work on the windows follows the last run
-    if (cmhip_engine_settle_node(b))
-        return COOLMIC_ERROR_GENERIC;
     VuState v;
-    HIP_TRY(hipMemcpyAsync(&v, b->d_vu + stream, sizeof(v), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    const int rc = finish_window(b, v, b->parity, out);
+    if (read_window(b, stream, &v))
+        return COOLMIC_ERROR_GENERIC;
+    const unsigned C = b->d.channels;
+    const int rc = finish(v.samples[b->parity] / C, C, b->d.rate, v.power, v.key, 1, max_key(v.key, 1, C),
+                          KEY_ABS_SHIFT, out);
     if (rc == COOLMIC_ERROR_NONE)
         HIP_TRY(hipMemsetAsync(b->d_vu + stream, 0, sizeof(VuState), b->stream));
     return rc;
@@ -166,11 +159,16 @@ static unsigned pool_threads()
     return n;
 }
 
+// a packed snapshot is [word][stream]: samples, C sums, C keys
 static void collect_body(void *p, unsigned lo, unsigned hi)
 {
     cmhip_batch_t *b = (cmhip_batch_t *)p;
+    const unsigned C = b->d.channels;
+    const size_t S = b->d.streams;
+    const unsigned long long *pack = b->h_pack[b->job_slot];
     for (unsigned s = lo; s < hi; s++) {
-        const int r = finish_packed(b, b->h_pack[b->job_slot], s, &b->job_out[s]);
+        const unsigned long long *sum = pack + S + s, *key = sum + C * S;
+        const int r = finish(pack[s] / C, C, b->d.rate, sum, key, S, max_key(key, S, C), KEY_ABS_SHIFT, &b->job_out[s]);
         if (b->job_rc)
             b->job_rc[s] = r;
     }
@@ -264,18 +262,14 @@ extern "C" int cmhip_batch_vu_raw(cmhip_batch_t *b, unsigned int stream, int64_t
         return fail(COOLMIC_ERROR_FAULT, "vu_raw: batch is NULL");
     if (stream >= b->d.streams)
         return fail(COOLMIC_ERROR_INVAL, "vu_raw: stream out of range");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    if (cmhip_engine_settle_node(b))
-        return COOLMIC_ERROR_GENERIC;
     VuState v;
-    HIP_TRY(hipMemcpyAsync(&v, b->d_vu + stream, sizeof(v), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (read_window(b, stream, &v))
+        return COOLMIC_ERROR_GENERIC;
     for (unsigned c = 0; c < MAX_CH; c++) {
         if (power)
             power[c] = (int64_t)v.power[c];
         if (peak)
-            peak[c] = key_peak(v.key[c]);
+            peak[c] = key_peak(v.key[c], KEY_ABS_SHIFT);
     }
     if (frames)
         *frames = v.samples[b->parity] / b->d.channels;
@@ -359,11 +353,9 @@ extern "C" CMHIP_INTERNAL int cmhip_batch_vu_raw_state(cmhip_batch_t *b, unsigne
         return fail(COOLMIC_ERROR_FAULT, "vu_raw_state: NULL argument");
     if (stream >= b->d.streams || !(b->d.flags & CMHIP_VU))
         return fail(COOLMIC_ERROR_INVAL, "vu_raw_state: stream out of range or batch without VU");
-    if (use(b) || cmhip_engine_settle_node(b))
-        return COOLMIC_ERROR_GENERIC;
     VuState v;
-    HIP_TRY(hipMemcpyAsync(&v, b->d_vu + stream, sizeof(v), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (read_window(b, stream, &v))
+        return COOLMIC_ERROR_GENERIC;
     raw_from_state(v, b->parity, out);
     return COOLMIC_ERROR_NONE;
 }
@@ -388,24 +380,8 @@ extern "C" CMHIP_INTERNAL int cmhip_vu_raw_finish(const cmhip_vu_raw_t *w, unsig
 {
     if (!w || !out || channels == 0 || channels > MAX_CH)
         return COOLMIC_ERROR_FAULT;
-    const unsigned long long frames = w->samples / channels;
-    if (frames == 0)
-        return COOLMIC_ERROR_INVAL;                      // ref: src/vumeter.c:198-199
-    memset(out, 0, sizeof(*out));
-    out->rate = rate;
-    out->channels = channels;
-    out->frames = (size_t)frames;
-    unsigned long long all = 0, best = 0;
-    for (unsigned c = 0; c < channels; c++) {
-        all += w->power[c];
-        out->channel_power[c] = power_db(w->power[c], frames);
-        out->channel_peak[c] = key_peak(w->key[c]);
-        if (w->key[c] > best)
-            best = w->key[c];
-    }
-    out->global_power = power_db(all, frames * channels);
-    out->global_peak = key_peak(best);
-    return COOLMIC_ERROR_NONE;
+    return finish(w->samples / channels, channels, rate, w->power, w->key, 1, max_key(w->key, 1, channels),
+                  KEY_ABS_SHIFT, out);
 }
 
 // test hook (host logic, needs no GPU): `count` raw windows of 33 words each (16 sums, 16 keys, samples), one after
@@ -429,12 +405,10 @@ extern "C" int cmhip_test_merge_windows(const uint64_t *windows, unsigned int co
 // ---------------------------------------------------------------------------
 // node-global VU
 
-// the node record of the batch's windows, its sums and its keys in two places, on the main stream
+// the node record of the batch's windows, its sums and its keys in two places, on the main stream (after use())
 static int node_partial_split(cmhip_batch_t *b, long long *dst_sum, long long *dst_key,
                               uint64_t first_global, uint64_t global_step)
 {
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
     // This kernel reads the windows after the last run, on the same stream: its own end, stamped by
     // its dispatch, is what the next snapshot has to wait for -- no event packet on the main stream.
     if (cmhip_engine_settle_node(b))
@@ -503,8 +477,6 @@ int cmhip_batch_node_partial_side(cmhip_batch_t *b, long long *dst_sum, long lon
     return COOLMIC_ERROR_NONE;
 }
 
-void *cmhip_batch_side_stream(cmhip_batch_t *b) { return (void *)b->copy_stream; }
-
 // internal (transform.c): a batch with windows runs without touching them while paused -- the
 // transform accumulates only the blocks its fused meter has asked for
 extern "C" __attribute__((visibility("hidden"))) void cmhip_batch_vu_pause(cmhip_batch_t *b, int paused)
@@ -513,9 +485,6 @@ extern "C" __attribute__((visibility("hidden"))) void cmhip_batch_vu_pause(cmhip
         b->vu_off = paused != 0;
 }
 
-int cmhip_batch_device(const cmhip_batch_t *b) { return b->d.device; }
-unsigned int cmhip_batch_flags(const cmhip_batch_t *b) { return b->d.flags; }
-
 extern "C" int cmhip_node_finish(const int64_t *w, unsigned int channels, unsigned int rate,
                                  coolmic_vumeter_result_t *out)
 {
@@ -523,25 +492,8 @@ extern "C" int cmhip_node_finish(const int64_t *w, unsigned int channels, unsign
         return fail(COOLMIC_ERROR_FAULT, "node_finish: NULL argument");
     if (channels == 0 || channels > MAX_CH)
         return fail(COOLMIC_ERROR_INVAL, "node_finish: channels out of range");
-    const unsigned long long frames = (unsigned long long)w[MAX_CH];
-    if (frames == 0)
-        return COOLMIC_ERROR_INVAL;
-    memset(out, 0, sizeof(*out));
-    out->rate = rate;
-    out->channels = channels;
-    out->frames = (size_t)frames;
-    unsigned long long all = 0;
-    for (unsigned c = 0; c < channels; c++) {
-        const unsigned long long k = (unsigned long long)w[MAX_CH + 1 + c];
-        all += (unsigned long long)w[c];
-        out->channel_power[c] = power_db((unsigned long long)w[c], frames);
-        const int mag = (int)(k >> 46);
-        out->channel_peak[c] = (int16_t)((k & 1ull) ? -mag : mag);
-    }
-    const unsigned long long g = (unsigned long long)w[2 * MAX_CH + 1];
-    const int gm = (int)(g >> 46);
-    out->global_peak = (int16_t)((g & 1ull) ? -gm : gm);
-    out->global_power = power_db(all, frames * channels);
-    return COOLMIC_ERROR_NONE;
+    // [0, 16): sums, [16]: frames, [17, 33): keys, [33]: the key of the global peak
+    return finish((unsigned long long)w[MAX_CH], channels, rate, w, w + MAX_CH + 1, 1,
+                  (unsigned long long)w[2 * MAX_CH + 1], NODE_KEY_ABS_SHIFT, out);
 }
 

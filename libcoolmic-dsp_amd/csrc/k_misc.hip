@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64) void k_node_partial(const VuState *vu, u32 stre
                     const u64 idx = ~(k0 >> 1) & KEY_IDX_MASK;
                     u64 fr = NC == 1 ? idx : NC == 2 ? (channels == 2 ? idx >> 1 : idx) : idx / channels;
                     fr = fr > 0x1fffffffull ? 0x1fffffffull : fr;
-                    const u64 nk = (mag << 46) | ((0x1fffffffull - fr) << 17) |
+                    const u64 nk = (mag << NODE_KEY_ABS_SHIFT) | ((0x1fffffffull - fr) << 17) |
                                    ((65535ull - (gs & 65535ull)) << 1) | (k0 & 1ull);
                     key[c] = nk > key[c] ? nk : key[c];
                     key[NC] = nk > key[NC] ? nk : key[NC];

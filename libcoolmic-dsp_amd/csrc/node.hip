@@ -7,10 +7,7 @@
 //
 // librccl.so.1 is a 570 MB library, so it is not a link-time dependency of the engine: it is
 // loaded when the first node is created and only its six entry points are resolved.
-#include "cmhip_internal.h"
-
-#include <coolmic-dsp/coolmic-dsp.h>
-#include <coolmic_hip.h>
+#include "cmhip_engine.h"
 
 #include <rccl/rccl.h>
 
@@ -21,17 +18,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-using namespace cmhip;
-
-#define fail cmhip_fail
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return fail(COOLMIC_ERROR_GENERIC, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                \
-    } while (0)
 
 namespace {
 
@@ -225,15 +211,8 @@ extern "C" cmhip_node_t *cmhip_node_new(int device, int nranks, int rank, const 
         return nullptr;
     }
     cmhip_node_t *n = new cmhip_node();
-    n->comm = nullptr;
-    n->stream = nullptr;
-    n->d_words = n->h_words = nullptr;
-    n->ev_filled = nullptr;
-    for (unsigned i = 0; i < NODE_SETS; i++) {
-        n->ev_done[i] = nullptr;
-        n->exchanged[i] = false;
-        n->filled[i].assign(max_records, false);       // (the buffer starts zeroed)
-    }
+    for (auto &f : n->filled)
+        f.assign(max_records, false);                  // (the buffer starts zeroed)
     n->device = device;
     n->nranks = nranks;
     n->rank = rank;
@@ -263,10 +242,10 @@ extern "C" int cmhip_node_partial(cmhip_node_t *n, cmhip_batch_t *b, unsigned in
         return fail(COOLMIC_ERROR_FAULT, "node_partial: NULL argument");
     if (set >= NODE_SETS || slot >= n->max_records)
         return fail(COOLMIC_ERROR_INVAL, "node_partial: set %u / slot %u out of range", set, slot);
-    if (cmhip_batch_device(b) != n->device || !(cmhip_batch_flags(b) & CMHIP_VU))
+    if (b->d.device != n->device || !(b->d.flags & CMHIP_VU))
         return fail(COOLMIC_ERROR_INVAL, "node_partial: the batch must have VU windows on device %d", n->device);
     HIP_TRY(hipSetDevice(n->device));
-    hipStream_t bs = (hipStream_t)cmhip_batch_side_stream(b);  // records are built beside the batch's next run
+    hipStream_t bs = b->copy_stream;       // records are built beside the batch's next run
     if (n->exchanged[set]) {               // the set's last exchange must be through before it is refilled
         if (hipEventQuery(n->ev_done[set]) != hipSuccess)
             HIP_TRY(hipStreamWaitEvent(bs, n->ev_done[set], 0));
@@ -291,7 +270,7 @@ extern "C" int cmhip_node_allreduce(cmhip_node_t *n, unsigned int set, unsigned 
     const Rccl *rc = rccl();
     HIP_TRY(hipSetDevice(n->device));
     if (after) {
-        HIP_TRY(hipEventRecord(n->ev_filled, (hipStream_t)cmhip_batch_side_stream(after)));
+        HIP_TRY(hipEventRecord(n->ev_filled, after->copy_stream));
         HIP_TRY(hipStreamWaitEvent(n->stream, n->ev_filled, 0));
     }
     // sums of all slots, then keys of all slots: two collectives, one launch (keys are below 2^63

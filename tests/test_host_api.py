@@ -444,7 +444,7 @@ def _raw_window(x, C):
     return w
 
 
-@pytest.mark.parametrize("C", [1, 2, 6])
+@pytest.mark.parametrize("C", [1, 2, 6, 16])
 def test_window_records_merge_like_one_window(cm, oracle, C):
     """The host arithmetic a meter behind a tee relies on (csrc/vumeter.c, cmhip_vu_raw_merge / _finish): the
     windows of consecutive launches, merged in stream order, give the reference's result over the whole stretch

@@ -26,23 +26,28 @@ def _stream_pcm(orc, gs):
     return orc.gain_apply(g, orc.lcg(777 + gs, T * C), C)
 
 
+def _add_stream(w, pcm, gs):
+    """adds global stream gs's interleaved block to the node record w, as cmhip_batch_vu_node_partial does
+    (see the key layout in include/coolmic_hip.h and csrc/k_misc.hip:k_node_partial)"""
+    x = pcm.astype(np.int64).reshape(-1, C)
+    w[16] += x.shape[0]
+    for c in range(C):
+        w[c] += int((x[:, c] ** 2).sum())
+        mag = int(np.abs(x[:, c]).max(initial=0))
+        if mag == 0:
+            continue
+        fr = int(np.argmax(np.abs(x[:, c]) == mag))
+        neg = 1 if x[fr, c] < 0 else 0
+        key = (mag << 46) | ((0x1FFFFFFF - min(fr, 0x1FFFFFFF)) << 17) | ((65535 - gs % 65536) << 1) | neg
+        w[17 + c] = max(w[17 + c], key)
+        w[33] = max(w[33], key)
+
+
 def _node_record(orc, streams):
-    """what cmhip_batch_vu_node_partial writes for these global streams (see the key layout
-    in include/coolmic_hip.h and csrc/k_misc.hip:k_node_partial)"""
+    """what cmhip_batch_vu_node_partial writes for these global streams"""
     w = np.zeros(34, dtype=np.int64)
     for gs in streams:
-        x = _stream_pcm(orc, gs).astype(np.int64).reshape(-1, C)
-        w[16] += T
-        for c in range(C):
-            w[c] += int((x[:, c] ** 2).sum())
-            mag = int(np.abs(x[:, c]).max())
-            if mag == 0:
-                continue
-            fr = int(np.argmax(np.abs(x[:, c]) == mag))
-            neg = 1 if x[fr, c] < 0 else 0
-            key = (mag << 46) | ((0x1FFFFFFF - min(fr, 0x1FFFFFFF)) << 17) | ((65535 - gs % 65536) << 1) | neg
-            w[17 + c] = max(w[17 + c], key)
-            w[33] = max(w[33], key)
+        _add_stream(w, _stream_pcm(orc, gs), gs)
     return w
 
 
@@ -87,7 +92,7 @@ def _worker(rank, world, port, out):
         dist.destroy_process_group()
 
 
-def test_sharding_and_node_vu_world2(oracle):
+def test_sharding_and_node_vu_world2(cm, oracle):
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.SimpleQueue()
@@ -117,6 +122,24 @@ def test_sharding_and_node_vu_world2(oracle):
         assert got["channel_peak"][c] == best[c][3]
     assert got["global_power"] == oracle.lib.oracle_power_db(int(pw.sum()), TOTAL * T * C)
     assert got["global_peak"] == max(best, key=lambda b: b[:3])[3]
+    # the edges of the host finish, against the oracle over the same samples: no frames, silence, full scale
+    from oracle import oracle_ffi
+    for x in (np.zeros(0, np.int16), np.zeros(T * C, np.int16), np.full(T * C, -32768, np.int16)):
+        w = np.zeros(34, dtype=np.int64)
+        _add_stream(w, x, 0)
+        v = oracle.vu_new(C)
+        if x.size:
+            oracle.vu_accumulate(v, x)
+        rc_o, r_o = oracle.vu_result(v)
+        rc, r = cm.node_finish(w, C)
+        assert rc == rc_o
+        if x.size == 0:
+            assert rc == cm.ERROR_INVAL
+            continue
+        assert rc == 0 and r.as_dict() == oracle_ffi.vu_result_dict(r_o)
+        full = bool(x[0])
+        assert r.global_power == (0.0 if full else -np.inf) and r.global_peak == (-32768 if full else 0)
+        assert all(r.channel_peak[c] == r.global_peak for c in range(C))
 
 
 def test_shard_edges():
