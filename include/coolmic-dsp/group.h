@@ -97,6 +97,19 @@ int                 coolmic_group_set_pull_threads(coolmic_group_t *self, unsign
 int                 coolmic_group_vumeter_result(coolmic_group_t *self, unsigned int slot,
                                                  coolmic_vumeter_result_t *result);
 
+/* Every stream's VU window since its last result, all closed at one point -- after everything pumped so far, the
+ * block in flight included -- in ONE snapshot and collect of the group's engine instead of a copy and a wait per
+ * stream.  results[] and rc[] (rc may be NULL) have coolmic_group_streams() entries; per slot the contract of
+ * coolmic_group_vumeter_result(): rc[slot] is COOLMIC_ERROR_INVAL and results[slot] is left alone for a window
+ * without a frame. */
+int                 coolmic_group_vumeter_results(coolmic_group_t *self, coolmic_vumeter_result_t *results, int *rc);
+
+/* Where coolmic_group_vumeter_results() finishes the dB values: CMHIP_VU_FINISH_HOST (0, how a group starts:
+ * bit-equal to coolmic_vumeter_result()) or CMHIP_VU_FINISH_DEVICE (1: no host arithmetic, last bits of the power
+ * doubles may differ) of <coolmic_hip.h>, with cmhip_batch_vu_set_finish()'s return values.
+ * coolmic_group_vumeter_result() for one slot is finished on the host either way. */
+int                 coolmic_group_set_vu_finish(coolmic_group_t *self, int where);
+
 unsigned int        coolmic_group_streams(coolmic_group_t *self);
 
 #ifdef __cplusplus

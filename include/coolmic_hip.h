@@ -186,6 +186,23 @@ int cmhip_batch_vu_collect(cmhip_batch_t *b, coolmic_vumeter_result_t *out, int 
 int cmhip_batch_vu_collect_begin(cmhip_batch_t *b, coolmic_vumeter_result_t *out, int *rc);
 int cmhip_batch_vu_collect_end(cmhip_batch_t *b);
 int cmhip_batch_vu_reset(cmhip_batch_t *b, long stream);
+/* Where the dB values of a snapshot are finished.  CMHIP_VU_FINISH_HOST (how every batch starts): the snapshot
+ * carries raw sums and keys, the collect runs the reference's arithmetic on them with the host's libm -- results are
+ * bit-equal to coolmic_vumeter_result().  CMHIP_VU_FINISH_DEVICE: the snapshot's kernel runs the same sequence of
+ * double operations itself (integer mean, sqrt, / 32768, log10, * 20, capped at 0) and the collect only copies: no
+ * libm call on the host, thousands of windows per block cost the host no arithmetic.  The trade: the device's log10
+ * is another implementation than the host's, so channel_power / global_power may differ from the host finish in
+ * their last bits (measured on MI355X against glibc 2.35: at most 2 units in the last place); -inf for a silent window, 0.0 at full scale, every
+ * peak, frames, rate, channels and every rc are exactly the same.
+ * The mode governs cmhip_batch_vu_snapshot and what collects it: cmhip_batch_vu_collect, _collect_begin / _end and
+ * cmhip_batch_vu_results.  Out of its reach, always finished on the host and bit-equal: cmhip_batch_vu_result (one
+ * stream), the per-launch windows of a meter behind a tee, cmhip_node_finish.
+ * COOLMIC_ERROR_INVAL for a batch without CMHIP_VU or an unknown value, COOLMIC_ERROR_BUSY while a snapshot is
+ * pending or a collect is under way.  The getter returns the mode, or a negative error. */
+#define CMHIP_VU_FINISH_HOST   0
+#define CMHIP_VU_FINISH_DEVICE 1
+int cmhip_batch_vu_set_finish(cmhip_batch_t *b, int where);
+int cmhip_batch_vu_get_finish(const cmhip_batch_t *b);
 /* raw accumulators of a stream (synchronises): power[16], peak[16], frames */
 int cmhip_batch_vu_raw(cmhip_batch_t *b, unsigned int stream, int64_t *power, int16_t *peak,
                        uint64_t *frames);

@@ -32,6 +32,7 @@ ERROR_INVAL, ERROR_NOMEM, ERROR_BUSY = -10, -11, -12
 OUT_PCM, OUT_F32, VU, INPLACE, EQ, HOSTPCM, EXTSLOTS = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 PLACE_SEARCH = 0x80
 GEN_NULL, GEN_SINE, GEN_NOISE = 0, 1, 2
+VU_FINISH_HOST, VU_FINISH_DEVICE = 0, 1
 NODE_WORDS = 34
 
 READ_FN = C.CFUNCTYPE(ssize_t, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -129,6 +130,8 @@ SIGNATURES = {
     "cmhip_batch_vu_collect_begin": (C.c_int, [_vp, _vp, _vp]),
     "cmhip_batch_vu_collect_end": (C.c_int, [_vp]),
     "cmhip_batch_vu_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_batch_vu_set_finish": (C.c_int, [_vp, C.c_int]),
+    "cmhip_batch_vu_get_finish": (C.c_int, [_vp]),
     "cmhip_batch_vu_raw": (C.c_int, [_vp, C.c_uint, _vp, _vp, _P(C.c_uint64)]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
@@ -208,6 +211,8 @@ SIGNATURES = {
     "coolmic_group_pump": (C.c_int, [_vp]),
     "coolmic_group_set_pull_threads": (C.c_int, [_vp, C.c_uint]),
     "coolmic_group_vumeter_result": (C.c_int, [_vp, C.c_uint, _P(VuResult)]),
+    "coolmic_group_vumeter_results": (C.c_int, [_vp, _vp, _vp]),
+    "coolmic_group_set_vu_finish": (C.c_int, [_vp, C.c_int]),
     "coolmic_group_streams": (C.c_uint, [_vp]),
 }
 MISSING = []        # entry points this build of the library lacks (an older build under tools/ab_two_libs.py)
@@ -230,6 +235,11 @@ if hasattr(lib, "cmhip_test_plan_run"):         # (not in builds older than the 
                                         C.c_void_p]
 lib.cmhip_test_merge_windows.restype = C.c_int
 lib.cmhip_test_merge_windows.argtypes = [_P(C.c_uint64), C.c_uint, C.c_uint, C.c_uint, _P(VuResult)]
+if hasattr(lib, "cmhip_test_unpack_finished"):  # (not in builds older than the device-side dB finish)
+    lib.cmhip_test_unpack_finished.restype = C.c_int
+    lib.cmhip_test_unpack_finished.argtypes = [_vp, C.c_uint, C.c_uint, C.c_uint, _vp, _vp]
+    lib.cmhip_test_power_db_device.restype = C.c_int
+    lib.cmhip_test_power_db_device.argtypes = [_vp, _vp, C.c_uint, _vp, _vp]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -307,6 +317,30 @@ def merge_windows(windows, channels, rate=48000):
     r = VuResult()
     rc = lib.cmhip_test_merge_windows(w.ctypes.data_as(_P(C.c_uint64)), w.shape[0], channels, rate, C.byref(r))
     return rc, r
+
+
+def unpack_finished(words, streams, channels, rate=48000, out=None):
+    """Test hook (host logic, needs no GPU): the collect's unpack of a device-finished snapshot record, uint64
+    [word][stream] as k_vu_finish writes it (csrc/k_misc.hip) -> (results, rc list).  `out`: a VuResult array to
+    unpack into (to see what is left alone)."""
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    out = out if out is not None else (VuResult * streams)()
+    rc = (C.c_int * streams)()
+    _check("unpack_finished", lib.cmhip_test_unpack_finished(w.ctypes.data, streams, channels, rate, out, rc))
+    return out, list(rc)
+
+
+def power_db_device(sums, counts, want_log=False):
+    """Test hook: the kernels' own dB finish (vu_power_db, csrc/k_misc.hip) over (sum, count) pairs on the GPU ->
+    float64 array of dB values (and, with want_log, the log10 values before the * 20)."""
+    s = np.ascontiguousarray(sums, dtype=np.uint64)
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    assert s.shape == c.shape and s.ndim == 1
+    db = np.empty(s.size, dtype=np.float64)
+    lg = np.empty(s.size, dtype=np.float64) if want_log else None
+    _check("power_db_device", lib.cmhip_test_power_db_device(s.ctypes.data, c.ctypes.data, s.size, db.ctypes.data,
+                                                             lg.ctypes.data if want_log else None))
+    return (db, lg) if want_log else db
 
 
 def sine_period(rate):
@@ -461,6 +495,13 @@ class Batch:
 
     def vu_collect_end(self):
         _check("vu_collect_end", lib.cmhip_batch_vu_collect_end(self.h))
+
+    def vu_set_finish(self, where):
+        """VU_FINISH_HOST / VU_FINISH_DEVICE for the snapshots to come; the error number (BUSY while one is pending)"""
+        return lib.cmhip_batch_vu_set_finish(self.h, where)
+
+    def vu_get_finish(self):
+        return lib.cmhip_batch_vu_get_finish(self.h)
 
     def vu_reset(self, stream=-1):
         _check("vu_reset", lib.cmhip_batch_vu_reset(self.h, stream))
@@ -887,6 +928,17 @@ class Group:
         r = VuResult()
         rc = lib.coolmic_group_vumeter_result(self.ptr, slot, C.byref(r))
         return rc, r
+
+    def vumeter_results(self, out=None):
+        """every slot's window in one snapshot and collect -> (VuResult array, rc list); `out`: the array to fill"""
+        n = self.streams()
+        out = out if out is not None else (VuResult * n)()
+        rc = (C.c_int * n)()
+        _check("group_vumeter_results", lib.coolmic_group_vumeter_results(self.ptr, out, rc))
+        return out, list(rc)
+
+    def set_vu_finish(self, where):
+        return lib.coolmic_group_set_vu_finish(self.ptr, where)
 
     def streams(self):
         return lib.coolmic_group_streams(self.ptr)

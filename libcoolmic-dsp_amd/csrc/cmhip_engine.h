@@ -93,8 +93,11 @@ struct cmhip_batch {
 
     // three snapshots may be pending (one being finished by the helper threads, one waiting, one on its way):
     // each a packed copy of a window set, [1 + 2C][S] words in pinned, device-mapped host memory that
-    // k_vu_pack writes itself (h_pack / d_pack: host / device view)
+    // k_vu_pack writes itself (h_pack / d_pack: host / device view).  With vu_finish == CMHIP_VU_FINISH_DEVICE
+    // k_vu_finish writes finished records there instead (never longer); the mode changes only while no snapshot
+    // is pending, so a slot is always read the way it was written.
     unsigned long long *h_pack[3], *d_pack[3];
+    int vu_finish = CMHIP_VU_FINISH_HOST;  // cmhip_batch_vu_set_finish
     unsigned int snap_set2[3];             // which of the three window sets the snapshot closed (its event: ev_reset)
     bool collecting;                       // between cmhip_batch_vu_collect_begin and _end
     coolmic_vumeter_result_t *job_out;

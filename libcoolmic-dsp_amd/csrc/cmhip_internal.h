@@ -161,6 +161,12 @@ hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t cha
 // (a set of windows -> [1 + 2C][streams] words in pinned, device-mapped host memory; clears the set)
 hipError_t launch_vu_pack(VuState *vu, uint32_t streams, uint32_t channels, uint32_t parity,
                           unsigned long long *dst_host_mapped, hipStream_t st, hipEvent_t ev_stop);
+// (the same with the dB finish on the device: finished doubles and int16 peaks, the layout stated at k_vu_finish)
+hipError_t launch_vu_finish(VuState *vu, uint32_t streams, uint32_t channels, uint32_t parity,
+                            unsigned long long *dst_host_mapped, hipStream_t st, hipEvent_t ev_stop);
+// (test hook: the device finish over n (sum, count) pairs in device memory; lg may be nullptr)
+hipError_t launch_test_power_db(const unsigned long long *sum, const unsigned long long *count, uint32_t n, double *db,
+                                double *lg, hipStream_t st);
 hipError_t launch_ceiling(int mode, const void *src, void *dst, size_t bytes,
                           unsigned long long *sink, hipStream_t st);
 

@@ -47,7 +47,8 @@ static int finish(unsigned long long frames, unsigned C, unsigned rate, const Wo
         out->channel_power[c] = power_db((unsigned long long)sum[c * stride], frames);
         out->channel_peak[c] = key_peak((unsigned long long)key[c * stride], shift);
     }
-    out->global_power = power_db(all, frames * C);
+    // (mono: the same arguments as channel 0, hence the same bits)
+    out->global_power = C == 1 ? out->channel_power[0] : power_db(all, frames * C);
     out->global_peak = key_peak(global_key, shift);
     return COOLMIC_ERROR_NONE;
 }
@@ -118,8 +119,14 @@ extern "C" int cmhip_batch_vu_snapshot(cmhip_batch_t *b)
         HIP_TRY(hipEventRecord(b->ev_main, b->stream));
         HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_main, 0));
     }
-    HIP_TRY(launch_vu_pack(b->d_vu2[i], b->d.streams, b->d.channels, b->parity, b->d_pack[slot], b->copy_stream,
-                           b->ev_reset[i]));
+    // (CMHIP_VU_FINISH_DEVICE: k_vu_finish in its place -- same stream, same event, same clear; the record
+    // holds finished dB doubles and peaks)
+    if (b->vu_finish == CMHIP_VU_FINISH_DEVICE)
+        HIP_TRY(launch_vu_finish(b->d_vu2[i], b->d.streams, b->d.channels, b->parity, b->d_pack[slot],
+                                 b->copy_stream, b->ev_reset[i]));
+    else
+        HIP_TRY(launch_vu_pack(b->d_vu2[i], b->d.streams, b->d.channels, b->parity, b->d_pack[slot],
+                               b->copy_stream, b->ev_reset[i]));
     b->snap_set2[slot] = i;
     b->reset_pending[i] = true;
     b->cur = (i + 1u) % 3u;
@@ -159,13 +166,46 @@ static unsigned pool_threads()
     return n;
 }
 
-// a packed snapshot is [word][stream]: samples, C sums, C keys
+// A record k_vu_finish wrote (the layout is stated there), [word][stream] over S streams, into a result: copies
+// only -- no libm call.  Out is left alone while the window holds no frame.
+static int unpack_finished(const unsigned long long *words, size_t S, size_t s, unsigned C, unsigned rate,
+                           coolmic_vumeter_result_t *out)
+{
+    const unsigned long long frames = words[s] / C;
+    if (frames == 0)
+        return COOLMIC_ERROR_INVAL;                      // ref: src/vumeter.c:198-199
+    memset(out, 0, sizeof(*out));
+    out->rate = rate;
+    out->channels = C;
+    out->frames = (size_t)frames;
+    const unsigned P = C == 1 ? 1u : C + 1u;             // power words: mono has no global word of its own
+    for (unsigned c = 0; c < C; c++) {
+        memcpy(&out->channel_power[c], &words[(1u + c) * S + s], sizeof(double));
+        out->channel_peak[c] = (int16_t)(words[(1u + P + c / 4u) * S + s] >> (16u * (c % 4u)));
+    }
+    if (C == 1)
+        out->global_power = out->channel_power[0];
+    else
+        memcpy(&out->global_power, &words[(1u + C) * S + s], sizeof(double));
+    out->global_peak = (int16_t)(words[(1u + P + C / 4u) * S + s] >> (16u * (C % 4u)));
+    return COOLMIC_ERROR_NONE;
+}
+
+// a packed snapshot is [word][stream]: samples, C sums, C keys -- or, finished on the device, what unpack_finished reads
 static void collect_body(void *p, unsigned lo, unsigned hi)
 {
     cmhip_batch_t *b = (cmhip_batch_t *)p;
     const unsigned C = b->d.channels;
     const size_t S = b->d.streams;
     const unsigned long long *pack = b->h_pack[b->job_slot];
+    if (b->vu_finish == CMHIP_VU_FINISH_DEVICE) {
+        for (unsigned s = lo; s < hi; s++) {
+            const int r = unpack_finished(pack, S, s, C, b->d.rate, &b->job_out[s]);
+            if (b->job_rc)
+                b->job_rc[s] = r;
+        }
+        return;
+    }
     for (unsigned s = lo; s < hi; s++) {
         const unsigned long long *sum = pack + S + s, *key = sum + C * S;
         const int r = finish(pack[s] / C, C, b->d.rate, sum, key, S, max_key(key, S, C), KEY_ABS_SHIFT, &b->job_out[s]);
@@ -226,6 +266,27 @@ extern "C" int cmhip_batch_vu_collect(cmhip_batch_t *b, coolmic_vumeter_result_t
 {
     const int r = cmhip_batch_vu_collect_begin(b, out, rc);
     return r != COOLMIC_ERROR_NONE ? r : cmhip_batch_vu_collect_end(b);
+}
+
+extern "C" int cmhip_batch_vu_set_finish(cmhip_batch_t *b, int where)
+{
+    if (!b)
+        return fail(COOLMIC_ERROR_FAULT, "vu_set_finish: batch is NULL");
+    if (!(b->d.flags & CMHIP_VU) || (where != CMHIP_VU_FINISH_HOST && where != CMHIP_VU_FINISH_DEVICE))
+        return fail(COOLMIC_ERROR_INVAL, "vu_set_finish: batch without VU, or unknown place %d", where);
+    if (b->snap_count || b->collecting)      // a pending snapshot is read the way it was written
+        return fail(COOLMIC_ERROR_BUSY, "vu_set_finish: %u snapshot(s) wait to be collected", b->snap_count);
+    b->vu_finish = where;
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_batch_vu_get_finish(const cmhip_batch_t *b)
+{
+    if (!b)
+        return fail(COOLMIC_ERROR_FAULT, "vu_get_finish: batch is NULL");
+    if (!(b->d.flags & CMHIP_VU))
+        return fail(COOLMIC_ERROR_INVAL, "vu_get_finish: batch without VU");
+    return b->vu_finish;
 }
 
 extern "C" int cmhip_batch_vu_results(cmhip_batch_t *b, coolmic_vumeter_result_t *out, int *rc)
@@ -400,6 +461,51 @@ extern "C" int cmhip_test_merge_windows(const uint64_t *windows, unsigned int co
         cmhip_vu_raw_merge(&acc, &w, channels);
     }
     return cmhip_vu_raw_finish(&acc, channels, rate, out);
+}
+
+// test hook (host logic, needs no GPU): the unpack of a device-finished record the caller made up, [word][stream]
+// over `streams` streams of `channels` channels
+extern "C" int cmhip_test_unpack_finished(const uint64_t *words, unsigned int streams, unsigned int channels,
+                                          unsigned int rate, coolmic_vumeter_result_t *out, int *rc)
+{
+    if (!words || !out)
+        return COOLMIC_ERROR_FAULT;
+    if (channels == 0 || channels > MAX_CH)
+        return COOLMIC_ERROR_INVAL;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "a record's word");
+    for (unsigned int s = 0; s < streams; s++) {
+        const int r = unpack_finished((const unsigned long long *)words, streams, s, channels, rate, &out[s]);
+        if (rc)
+            rc[s] = r;
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+// test hook: the kernels' own __device__ finish (vu_power_db, k_misc.hip) over n (sum, count) pairs on the default
+// device; out_log (may be NULL) takes log10(...) before the * 20, so that a deviation can be put to a stage
+extern "C" int cmhip_test_power_db_device(const uint64_t *sum, const uint64_t *count, unsigned int n, double *out_db,
+                                          double *out_log)
+{
+    if (!sum || !count || !out_db)
+        return fail(COOLMIC_ERROR_FAULT, "test_power_db_device: NULL argument");
+    if (n == 0)
+        return COOLMIC_ERROR_NONE;
+    HIP_TRY(hipSetDevice(coolmic_hip_default_device()));
+    const size_t bytes = (size_t)n * 8u;
+    unsigned long long *d = nullptr;                     // sums, counts, dB values, logarithms
+    HIP_TRY(hipMalloc((void **)&d, 4u * bytes));
+    hipError_t e = hipMemcpy(d, sum, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(d + n, count, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = launch_test_power_db(d, d + n, n, (double *)(d + 2u * (size_t)n), (double *)(d + 3u * (size_t)n), nullptr);
+    if (e == hipSuccess)
+        e = hipMemcpy(out_db, d + 2u * (size_t)n, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_log)
+        e = hipMemcpy(out_log, d + 3u * (size_t)n, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(e);
+    return COOLMIC_ERROR_NONE;
 }
 
 // ---------------------------------------------------------------------------

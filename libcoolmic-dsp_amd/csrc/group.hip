@@ -59,6 +59,8 @@ struct coolmic_group {
     std::vector<uint32_t> *flight;           // ... of the block on the GPU
     bool in_flight;                          // a block's launch is queued
     WorkPool *pullers;                       // helpers for the pull of a pump (coolmic_group_set_pull_threads)
+    std::vector<coolmic_vumeter_result_t> *vu_out;   // coolmic_group_vumeter_results of a group that is not full:
+    std::vector<int> *vu_rc;                 // the engine's max_streams results and codes (made on first use)
 };
 
 struct GroupHandle {
@@ -70,6 +72,8 @@ static void group_destroy(void *self)
 {
     coolmic_group_t *g = (coolmic_group_t *)self;
     delete g->pullers;
+    delete g->vu_out;
+    delete g->vu_rc;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -498,4 +502,39 @@ extern "C" int coolmic_group_vumeter_result(coolmic_group_t *self, unsigned int 
     if (slot >= self->streams->size())
         return COOLMIC_ERROR_INVAL;
     return cmhip_batch_vu_result(self->batch, slot, result);
+}
+
+extern "C" int coolmic_group_vumeter_results(coolmic_group_t *self, coolmic_vumeter_result_t *results, int *rc)
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return cmhip_batch_vu_results(self->batch, results, rc);
+    if (!self->vu_rc) {
+        try {
+            if (!self->vu_out)
+                self->vu_out = new std::vector<coolmic_vumeter_result_t>(self->max_streams);
+            self->vu_rc = new std::vector<int>(self->max_streams);
+        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
+            return COOLMIC_ERROR_NOMEM;
+        }
+    }
+    const int r = cmhip_batch_vu_results(self->batch, self->vu_out->data(), self->vu_rc->data());
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        if ((*self->vu_rc)[i] == COOLMIC_ERROR_NONE)
+            results[i] = (*self->vu_out)[i];
+        if (rc)
+            rc[i] = (*self->vu_rc)[i];
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int coolmic_group_set_vu_finish(coolmic_group_t *self, int where)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_vu_set_finish(self->batch, where);
 }

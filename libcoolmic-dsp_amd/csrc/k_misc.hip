@@ -1,5 +1,5 @@
-// k_misc.hip -- small kernels beside the path: synthetic inputs, the node-global VU partial,
-// plain HBM ceilings.
+// k_misc.hip -- small kernels beside the path: synthetic inputs, the node-global VU partial, the snapshot of a
+// window set (raw, or with the dB finish done on the device), plain HBM ceilings.
 #include "cmhip_device.h"
 
 namespace cmhip {
@@ -226,6 +226,110 @@ hipError_t launch_vu_pack(VuState *vu, u32 streams, u32 channels, u32 parity, un
     else
         hipExtLaunchKernelGGL(k_vu_pack<MAX_CH>, dim3(grid), dim3(64), 0, st, nullptr, ev_stop, 0, vu, streams, channels,
                               parity, dst_host_mapped);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The same snapshot with the dB finish done here (CMHIP_VU_FINISH_DEVICE): instead of raw sums and keys the
+// record carries what coolmic_vumeter_result_t wants, [word][stream] like k_vu_pack's and never longer:
+//   [0]                  samples accounted (the host divides by C and refuses a window without a frame)
+//   [1, 1 + C)           channel_power[c], the double's bits
+//   [1 + C]              global_power -- C > 1 only: for mono it has channel 0's arguments, hence its bits
+//   then ceil((C + 1) / 4) words of int16 peaks, four to a word from bit 0 up: channel 0 .. C - 1, global
+// (P = 1 for mono, C + 1 otherwise, is the number of power words below.)
+
+// power_db of cmhip_vu.hip, operation for operation: integer mean, to double, sqrt, / 32768, log10, * 20, capped at
+// 0 -- all in double, nothing fused (-ffp-contract=off).  lg, if not null, takes the logarithm before the * 20.
+__device__ double vu_power_db(u64 sum, u64 count, double *lg)
+{
+    double p = (double)(sum / count);
+    p = log10(sqrt(p) / 32768.);
+    if (lg)
+        *lg = p;
+    return fmin(20. * p, 0.);
+}
+
+__device__ __forceinline__ u64 vu_key_peak16(u64 key)
+{
+    const int mag = (int)(key >> KEY_ABS_SHIFT);
+    return (u64)(uint16_t)(int16_t)((key & 1ull) ? -mag : mag);
+}
+
+// One lane per stream, as k_vu_pack: the global power needs every channel's sum and the clear of the window belongs
+// to whoever read it last, so a stream's C + 1 logarithms stay in one lane and the stores stay whole lines.
+template <u32 NC>
+__global__ __launch_bounds__(64) void k_vu_finish(VuState *vu, u32 streams, u32 channels, u32 parity, u64 *dst)
+{
+    const u32 s = blockIdx.x * 64u + threadIdx.x;
+    if (s >= streams)
+        return;
+    VuState *v = vu + s;
+    const u64 samples = v->samples[parity];
+    const u64 frames = NC == 1 ? samples : samples / channels;
+    const u32 P = NC == 1 ? 1u : channels + 1u;
+    dst[s] = samples;
+    u64 all = 0, best = 0, peaks = 0;
+#pragma unroll
+    for (u32 c = 0; c < NC; c++) {
+        if (c < channels) {
+            const u64 sum = v->power[c], key = v->key[c];
+            all += sum;
+            best = key > best ? key : best;
+            const double db = frames ? vu_power_db(sum, frames, nullptr) : 0.;
+            dst[(u64)(1u + c) * streams + s] = (u64)__double_as_longlong(db);
+            peaks |= vu_key_peak16(key) << (16u * (c & 3u));
+            if ((c & 3u) == 3u) {
+                dst[(u64)(1u + P + (c >> 2)) * streams + s] = peaks;
+                peaks = 0;
+            }
+            v->power[c] = 0;
+            v->key[c] = 0;
+        }
+    }
+    if (NC > 1) {
+        const double db = frames ? vu_power_db(all, frames * channels, nullptr) : 0.;
+        dst[(u64)(1u + channels) * streams + s] = (u64)__double_as_longlong(db);
+    }
+    peaks |= vu_key_peak16(best) << (16u * (channels & 3u));
+    dst[(u64)(1u + P + (channels >> 2)) * streams + s] = peaks;
+    v->samples[0] = 0;
+    v->samples[1] = 0;
+}
+
+hipError_t launch_vu_finish(VuState *vu, u32 streams, u32 channels, u32 parity, unsigned long long *dst_host_mapped,
+                            hipStream_t st, hipEvent_t ev_stop)
+{
+    const u32 grid = (streams + 63u) / 64u;
+    if (channels == 1)
+        hipExtLaunchKernelGGL(k_vu_finish<1>, dim3(grid), dim3(64), 0, st, nullptr, ev_stop, 0, vu, streams, channels,
+                              parity, dst_host_mapped);
+    else if (channels == 2)
+        hipExtLaunchKernelGGL(k_vu_finish<2>, dim3(grid), dim3(64), 0, st, nullptr, ev_stop, 0, vu, streams, channels,
+                              parity, dst_host_mapped);
+    else
+        hipExtLaunchKernelGGL(k_vu_finish<MAX_CH>, dim3(grid), dim3(64), 0, st, nullptr, ev_stop, 0, vu, streams,
+                              channels, parity, dst_host_mapped);
+    return hipGetLastError();
+}
+
+// test hook's kernel: vu_power_db over n (sum, count) pairs in device memory (a count of 0 gives NaN)
+__global__ __launch_bounds__(256) void k_test_power_db(const u64 *sum, const u64 *count, u32 n, double *db, double *lg)
+{
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n)
+        return;
+    double l = __longlong_as_double(0x7ff8000000000000ll);
+    db[i] = count[i] ? vu_power_db(sum[i], count[i], &l) : l;
+    if (lg)
+        lg[i] = l;
+}
+
+hipError_t launch_test_power_db(const unsigned long long *sum, const unsigned long long *count, u32 n, double *db,
+                                double *lg, hipStream_t st)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_test_power_db, dim3((n + 255u) / 256u), dim3(256), 0, st, sum, count, n, db, lg);
     return hipGetLastError();
 }
 
