@@ -110,6 +110,21 @@ int                 coolmic_group_vumeter_results(coolmic_group_t *self, coolmic
  * coolmic_group_vumeter_result() for one slot is finished on the host either way. */
 int                 coolmic_group_set_vu_finish(coolmic_group_t *self, int where);
 
+/* True peak (ITU-R BS.1770 Annex 2, 4x oversampling) of every stream, opt-in: cmhip_batch_set_true_peak() of
+ * <coolmic_hip.h> on the group's engine, with its return values.  While it is on every block runs the true-peak
+ * kernel ahead of the block kernel; the group's blocks lie in host memory, so the input set is read a SECOND time
+ * over PCIe -- that read is the cost of the group form.  The filter measures the transformed stream (map, gain,
+ * saturation), not the equaliser's result: coolmic_group_set_eq() with sections returns COOLMIC_ERROR_INVAL while
+ * true peak is on, and turning it on does while the group's equaliser has sections. */
+int                 coolmic_group_set_true_peak(coolmic_group_t *self, int on);
+/* One slot's true-peak window since its last result, and all of them at once (results[] and rc[], which may be
+ * NULL, have coolmic_group_streams() entries): the slot handling and the per-slot contract of
+ * coolmic_group_vumeter_result(s) -- COOLMIC_ERROR_INVAL with the result left alone for a window without a frame,
+ * the window closed after everything pumped so far, the block in flight included.  The true-peak windows are
+ * independent of the VU windows; a host that wants them aligned asks for both between the same two pumps. */
+int                 coolmic_group_true_peak(coolmic_group_t *self, unsigned int slot, coolmic_truepeak_result_t *result);
+int                 coolmic_group_true_peaks(coolmic_group_t *self, coolmic_truepeak_result_t *results, int *rc);
+
 unsigned int        coolmic_group_streams(coolmic_group_t *self);
 
 #ifdef __cplusplus

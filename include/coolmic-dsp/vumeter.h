@@ -56,6 +56,22 @@ int                 coolmic_vumeter_result(coolmic_vumeter_t *self,
  * $COOLMIC_HIP_DEVICE, else 0. */
 int                 coolmic_vumeter_set_device(coolmic_vumeter_t *self, int device);
 
+/* Result of one true-peak window (ITU-R BS.1770 Annex 2 / EBU R128: the maximum of the 4x oversampled signal), as
+ * the batch engine (cmhip_batch_tp_result, <coolmic_hip.h>) and the group (coolmic_group_true_peak, group.h) report
+ * it; the per-stream coolmic_vumeter_t does not measure it.  Peaks are magnitudes of the integer filter's output in
+ * units of 2^-28 of full scale (268435456 = 8192 * 32768 is 0 dBTP; the largest possible value is 542986257);
+ * the dBTP values are 20 * log10(peak / 268435456.) in double, NOT capped at 0 (true peak may reach +6.12 dBTP),
+ * -inf for a silent window.  224 bytes on LP64. */
+typedef struct {
+    uint_least32_t rate;
+    unsigned int channels;
+    size_t frames;
+    uint32_t global_peak;
+    uint32_t channel_peak[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
+    double global_dbtp;
+    double channel_dbtp[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
+} coolmic_truepeak_result_t;
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,38 @@ int cmhip_batch_vu_get_finish(const cmhip_batch_t *b);
 int cmhip_batch_vu_raw(cmhip_batch_t *b, unsigned int stream, int64_t *power, int16_t *peak,
                        uint64_t *frames);
 
+/* ---- true peak (ITU-R BS.1770 Annex 2 / EBU R128), opt-in ------------------- */
+/* The maximum of the 4x oversampled TRANSFORMED stream (after channel map, gain and saturation: the samples the VU
+ * window accounts and CMHIP_OUT_PCM writes), by the 48-tap polyphase FIR whose int16 coefficients, in units of
+ * 2^-13, cmhip_tp_coefficients() returns: y_p[n] = sum_{k<12} H[p][k] * x[n-k], p = 0..3, in exact int32.  A window's
+ * value per channel is max |y_p[n]| over p and the frames accounted since it opened; 268435456 (2^28) is full scale.
+ * The filter belongs to the stream, not to the window: its history (the last 11 transformed frames per channel) is
+ * zero when true peak is turned on and after cmhip_batch_tp_reset, and is kept across runs AND across window closes;
+ * a change of gain or map does not touch it.  A stream that gets 0 frames in a run keeps history and window.
+ * The filter runs 4x whatever `rate` says: Annex 2's lower factors for rates of 96 kHz and above are not applied.
+ *
+ * cmhip_batch_set_true_peak(b, 1), between runs (it waits for the batch's stream), allocates the state on first use
+ * and opens empty windows with zero history; from then on every cmhip_batch_run / _run_slots launches the true-peak
+ * kernel on the batch's stream AHEAD of the block kernel (it reads the run's input slots and applies map and gain
+ * itself).  (b, 0) stops that and discards windows and history.  True peak of the equaliser's result is not
+ * measured: COOLMIC_ERROR_INVAL while the batch's equaliser has sections, and cmhip_batch_set_eq with nsec > 0
+ * returns COOLMIC_ERROR_INVAL while true peak is on (nsec == 0 stays allowed).
+ * The result calls follow their VU counterparts: COOLMIC_ERROR_INVAL with `out` left alone for a window without a
+ * frame (per stream in rc[] for _results, rc may be NULL) and for a batch without true peak; the window is closed on
+ * success, by these calls only -- the true-peak windows are independent of the VU windows (ask for both between the
+ * same two runs for aligned windows).  One device round trip serves all streams; the dBTP doubles are finished on
+ * the host with cmhip_tp_dbtp.  cmhip_batch_tp_reset clears window AND history (stream -1: all).
+ * cmhip_batch_timing keeps bracketing the block kernel only. */
+int    cmhip_batch_set_true_peak(cmhip_batch_t *b, int on);
+int    cmhip_batch_get_true_peak(const cmhip_batch_t *b);     /* 0 / 1, negative error */
+int    cmhip_batch_tp_result(cmhip_batch_t *b, unsigned int stream, coolmic_truepeak_result_t *out);
+int    cmhip_batch_tp_results(cmhip_batch_t *b, coolmic_truepeak_result_t *out, int *rc);
+int    cmhip_batch_tp_reset(cmhip_batch_t *b, long stream);
+/* the host finish, no device needed: 20. * log10((double)peak / 268435456.) -- not capped at 0, -inf for 0 */
+double cmhip_tp_dbtp(uint32_t peak);
+/* the filter, no device needed: H[0..3] in order, 12 taps each */
+void   cmhip_tp_coefficients(int16_t h[48]);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

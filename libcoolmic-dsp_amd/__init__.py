@@ -55,6 +55,20 @@ class VuResult(C.Structure):
                 "channel_power": [self.channel_power[i] for i in range(ch)]}
 
 
+class TruePeakResult(C.Structure):
+    """coolmic_truepeak_result_t (include/coolmic-dsp/vumeter.h): peaks in units of 2^-28 of full scale"""
+    _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t),
+                ("global_peak", C.c_uint32), ("channel_peak", C.c_uint32 * MAX_CH),
+                ("global_dbtp", C.c_double), ("channel_dbtp", C.c_double * MAX_CH)]
+
+    def as_dict(self):
+        ch = self.channels
+        return {"rate": self.rate, "channels": ch, "frames": self.frames,
+                "global_peak": self.global_peak, "global_dbtp": self.global_dbtp,
+                "channel_peak": [self.channel_peak[i] for i in range(ch)],
+                "channel_dbtp": [self.channel_dbtp[i] for i in range(ch)]}
+
+
 class BatchDesc(C.Structure):
     _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint),
                 ("rate", C.c_uint), ("max_frames", C.c_size_t), ("flags", C.c_uint),
@@ -133,6 +147,13 @@ SIGNATURES = {
     "cmhip_batch_vu_set_finish": (C.c_int, [_vp, C.c_int]),
     "cmhip_batch_vu_get_finish": (C.c_int, [_vp]),
     "cmhip_batch_vu_raw": (C.c_int, [_vp, C.c_uint, _vp, _vp, _P(C.c_uint64)]),
+    "cmhip_batch_set_true_peak": (C.c_int, [_vp, C.c_int]),
+    "cmhip_batch_get_true_peak": (C.c_int, [_vp]),
+    "cmhip_batch_tp_result": (C.c_int, [_vp, C.c_uint, _P(TruePeakResult)]),
+    "cmhip_batch_tp_results": (C.c_int, [_vp, _vp, _vp]),
+    "cmhip_batch_tp_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_tp_dbtp": (C.c_double, [C.c_uint32]),
+    "cmhip_tp_coefficients": (None, [_vp]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -213,6 +234,9 @@ SIGNATURES = {
     "coolmic_group_vumeter_result": (C.c_int, [_vp, C.c_uint, _P(VuResult)]),
     "coolmic_group_vumeter_results": (C.c_int, [_vp, _vp, _vp]),
     "coolmic_group_set_vu_finish": (C.c_int, [_vp, C.c_int]),
+    "coolmic_group_set_true_peak": (C.c_int, [_vp, C.c_int]),
+    "coolmic_group_true_peak": (C.c_int, [_vp, C.c_uint, _P(TruePeakResult)]),
+    "coolmic_group_true_peaks": (C.c_int, [_vp, _vp, _vp]),
     "coolmic_group_streams": (C.c_uint, [_vp]),
 }
 MISSING = []        # entry points this build of the library lacks (an older build under tools/ab_two_libs.py)
@@ -240,6 +264,11 @@ if hasattr(lib, "cmhip_test_unpack_finished"):  # (not in builds older than the 
     lib.cmhip_test_unpack_finished.argtypes = [_vp, C.c_uint, C.c_uint, C.c_uint, _vp, _vp]
     lib.cmhip_test_power_db_device.restype = C.c_int
     lib.cmhip_test_power_db_device.argtypes = [_vp, _vp, C.c_uint, _vp, _vp]
+if hasattr(lib, "cmhip_test_plan_tpeak"):       # (not in builds older than true peak)
+    lib.cmhip_test_plan_tpeak.restype = None
+    lib.cmhip_test_plan_tpeak.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.cmhip_debug_tp_count.restype = C.c_ulonglong
+    lib.cmhip_debug_tp_count.argtypes = []
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -292,6 +321,31 @@ class RunPlan(C.Structure):
     _fields_ = [(name, C.c_int if name == "err" else C.c_uint32)
                 for name in ("err", "family", "channels", "tile_u", "waves", "map", "stage", "grid", "block",
                              "chunks", "W", "rows_per_tile", "keep_flag")]
+
+
+class TpPlan(C.Structure):
+    """cmhip::TpPlan (csrc/cmhip_internal.h): what the true-peak launcher launches for a run"""
+    _fields_ = [("err", C.c_int), ("fast", C.c_uint32), ("grid", C.c_uint32), ("block", C.c_uint32),
+                ("chunks", C.c_uint32)]
+
+
+def plan_tpeak(streams, channels, frames):
+    """Test hook: the true-peak launcher's plan for a run (host logic, needs no GPU)"""
+    p = TpPlan()
+    lib.cmhip_test_plan_tpeak(streams, channels, frames, C.addressof(p))
+    return p
+
+
+def tp_dbtp(peak):
+    """the host finish of a true-peak value: 20 * log10(peak / 2^28), -inf for 0"""
+    return lib.cmhip_tp_dbtp(peak)
+
+
+def tp_coefficients():
+    """the 4 x 12 int16 coefficients of the true-peak filter, in units of 2^-13"""
+    h = np.zeros(48, dtype=np.int16)
+    lib.cmhip_tp_coefficients(h.ctypes.data)
+    return h.reshape(4, 12)
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -505,6 +559,28 @@ class Batch:
 
     def vu_reset(self, stream=-1):
         _check("vu_reset", lib.cmhip_batch_vu_reset(self.h, stream))
+
+    # true peak (opt-in)
+    def set_true_peak(self, on):
+        """the error number (INVAL while the equaliser has sections)"""
+        return lib.cmhip_batch_set_true_peak(self.h, int(bool(on)))
+
+    def get_true_peak(self):
+        return lib.cmhip_batch_get_true_peak(self.h)
+
+    def tp_result(self, stream):
+        r = TruePeakResult()
+        rc = lib.cmhip_batch_tp_result(self.h, stream, C.byref(r))
+        return rc, r
+
+    def tp_results(self):
+        out = (TruePeakResult * self.streams)()
+        rc = (C.c_int * self.streams)()
+        _check("tp_results", lib.cmhip_batch_tp_results(self.h, out, rc))
+        return out, list(rc)
+
+    def tp_reset(self, stream=-1):
+        _check("tp_reset", lib.cmhip_batch_tp_reset(self.h, stream))
 
     def vu_raw(self, stream):
         power = np.zeros(MAX_CH, dtype=np.int64)
@@ -939,6 +1015,22 @@ class Group:
 
     def set_vu_finish(self, where):
         return lib.coolmic_group_set_vu_finish(self.ptr, where)
+
+    def set_true_peak(self, on):
+        return lib.coolmic_group_set_true_peak(self.ptr, int(bool(on)))
+
+    def true_peak(self, slot):
+        r = TruePeakResult()
+        rc = lib.coolmic_group_true_peak(self.ptr, slot, C.byref(r))
+        return rc, r
+
+    def true_peaks(self, out=None):
+        """every slot's true-peak window at once -> (TruePeakResult array, rc list); `out`: the array to fill"""
+        n = self.streams()
+        out = out if out is not None else (TruePeakResult * n)()
+        rc = (C.c_int * n)()
+        _check("group_true_peaks", lib.coolmic_group_true_peaks(self.ptr, out, rc))
+        return out, list(rc)
 
     def streams(self):
         return lib.coolmic_group_streams(self.ptr)

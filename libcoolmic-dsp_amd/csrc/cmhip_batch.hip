@@ -212,6 +212,8 @@ extern "C" void cmhip_batch_free(cmhip_batch_t *b)
     (void)hipFree(b->d_sink);
     (void)hipFree(b->d_node_scratch);
     (void)hipFree(b->d_ring);
+    (void)hipFree(b->d_tp_peak);
+    (void)hipFree(b->d_tp_hist);
     if (b->h_ring)
         (void)hipHostFree(b->h_ring);
     for (int i = 0; i < 3; i++)
@@ -456,6 +458,8 @@ extern "C" int cmhip_batch_set_eq(cmhip_batch_t *b, long stream, unsigned int ns
         return fail(COOLMIC_ERROR_INVAL, "set_eq: at most %u sections", MAX_EQ);
     if (stream >= (long)b->d.streams || stream < -1)
         return fail(COOLMIC_ERROR_INVAL, "set_eq: stream %ld out of range", stream);
+    if (nsec && b->tp_on)
+        return fail(COOLMIC_ERROR_INVAL, "set_eq: true peak is on, and it does not measure the equaliser's result");
     if (stream >= 0 && nsec != b->nsec)
         return fail(COOLMIC_ERROR_INVAL,
                     "set_eq: the section count is a batch property (%u); set it with stream -1",
@@ -939,6 +943,16 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
                                           frames_per_stream ? b->d_nframes : nullptr, vu ? window : nullptr, parity);
         a.done_flag = flag;
         a.done_seq = flag_seq;
+        // True peak, when the batch has it on (then the equaliser has no sections: this branch): a pass of its own
+        // over the input slots, queued AHEAD of the block kernel.  The stream runs the two in order, so the end of
+        // the block kernel -- its completion flag included -- still marks the end of both.  (A run the block
+        // kernels' plan refuses launches nothing, this pass included.)
+        if (b->tp_on) {
+            if (plan_run(a).err != hipSuccess)
+                return fail(COOLMIC_ERROR_GENERIC, "run: the grid would reach 2^31 workgroups");
+            if (cmhip_engine_tp_run(b, slots_in, frames, frames_per_stream))
+                return COOLMIC_ERROR_GENERIC;
+        }
         HIP_TRY(launch_run(a, b->stream, ev.a, ev.b, &flagged));
         b->in_flight = true;
     }

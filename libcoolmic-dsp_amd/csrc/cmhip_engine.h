@@ -2,6 +2,7 @@
 //   cmhip_batch.hip    the object, parameters, transfers, the run
 //   cmhip_place.hip    the opt-in placement search for a batch's two PCM arrays
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
+//   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
 #pragma once
@@ -117,6 +118,14 @@ struct cmhip_batch {
     // hipMalloc put them -- are the input and the output
     cmhip_placement_t place = {0, 2, 0, 1, 0, 0, 0, 0, 0, 0};
     bool vu_off;                           // runs leave the windows alone for now (cmhip_batch_vu_pause)
+
+    // true peak (cmhip_tp.hip), all of it unused until cmhip_batch_set_true_peak(b, 1)
+    bool tp_on = false;
+    uint32_t *d_tp_peak = nullptr;         // [S][16] window maxima of |y|
+    int16_t *d_tp_hist = nullptr;          // [2][S][16][11] the streams' filter history, slot tp_parity current
+    unsigned int tp_parity = 0;
+    std::vector<unsigned long long> tp_frames;   // frames accounted per stream since its window opened
+    std::vector<uint32_t> tp_host;         // [S][16] staging of a result call
 };
 
 
@@ -134,6 +143,10 @@ CMHIP_INTERNAL int cmhip_engine_flush_params(cmhip_batch_t *b);
 // windows, or nullptr); the completion flag is left to the caller
 CMHIP_INTERNAL RunArgs cmhip_engine_run_args(const cmhip_batch_t *b, const int16_t *in, int16_t *out, size_t frames,
                                              const uint32_t *nframes, VuState *window, uint32_t parity);
+// cmhip_tp.hip: the true-peak pass of a run over `in`, queued on the batch's stream ahead of the block kernel
+// (only called while b->tp_on; frames_per_stream: the run's host array or nullptr, already uploaded to d_nframes)
+CMHIP_INTERNAL int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
+                                       const uint32_t *frames_per_stream);
 // cmhip_place.hip: called once, at the end of a batch's creation, when it has PCM arrays of its own
 CMHIP_INTERNAL int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes);
 // cmhip_vu.hip (for node.hip): the node record of the batch's windows, built on the copy stream

@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip (the gfx950 kernels) and cmhip_batch.hip (the engine).
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip (the gfx950 kernels) and cmhip_batch.hip (the engine).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -118,6 +118,35 @@ struct EqArgs {
     uint32_t       done_seq;
 };
 
+// True peak (ITU-R BS.1770 Annex 2, 4x oversampling): a 48-tap polyphase FIR over the TRANSFORMED stream (map,
+// gain, saturation -- the samples the VU window accounts), coefficients in units of 2^-13.  Row p of TP_H is phase
+// p: y_p[n] = sum_k TP_H[p][k] * x[n - k]; rows 2 and 3 are rows 1 and 0 reversed.  sum|h| <= 16571 per row, so
+// |y| <= 16571 * 32768 < 2^31: int32 accumulators are exact.  (k_tpeak.hip; cmhip_tp.hip hands the table out.)
+constexpr unsigned TP_TAPS = 12;
+constexpr unsigned TP_HIST = TP_TAPS - 1;      // frames of history a stream keeps per channel
+constexpr int16_t TP_P0[TP_TAPS] = {14, 90, -161, 272, -487, 1125, 7964, -838, 390, -218, 122, -68};
+constexpr int16_t TP_P1[TP_TAPS] = {-239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155};
+constexpr int16_t tp_h(unsigned p, unsigned k)
+{
+    return p == 0 ? TP_P0[k] : p == 1 ? TP_P1[k] : p == 2 ? TP_P1[TP_TAPS - 1 - k] : TP_P0[TP_TAPS - 1 - k];
+}
+
+struct TpArgs {
+    const int16_t *in;             // the run's INPUT slots: the kernel applies map and gain itself
+    const StreamParam *param;
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    uint32_t      *peak;           // [S][MAX_CH] window maxima of |y|
+    // [2][S][MAX_CH][TP_HIST] the last 11 transformed frames per channel, oldest first.  Two slots: a run reads slot
+    // `parity`, the stream's last tile writes slot `parity ^ 1` (as VuState::samples); the host flips parity per run.
+    int16_t       *hist;
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       parity;
+    uint64_t       stride;         // samples between stream slots (multiple of 8)
+    uint32_t       chunks;         // tiles per stream (the launcher fills it in)
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -153,6 +182,16 @@ hipError_t launch_run(const RunArgs &a, hipStream_t st, hipEvent_t ev_start = nu
 hipError_t prepare_eq(int device);
 hipError_t launch_eq(const EqArgs &a, hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
                      bool *flagged = nullptr);
+// True peak (k_tpeak.hip): the kernel of a run and its grid.  fast: the mono / stereo kernel (one wave per 8 KiB tile);
+// otherwise the any-channel-count kernel (one workgroup per 1024 frames).
+struct TpPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   fast;
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+    uint32_t   chunks;             // TpArgs::chunks: tiles per stream
+};
+TpPlan plan_tpeak(const TpArgs &a);
+hipError_t launch_tpeak(const TpArgs &a, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

@@ -61,6 +61,8 @@ struct coolmic_group {
     WorkPool *pullers;                       // helpers for the pull of a pump (coolmic_group_set_pull_threads)
     std::vector<coolmic_vumeter_result_t> *vu_out;   // coolmic_group_vumeter_results of a group that is not full:
     std::vector<int> *vu_rc;                 // the engine's max_streams results and codes (made on first use)
+    std::vector<coolmic_truepeak_result_t> *tp_out;  // the same for coolmic_group_true_peaks
+    std::vector<int> *tp_rc;
 };
 
 struct GroupHandle {
@@ -74,6 +76,8 @@ static void group_destroy(void *self)
     delete g->pullers;
     delete g->vu_out;
     delete g->vu_rc;
+    delete g->tp_out;
+    delete g->tp_rc;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -537,4 +541,50 @@ extern "C" int coolmic_group_set_vu_finish(coolmic_group_t *self, int where)
     if (!self)
         return COOLMIC_ERROR_FAULT;
     return cmhip_batch_vu_set_finish(self->batch, where);
+}
+
+// True peak: thin wrappers over the engine (cmhip_tp.hip).  The group's blocks lie in host memory, so the true-peak
+// kernel's pass reads the input set a second time over PCIe.
+extern "C" int coolmic_group_set_true_peak(coolmic_group_t *self, int on)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_set_true_peak(self->batch, on);
+}
+
+extern "C" int coolmic_group_true_peak(coolmic_group_t *self, unsigned int slot, coolmic_truepeak_result_t *result)
+{
+    if (!self || !result)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= self->streams->size())
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_tp_result(self->batch, slot, result);
+}
+
+extern "C" int coolmic_group_true_peaks(coolmic_group_t *self, coolmic_truepeak_result_t *results, int *rc)
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return cmhip_batch_tp_results(self->batch, results, rc);
+    if (!self->tp_rc) {
+        try {
+            if (!self->tp_out)
+                self->tp_out = new std::vector<coolmic_truepeak_result_t>(self->max_streams);
+            self->tp_rc = new std::vector<int>(self->max_streams);
+        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
+            return COOLMIC_ERROR_NOMEM;
+        }
+    }
+    const int r = cmhip_batch_tp_results(self->batch, self->tp_out->data(), self->tp_rc->data());
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        if ((*self->tp_rc)[i] == COOLMIC_ERROR_NONE)
+            results[i] = (*self->tp_out)[i];
+        if (rc)
+            rc[i] = (*self->tp_rc)[i];
+    }
+    return COOLMIC_ERROR_NONE;
 }
