@@ -1,15 +1,20 @@
 // cmhip_device.h -- device-side helpers shared by the kernel files: exact gain arithmetic on packed
-// int16, the VU window key, DPP wave reductions.  (Included by k_block.hip, k_eq.hip, k_misc.hip.)
+// int16, tile edges (a stream's extent, its ragged last vector), the VU window position, key and peak lookups,
+// DPP wave reductions.  (Included by k_block.hip, k_eq.hip, k_misc.hip, k_tpeak.hip.)
 #ifndef CMHIP_DEVICE_H
 #define CMHIP_DEVICE_H
 
 #include "cmhip_internal.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace cmhip {
 
 using u32 = uint32_t;
 using u64 = unsigned long long;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 
 __device__ __forceinline__ u32 uniform(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -121,6 +126,151 @@ __device__ __forceinline__ u32 gain2_identity(u32 w, u32 &out)
     return pk_sub(w ^ sg, sg);
 }
 
+// the scalar form of gain2, in plain integers, for the places that take samples one by one: floor(|x| * gain /
+// scale) = |x| * mi + mulhi(|x|, mf), saturated at 32767 / -32768
+__device__ __forceinline__ int gain1(int x, u32 mi, u32 mf)
+{
+    const u32 neg = x < 0 ? 1u : 0u;
+    const u32 ax = (u32)(neg ? -x : x);
+    u32 q = ax * mi + __umulhi(ax, mf);              // < 2^31: 32768 * 65535 + 32767
+    q = min(q, 32767u + neg);
+    return neg ? -(int)q : (int)q;
+}
+
+// StreamParam::mode as a compile-time constant: f(integral_constant<u32, GAIN_...>) on the stream's form of the
+// gain where the caller takes the shorter forms (MODES), on the general one otherwise.  (mode is uniform: a wave
+// works on one stream.)
+template <bool MODES, class F>
+__device__ __forceinline__ void with_gain_mode(u32 mode, F &&f)
+{
+    if constexpr (MODES) {
+        if (mode == GAIN_IDENTITY)
+            f(std::integral_constant<u32, GAIN_IDENTITY>{});
+        else if (mode == GAIN_BELOW_SCALE)
+            f(std::integral_constant<u32, GAIN_BELOW_SCALE>{});
+        else
+            f(std::integral_constant<u32, GAIN_GENERAL>{});
+    } else {
+        f(std::integral_constant<u32, GAIN_GENERAL>{});
+    }
+}
+
+// the signed int16 number j of an array of packed dwords (selects, not an index: the array lives in registers
+// and j may be a run-time value)
+template <u32 N>
+__device__ __forceinline__ int half_at(const u32 (&o)[N], u32 j)
+{
+    u32 w = 0;
+#pragma unroll
+    for (u32 i = 0; i < N; i++)
+        if (i == (j >> 1))
+            w = o[i];
+    return (int)(short)(w >> (16u * (j & 1u)));
+}
+
+// ---------------------------------------------------------------------------
+// Tile edges of the block kernels: a stream is nfull whole 16-byte vectors and, when ntail is not 0, a ragged
+// last one of ntail samples.
+struct Extent {
+    u32 nfr, nsamp;
+    u32 nfull;                                   // whole 16-byte vectors
+    u32 ntail;                                   // samples in the partial last vector
+};
+__device__ __forceinline__ Extent stream_extent(const uint32_t *nframes, u32 frames, u32 s, u32 C)
+{
+    Extent e;
+    e.nfr = nframes ? nframes[s] : frames;
+    e.nsamp = e.nfr * C;
+    e.nfull = e.nsamp >> 3;
+    e.ntail = e.nsamp & 7u;
+    return e;
+}
+
+// vector v of a stream: one 16-byte load (full), or the ragged end sample by sample and zero padded (tail);
+// zeros when neither
+__device__ __forceinline__ void load_vec(u32 (&x)[4], const int16_t *ins, u32 v, bool full, bool tail, u32 ntail)
+{
+    u32x4 w = {0, 0, 0, 0};
+    if (full)
+        w = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ins) + v);
+    x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
+    if (tail) {
+        for (u32 j = 0; j < ntail; j++) {
+            const u32 val = (u32)(uint16_t)ins[(u64)v * 8 + j];
+#pragma unroll
+            for (u32 i = 0; i < 4; i++)
+                if (i == (j >> 1))
+                    x[i] |= val << (16u * (j & 1u));
+        }
+    }
+}
+// the ragged last vector's PCM out of o, sample by sample
+__device__ __forceinline__ void store_tail(int16_t *outs, u32 v, const u32 (&o)[4], u32 ntail)
+{
+    for (u32 j = 0; j < ntail; j++)
+        outs[(u64)v * 8 + j] = (int16_t)half_at(o, j);
+}
+
+// window position: read from one slot of VuState::samples, the stream's first tile writes the other
+__device__ __forceinline__ u64 window_base(const RunArgs &a, VuState *vs, u32 k, u32 nsamp)
+{
+    const u64 base = vs->samples[a.parity];
+    if (k == 0 && (threadIdx.x & 63u) == 0)
+        vs->samples[a.parity ^ 1u] = base + nsamp;
+    return base;
+}
+
+// The wave's peak of one channel slot, from the reduced key wkey = (magnitude << 16) | (TU-1-u) << 6 | (63-lane):
+// the winning vector (lowest ordinal u, then lowest lane) is fetched into SGPRs, and `first` is the first of its
+// eight positions that belongs to the slot (position j feeds slot j % NS; mono is NS = 1: every position) and
+// has that magnitude, `neg` its sign.
+struct PeakAt {
+    u32 u, lane, first, neg;
+};
+template <u32 NS, u32 TU>
+__device__ __forceinline__ PeakAt locate_peak(u32 wkey, const u32 (&qw)[TU][4], const u32 (&x)[TU][4], u32 slot)
+{
+    const u32 mag = wkey >> 16;
+    PeakAt p = {TU - 1u - ((wkey >> 6) & (TU - 1u)), 63u - (wkey & 63u), 8, 0};
+    u32 Q[4], X[4];
+#pragma unroll
+    for (u32 u = 0; u < TU; u++) {
+        if (p.u == u) {
+#pragma unroll
+            for (u32 i = 0; i < 4; i++) {
+                Q[i] = (u32)__builtin_amdgcn_readlane((int)qw[u][i], (int)p.lane);
+                X[i] = (u32)__builtin_amdgcn_readlane((int)x[u][i], (int)p.lane);
+            }
+        }
+    }
+#pragma unroll
+    for (u32 j = 0; j < 8; j++) {
+        if (j % NS != slot)
+            continue;
+        if (((u32)half_at(Q, j) & 0xffffu) == mag && p.first == 8) {
+            p.first = j;
+            p.neg = half_at(X, j) < 0 ? 1u : 0u;
+        }
+    }
+    return p;
+}
+
+// the first of four results (in time order) with magnitude mag, and its sign
+__device__ __forceinline__ u32 first_of_four(const int (&sv)[4], u32 mag, u32 &neg)
+{
+    u32 first = 0;
+    neg = 0;
+#pragma unroll
+    for (u32 j = 4; j-- > 0;) {
+        const u32 am = (u32)(sv[j] < 0 ? -sv[j] : sv[j]);
+        if (am == mag) {
+            first = j;
+            neg = sv[j] < 0 ? 1u : 0u;
+        }
+    }
+    return first;
+}
+
 // sum of squares with as few 64-bit additions as exactness allows: three squares
 // (each <= 2^30) fit a u32
 struct PowAcc {
@@ -182,7 +332,6 @@ __device__ __forceinline__ void store_f32(float *f32s, u64 plane, u32 v, const u
         f[2 * i] = (float)(int)(short)(o[i] & 0xffffu) * k;
         f[2 * i + 1] = (float)((int)o[i] >> 16) * k;
     }
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     if constexpr (C == 1) {
         // two 16-byte halves of one 32-byte run per lane: each instruction writes half of
         // every line, so these stay ordinary stores and L2 merges them (non-temporal ones
@@ -238,8 +387,6 @@ __device__ __forceinline__ u64 wave_add_u40(u64 v)
     const u32 hi = wave_add_u32((u32)(v >> 24));              // 64 * 2^16 fits
     return (u64)lo + ((u64)hi << 24);
 }
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // the tile of the hot kernel (and of the plain-copy ceilings that mirror its access shape)
 constexpr u32 TILE_U = 4;                        // 16-byte vectors per lane when PCM is written

@@ -84,8 +84,6 @@ struct RunArgs {
     uint32_t       chunks;         // 4 KiB tiles (one wave each) per stream slot
     uint32_t       parity;         // which VuState::samples slot is current
     uint32_t       identity_maps;  // 1 when no stream of the batch has a channel map
-    uint32_t       identity_gains; // 0: read by no kernel now, kept so that the kernel-argument offsets below stay as
-                                   // they are
     // Completion by flag, for launches of ONE workgroup (the 1 KiB pulls of the per-stream stages): when not
     // null the workgroup, at its very end, makes its stores visible to the host and stores done_seq there
     // (pinned, device-mapped host memory).  The host spins on the word instead of waiting for the stream:
@@ -112,8 +110,6 @@ struct EqArgs {
     uint32_t       parity;
     uint64_t       stride;
     uint64_t       plane;
-    unsigned long long *dbg;       // read by no kernel now, kept so that the kernel-argument offsets below stay as
-                                   // they are
     uint32_t      *done_flag;      // as RunArgs::done_flag
     uint32_t       done_seq;
 };

@@ -18,7 +18,6 @@
 //   VU       ref: src/vumeter.c:161-177     first max-|x| peak, sum of squares
 //   float    ref: src/enc_vorbis.c:108-115  x / 32768.f, planar
 #include "cmhip_device.h"
-#include <type_traits>
 
 namespace cmhip {
 
@@ -41,15 +40,6 @@ struct FastShare {
     u32 arrived;
 };
 
-// window position: read from one slot of VuState::samples, the stream's first tile writes the other
-__device__ __forceinline__ u64 window_base(const RunArgs &a, VuState *vs, u32 k, u32 nsamp)
-{
-    const u64 base = vs->samples[a.parity];
-    if (k == 0 && (threadIdx.x & 63u) == 0)
-        vs->samples[a.parity ^ 1u] = base + nsamp;
-    return base;
-}
-
 template <int C, bool WRITE_PCM, bool WRITE_F32, bool DO_VU, int U, bool FULL>
 __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 nsamp, u32 nfull, u32 ntail,
                                           u64 base, VuState *vs, FastShare *share, const int16_t *a_in,
@@ -61,7 +51,6 @@ __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 ns
     const u32 v0 = k * TILE_VEC;
 
     const int16_t *ins = a_in + (u64)s * a_stride;
-    const u32x4 *src = reinterpret_cast<const u32x4 *>(ins);
     int16_t *outs = WRITE_PCM ? a_out + (u64)s * a_stride : nullptr;
     u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
     float *f32s = WRITE_F32 ? a.f32 + (u64)s * a.plane * C : nullptr;
@@ -74,19 +63,7 @@ __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 ns
         const u32 v = v0 + 64u * u + lane;
         full[u] = FULL || v < nfull;
         tail[u] = !FULL && ntail && v == nfull;
-        u32x4 w = {0, 0, 0, 0};
-        if (full[u])
-            w = __builtin_nontemporal_load(src + v);
-        x[u][0] = w.x; x[u][1] = w.y; x[u][2] = w.z; x[u][3] = w.w;
-        if (tail[u]) {                           // ragged end: sample by sample, zero padded
-            for (u32 j = 0; j < ntail; j++) {
-                const u32 val = (u32)(uint16_t)ins[(u64)v * 8 + j];
-#pragma unroll
-                for (u32 i = 0; i < 4; i++)
-                    if (i == (j >> 1))
-                        x[u][i] |= val << (16u * (j & 1u));
-            }
-        }
+        load_vec(x[u], ins, v, full[u], tail[u], ntail);
     }
 
     // ---- the stream's parameters, read only now: the tile's loads above depend on kernel arguments (and the
@@ -184,7 +161,6 @@ __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 ns
                 wr[0] = make_float4(f[0], f[1], f[2], f[3]);
                 wr[1] = make_float4(f[4], f[5], f[6], f[7]);
                 __syncthreads();
-                typedef float f32x4 __attribute__((ext_vector_type(4)));
                 const float4 r0 = reinterpret_cast<const float4 *>(fst)[lane];
                 const float4 r1 = reinterpret_cast<const float4 *>(fst)[64u + lane];
                 f32x4 *pd = reinterpret_cast<f32x4 *>(f32s + (u64)(v0 + 64u * u) * 8) + lane;
@@ -194,13 +170,10 @@ __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 ns
                 store_f32<C>(f32s, a.plane, v, o);
             }
         } else if (tail[u]) {
+            // (PCM and floats in one loop of its own, not store_tail plus a second loop: that form takes 74 and 76
+            // registers for 72 in the one-wave mono kernels that write PCM and keep a window -- six waves for seven)
             for (u32 j = 0; j < ntail; j++) {
-                u32 ow = 0;
-#pragma unroll
-                for (u32 i = 0; i < 4; i++)
-                    if (i == (j >> 1))
-                        ow = o[i];
-                const int q = (int)(short)((ow >> (16u * (j & 1u))) & 0xffffu);
+                const int q = half_at(o, j);
                 if constexpr (WRITE_PCM)
                     outs[(u64)v * 8 + j] = (int16_t)q;
                 if constexpr (WRITE_F32)
@@ -209,16 +182,7 @@ __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 ns
         }
     }
     };
-    if constexpr (MODES) {
-        if (mode == GAIN_IDENTITY)
-            arithmetic(std::integral_constant<u32, GAIN_IDENTITY>{});
-        else if (mode == GAIN_BELOW_SCALE)
-            arithmetic(std::integral_constant<u32, GAIN_BELOW_SCALE>{});
-        else
-            arithmetic(std::integral_constant<u32, GAIN_GENERAL>{});
-    } else {
-        arithmetic(std::integral_constant<u32, GAIN_GENERAL>{});
-    }
+    with_gain_mode<MODES>(mode, arithmetic);
 
     // ---- epilogue: one add and one max per channel into the stream's window
     if constexpr (DO_VU) {
@@ -243,34 +207,9 @@ __device__ __forceinline__ void fast_tile(const RunArgs &a, u32 s, u32 k, u32 ns
             const u32 mag = wkey[c] >> 16;
             if (mag == 0)
                 continue;
-            // the winning vector: lowest ordinal, then lowest lane; fetch it into SGPRs
-            const u32 uw = TILE_U - 1u - ((wkey[c] >> 6) & (TILE_U - 1u));
-            const u32 lw = 63u - (wkey[c] & 63u);
-            u32 Q[4], X[4];
-#pragma unroll
-            for (u32 u = 0; u < TILE_U; u++) {
-                if (uw == u) {
-#pragma unroll
-                    for (u32 i = 0; i < 4; i++) {
-                        Q[i] = (u32)__builtin_amdgcn_readlane((int)qw[u][i], (int)lw);
-                        X[i] = (u32)__builtin_amdgcn_readlane((int)x[u][i], (int)lw);
-                    }
-                }
-            }
-            // first sample of this channel with that magnitude, and its sign
-            u32 first = 8, neg = 0;
-#pragma unroll
-            for (u32 j = 0; j < 8; j++) {
-                if (C == 2 && (j & 1u) != (u32)c)
-                    continue;
-                const u32 m = (Q[j >> 1] >> (16u * (j & 1u))) & 0xffffu;
-                if (m == mag && first == 8) {
-                    first = j;
-                    neg = (X[j >> 1] >> (16u * (j & 1u) + 15u)) & 1u;
-                }
-            }
+            const PeakAt pk = locate_peak<(u32)C>(wkey[c], qw, x, (u32)c);
             // (c counts dword halves here; with sw the half's output position is the other one of its frame)
-            gkey[c] = make_key(mag, base + 8ull * (v0 + 64u * uw + lw) + (first ^ sw), neg);
+            gkey[c] = make_key(mag, base + 8ull * (v0 + 64u * pk.u + pk.lane) + (pk.first ^ sw), pk.neg);
         }
         if (lane < (u32)C) {                     // lane = output channel, fed by half lane ^ sw
             const u64 ssum = (lane ^ sw) == 0 ? sum[0] : sum[1];
@@ -328,10 +267,8 @@ __device__ __forceinline__ void run_fast(const RunArgs &a)
         __syncthreads();                         // (the only barrier: all waves are at their start)
     }
 
-    const u32 nfr = a.nframes ? a.nframes[s] : a_frames;
-    const u32 nsamp = nfr * (u32)C;
-    const u32 nfull = nsamp >> 3;                // whole 16-byte vectors
-    const u32 ntail = nsamp & 7u;                // samples in the partial last vector
+    const Extent e = stream_extent(a.nframes, a_frames, s, (u32)C);
+    const u32 nsamp = e.nsamp, nfull = e.nfull, ntail = e.ntail;
     const u32 v0 = k * TILE_VEC;
 
     VuState *vs = DO_VU ? a.vu + s : nullptr;
@@ -413,19 +350,14 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
     const u32 s = blockIdx.x / a.chunks;
     const u32 k = blockIdx.x - s * a.chunks;
 
-    const u32 nfr = a.nframes ? a.nframes[s] : a.frames;
-    const u32 nsamp = nfr * (u32)C;
-    const u32 nfull = nsamp >> 3;
-    const u32 ntail = nsamp & 7u;                // only possible for 4 channels (one frame)
+    const Extent e = stream_extent(a.nframes, a.frames, s, (u32)C);
+    const u32 nfull = e.nfull, ntail = e.ntail;  // (a tail: only possible for 4 channels, one frame)
     const u32 v0 = k * TILE_VEC;
 
     VuState *vs = DO_VU ? a.vu + s : nullptr;
     u64 base = 0;
-    if constexpr (DO_VU) {
-        base = vs->samples[a.parity];
-        if (k == 0 && lane == 0)
-            vs->samples[a.parity ^ 1u] = base + nsamp;
-    }
+    if constexpr (DO_VU)
+        base = window_base(a, vs, k, e.nsamp);
     if (v0 >= nfull + (ntail ? 1u : 0u)) {
         done_epilogue(a.done_flag, a.done_seq);
         return;
@@ -441,7 +373,6 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
         mipk[g] = (u32)p->mi[2u * g] | ((u32)p->mi[2u * g + 1u] << 16);
 
     const int16_t *ins = a.in + (u64)s * a.stride;
-    const u32x4 *src = reinterpret_cast<const u32x4 *>(ins);
     int16_t *outs = WRITE_PCM ? a.out + (u64)s * a.stride : nullptr;
     u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
     float *f32s = WRITE_F32 ? a.f32 + (u64)s * a.plane * C : nullptr;
@@ -453,19 +384,7 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
         const u32 v = v0 + 64u * u + lane;
         full[u] = v < nfull;
         tail[u] = ntail && v == nfull;
-        u32x4 w = {0, 0, 0, 0};
-        if (full[u])
-            w = __builtin_nontemporal_load(src + v);
-        x[u][0] = w.x; x[u][1] = w.y; x[u][2] = w.z; x[u][3] = w.w;
-        if (tail[u]) {
-            for (u32 j = 0; j < ntail; j++) {
-                const u32 val = (u32)(uint16_t)ins[(u64)v * 8 + j];
-#pragma unroll
-                for (u32 i = 0; i < 4; i++)
-                    if (i == (j >> 1))
-                        x[u][i] |= val << (16u * (j & 1u));
-            }
-        }
+        load_vec(x[u], ins, v, full[u], tail[u], ntail);
     }
 
     u32 qw[TILE_U][4];
@@ -510,16 +429,8 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
                 __builtin_nontemporal_store(ov, dst + v);
             }
         } else if (tail[u]) {
-            if constexpr (WRITE_PCM) {
-                for (u32 j = 0; j < ntail; j++) {
-                    u32 ow = 0;
-#pragma unroll
-                    for (u32 i = 0; i < 4; i++)
-                        if (i == (j >> 1))
-                            ow = o[i];
-                    outs[(u64)v * 8 + j] = (int16_t)((ow >> (16u * (j & 1u))) & 0xffffu);
-                }
-            }
+            if constexpr (WRITE_PCM)
+                store_tail(outs, v, o, ntail);
         }
         if constexpr (WRITE_F32) {
             // planar float: consecutive lanes hold consecutive frames, so each of these
@@ -528,8 +439,7 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
             for (u32 j = 0; j < 8; j++) {
                 if (j < cnt) {
                     const u32 idx = v * 8u + j;
-                    const int q = (int)(short)((o[j >> 1] >> (16u * (j & 1u))) & 0xffffu);
-                    f32s[(u64)(idx % (u32)C) * a.plane + idx / (u32)C] = q * (1.0f / 32768.0f);
+                    f32s[(u64)(idx % (u32)C) * a.plane + idx / (u32)C] = half_at(o, j) * (1.0f / 32768.0f);
                 }
             }
         }
@@ -546,31 +456,8 @@ __global__ __launch_bounds__(64) void k_run_wide(RunArgs a)
             const u32 mag = wkey >> 16;
             u64 gkey = 0;
             if (mag) {
-                const u32 uw = TILE_U - 1u - ((wkey >> 6) & (TILE_U - 1u));
-                const u32 lw = 63u - (wkey & 63u);
-                u32 Q[4], X[4];
-#pragma unroll
-                for (u32 u = 0; u < TILE_U; u++) {
-                    if (uw == u) {
-#pragma unroll
-                        for (u32 i = 0; i < 4; i++) {
-                            Q[i] = (u32)__builtin_amdgcn_readlane((int)qw[u][i], (int)lw);
-                            X[i] = (u32)__builtin_amdgcn_readlane((int)x[u][i], (int)lw);
-                        }
-                    }
-                }
-                u32 first = 8, neg = 0;
-#pragma unroll
-                for (u32 j = 0; j < 8; j++) {
-                    if (j % NS != sl)
-                        continue;
-                    const u32 m = (Q[j >> 1] >> (16u * (j & 1u))) & 0xffffu;
-                    if (m == mag && first == 8) {
-                        first = j;
-                        neg = (X[j >> 1] >> (16u * (j & 1u) + 15u)) & 1u;
-                    }
-                }
-                gkey = make_key(mag, base + 8ull * (v0 + 64u * uw + lw) + first, neg);
+                const PeakAt pk = locate_peak<NS>(wkey, qw, x, sl);
+                gkey = make_key(mag, base + 8ull * (v0 + 64u * pk.u + pk.lane) + pk.first, pk.neg);
             }
             if (lane == 0) {
                 if (sum)
@@ -653,20 +540,15 @@ __global__ __launch_bounds__(64) void k_run_rows(RunArgs a, u32 W, u32 rows_per_
     const u32 k = blockIdx.x - s * a.chunks;
     const u32 C = a.channels;
 
-    const u32 nfr = a.nframes ? a.nframes[s] : a.frames;
-    const u32 nsamp = nfr * C;
-    const u32 nfull = nsamp >> 3;                // whole 16-byte vectors
-    const u32 ntail = nsamp & 7u;                // samples in the partial last vector
+    const Extent e = stream_extent(a.nframes, a.frames, s, C);
+    const u32 nfr = e.nfr, nfull = e.nfull, ntail = e.ntail;
     const u32 nvec = nfull + (ntail ? 1u : 0u);
     const u32 row0 = k * rows_per_tile;
 
     VuState *vs = DO_VU ? a.vu + s : nullptr;
     u64 base = 0;
-    if constexpr (DO_VU) {
-        base = vs->samples[a.parity];
-        if (k == 0 && lane == 0)
-            vs->samples[a.parity ^ 1u] = base + nsamp;
-    }
+    if constexpr (DO_VU)
+        base = window_base(a, vs, k, e.nsamp);
     if ((u64)row0 * W >= nvec) {
         done_epilogue(a.done_flag, a.done_seq);
         return;
@@ -785,16 +667,8 @@ __global__ __launch_bounds__(64) void k_run_rows(RunArgs a, u32 W, u32 rows_per_
                     __builtin_nontemporal_store(ov, dst + v);
                 }
             } else if (tail[u]) {
-                if constexpr (WRITE_PCM) {
-                    for (u32 j = 0; j < ntail; j++) {
-                        u32 ow = 0;
-#pragma unroll
-                        for (u32 i = 0; i < 4; i++)
-                            if (i == (j >> 1))
-                                ow = o[u][i];
-                        outs[(u64)v * 8 + j] = (int16_t)((ow >> (16u * (j & 1u))) & 0xffffu);
-                    }
-                }
+                if constexpr (WRITE_PCM)
+                    store_tail(outs, v, o[u], ntail);
             }
             if constexpr (WRITE_F32) {
                 if constexpr (!STAGE) {
@@ -805,17 +679,14 @@ __global__ __launch_bounds__(64) void k_run_rows(RunArgs a, u32 W, u32 rows_per_
 #pragma unroll
                     for (u32 j = 0; j < 8; j++) {
                         if (j < cnt) {
-                            const int q = (int)(short)((o[u][j >> 1] >> (16u * (j & 1u))) & 0xffffu);
-                            f32s[(u64)ch[j] * a.plane + fr + df[j]] = q * (1.0f / 32768.0f);
+                            f32s[(u64)ch[j] * a.plane + fr + df[j]] = half_at(o[u], j) * (1.0f / 32768.0f);
                         }
                     }
                 } else if (active) {
                     // this lane's eight samples to [channel][frame of the UR-row step]
 #pragma unroll
-                    for (u32 j = 0; j < 8; j++) {
-                        const int q = (int)(short)((o[u][j >> 1] >> (16u * (j & 1u))) & 0xffffu);
-                        fstage[ch[j] * (UR * FW) + u * FW + lane_fr + df[j]] = q * (1.0f / 32768.0f);
-                    }
+                    for (u32 j = 0; j < 8; j++)
+                        fstage[ch[j] * (UR * FW) + u * FW + lane_fr + df[j]] = half_at(o[u], j) * (1.0f / 32768.0f);
                 }
             }
         }
@@ -829,7 +700,6 @@ __global__ __launch_bounds__(64) void k_run_rows(RunArgs a, u32 W, u32 rows_per_
                 for (u32 i4 = lane * 4u; i4 < fcnt; i4 += 256u) {
                     const float4 v4 = *reinterpret_cast<const float4 *>(&fstage[c * fcnt + i4]);
                     if (fbase + i4 + 4u <= nfr) {
-                        typedef float f32x4 __attribute__((ext_vector_type(4)));
                         const f32x4 vv = {v4.x, v4.y, v4.z, v4.w};
                         __builtin_nontemporal_store(vv, reinterpret_cast<f32x4 *>(plane_dst + i4));
                     } else if (fbase + i4 < nfr) {
@@ -896,57 +766,30 @@ __global__ __launch_bounds__(64) void k_run_rows(RunArgs a, u32 W, u32 rows_per_
             const u32 v = (row0 + r0 + u) * W + lane;
             full[u] = active && v < nfull;
             tail[u] = active && ntail && v == nfull;
-            u32x4 w = {0, 0, 0, 0};
-            if (full[u])
-                w = __builtin_nontemporal_load(src + v);
-            x[u][0] = w.x; x[u][1] = w.y; x[u][2] = w.z; x[u][3] = w.w;
-            if (tail[u]) {
-                for (u32 j = 0; j < ntail; j++) {
-                    const u32 val = (u32)(uint16_t)ins[(u64)v * 8 + j];
-#pragma unroll
-                    for (u32 i = 0; i < 4; i++)
-                        if (i == (j >> 1))
-                            x[u][i] |= val << (16u * (j & 1u));
-                }
-            }
+            load_vec(x[u], ins, v, full[u], tail[u], ntail);
         }
         finish_step(r0, x, full, tail);
     }
     };
-    if constexpr (MODES) {
-        if (mode == GAIN_IDENTITY)
-            tile(std::integral_constant<u32, GAIN_IDENTITY>{});
-        else if (mode == GAIN_BELOW_SCALE)
-            tile(std::integral_constant<u32, GAIN_BELOW_SCALE>{});
-        else
-            tile(std::integral_constant<u32, GAIN_GENERAL>{});
-    } else {
-        tile(std::integral_constant<u32, GAIN_GENERAL>{});
-    }
+    with_gain_mode<MODES>(mode, tile);
 
     if constexpr (DO_VU) {
         __syncthreads();                         // accumulators cleared (one wave: cheap)
 #pragma unroll
         for (u32 j = 0; j < 8; j++) {
-            const u32 i = j >> 1, sh = 16u * (j & 1u);
+            const u32 i = j >> 1, h = j & 1u;
             const u32 mag = vu.best[j] >> 16;
             if (!active)                         // (lanes beyond W held copies in the pipelined loop)
                 continue;
             if (vu.pw[j])
                 atomicAdd(reinterpret_cast<unsigned long long *>(&lsum[ch[j]]), (unsigned long long)vu.pw[j]);
             if (mag) {
-                // the first of the winning step's four results with that magnitude, and its sign
+                // which of the winning step's four results (half h of dword i in each of its rows) came first
                 const u32 step = 0x7fffu - (vu.best[j] & 0xffffu);
-                u32 first = UR, neg = 0;
-#pragma unroll
-                for (u32 u = 0; u < UR; u++) {
-                    const int sv = (int)(short)((vu.sv[i][u] >> sh) & 0xffffu);
-                    const u32 am = (u32)(sv < 0 ? -sv : sv);
-                    if (am == mag && first == UR) {
-                        first = u;
-                        neg = sv < 0 ? 1u : 0u;
-                    }
-                }
+                const int sv[UR] = {half_at(vu.sv[i], h), half_at(vu.sv[i], 2u + h), half_at(vu.sv[i], 4u + h),
+                                    half_at(vu.sv[i], 6u + h)};
+                u32 neg;
+                const u32 first = first_of_four(sv, mag, neg);
                 const u64 v = (u64)(row0 + step * UR + first) * W + lane;
                 const u64 key = make_key(mag, base + 8ull * v + j, neg);
                 atomicMax(reinterpret_cast<unsigned long long *>(&lkey[ch[j]]), (unsigned long long)key);

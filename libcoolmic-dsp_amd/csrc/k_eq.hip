@@ -1,6 +1,5 @@
 // k_eq.hip -- the pipelined equaliser kernel (BASELINE config 3) and its launcher.
 #include "cmhip_device.h"
-#include <type_traits>
 #include <mutex>
 
 namespace cmhip {
@@ -337,10 +336,8 @@ void k_eq_pipe(EqArgs a)
         keep_n = 3u;
         auto gain_one = [&](const u32 frame) -> float {
             const int xs = (int)l_src[MONO ? frame : frame * C + l_m];
-            const u32 ax = (u32)(xs < 0 ? -xs : xs);
-            const u32 qq = __umul24(ax, l_mi) + __umulhi(ax, l_mf);
-            const float m = fminf((float)qq, xs < 0 ? 32768.0f : 32767.0f);
-            return (xs < 0 ? -m : m) * (1.0f / 32768.0f);
+            // (the sample's sign, not the result's: a negative sample with quotient 0 is -0.0f, as in tin_step)
+            return __builtin_copysignf((float)gain1(xs, l_mi, l_mf), (float)xs) * (1.0f / 32768.0f);
         };
         keep1 = gain_one(l_n - 1u);
         keep2 = l_n >= 2u ? gain_one(l_n - 2u) : a.state[l_sidx].s[0][0];
@@ -648,7 +645,7 @@ void k_eq_pipe(EqArgs a)
                     const u32 e[4] = {v.x, v.y, v.z, v.w};
                     for (u32 j = 0; j < 8; j++)
                         if (fb + (co_s8 + j) / C < co_n)
-                            dst[j] = (int16_t)(e[j >> 1] >> (16u * (j & 1u)));
+                            dst[j] = (int16_t)half_at(e, j);
                 }
             }
         }
@@ -680,7 +677,6 @@ void k_eq_pipe(EqArgs a)
                 if (a.f32) {
                     float *dstf = a.f32 + ((u64)vs_ * C + vc_) * a.plane + f0;
                     if (f0 + 4u <= n) {
-                        typedef float f32x4 __attribute__((ext_vector_type(4)));
                         const f32x4 vv = {v.x, v.y, v.z, v.w};
                         __builtin_nontemporal_store(vv, reinterpret_cast<f32x4 *>(dstf));
                     } else if (f0 < n) {
@@ -701,24 +697,23 @@ void k_eq_pipe(EqArgs a)
                     // (v_cvt_pk_i16_i32 saturates: the clamp and the packing of a sample pair in one)
                     const u32 p01 = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
                     const u32 p23 = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
+                    const u32 pk4[2] = {p01, p23};
                     const bool whole = __all(f0 + 4u <= n);     // no stream ends inside these
                     if (a.out) {
                         if constexpr (MONO) {
                             int16_t *d16 = a.out + (u64)vs_ * a.stride + f0;
                             if (f0 + 4u <= n) {
-                                typedef u32 u32x2 __attribute__((ext_vector_type(2)));
                                 const u32x2 pk = {p01, p23};
                                 __builtin_nontemporal_store(pk, reinterpret_cast<u32x2 *>(d16));
                             } else if (f0 < n) {
                                 for (u32 j = 0; j < n - f0; j++)
-                                    d16[j] = (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
+                                    d16[j] = (int16_t)half_at(pk4, j);
                             }
                         } else if constexpr (STEREO) {
                             // The two rows of a stream are 32 lanes apart (s_row): swap halves with the
                             // partner (v_permlane32_swap) so that the left row's lanes hold
                             // frames f0, f0+1 of both channels and the right row's lanes frames
                             // f0+2, f0+3 -- whole interleaved frames, 8 bytes per lane.
-                            typedef u32 u32x2 __attribute__((ext_vector_type(2)));
                             const u32x2 sw2 = __builtin_amdgcn_permlane32_swap(p01, p23, false, false);
                             const u32 left = sw2.x, right = sw2.y;   // this frame pair: channel 0, channel 1
                             const u32 d0 = __builtin_amdgcn_perm(right, left, 0x05040100u);
@@ -737,7 +732,6 @@ void k_eq_pipe(EqArgs a)
                             // halves as the stereo form does -- L keeps frames f0, f0 + 1 of both channels, L + 32
                             // frames f0 + 2, f0 + 3 -- and every sample pair is one aligned dword of a frame:
                             // two 4-byte stores per lane instead of four 2-byte ones, staged or not.
-                            typedef u32 u32x2 __attribute__((ext_vector_type(2)));
                             const u32x2 sw2 = __builtin_amdgcn_permlane32_swap(p01, p23, false, false);
                             const u32 d0 = __builtin_amdgcn_perm(sw2.y, sw2.x, 0x05040100u);
                             const u32 d1 = __builtin_amdgcn_perm(sw2.y, sw2.x, 0x07060302u);
@@ -758,14 +752,13 @@ void k_eq_pipe(EqArgs a)
                             unsigned char *st16 = outstage + (b & 1u) * EQ_STAGE_OUT + so_base[i];
 #pragma unroll
                             for (u32 j = 0; j < 4; j++)
-                                *reinterpret_cast<int16_t *>(st16 + j * 2u * C) =
-                                    (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
+                                *reinterpret_cast<int16_t *>(st16 + j * 2u * C) = (int16_t)half_at(pk4, j);
                         } else {                      // ... or, a stream shared with a neighbour, this row's channel
                             int16_t *d16 = a.out + (u64)vs_ * a.stride + (u64)f0 * C + vc_;
 #pragma unroll
                             for (u32 j = 0; j < 4; j++)
                                 if (f0 + j < n)
-                                    d16[j * C] = (int16_t)((j < 2u ? p01 : p23) >> (16u * (j & 1u)));
+                                    d16[j * C] = (int16_t)half_at(pk4, j);
                         }
                     }
                     if (a.vu) {
@@ -834,16 +827,10 @@ void k_eq_pipe(EqArgs a)
 #pragma unroll
         for (u32 i = 0; i < NSL; i++) {
             {
-                u32 first = 0, neg = 0;                   // the first of the four with that magnitude, and its sign
-#pragma unroll
-                for (u32 j = 4; j-- > 0;) {
-                    const int sv = (int)(short)(((j < 2u ? vq01[i] : vq23[i]) >> (16u * (j & 1u))) & 0xffffu);
-                    const u32 am = (u32)(sv < 0 ? -sv : sv);
-                    if (am == vmag[i]) {
-                        first = j;
-                        neg = sv < 0 ? 1u : 0u;
-                    }
-                }
+                const u32 vq[2] = {vq01[i], vq23[i]};
+                const int sv[4] = {half_at(vq, 0), half_at(vq, 1), half_at(vq, 2), half_at(vq, 3)};
+                u32 neg;
+                const u32 first = first_of_four(sv, vmag[i], neg);
                 vky[i] = make_key(vmag[i], vbase[i] + (u64)(vfr[i] + first) * C + v_ch[i], neg);
             }
             u64 pw = vpw[i], ky = vky[i];

@@ -15,17 +15,6 @@
 
 namespace cmhip {
 
-// the transform of one sample in plain integers: the arithmetic of gain2 (floor(|x| * gain / scale) =
-// |x| * mi + mulhi(|x|, mf), saturated at 32767 / -32768), for the places that take samples one by one
-__device__ __forceinline__ int tp_sample(int x, u32 mi, u32 mf)
-{
-    const u32 neg = x < 0 ? 1u : 0u;
-    const u32 ax = (u32)(neg ? -x : x);
-    u32 q = ax * mi + __umulhi(ax, mf);              // < 2^31: 32768 * 65535 + 32767
-    q = min(q, 32767u + neg);
-    return neg ? -(int)q : (int)q;
-}
-
 // The stream's new history: the last 11 transformed frames of (old history, this run's frames), into the slot the
 // next run reads.  Done by the workgroup of the stream's last tile (its first when the stream got no frame: the
 // history moves over unchanged); fewer than 11 frames shift the old history by that many.
@@ -41,7 +30,7 @@ __device__ __forceinline__ void tp_history(const TpArgs &a, u32 s, u32 nfr, u32 
             val = hrd[c * TP_HIST + i + nfr];
         } else {
             const u64 m = (u64)nfr - TP_HIST + i;
-            val = tp_sample(ins[m * C + p->chmap[c]], p->mi[c], p->mf[c]);
+            val = gain1(ins[m * C + p->chmap[c]], p->mi[c], p->mf[c]);
         }
         hwr[c * TP_HIST + i] = (int16_t)val;
     }
@@ -232,7 +221,7 @@ __global__ __launch_bounds__(256) void k_tpeak_any(TpArgs a)
             if (f0 + lf < TP_HIST)                           // before this run (only the stream's first tile)
                 val = hrd[c * TP_HIST + f0 + lf];
             else if (f0 + lf - TP_HIST < nfr)
-                val = tp_sample(ins[(u64)(f0 + lf - TP_HIST) * C + p->chmap[c]], p->mi[c], p->mf[c]);
+                val = gain1(ins[(u64)(f0 + lf - TP_HIST) * C + p->chmap[c]], p->mi[c], p->mf[c]);
             plane[c * TP_ANY_ROW + lf] = (int16_t)val;
         }
         __syncthreads();

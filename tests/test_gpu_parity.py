@@ -407,7 +407,8 @@ def test_peak_tie_breaks_across_lanes_waves_chunks_and_launches(gpu, oracle):
     cm = gpu
     T = 70000                      # several tiles per stream
     for C, flags in ((1, cm.VU), (2, cm.VU), (3, cm.VU), (3, cm.OUT_PCM | cm.VU | cm.INPLACE), (6, cm.VU),
-                     (6, cm.OUT_PCM | cm.VU), (12, cm.VU), (12, cm.OUT_PCM | cm.VU | cm.INPLACE)):
+                     (6, cm.OUT_PCM | cm.VU), (12, cm.VU), (12, cm.OUT_PCM | cm.VU | cm.INPLACE),
+                     (4, cm.OUT_PCM | cm.VU), (8, cm.OUT_PCM | cm.VU | cm.INPLACE)):     # the last two: k_run_wide
         spots = [(5, 3000), (9, -3000), (1023, 3000), (1024, -3000), (8 * 64 * 4 + 1, 3000),
                  (40000, -3000), (69999, 3000)]
         cases = []

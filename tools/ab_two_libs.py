@@ -2,7 +2,8 @@
 """A/B of several builds of the library in ONE process, interleaved, at sustained clocks: every library
 is loaded under a module name of its own, each gets its own batch of the same shape, and timed
 blocks of launches alternate between them (process-to-process differences -- placement of the
-arrays, clocks -- cancel).  usage: ab_two_libs.py SHAPE lib1.so lib2.so ...   SHAPE: eq3 | eq3vu | eq3vu1 | eq3all | eq3vu6 | c2 | c2s | c4 | vu1 | vu2 | vu6"""
+arrays, clocks -- cancel).  usage: ab_two_libs.py SHAPE lib1.so lib2.so ...   SHAPE: eq3 | eq3vu | eq3vu1 | eq3all | eq3vu6 | c2 | c2s | c4 | vu1 | vu2 | vu6
+| w8 | w4 | w8f | r6 | r6m | r5f (the many-channel kernels, sized as tools/bench_generic.py sizes them)"""
 import importlib.util
 import os
 import sys
@@ -42,6 +43,18 @@ def make(cm, shape):
         b = cm.Batch(S, C, T, flags=cm.OUT_PCM | cm.VU)
         b.set_gain(-1, 2, 1000, [750, 1250])
         b.set_chmap(-1, [1, 0])
+    elif shape in ("w8", "w4", "w8f", "r6", "r6m", "r5f"):
+        # k_run_wide: 8 / 4 channels PCM + VU, 8 channels float planes; k_run_rows: 5.1 PCM + VU with identity maps
+        # and with a channel map (MAP), 5 channels float planes (STAGE).  ~0.5 GB of PCM per launch
+        C = int(shape[1])
+        T = 16384
+        S = (1 << 28) // (T * C)
+        f32 = shape.endswith("f")
+        b = cm.Batch(S, C, T, flags=cm.OUT_F32 if f32 else cm.OUT_PCM | cm.VU)
+        b.set_gain(-1, 1, 1000, [900])
+        if shape == "r6m":
+            b.set_chmap(-1, [(c + 1) % C for c in range(C)])
+        bps = 6 if f32 else 4
     else:
         S, C, T, bps = 2730, 6, 16384, 2
         b = cm.Batch(S, C, T, flags=cm.VU)
