@@ -10,10 +10,12 @@
  *
  *   cc -I include examples/group_meters.c -L libcoolmic-dsp_amd/lib -lcoolmic-dsp-hip -lpthread \
  *      -Wl,-rpath,$PWD/libcoolmic-dsp_amd/lib -o group_meters
- *   ./group_meters [streams] [block] [rounds] [host|device]
+ *   ./group_meters [streams] [block] [rounds] [host|device] [r128]
  *
  * Prints the time per block, how many meters were taken, and the last block's meter of stream 0 and of the
- * last stream.
+ * last stream.  With "r128" as the fifth argument the group also measures true peak and programme loudness
+ * (ITU-R BS.1770 / EBU R128: coolmic_group_set_true_peak, coolmic_group_set_loudness) and two more lines give the
+ * same two streams' true peak over the whole run beside their momentary, short-term and integrated loudness.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +39,7 @@ int main(int argc, char **argv)
     const size_t block = argc > 2 ? (size_t)atoi(argv[2]) : 512;
     const unsigned rounds = argc > 3 ? (unsigned)atoi(argv[3]) : 64;
     const char *where = argc > 4 ? argv[4] : "host";
+    const int r128 = argc > 5 && !strcmp(argv[5], "r128");
     static const uint16_t unity[1] = {1000};
     const size_t nbytes = block * 2;                      /* mono int16 */
     coolmic_group_t *grp;
@@ -49,7 +52,7 @@ int main(int argc, char **argv)
     unsigned s, r;
 
     if (!streams || !block || !rounds || (strcmp(where, "host") && strcmp(where, "device"))) {
-        fprintf(stderr, "usage: group_meters [streams] [block] [rounds] [host|device]\n");
+        fprintf(stderr, "usage: group_meters [streams] [block] [rounds] [host|device] [r128]\n");
         return 1;
     }
     grp = coolmic_group_new(NULL, igloo_RO_NULL, 48000, 1, streams, block, 2);
@@ -64,6 +67,11 @@ int main(int argc, char **argv)
     if (coolmic_group_set_vu_finish(grp, strcmp(where, "device") ? CMHIP_VU_FINISH_HOST : CMHIP_VU_FINISH_DEVICE) !=
         COOLMIC_ERROR_NONE)
         goto done;
+    if (r128 && (coolmic_group_set_true_peak(grp, 1) != COOLMIC_ERROR_NONE ||
+                 coolmic_group_set_loudness(grp, 1) != COOLMIC_ERROR_NONE)) {
+        fprintf(stderr, "r128: %s\n", cmhip_last_error());
+        goto done;
+    }
     for (s = 0; s < streams; s++) {
         coolmic_snddev_t *dev = coolmic_snddev_new(NULL, igloo_RO_NULL, "sine", NULL, 48000, 1,
                                                    COOLMIC_DSP_SNDDEV_RX, -1);
@@ -100,6 +108,15 @@ int main(int argc, char **argv)
     for (s = 0; s < streams; s += streams > 1 ? streams - 1 : 1)
         printf("stream %u: frames %zu peak %d power %.17g\n", s, meters[s].frames, (int)meters[s].global_peak,
                meters[s].global_power);
+    for (s = 0; r128 && s < streams; s += streams > 1 ? streams - 1 : 1) {
+        coolmic_truepeak_result_t tp;
+        coolmic_loudness_result_t loud;
+        if (coolmic_group_true_peak(grp, s, &tp) != COOLMIC_ERROR_NONE ||
+            coolmic_group_loudness(grp, s, &loud) != COOLMIC_ERROR_NONE)
+            goto done;
+        printf("stream %u: true peak %.2f dBTP over %zu frames; loudness M %.2f S %.2f I %.2f LUFS (%zu sub-blocks)\n", s,
+               tp.global_dbtp, tp.frames, loud.momentary, loud.short_term, loud.integrated, loud.blocks);
+    }
     rc = 0;
 done:
     for (s = 0; s < streams; s++)

@@ -125,6 +125,23 @@ int                 coolmic_group_set_true_peak(coolmic_group_t *self, int on);
 int                 coolmic_group_true_peak(coolmic_group_t *self, unsigned int slot, coolmic_truepeak_result_t *result);
 int                 coolmic_group_true_peaks(coolmic_group_t *self, coolmic_truepeak_result_t *results, int *rc);
 
+/* Programme loudness (ITU-R BS.1770 / EBU R128) of every stream, opt-in: cmhip_batch_set_loudness() of
+ * <coolmic_hip.h> on the group's engine, with its return values and its specification.  While it is on every block
+ * runs the loudness kernel ahead of the block kernel (beside the true-peak kernel when that is on too); the group's
+ * blocks lie in host memory, so the input set is read once more over PCIe.  It measures the transformed stream, not
+ * the equaliser's result: the two exclude each other with COOLMIC_ERROR_INVAL both ways round. */
+int                 coolmic_group_set_loudness(coolmic_group_t *self, int on);
+/* One slot's loudness since the group turned it on or the slot was reset, and all of them at once (results[] and
+ * rc[], which may be NULL, have coolmic_group_streams() entries): the slot handling of coolmic_group_true_peak(s).
+ * NOT destructive -- loudness integrates until coolmic_group_loudness_reset (slot -1: all).  rc[] is
+ * COOLMIC_ERROR_NONE for every slot: a slot without a frame reports zeros and -inf.  Everything pumped so far
+ * counts, the block in flight included. */
+int                 coolmic_group_loudness(coolmic_group_t *self, unsigned int slot, coolmic_loudness_result_t *result);
+int                 coolmic_group_loudnesses(coolmic_group_t *self, coolmic_loudness_result_t *results, int *rc);
+/* cmhip_batch_loud_set_weights / cmhip_batch_loud_reset for a slot, or -1 for every stream of the engine */
+int                 coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights);
+int                 coolmic_group_loudness_reset(coolmic_group_t *self, long slot);
+
 unsigned int        coolmic_group_streams(coolmic_group_t *self);
 
 #ifdef __cplusplus

@@ -72,6 +72,26 @@ typedef struct {
     double channel_dbtp[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
 } coolmic_truepeak_result_t;
 
+/* Programme loudness of one stream (ITU-R BS.1770 / EBU R128: K-weighting, 100 ms sub-blocks, 400 ms momentary,
+ * 3 s short-term, gated integrated loudness), as the batch engine (cmhip_batch_loud_result, <coolmic_hip.h>) and the
+ * group (coolmic_group_loudness, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  The
+ * arithmetic is specified to the bit in <coolmic_hip.h>.  frames: since loudness was turned on or reset; blocks:
+ * complete 100 ms sub-blocks among them; gated_blocks: the 400 ms blocks that passed both gates and make up
+ * `integrated`.  The four loudness values are LUFS doubles, -inf while there is nothing to report (momentary:
+ * fewer than 4 sub-blocks, short_term: fewer than 30, integrated and relative_threshold: no block above -70 LUFS).
+ * 64 bytes on LP64. */
+typedef struct {
+    uint_least32_t rate;
+    unsigned int channels;
+    size_t frames;
+    size_t blocks;
+    size_t gated_blocks;
+    double momentary;
+    double short_term;
+    double integrated;
+    double relative_threshold;
+} coolmic_loudness_result_t;
+
 #ifdef __cplusplus
 }
 #endif

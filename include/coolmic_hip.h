@@ -239,6 +239,76 @@ double cmhip_tp_dbtp(uint32_t peak);
 /* the filter, no device needed: H[0..3] in order, 12 taps each */
 void   cmhip_tp_coefficients(int16_t h[48]);
 
+/* ---- programme loudness (ITU-R BS.1770 / EBU R128), opt-in -------------------- */
+/* Momentary, short-term and gated integrated loudness of the TRANSFORMED stream (after channel map, gain and
+ * saturation: the samples the VU window accounts, as for true peak).  The arithmetic is specified to the bit:
+ *
+ * Signal.  u = (double)x / 32768.0 (exact).
+ * Filter.  Two biquad sections in double, Direct Form I, history zero at enable and reset; every product and every
+ *   sum rounded once (no fused multiply-add), double denormals kept:
+ *       f = (b0*u + b1*u1) + b2*u2      y = (f - a2*y2) - a1*y1      (then u2=u1, u1=u, y2=y1, y1=y)
+ *   Section 2 takes section 1's y as its u; its numerator is exactly 1, -2, 1.
+ * Coefficients.  cmhip_loud_coefficients(rate, c) returns {b0,b1,b2,a1,a2} twice, from libm's tan and pow in exactly
+ *   this order:
+ *     stage 1: f0=1681.974450955533  G=3.999843853973347  Q=0.7071752369554196
+ *              K=tan(M_PI*f0/rate)  Vh=pow(10.0,G/20.0)  Vb=pow(Vh,0.4996667741545416)  a0=1.0+K/Q+K*K
+ *              b0=(Vh+Vb*K/Q+K*K)/a0  b1=2.0*(K*K-Vh)/a0  b2=(Vh-Vb*K/Q+K*K)/a0  a1=2.0*(K*K-1.0)/a0
+ *              a2=(1.0-K/Q+K*K)/a0
+ *     stage 2: f0=38.13547087602444  Q=0.5003270373238773  K=tan(M_PI*f0/rate)  a0=1.0+K/Q+K*K
+ *              b = 1.0, -2.0, 1.0   a1=2.0*(K*K-1.0)/a0   a2=(1.0-K/Q+K*K)/a0
+ *   At 48000 Hz these are the table values of BS.1770-4 to 9e-16.  Loudness needs 8000 <= rate <= 384000:
+ *   cmhip_batch_set_loudness returns COOLMIC_ERROR_INVAL for a batch of any other rate.
+ * Sub-blocks.  L = (rate + 5) / 10 frames (100 ms), counted per stream from enable or reset.  Per channel e += y*y,
+ *   product and sum each rounded once, sequential in frame order, from 0.0 at each sub-block's start.  A completed
+ *   sub-block's e per channel is what the device produces (cmhip_batch_loud_raw).  A stream that gets 0 frames in a
+ *   run keeps everything, and the sums do not depend on how the stream was cut into runs.
+ * Host finish, all in double, in this order:
+ *   z_j = (sum over c ascending of w_c * e_c,j, each product rounded, the sum from 0.0) / (double)L
+ *   lufs(v) = -0.691 + 10.0*log10(v), -inf for v == 0                                     (cmhip_loud_lufs)
+ *   momentary  = lufs((((z[n-4]+z[n-3])+z[n-2])+z[n-1]) * 0.25), -inf while n < 4
+ *   short-term = lufs((z[n-30] + ... + z[n-1], in that order) / 30.0), -inf while n < 30
+ *   integrated (cmhip_loud_integrate): blocks B_i = (((z[i-3]+z[i-2])+z[i-1])+z[i]) * 0.25 for i >= 3; keep those
+ *     with lufs(B_i) > -70.0; relative threshold = lufs(mean of the kept) - 10.0; the result is lufs(mean of the kept
+ *     B_i with lufs(B_i) > threshold), and `gated` counts those.  A mean is the sum in ascending i from 0.0, divided
+ *     by (double)count.  With nothing kept by the first gate both values are -inf and gated is 0; with nothing kept
+ *     by the second, integrated is -inf.
+ *   Default weight w_c is 1.0 for every channel; the library does not know layouts.  A 5.1 host in L R C LFE Ls Rs
+ *   order sets {1,1,1,0,1.41,1.41}.
+ *
+ * cmhip_batch_set_loudness(b, 1), between runs (it waits for the batch's stream), allocates the state on first use
+ * (COOLMIC_ERROR_NOMEM when that fails; the batch stays usable) and opens every stream with zero history, no frames
+ * and the weights it had (1.0 at first); from then on every cmhip_batch_run / _run_slots launches the loudness
+ * kernel on the batch's stream AHEAD of the block kernel, beside the true-peak pass when that is on too.  (b, 0)
+ * stops that and discards everything but the weights.  Loudness of the equaliser's result is not measured: the two
+ * exclude each other with COOLMIC_ERROR_INVAL both ways round, nsec == 0 stays allowed.
+ * The device keeps a ring of completed sub-block sums; the host knows every run's counts and drains the ring (a
+ * stream synchronisation and one copy) before a run that could overflow it and at every result call, appending one
+ * z_j -- 8 bytes per 100 ms and stream, until reset -- to the stream's array.
+ * Results are NOT destructive: loudness integrates until cmhip_batch_loud_reset (stream -1: all), which clears
+ * history, the open sub-block and the host's arrays.  A stream without a frame reports zeros and -inf with
+ * COOLMIC_ERROR_NONE; rc[] of _results (may be NULL) is COOLMIC_ERROR_NONE for every stream.
+ * cmhip_batch_loud_set_weights (stream -1: all): COOLMIC_ERROR_BUSY while a named stream holds completed sub-blocks
+ * (reset first), COOLMIC_ERROR_INVAL for a negative or non-finite weight; nothing is changed then.
+ * cmhip_batch_loud_raw: the per-channel sums e of the trailing min(cap, 30) complete sub-blocks, oldest first, into
+ * sums[i * channels + c]; *returned: how many; *completed: the stream's complete sub-blocks in all (both may be NULL).
+ * NULL is COOLMIC_ERROR_FAULT; a stream out of range or a batch without loudness COOLMIC_ERROR_INVAL.
+ * cmhip_batch_timing keeps bracketing the block kernel only.  The pass is queued, and its frames are counted, before
+ * the block kernel is launched: after a cmhip_batch_run that returns an error, loudness (like true peak) may or may
+ * not hold that run's frames -- reset the stream's meters before trying the run again. */
+int    cmhip_batch_set_loudness(cmhip_batch_t *b, int on);
+int    cmhip_batch_get_loudness(const cmhip_batch_t *b);      /* 0 / 1, negative error */
+int    cmhip_batch_loud_set_weights(cmhip_batch_t *b, long stream, const double *w /* [channels] */);
+int    cmhip_batch_loud_result(cmhip_batch_t *b, unsigned int stream, coolmic_loudness_result_t *out);
+int    cmhip_batch_loud_results(cmhip_batch_t *b, coolmic_loudness_result_t *out, int *rc);
+int    cmhip_batch_loud_raw(cmhip_batch_t *b, unsigned int stream, double *sums /* [cap][channels] */, size_t cap,
+                            size_t *returned, unsigned long long *completed);
+int    cmhip_batch_loud_reset(cmhip_batch_t *b, long stream);
+/* host only, no device needed.  _coefficients: c == NULL does nothing; a rate of 0 gives non-finite values.
+ * _integrate: any of the three results may be NULL; z == NULL with n > 0 is COOLMIC_ERROR_FAULT. */
+void   cmhip_loud_coefficients(unsigned int rate, double c[10]);
+double cmhip_loud_lufs(double mean_square);
+int    cmhip_loud_integrate(const double *z, size_t n, double *integrated, double *threshold, size_t *gated);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

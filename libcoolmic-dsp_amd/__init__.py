@@ -69,6 +69,16 @@ class TruePeakResult(C.Structure):
                 "channel_dbtp": [self.channel_dbtp[i] for i in range(ch)]}
 
 
+class LoudnessResult(C.Structure):
+    """coolmic_loudness_result_t (include/coolmic-dsp/vumeter.h): LUFS doubles, -inf while there is nothing to report"""
+    _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t), ("blocks", C.c_size_t),
+                ("gated_blocks", C.c_size_t), ("momentary", C.c_double), ("short_term", C.c_double),
+                ("integrated", C.c_double), ("relative_threshold", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class BatchDesc(C.Structure):
     _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint),
                 ("rate", C.c_uint), ("max_frames", C.c_size_t), ("flags", C.c_uint),
@@ -154,6 +164,16 @@ SIGNATURES = {
     "cmhip_batch_tp_reset": (C.c_int, [_vp, C.c_long]),
     "cmhip_tp_dbtp": (C.c_double, [C.c_uint32]),
     "cmhip_tp_coefficients": (None, [_vp]),
+    "cmhip_batch_set_loudness": (C.c_int, [_vp, C.c_int]),
+    "cmhip_batch_get_loudness": (C.c_int, [_vp]),
+    "cmhip_batch_loud_set_weights": (C.c_int, [_vp, C.c_long, _vp]),
+    "cmhip_batch_loud_result": (C.c_int, [_vp, C.c_uint, _P(LoudnessResult)]),
+    "cmhip_batch_loud_results": (C.c_int, [_vp, _vp, _vp]),
+    "cmhip_batch_loud_raw": (C.c_int, [_vp, C.c_uint, _vp, C.c_size_t, _P(C.c_size_t), _P(C.c_ulonglong)]),
+    "cmhip_batch_loud_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_loud_coefficients": (None, [C.c_uint, _vp]),
+    "cmhip_loud_lufs": (C.c_double, [C.c_double]),
+    "cmhip_loud_integrate": (C.c_int, [_vp, C.c_size_t, _P(C.c_double), _P(C.c_double), _P(C.c_size_t)]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -237,6 +257,11 @@ SIGNATURES = {
     "coolmic_group_set_true_peak": (C.c_int, [_vp, C.c_int]),
     "coolmic_group_true_peak": (C.c_int, [_vp, C.c_uint, _P(TruePeakResult)]),
     "coolmic_group_true_peaks": (C.c_int, [_vp, _vp, _vp]),
+    "coolmic_group_set_loudness": (C.c_int, [_vp, C.c_int]),
+    "coolmic_group_loudness": (C.c_int, [_vp, C.c_uint, _P(LoudnessResult)]),
+    "coolmic_group_loudnesses": (C.c_int, [_vp, _vp, _vp]),
+    "coolmic_group_loudness_set_weights": (C.c_int, [_vp, C.c_long, _vp]),
+    "coolmic_group_loudness_reset": (C.c_int, [_vp, C.c_long]),
     "coolmic_group_streams": (C.c_uint, [_vp]),
 }
 MISSING = []        # entry points this build of the library lacks (an older build under tools/ab_two_libs.py)
@@ -269,6 +294,11 @@ if hasattr(lib, "cmhip_test_plan_tpeak"):       # (not in builds older than true
     lib.cmhip_test_plan_tpeak.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.cmhip_debug_tp_count.restype = C.c_ulonglong
     lib.cmhip_debug_tp_count.argtypes = []
+if hasattr(lib, "cmhip_test_plan_loud"):        # (not in builds older than loudness)
+    lib.cmhip_test_plan_loud.restype = None
+    lib.cmhip_test_plan_loud.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.cmhip_debug_loud_count.restype = C.c_ulonglong
+    lib.cmhip_debug_loud_count.argtypes = []
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -346,6 +376,38 @@ def tp_coefficients():
     h = np.zeros(48, dtype=np.int16)
     lib.cmhip_tp_coefficients(h.ctypes.data)
     return h.reshape(4, 12)
+
+
+class LoudPlan(C.Structure):
+    """cmhip::LoudPlan (csrc/cmhip_internal.h): what the loudness launcher launches for a run"""
+    _fields_ = [("err", C.c_int), ("vec", C.c_uint32), ("grid", C.c_uint32), ("block", C.c_uint32)]
+
+
+def plan_loud(streams, channels, frames):
+    """Test hook: the loudness launcher's plan for a run (host logic, needs no GPU)"""
+    p = LoudPlan()
+    lib.cmhip_test_plan_loud(streams, channels, frames, C.addressof(p))
+    return p
+
+
+def loud_coefficients(rate):
+    """the K-weighting biquads for a rate: {b0, b1, b2, a1, a2} of section 1, then of section 2"""
+    c = (C.c_double * 10)()
+    lib.cmhip_loud_coefficients(rate, c)
+    return list(c)
+
+
+def loud_lufs(mean_square):
+    """-0.691 + 10 * log10(mean_square), -inf for 0"""
+    return lib.cmhip_loud_lufs(mean_square)
+
+
+def loud_integrate(z):
+    """gated integrated loudness of sub-block mean squares z -> (integrated, relative threshold, gated blocks)"""
+    arr = (C.c_double * len(z))(*z)
+    i, t, g = C.c_double(), C.c_double(), C.c_size_t()
+    _check("loud_integrate", lib.cmhip_loud_integrate(arr, len(z), C.byref(i), C.byref(t), C.byref(g)))
+    return i.value, t.value, g.value
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -581,6 +643,43 @@ class Batch:
 
     def tp_reset(self, stream=-1):
         _check("tp_reset", lib.cmhip_batch_tp_reset(self.h, stream))
+
+    # loudness (opt-in)
+    def set_loudness(self, on):
+        """the error number (INVAL while the equaliser has sections or for a rate outside 8000..384000)"""
+        return lib.cmhip_batch_set_loudness(self.h, int(bool(on)))
+
+    def get_loudness(self):
+        return lib.cmhip_batch_get_loudness(self.h)
+
+    def loud_set_weights(self, stream, weights):
+        """the error number (BUSY while the stream holds completed sub-blocks)"""
+        if len(weights) != self.channels:
+            raise ValueError("loud_set_weights: %d weights for %d channels" % (len(weights), self.channels))
+        w = (C.c_double * self.channels)(*weights)
+        return lib.cmhip_batch_loud_set_weights(self.h, stream, w)
+
+    def loud_result(self, stream):
+        r = LoudnessResult()
+        rc = lib.cmhip_batch_loud_result(self.h, stream, C.byref(r))
+        return rc, r
+
+    def loud_results(self):
+        out = (LoudnessResult * self.streams)()
+        rc = (C.c_int * self.streams)()
+        _check("loud_results", lib.cmhip_batch_loud_results(self.h, out, rc))
+        return out, list(rc)
+
+    def loud_raw(self, stream, cap=30):
+        """the trailing min(cap, 30) complete sub-blocks' per-channel sums, oldest first -> ([n][channels] array,
+        sub-blocks completed in all)"""
+        sums = np.zeros((max(cap, 1), self.channels), dtype=np.float64)
+        n, done = C.c_size_t(), C.c_ulonglong()
+        _check("loud_raw", lib.cmhip_batch_loud_raw(self.h, stream, sums.ctypes.data, cap, C.byref(n), C.byref(done)))
+        return sums[:n.value].copy(), done.value
+
+    def loud_reset(self, stream=-1):
+        _check("loud_reset", lib.cmhip_batch_loud_reset(self.h, stream))
 
     def vu_raw(self, stream):
         power = np.zeros(MAX_CH, dtype=np.int64)
@@ -1031,6 +1130,31 @@ class Group:
         rc = (C.c_int * n)()
         _check("group_true_peaks", lib.coolmic_group_true_peaks(self.ptr, out, rc))
         return out, list(rc)
+
+    def set_loudness(self, on):
+        return lib.coolmic_group_set_loudness(self.ptr, int(bool(on)))
+
+    def loudness(self, slot):
+        r = LoudnessResult()
+        rc = lib.coolmic_group_loudness(self.ptr, slot, C.byref(r))
+        return rc, r
+
+    def loudnesses(self, out=None):
+        """every slot's loudness at once -> (LoudnessResult array, rc list); `out`: the array to fill"""
+        n = self.streams()
+        out = out if out is not None else (LoudnessResult * n)()
+        rc = (C.c_int * n)()
+        _check("group_loudnesses", lib.coolmic_group_loudnesses(self.ptr, out, rc))
+        return out, list(rc)
+
+    def loudness_set_weights(self, slot, weights):
+        if len(weights) != self.channels:
+            raise ValueError("loudness_set_weights: %d weights for %d channels" % (len(weights), self.channels))
+        w = (C.c_double * self.channels)(*weights)
+        return lib.coolmic_group_loudness_set_weights(self.ptr, slot, w)
+
+    def loudness_reset(self, slot=-1):
+        return lib.coolmic_group_loudness_reset(self.ptr, slot)
 
     def streams(self):
         return lib.coolmic_group_streams(self.ptr)

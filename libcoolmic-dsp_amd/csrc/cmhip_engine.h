@@ -3,6 +3,7 @@
 //   cmhip_place.hip    the opt-in placement search for a batch's two PCM arrays
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
 //   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
+//   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
 #pragma once
@@ -126,6 +127,19 @@ struct cmhip_batch {
     unsigned int tp_parity = 0;
     std::vector<unsigned long long> tp_frames;   // frames accounted per stream since its window opened
     std::vector<uint32_t> tp_host;         // [S][16] staging of a result call
+    // loudness (cmhip_loud.hip), all of it unused until cmhip_batch_set_loudness(b, 1)
+    bool loud_on = false;
+    LoudState *d_loud = nullptr;           // [S][C] the rows' filter history and open sub-block
+    double *d_loud_ring = nullptr;         // [S][loud_slots][C] completed sub-block sums
+    unsigned int loud_sub = 0;             // L: frames per sub-block
+    unsigned int loud_slots = 0;           // R: sub-blocks the ring holds per stream
+    double loud_coef[10] = {};
+    std::vector<double> loud_w;            // [S][C] channel weights (kept across enable / reset)
+    std::vector<unsigned long long> loud_frames;    // frames per stream since enable / reset: completed = frames / L
+    std::vector<unsigned long long> loud_drained;   // sub-blocks per stream taken out of the ring so far
+    std::vector<std::vector<double>> loud_z;        // per stream: z_j of every drained sub-block
+    std::vector<double> loud_recent;       // [S][30][C] per-channel sums of the trailing sub-blocks, number j at j % 30
+    std::vector<double> loud_host;         // [S][loud_slots][C] staging of a drain
 };
 
 
@@ -147,6 +161,10 @@ CMHIP_INTERNAL RunArgs cmhip_engine_run_args(const cmhip_batch_t *b, const int16
 // (only called while b->tp_on; frames_per_stream: the run's host array or nullptr, already uploaded to d_nframes)
 CMHIP_INTERNAL int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                        const uint32_t *frames_per_stream);
+// cmhip_loud.hip: the loudness pass of a run over `in`, queued on the batch's stream ahead of the block kernel (only
+// called while b->loud_on; drains the ring first when the run could overflow it).  Returns an error number.
+CMHIP_INTERNAL int cmhip_engine_loud_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
+                                         const uint32_t *frames_per_stream);
 // cmhip_place.hip: called once, at the end of a batch's creation, when it has PCM arrays of its own
 CMHIP_INTERNAL int cmhip_engine_place_arrays_apart(cmhip_batch_t *b, size_t bytes);
 // cmhip_vu.hip (for node.hip): the node record of the batch's windows, built on the copy stream

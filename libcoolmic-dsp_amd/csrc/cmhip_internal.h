@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip (the gfx950 kernels) and cmhip_batch.hip (the engine).
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip (the gfx950 kernels) and cmhip_batch.hip (the engine).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -143,6 +143,36 @@ struct TpArgs {
     uint32_t       chunks;         // tiles per stream (the launcher fills it in)
 };
 
+// Loudness (ITU-R BS.1770 K-weighting, 100 ms sub-block sums): one row is one channel of one stream.
+// LoudState [S][C]: the two biquads' Direct Form I history in double (section 2's inputs are section 1's outputs, so
+// six values), the open sub-block's sum of squares, the frames it holds, and the sub-blocks the row has completed.
+// Exactly one lane owns a row in a launch, so the state is updated in place.  All zero = freshly reset.
+struct LoudState {
+    double   u1, u2;               // section 1 inputs n-1, n-2
+    double   y1, y2;               // section 1 outputs n-1, n-2 (= section 2's inputs)
+    double   v1, v2;               // section 2 outputs n-1, n-2
+    double   e;                    // sum of squares of the open sub-block, in frame order from 0.0
+    uint32_t pos;                  // frames in the open sub-block (< LoudArgs::sub)
+    uint32_t pad;
+    uint64_t done;                 // sub-blocks completed since enable / reset; number j went to ring slot j % ring
+};
+static_assert(sizeof(LoudState) == 72, "nine 8-byte words");
+
+struct LoudArgs {
+    const int16_t *in;             // the run's INPUT slots: the kernel applies map and gain itself
+    const StreamParam *param;
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    LoudState     *state;          // [S][C]
+    double        *ring;           // [S][ring][C] completed sub-block sums
+    double         coef[10];       // cmhip_loud_coefficients: {b0,b1,b2,a1,a2} of section 1, of section 2
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       sub;            // frames per sub-block: (rate + 5) / 10
+    uint32_t       ring_slots;
+    uint64_t       stride;         // samples between stream slots (multiple of 8)
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -188,6 +218,14 @@ struct TpPlan {
 };
 TpPlan plan_tpeak(const TpArgs &a);
 hipError_t launch_tpeak(const TpArgs &a, hipStream_t st);
+// Loudness (k_loud.hip): one lane per row, one wave per workgroup.
+struct LoudPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   vec;                // mono / stereo: the lanes walk their slots in 16-byte vectors
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+};
+LoudPlan plan_loud(const LoudArgs &a);
+hipError_t launch_loud(const LoudArgs &a, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

@@ -63,6 +63,7 @@ struct coolmic_group {
     std::vector<int> *vu_rc;                 // the engine's max_streams results and codes (made on first use)
     std::vector<coolmic_truepeak_result_t> *tp_out;  // the same for coolmic_group_true_peaks
     std::vector<int> *tp_rc;
+    std::vector<coolmic_loudness_result_t> *loud_out;    // and for coolmic_group_loudnesses
 };
 
 struct GroupHandle {
@@ -78,6 +79,7 @@ static void group_destroy(void *self)
     delete g->vu_rc;
     delete g->tp_out;
     delete g->tp_rc;
+    delete g->loud_out;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -587,4 +589,64 @@ extern "C" int coolmic_group_true_peaks(coolmic_group_t *self, coolmic_truepeak_
             rc[i] = (*self->tp_rc)[i];
     }
     return COOLMIC_ERROR_NONE;
+}
+
+// Loudness: thin wrappers over the engine (cmhip_loud.hip), with the slot handling of the true-peak calls.
+extern "C" int coolmic_group_set_loudness(coolmic_group_t *self, int on)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_set_loudness(self->batch, on);
+}
+
+extern "C" int coolmic_group_loudness(coolmic_group_t *self, unsigned int slot, coolmic_loudness_result_t *result)
+{
+    if (!self || !result)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= self->streams->size())
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_loud_result(self->batch, slot, result);
+}
+
+extern "C" int coolmic_group_loudnesses(coolmic_group_t *self, coolmic_loudness_result_t *results, int *rc)
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return cmhip_batch_loud_results(self->batch, results, rc);
+    if (!self->loud_out) {
+        try {
+            self->loud_out = new std::vector<coolmic_loudness_result_t>(self->max_streams);
+        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
+            return COOLMIC_ERROR_NOMEM;
+        }
+    }
+    const int r = cmhip_batch_loud_results(self->batch, self->loud_out->data(), nullptr);
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        results[i] = (*self->loud_out)[i];
+        if (rc)
+            rc[i] = COOLMIC_ERROR_NONE;
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights)
+{
+    if (!self || !weights)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= (long)self->streams->size() || slot < -1)
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_loud_set_weights(self->batch, slot, weights);
+}
+
+extern "C" int coolmic_group_loudness_reset(coolmic_group_t *self, long slot)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= (long)self->streams->size() || slot < -1)
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_loud_reset(self->batch, slot);
 }
