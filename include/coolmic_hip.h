@@ -309,6 +309,78 @@ void   cmhip_loud_coefficients(unsigned int rate, double c[10]);
 double cmhip_loud_lufs(double mean_square);
 int    cmhip_loud_integrate(const double *z, size_t n, double *integrated, double *threshold, size_t *gated);
 
+/* ---- sample-rate conversion, an object of its own beside the batch ------------- */
+/* A resampler converts rate_in to rate_out for S streams of C interleaved int16 channels by a rational polyphase FIR
+ * in exact integers.  The signal is the raw int16 the caller hands in: no gain and no map, the batch does those.
+ *
+ * Arithmetic.  g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g; a table H[L][T] of int16 coefficients
+ *   in units of 2^-14 (unity = 16384).  Output frame m of a stream, counted from creation or reset, reads input frame
+ *   n = floor(m*M / L) with phase p = (m*M) mod L, per channel:
+ *       acc  = sum_{k<T} H[p][k] * x[n-k]            exact in int32
+ *       y[m] = saturate_int16((acc + 8192) >> 14)    arithmetic shift (floor)
+ *   x[i] for i < 0 is the stream's history: zero at creation and after cmhip_src_reset.
+ * Table validity (designed or supplied): L, M in 1..640 and L != M; T even, in 2..192; every phase has
+ *   sum_k |H[p][k]| <= 65535.  Then |acc + 8192| <= 65535*32768 + 8192 < 2^31: int32 never overflows and the result
+ *   does not depend on the order of summation.  Anything else is COOLMIC_ERROR_INVAL.
+ * Counts.  After N input frames in all a stream has produced K(N) = ceil(N*L / M) output frames (output m exists
+ *   once input floor(m*M/L) does); a run of F frames produces K(N+F) - K(N), at most floor(F*L/M) + 1.  Everything is
+ *   periodic -- M inputs give exactly L outputs -- so a stream's state is r = N mod M and its last T-1 input frames
+ *   per channel, and nothing overflows however long it runs.  A stream that gets 0 frames in a run keeps everything;
+ *   the concatenated output does not depend on how the stream was cut into runs.
+ *   cmhip_src_out_frames(L, M, r, F) = ceil((r+F)*L / M) - ceil(r*L / M) is that count.
+ * The designed table (cmhip_src_design, host only, double precision, in this order): T = 32 when L > M, else
+ *   32 * ceil(M/L); N = L*T, fc = 0.92 * 0.5 / max(L, M); for i in 0..N-1 with x = i - (N-1)/2:
+ *       w = I0(7.5 * sqrt(max(0, 1 - (x / (N/2))^2))) / I0(7.5)          h[i] = 2*fc * sinc(2*fc*x) * w * L
+ *   sinc(t) = sin(pi t) / (pi t), 1 at t = 0; I0 from its power series sum ((x/2)^k / k!)^2, summed until a term no
+ *   longer changes the sum.  H[p][k] = h[k*L + p]; every phase is divided by its own sum, multiplied by 16384 and
+ *   rounded with rint, and the difference between 16384 and the phase's integer sum is added to the phase's first tap
+ *   of largest magnitude: every phase sums to exactly 16384, a constant input comes out as the same constant once the
+ *   history is full.  The table's bits are not pinned across libms: whatever table the library returns is the
+ *   specification for the kernel.  Equal rates, a zero rate, or L or M above 640 are COOLMIC_ERROR_INVAL.
+ *   cmhip_src_design: h == NULL returns the geometry only (L, M, T may each be NULL); with h, cap counts its entries,
+ *   and a cap below L*T is COOLMIC_ERROR_INVAL with nothing written.
+ *
+ * cmhip_src_run: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in samples as in a batch, both
+ *   device-accessible; asynchronous on the resampler's stream.  `frames` input frames per stream, or
+ *   frames_per_stream[s] <= frames (host array of S entries, may be NULL).  COOLMIC_ERROR_INVAL, with nothing launched
+ *   and nothing changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or smaller than
+ *   the run needs (frames * C in; the run's largest output count * C out -- cmhip_src_max_out_frames() * C always
+ *   suffices), frames > max_in_frames, a per-stream count is above frames, or in == out; COOLMIC_ERROR_FAULT for NULL
+ *   arrays.  out_frames[] (host, S entries, may be NULL) receives every stream's output count, computed on the host
+ *   from its mirror of r before the call returns, without a device wait -- exactly the frames_per_stream argument of
+ *   a cmhip_batch_run on the result.  Outputs past a stream's count are not written.
+ * Composition: a batch created with rate = rate_out takes the output straight into its own slots
+ *   (out = cmhip_batch_dev_in(b), out_stride = cmhip_batch_stride(b)); a CMHIP_EXTSLOTS batch takes it through
+ *   cmhip_batch_run_slots; with hip_stream = cmhip_batch_hip_stream(b) the order is the stream's.
+ * cmhip_src_new designs the table for the descriptor's rates; cmhip_src_new_table takes the caller's H[L][T] (the
+ *   descriptor's rates are informational then).  max_in_frames * C and the matching output may not pass 2^31 samples.
+ *   Both return NULL on failure.  cmhip_src_reset (stream -1: all) zeroes history and r, on the resampler's stream. */
+typedef struct cmhip_src cmhip_src_t;
+typedef struct cmhip_src_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int rate_in;         /* Hz */
+    unsigned int rate_out;        /* Hz */
+    size_t       max_in_frames;   /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_src_desc_t;
+cmhip_src_t *cmhip_src_new(const cmhip_src_desc_t *d);
+cmhip_src_t *cmhip_src_new_table(const cmhip_src_desc_t *d, unsigned int L, unsigned int M, unsigned int T,
+                                 const int16_t *h /* [L][T] */);
+void     cmhip_src_free(cmhip_src_t *r);
+int      cmhip_src_geometry(const cmhip_src_t *r, unsigned int *L, unsigned int *M, unsigned int *T);
+size_t   cmhip_src_max_out_frames(const cmhip_src_t *r);      /* floor(max_in_frames * L / M) + 1 */
+int      cmhip_src_run(cmhip_src_t *r, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride, uint32_t *out_frames);
+int      cmhip_src_reset(cmhip_src_t *r, long stream);
+int      cmhip_src_sync(cmhip_src_t *r);
+void    *cmhip_src_hip_stream(cmhip_src_t *r);
+/* host only, no device needed */
+int      cmhip_src_design(unsigned int rate_in, unsigned int rate_out, unsigned int *L, unsigned int *M, unsigned int *T,
+                          int16_t *h, size_t cap /* entries */);
+uint32_t cmhip_src_out_frames(unsigned int L, unsigned int M, uint32_t r, uint32_t frames);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

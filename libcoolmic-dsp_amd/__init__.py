@@ -85,6 +85,12 @@ class BatchDesc(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+class SrcDesc(C.Structure):
+    """cmhip_src_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("rate_in", C.c_uint),
+                ("rate_out", C.c_uint), ("max_in_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
 class Placement(C.Structure):
     """cmhip_placement_t (include/coolmic_hip.h)"""
     _fields_ = [("searched", C.c_int), ("candidates", C.c_int), ("chosen_in", C.c_int),
@@ -174,6 +180,17 @@ SIGNATURES = {
     "cmhip_loud_coefficients": (None, [C.c_uint, _vp]),
     "cmhip_loud_lufs": (C.c_double, [C.c_double]),
     "cmhip_loud_integrate": (C.c_int, [_vp, C.c_size_t, _P(C.c_double), _P(C.c_double), _P(C.c_size_t)]),
+    "cmhip_src_new": (_vp, [_P(SrcDesc)]),
+    "cmhip_src_new_table": (_vp, [_P(SrcDesc), C.c_uint, C.c_uint, C.c_uint, _vp]),
+    "cmhip_src_free": (None, [_vp]),
+    "cmhip_src_geometry": (C.c_int, [_vp, _P(C.c_uint), _P(C.c_uint), _P(C.c_uint)]),
+    "cmhip_src_max_out_frames": (C.c_size_t, [_vp]),
+    "cmhip_src_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "cmhip_src_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_src_sync": (C.c_int, [_vp]),
+    "cmhip_src_hip_stream": (_vp, [_vp]),
+    "cmhip_src_design": (C.c_int, [C.c_uint, C.c_uint, _P(C.c_uint), _P(C.c_uint), _P(C.c_uint), _vp, C.c_size_t]),
+    "cmhip_src_out_frames": (C.c_uint32, [C.c_uint, C.c_uint, C.c_uint32, C.c_uint32]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -299,6 +316,9 @@ if hasattr(lib, "cmhip_test_plan_loud"):        # (not in builds older than loud
     lib.cmhip_test_plan_loud.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.cmhip_debug_loud_count.restype = C.c_ulonglong
     lib.cmhip_debug_loud_count.argtypes = []
+if hasattr(lib, "cmhip_test_plan_src"):         # (not in builds older than sample-rate conversion)
+    lib.cmhip_test_plan_src.restype = None
+    lib.cmhip_test_plan_src.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -408,6 +428,35 @@ def loud_integrate(z):
     i, t, g = C.c_double(), C.c_double(), C.c_size_t()
     _check("loud_integrate", lib.cmhip_loud_integrate(arr, len(z), C.byref(i), C.byref(t), C.byref(g)))
     return i.value, t.value, g.value
+
+
+class SrcPlan(C.Structure):
+    """cmhip::SrcPlan (csrc/cmhip_internal.h): what the resampler's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_out", "tile_in",
+                                                               "row", "table_lds", "lds_bytes")]
+
+
+def plan_src(streams, channels, L, M, T, out_frames):
+    """Test hook: the resampler launcher's plan for a run that gives its longest stream out_frames frames (host
+    logic, needs no GPU)"""
+    p = SrcPlan()
+    lib.cmhip_test_plan_src(streams, channels, L, M, T, out_frames, C.addressof(p))
+    return p
+
+
+def src_design(rate_in, rate_out):
+    """the designed resampling table for a pair of rates -> (L, M, T, int16 array [L][T]); CoolmicError when the pair
+    has none"""
+    L, M, T = C.c_uint(), C.c_uint(), C.c_uint()
+    _check("src_design", lib.cmhip_src_design(rate_in, rate_out, C.byref(L), C.byref(M), C.byref(T), None, 0))
+    h = np.zeros(L.value * T.value, dtype=np.int16)
+    _check("src_design", lib.cmhip_src_design(rate_in, rate_out, None, None, None, h.ctypes.data, h.size))
+    return L.value, M.value, T.value, h.reshape(L.value, T.value)
+
+
+def src_out_frames(L, M, r, frames):
+    """output frames of a run of `frames` input frames for a stream at position r = (frames so far) mod M"""
+    return lib.cmhip_src_out_frames(L, M, r, frames)
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -723,6 +772,69 @@ class Batch:
     @property
     def dev_out(self):
         return lib.cmhip_batch_dev_out(self.h)
+
+
+class Resampler:
+    """cmhip_src_t: sample-rate conversion of S streams beside a batch.  Without `table` the library designs one for
+    the rates; with it, table = (L, M, int16 array [L][T])."""
+
+    def __init__(self, streams, channels, rate_in, rate_out, max_in_frames, table=None, device=0, hip_stream=None):
+        d = SrcDesc(device, streams, channels, rate_in, rate_out, max_in_frames, hip_stream)
+        if table is None:
+            self.h = lib.cmhip_src_new(C.byref(d))
+        else:
+            L, M, h = table
+            h = np.ascontiguousarray(h, dtype=np.int16)
+            assert h.ndim == 2 and h.shape[0] == L
+            self.h = lib.cmhip_src_new_table(C.byref(d), L, M, h.shape[1], h.ctypes.data)
+        if not self.h:
+            raise CoolmicError("cmhip_src_new", ERROR_INVAL)
+        self.streams, self.channels, self.max_in_frames = streams, channels, max_in_frames
+
+    def close(self):
+        if self.h:
+            lib.cmhip_src_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def geometry(self):
+        L, M, T = C.c_uint(), C.c_uint(), C.c_uint()
+        _check("src_geometry", lib.cmhip_src_geometry(self.h, C.byref(L), C.byref(M), C.byref(T)))
+        return L.value, M.value, T.value
+
+    def max_out_frames(self):
+        return lib.cmhip_src_max_out_frames(self.h)
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_src_run as it is -> (error number, uint32 array of the streams' output counts)"""
+        fps = None
+        if frames_per_stream is not None:
+            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
+            assert fps.size == self.streams
+        got = np.zeros(self.streams, dtype=np.uint32)
+        rc = lib.cmhip_src_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
+                               out_stride, got.ctypes.data)
+        return rc, got
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers) -> the streams' output counts"""
+        rc, got = self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream)
+        _check("src_run", rc)
+        return got
+
+    def reset(self, stream=-1):
+        _check("src_reset", lib.cmhip_src_reset(self.h, stream))
+
+    def sync(self):
+        _check("src_sync", lib.cmhip_src_sync(self.h))
+
+    def hip_stream(self):
+        return lib.cmhip_src_hip_stream(self.h) or 0
 
 
 class PinnedPcm:

@@ -4,6 +4,7 @@
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
 //   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
 //   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
+//   cmhip_src.hip      sample-rate conversion: the resampler object beside the batch (uses fail / HIP_TRY only)
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
 #pragma once

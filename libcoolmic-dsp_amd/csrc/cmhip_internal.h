@@ -1,5 +1,6 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip (the gfx950 kernels) and cmhip_batch.hip (the engine).
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip (the gfx950 kernels) and cmhip_batch.hip (the
+// engine).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -173,6 +174,32 @@ struct LoudArgs {
     uint64_t       stride;         // samples between stream slots (multiple of 8)
 };
 
+// Sample-rate conversion (k_src.hip; the arithmetic: include/coolmic_hip.h): a resampler's run over S stream slots.
+struct SrcArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *nframes;       // per-stream input frame counts or nullptr
+    // [L][T8 + 8] the table in the kernel's form: rows padded with zero taps to T8 = T rounded up to 8 and by 8 more
+    // samples, every tap pair swapped (H[p][k+1], H[p][k]) -- the order v_dot2c_i32_i16 meets a pair of samples in
+    const int16_t *table;
+    // [2][S][C][T-1] the last T-1 input frames per channel, oldest first, and [2][S] r = (frames so far) mod M.  Two
+    // slots each: a run reads slot `parity`, the stream's last tile writes slot `parity ^ 1`; the host flips parity.
+    int16_t       *hist;
+    uint32_t      *rpos;
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       parity;
+    uint32_t       L, M, T;
+    // (the launcher fills these in)
+    uint32_t       inv_l;          // ceil(2^32 / L), 0 for L == 1
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_out;       // output frames per tile
+    uint32_t       row;            // samples between the planes of a tile in LDS
+    uint32_t       table_lds;      // the table is copied into LDS
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -226,6 +253,21 @@ struct LoudPlan {
 };
 LoudPlan plan_loud(const LoudArgs &a);
 hipError_t launch_loud(const LoudArgs &a, hipStream_t st);
+// Sample-rate conversion (k_src.hip): one workgroup per stream and tile of tile_out output frames.  fast: the mono /
+// stereo kernel; otherwise the any-channel-count kernel.  out_frames: what the run gives its longest stream.
+struct SrcPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   fast;
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+    uint32_t   chunks;             // SrcArgs::chunks: tiles per stream
+    uint32_t   tile_out;           // output frames per tile
+    uint32_t   tile_in;            // input frames a tile stages at most, its halo included
+    uint32_t   row;                // SrcArgs::row
+    uint32_t   table_lds;          // SrcArgs::table_lds
+    uint32_t   lds_bytes;          // dynamic LDS of the launch
+};
+SrcPlan plan_src(const SrcArgs &a, uint32_t out_frames);
+hipError_t launch_src(const SrcArgs &a, uint32_t out_frames, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,
