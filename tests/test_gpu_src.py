@@ -2,7 +2,12 @@
 
 Bar: bit-exact against the numpy model below of the arithmetic include/coolmic_hip.h specifies -- int64, per-stream
 history and r -- never another run of the device code.  Tables are taken from the library (cmhip_src_design), or are
-the test's own where the test is about a table.
+the test's own where the test is about a table: the designed tables are windowed sincs whose outer taps are next to
+nothing (at 48000 -> 8000 the first and last six are zero), so whatever a kernel does wrong at the ends of the filter
+-- the oldest history frames, the oldest frames of a tile's halo, the last tap pair -- adds nothing to their sums.
+dense_table() gives every tap weight; CASES lists the geometries that reach each staging path of the kernel, with
+the property that makes a case reach its path asserted from plan_src and host arithmetic (tests/test_src_host.py
+runs the same list through its emulation of the kernel, without a GPU).
 """
 import os
 import subprocess
@@ -93,6 +98,10 @@ class Rig:
         self.src = cm.MappedPcm(types.SimpleNamespace(streams=streams, stride=self.in_stride))
         self.dst = cm.MappedPcm(types.SimpleNamespace(streams=streams, stride=self.out_stride))
         self.models = [Model(L, M, H, channels) for _ in range(streams)]
+        self.samples = self.saturated = 0                        # of the models' outputs so far
+
+    def saturated_share(self):
+        return self.saturated / max(self.samples, 1)
 
     def close(self):
         self.r.close()
@@ -115,6 +124,8 @@ class Rig:
             want = self.models[s].run(x)
             assert got[s] == want.shape[0], (s, got[s], want.shape[0])
             n = want.size
+            self.samples += n
+            self.saturated += int(((want == 32767) | (want == -32768)).sum())
             have = self.dst.array[s, :n].reshape(-1, self.C)
             bad = np.argwhere(have != want)
             assert bad.size == 0, ("stream", s, "first mismatch (frame, channel)", bad[0].tolist(),
@@ -127,6 +138,171 @@ class Rig:
         self.r.reset(stream)
         for s in (range(self.S) if stream < 0 else [stream]):
             self.models[s].reset()
+
+
+# ---------------------------------------------------------------------------
+# dense tables, and the cases that reach every staging path
+
+SATURATED_MAX = 0.10              # of a dense case's outputs in the MODEL: a saturated output hides a wrong sum
+
+
+def dense_table(L, T, seed):
+    """int16 [L][T] with weight at every tap: |h| in [3B/4, B], B = min(65535 // T, 4096), random signs, no two phases
+    alike.  sum |h| <= 65535 per phase (what the library asks of a table); the phases do not sum to 16384."""
+    B = min(65535 // T, 4096)
+    rng = np.random.default_rng(seed)
+    while True:
+        H = rng.integers(-(-3 * B // 4), B + 1, size=(L, T)) * rng.choice([-1, 1], size=(L, T))
+        if len({row.tobytes() for row in H}) == L:
+            break
+    assert int(np.abs(H).min()) >= 3 * B / 4 and int(np.abs(H).sum(axis=1).max()) <= 65535
+    return H.astype(np.int16)
+
+
+def ragged(F, T):
+    """per-stream counts of one run: a full stream, one with nothing, one frame, T - 2 frames, F - 1 frames"""
+    return [F, 0, 1, T - 2, F - 1]
+
+
+def _case(name, geometry, channels, runs, table="dense", rates=None, plan=None, reach=()):
+    """runs: per run the streams' frame counts.  plan: the SrcPlan fields the case relies on, for its longest run.
+    reach: what tile_facts() must find (REACH)."""
+    L, M, T = geometry
+    return types.SimpleNamespace(name=name, L=L, M=M, T=T, C=channels, runs=runs, table=table, rates=rates,
+                                 plan=dict(plan or {}), reach=tuple(reach))
+
+
+def _twice(counts):
+    return [counts, counts[::-1]]
+
+
+def _rotated(counts):
+    """two streams: the list, and the list rotated by one run -- different r and fill of the history per run"""
+    return [list(c) for c in zip(counts, counts[1:] + counts[:1])]
+
+
+CASES = []
+# 1. 11025 -> 48000 as designed: 640 x 40 x 2 = 51200 bytes of table, read from global memory; 8708 outputs in three
+# tiles
+for _c in (1, 2, 3, 16):
+    CASES.append(_case("global-designed-c%d" % _c, (640, 147, 32), _c, _twice(ragged(2000, 32)), "designed",
+                       (11025, 48000), dict(table_lds=0, tile_out=4096, chunks=3),
+                       ("lds60000",) if _c == 16 else ()))
+# 2. 44100 -> 32000: the padded table is exactly the 46080 bytes a table in LDS may have
+for _t in ("designed", "dense"):
+    CASES.append(_case("bound-%s-c2" % _t, (320, 441, 64), 2, _twice(ragged(3000, 64)), _t, (44100, 32000),
+                       dict(table_lds=1, tile_out=1024, lds_bytes=57888, chunks=3)))
+    CASES.append(_case("bound-%s-c16" % _t, (320, 441, 64), 16, _twice(ragged(600, 64)), _t, (44100, 32000),
+                       dict(table_lds=1, tile_out=128, lds_bytes=61568, chunks=4), ("lds60000",)))
+# 3. the halo reaches behind the previous tile: a tile of 4096 outputs covers 6.4 (25.6, 17.9) input frames
+for _c, _T in ((1, 192), (2, 192), (16, 192), (3, 190)):
+    CASES.append(_case("halo-640x%d-c%d" % (_T, _c), (640, 1, _T), _c, _rotated([14, 1, 0, 14, 40]),
+                       plan=dict(table_lds=0, tile_out=4096), reach=("halo",)))
+CASES.append(_case("halo-160x32-c2", (160, 1, 32), 2, _rotated([60, 1, 0, 60]), plan=dict(table_lds=1, tile_out=4096),
+                   reach=("halo", "mix", "clear")))
+CASES.append(_case("halo-229x30-c1", (229, 1, 30), 1, _rotated([60, 1, 0, 60]), plan=dict(table_lds=1, tile_out=4096),
+                   reach=("halo", "mix")))
+# 4. the reciprocal's range (t = p0 + q M up to 2.6e6, inv = 2^31, inv = 0) and the small ends (T = 2, tiles of 2 and 8)
+# (five channels beside the table of 639 phases leave room for tiles of 1024 only: t goes up to 1023 * 640 there)
+for _c, _g, _tile in ((2, (640, 639, 6), 4096), (1, (639, 640, 10), 4096), (5, (639, 640, 10), 1024)):
+    CASES.append(_case("divmod-%dx%d-c%d" % (_g[0], _g[1], _c), _g, _c, [[5] * 5] + _twice(ragged(9000, _g[2])),
+                       plan=dict(table_lds=1, tile_out=_tile), reach=("t21" if _tile == 4096 else "tfull",)))
+CASES.append(_case("divmod-2x3-c2", (2, 3, 2), 2, _twice(ragged(13000, 2)), plan=dict(table_lds=1, tile_out=4096)))
+for _c, _tile in ((2, 8), (16, 2)):
+    CASES.append(_case("divmod-1x640-c%d" % _c, (1, 640, 192), _c, _twice(ragged(12800, 192)),
+                       plan=dict(table_lds=1, tile_out=_tile), reach=("tile8",)))
+
+
+def case_table(cm, case):
+    if case.table == "designed":
+        L, M, T, H = table(cm, *case.rates)
+        assert (L, M, T) == (case.L, case.M, case.T)
+        return H
+    return dense_table(case.L, case.T, 1000 + case.L + case.T)
+
+
+def tile_facts(cm, case):
+    """-> (the plan of the longest run, one record per run, stream and tile: j_lo, the first frame the tile stages as
+    the kernel computes it, t_hi, the largest t = p0 + q M it hands to src_divmod, and whether the tile is the
+    stream's first in its run) from plan_src and host arithmetic alone"""
+    L, M, T, Tp = case.L, case.M, case.T, (case.T + 7) // 8 * 8
+    S = len(case.runs[0])
+    r, recs, longest = [0] * S, [], None
+    for i, counts in enumerate(case.runs):
+        K = [cm.src_out_frames(L, M, r[s], counts[s]) for s in range(S)]
+        plan = cm.plan_src(S, case.C, L, M, T, max(K) or 1)      # (cmhip_src_run: at least one workgroup per stream)
+        assert plan.err == 0 and plan.grid == S * plan.chunks
+        if longest is None or plan.chunks > longest.chunks:
+            longest = plan
+        for s in range(S):
+            kb = -(-r[s] * L // M)
+            for q0 in range(0, K[s], plan.tile_out):
+                nq = min(plan.tile_out, K[s] - q0)
+                n0, p0 = divmod((kb + q0) * M, L)
+                recs.append(types.SimpleNamespace(run=i, stream=s, first=q0 == 0, j_lo=n0 - r[s] - (Tp - 1),
+                                                  t_hi=p0 + (nq - 1) * M))
+            r[s] = (r[s] + counts[s]) % M
+    return longest, recs
+
+
+REACH = {
+    "lds60000": lambda case, plan, recs: plan.lds_bytes > 60000,
+    # a tile after the stream's first stages frames from before the run
+    "halo": lambda case, plan, recs: any(not t.first and t.j_lo < 0 for t in recs),
+    # ... and it stages history frames AND frames of the run
+    "mix": lambda case, plan, recs: any(not t.first and -(case.T - 1) < t.j_lo < 0 for t in recs),
+    # ... and another one stages no history at all
+    "clear": lambda case, plan, recs: any(not t.first and t.j_lo >= 0 for t in recs),
+    "t21": lambda case, plan, recs: max(t.t_hi for t in recs) >= 1 << 21,
+    # the largest t the plan's tile can give: a whole tile
+    "tfull": lambda case, plan, recs: max(t.t_hi for t in recs) >= (plan.tile_out - 1) * case.M,
+    "tile8": lambda case, plan, recs: plan.tile_out <= 8 and plan.chunks >= 3,
+}
+
+
+def assert_reaches(cm, case):
+    """the case reaches what it is there for, or fails loudly (a planner that changed, say)"""
+    plan, recs = tile_facts(cm, case)
+    assert max(t.t_hi for t in recs) < 1 << 22                   # (what src_divmod is exact for)
+    assert plan.lds_bytes <= 65536
+    assert plan.fast == (1 if case.C <= 2 else 0)
+    for field, want in case.plan.items():
+        assert getattr(plan, field) == want, (case.name, field, getattr(plan, field), want)
+    for what in case.reach:
+        assert REACH[what](case, plan, recs), (case.name, what)
+    return plan, recs
+
+
+def run_case(cm, case):
+    assert_reaches(cm, case)
+    H = case_table(cm, case)
+    S = len(case.runs[0])
+    rig = Rig(cm, S, case.C, case.L, case.M, H, max(max(c) for c in case.runs))
+    for i, counts in enumerate(case.runs):
+        xs = [noise(1000 * i + 10 * case.C + s, n, case.C) for s, n in enumerate(counts)]
+        rig.run(xs, frames=max(max(counts), 1))
+    share = rig.saturated_share()
+    print("src case", case.name, "outputs", rig.samples, "saturated in the model %.4f" % share)
+    if case.table == "dense":
+        assert share < SATURATED_MAX
+    rig.close()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_staging_paths(gpu, case):
+    run_case(gpu, case)
+
+
+def test_many_streams_and_uniform_counts(gpu):
+    """300 stereo streams: the indexing of history, r, slots and grid by the stream, and nframes == NULL with S > 1"""
+    S, F = 300, 64
+    rig = Rig(gpu, S, 2, 3, 2, dense_table(3, 8, 5), F)
+    rig.run([noise(3000 + s, F, 2) for s in range(S)], uniform=True)
+    counts = [s % 65 for s in range(S)]
+    assert max(counts) == F and min(counts) == 0
+    rig.run([noise(4000 + s, n, 2) for s, n in enumerate(counts)], frames=F)
+    assert len({m.r for m in rig.models}) == 2 and rig.saturated_share() < SATURATED_MAX
+    rig.close()
 
 
 # ---------------------------------------------------------------------------
@@ -182,9 +358,17 @@ def test_designed_tables(gpu, rates, channels):
 # ---------------------------------------------------------------------------
 # 3. the output does not depend on how the stream was cut into runs
 
-@pytest.mark.parametrize("rates,channels", [((44100, 48000), 1), ((48000, 44100), 2), ((48000, 8000), 3)])
-def test_cutting(gpu, rates, channels):
-    L, M, T, H = table(gpu, *rates)
+def _table_of(cm, rates, dense):
+    """the designed table of a pair of rates, or a dense one of the same (L, M, T)"""
+    L, M, T, H = table(cm, *rates)
+    return L, M, T, dense_table(L, T, L + T) if dense else H
+
+
+CUTTING = [((44100, 48000), 1), ((48000, 44100), 2), ((48000, 8000), 3)]
+
+
+def _cutting(gpu, rates, channels, dense):
+    L, M, T, H = _table_of(gpu, rates, dense)
     plan = gpu.plan_src(1, channels, L, M, T, 1 << 20)
     total = 3 * M + 5 + 2 * plan.tile_in
     rig = Rig(gpu, 1, channels, L, M, H, total, rates)
@@ -199,7 +383,18 @@ def test_cutting(gpu, rates, channels):
         pos += n
     assert pos == total and wraps >= 3
     assert np.array_equal(np.concatenate(pieces), whole)
+    assert not dense or rig.saturated_share() < SATURATED_MAX
     rig.close()
+
+
+@pytest.mark.parametrize("rates,channels", CUTTING)
+def test_cutting(gpu, rates, channels):
+    _cutting(gpu, rates, channels, False)
+
+
+@pytest.mark.parametrize("rates,channels", CUTTING)
+def test_cutting_dense(gpu, rates, channels):
+    _cutting(gpu, rates, channels, True)
 
 
 # ---------------------------------------------------------------------------
@@ -215,10 +410,11 @@ def _reach(cm, L, M, want):
     raise AssertionError((L, M, want))
 
 
-@pytest.mark.parametrize("rates,channels", [((44100, 48000), 1), ((48000, 44100), 2), ((44100, 48000), 2),
-                                            ((48000, 8000), 3)])
-def test_tile_edges(gpu, rates, channels):
-    L, M, T, H = table(gpu, *rates)
+TILE_EDGES = [((44100, 48000), 1), ((48000, 44100), 2), ((44100, 48000), 2), ((48000, 8000), 3)]
+
+
+def _tile_edges(gpu, rates, channels, dense):
+    L, M, T, H = _table_of(gpu, rates, dense)
     plan = gpu.plan_src(1, channels, L, M, T, 1 << 20)
     assert plan.fast == (1 if channels <= 2 else 0)
     tile = plan.tile_out
@@ -229,14 +425,25 @@ def test_tile_edges(gpu, rates, channels):
     assert [m.r for m in rig.models] == [r for r, _ in reach]
     outs = rig.run([noise(50 + s, f, channels) for s, (_, f) in enumerate(reach)])
     assert [o.shape[0] for o in outs] == wants
+    assert not dense or rig.saturated_share() < SATURATED_MAX
     rig.close()
+
+
+@pytest.mark.parametrize("rates,channels", TILE_EDGES)
+def test_tile_edges(gpu, rates, channels):
+    _tile_edges(gpu, rates, channels, False)
+
+
+@pytest.mark.parametrize("rates,channels", TILE_EDGES)
+def test_tile_edges_dense(gpu, rates, channels):
+    _tile_edges(gpu, rates, channels, True)
 
 
 # ---------------------------------------------------------------------------
 # 5. reset
 
-def test_reset(gpu):
-    L, M, T, H = table(gpu, 44100, 48000)
+def _reset(gpu, dense):
+    L, M, T, H = _table_of(gpu, (44100, 48000), dense)
     rig = Rig(gpu, 3, 2, L, M, H, 500)
     xs = [noise(60 + s, 333 + s, 2) for s in range(3)]
     first = rig.run(xs)
@@ -248,7 +455,16 @@ def test_reset(gpu):
     third = rig.run(xs)
     for s in range(3):
         assert np.array_equal(third[s], first[s])
+    assert not dense or rig.saturated_share() < SATURATED_MAX
     rig.close()
+
+
+def test_reset(gpu):
+    _reset(gpu, False)
+
+
+def test_reset_dense(gpu):
+    _reset(gpu, True)
 
 
 # ---------------------------------------------------------------------------

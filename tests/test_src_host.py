@@ -1,7 +1,10 @@
 """CPU: the host side of sample-rate conversion (cmhip_src_*): the geometry and the designed tables, the response of
 the int16 tables, the output counts, the launcher's plan, NULL and table refusals, the headers, and the generated
 assembly of k_src.hip, and an emulation of the kernel's tile and lane decomposition against the model of the GPU
-tests.  Nothing here needs a GPU."""
+tests: on the designed tables at forced tile sizes, on the case list of tests/test_gpu_src.py at the plan's own, and
+with three mistakes at the ends of the filter made on purpose, which the dense tables of the GPU tests notice.  The
+reciprocal that replaces the division by L is checked for every L and every t the kernel can give it.  Nothing here
+needs a GPU."""
 import ctypes as C
 import importlib.util
 import os
@@ -85,9 +88,12 @@ def test_out_frames_equal_a_brute_force_count(cm):
 
 
 def test_plan(cm):
-    for C_, (L, M, T) in ((1, (160, 147, 32)), (2, (160, 147, 32)), (2, (147, 160, 64)), (6, (160, 147, 32)),
-                          (16, (1, 6, 192)), (1, (1, 6, 192)), (16, (320, 441, 64)), (2, (640, 1, 192)),
-                          (16, (1, 640, 192))):
+    shapes = [(1, (160, 147, 32)), (2, (160, 147, 32)), (2, (147, 160, 64)), (6, (160, 147, 32)), (16, (1, 6, 192)),
+              (1, (1, 6, 192)), (16, (320, 441, 64)), (2, (640, 1, 192)), (16, (1, 640, 192)), (2, (3, 2, 8)),
+              (2, (320, 441, 64)), (2, (321, 441, 64))]
+    shapes += sorted({(c.C, (c.L, c.M, c.T)) for c in TG.CASES} - set(shapes))       # what the GPU tests launch
+    assert len(shapes) >= 26
+    for C_, (L, M, T) in shapes:
         p = cm.plan_src(5, C_, L, M, T, 1)                       # a one-frame run: one workgroup per stream
         assert (p.err, p.grid, p.chunks, p.block) == (0, 5, 1, 256), (C_, L, M, T)
         assert p.fast == (1 if C_ <= 2 else 0)
@@ -101,6 +107,10 @@ def test_plan(cm):
         for out in (p.tile_out - 1, p.tile_out, p.tile_out + 1, 100000):
             q = cm.plan_src(3, C_, L, M, T, out)
             assert (q.chunks, q.grid) == (-(-out // p.tile_out), 3 * -(-out // p.tile_out))
+    # the bound of a table in LDS itself: 320 phases of 64 + 8 taps are exactly the 46080 bytes, 321 are above
+    at, above = cm.plan_src(1, 2, 320, 441, 64, 1), cm.plan_src(1, 2, 321, 441, 64, 1)
+    assert 320 * 72 * 2 == 46080 == 45 * 1024 and (at.table_lds, above.table_lds) == (1, 0)
+    assert at.lds_bytes == 46080 + 2 * 2 * at.row * 2 and above.lds_bytes == 2 * 2 * above.row * 2
     p = cm.plan_src(8192, 1, 160, 147, 32, 71500)
     assert p.tile_out == 4096 and p.grid == 8192 * 18
     # no grid of 2^31 workgroups
@@ -125,11 +135,17 @@ def _gpu_test_module():
     return mod
 
 
+TG = _gpu_test_module()            # the model, the dense tables and the case list of the GPU tests
 UNWRITTEN = 1 << 40
+# in-bounds mistakes a kernel could make at the ends of the filter (the `fault` of _emulate_run)
+FAULTS = ("oldest history frame read as zero", "later tiles take their history one frame too old",
+          "last tap pair skipped")
 
 
-def _emulate_run(L, M, T, H, C_, x, hist, r, tile_out):
-    """x int16 [F][C], hist [C][T-1] -> (y [K][C], the next history, the next r), as the kernel computes them"""
+def _emulate_run(L, M, T, H, C_, x, hist, r, tile_out, fault=None, trace=None):
+    """x int16 [F][C], hist [C][T-1] -> (y [K][C], the next history, the next r), as the kernel computes them: the
+    staging element by element, the lanes of a tile side by side.  fault: one of FAULTS.  trace: a list that gets
+    (q0, j_lo, npre, staged, the largest t) per tile."""
     Tp = (T + 7) // 8 * 8
     tab = np.zeros((L, Tp + 8), dtype=np.int64)                  # SrcArgs::table
     tab[:, 0:T:2], tab[:, 1:T:2] = H[:, 1::2], H[:, 0::2]
@@ -141,6 +157,9 @@ def _emulate_run(L, M, T, H, C_, x, hist, r, tile_out):
     row = (tile_in + 2) & ~1
     inv = 0 if L == 1 else ((1 << 32) + L - 1) // L
     out = np.zeros((K, C_), dtype=np.int64)
+    kk = np.arange(Tp // 2, dtype=np.int64)                      # the tap pairs
+    if fault == FAULTS[2]:
+        kk = kk[kk != T // 2 - 1]
     for q0 in range(0, K, tile_out):                             # one workgroup each
         nq = min(tile_out, K - q0)
         b0, bl = (kb + q0) * M, (kb + q0 + nq - 1) * M
@@ -155,7 +174,12 @@ def _emulate_run(L, M, T, H, C_, x, hist, r, tile_out):
         for idx in range(npre * C_):
             i, c = divmod(idx, C_)
             j = j_lo + i
-            val = hist[c][T - 1 + j] if j >= -(T - 1) else 0
+            at = T - 1 + j
+            if fault == FAULTS[1] and q0 > 0:
+                at = max(at - 1, 0)
+            val = hist[c][at] if j >= -(T - 1) else 0
+            if fault == FAULTS[0] and j == -(T - 1):
+                val = 0
             pl[c * row + i] = pl[(C_ + c) * row + i + 1] = val
         if staged > npre:
             jb = max(j_lo, 0)
@@ -167,23 +191,22 @@ def _emulate_run(L, M, T, H, C_, x, hist, r, tile_out):
                         assert e < F * C_                        # (never a sample past the stream's count)
                         pos = j - j_lo
                         pl[c * row + pos] = pl[(C_ + c) * row + pos + 1] = ins[e]
-        for q in range(nq):                                      # the lanes
-            t = p0 + q * M
-            assert t < 1 << 22
-            dn = (t * inv) >> 32 if inv else t
-            p = t - dn * L
-            assert dn == t // L and 0 <= p < L
-            a0 = dn + Tp - 1
-            for c in range(C_):
-                plane = ((0 if a0 & 1 else C_) + c) * row
-                acc = 0
-                for kk in range(Tp // 2):
-                    at = plane + 2 * ((a0 >> 1) - kk)
-                    assert plane <= at and at + 1 < plane + row
-                    lo, hi = pl[at], pl[at + 1]
-                    assert lo != UNWRITTEN and hi != UNWRITTEN, (q0, q, c, kk)
-                    acc += lo * tab[p][2 * kk] + hi * tab[p][2 * kk + 1]
-                out[q0 + q][c] = min(max((acc + 8192) >> 14, -32768), 32767)
+        t = p0 + np.arange(nq, dtype=np.int64) * M               # the lanes
+        assert t[-1] < 1 << 22
+        dn = (t * inv) >> 32 if inv else t
+        p = t - dn * L
+        assert (dn == t // L).all() and (0 <= p).all() and (p < L).all()
+        a0 = dn + Tp - 1
+        off = 2 * ((a0 >> 1)[:, None] - kk[None, :])             # [nq][pairs] inside the plane
+        assert off.min() >= 0 and off.max() + 1 < row
+        klo, khi = tab[p[:, None], 2 * kk[None, :]], tab[p[:, None], 2 * kk[None, :] + 1]
+        for c in range(C_):
+            at = (np.where(a0 & 1, c, C_ + c) * row)[:, None] + off
+            lo, hi = pl[at], pl[at + 1]
+            assert (lo != UNWRITTEN).all() and (hi != UNWRITTEN).all(), (q0, c)
+            out[q0:q0 + nq, c] = np.clip(((lo * klo + hi * khi).sum(axis=1) + 8192) >> 14, -32768, 32767)
+        if trace is not None:
+            trace.append((q0, j_lo, npre, staged, int(t[-1])))
     nh = np.zeros((C_, T - 1), dtype=np.int64)                   # src_history
     for c in range(C_):
         for i in range(T - 1):
@@ -195,7 +218,7 @@ def _emulate_run(L, M, T, H, C_, x, hist, r, tile_out):
                                                      ((48000, 44100), 2, 16), ((8000, 48000), 3, 256),
                                                      ((48000, 8000), 2, 2), ((48000, 16000), 16, 4)])
 def test_emulated_decomposition_equals_the_model(cm, rates, channels, tile_out):
-    tg = _gpu_test_module()
+    tg = TG
     L, M, T, H = cm.src_design(*rates)
     H = H.astype(np.int64)
     model = tg.Model(L, M, H, channels)
@@ -206,6 +229,85 @@ def test_emulated_decomposition_equals_the_model(cm, rates, channels, tile_out):
         got, hist, r = _emulate_run(L, M, T, H, channels, x, hist, r, tile_out)
         assert r == model.r and np.array_equal(hist.T, model.hist)
         assert np.array_equal(got, want.astype(np.int64)), (rates, channels, F)
+
+
+def _emulate_case(cm, case, tile_out, H, fault=None):
+    """every stream of a case through the emulation and the model -> (the tiles (run, stream, first, j_lo, t_hi) and
+    (npre, staged) of each, the streams' runs that differ from the model, outputs, saturated outputs of the model)"""
+    tiles, parts, differ, outputs, saturated = [], [], [], 0, 0
+    for s in range(len(case.runs[0])):
+        model = TG.Model(case.L, case.M, H, case.C)
+        hist, r = np.zeros((case.C, case.T - 1), dtype=np.int64), 0
+        for i, counts in enumerate(case.runs):
+            x = TG.noise(1000 * i + 10 * case.C + s, counts[s], case.C)
+            want = model.run(x).astype(np.int64)
+            trace = []
+            got, hist, r = _emulate_run(case.L, case.M, case.T, H, case.C, x, hist, r, tile_out, fault, trace)
+            assert r == model.r and np.array_equal(hist.T, model.hist)
+            if not np.array_equal(got, want):
+                differ.append((i, s))
+            tiles += [(i, s, q0 == 0, j_lo, t_hi) for q0, j_lo, _, _, t_hi in trace]
+            parts += [(q0, npre, staged) for q0, _, npre, staged, _ in trace]
+            outputs += want.size
+            saturated += int(((want == 32767) | (want == -32768)).sum())
+    return tiles, parts, differ, outputs, saturated
+
+
+@pytest.mark.parametrize("case", TG.CASES, ids=[c.name for c in TG.CASES])
+def test_cases_of_the_gpu_tests_emulated(cm, case):
+    """the runs tests/test_gpu_src.py launches, at the plan's own tile_out: each reaches what it is there for, every
+    plane element read was written and lies inside its plane, and the outputs are the model's"""
+    plan, recs = TG.assert_reaches(cm, case)
+    H = TG.case_table(cm, case).astype(np.int64)
+    tiles, parts, differ, outputs, saturated = _emulate_case(cm, case, plan.tile_out, H)
+    assert not differ, differ
+    # the emulation met the tiles the host arithmetic of the GPU test announces
+    assert sorted(tiles) == sorted((t.run, t.stream, t.first, t.j_lo, t.t_hi) for t in recs)
+    if "mix" in case.reach:
+        assert any(q0 > 0 and 0 < npre < case.T - 1 and npre < staged for q0, npre, staged in parts)
+    if "halo" in case.reach:
+        assert any(q0 > 0 and npre > 0 for q0, npre, _ in parts)
+    if case.table == "dense":
+        assert saturated < TG.SATURATED_MAX * outputs
+
+
+@pytest.mark.parametrize("geometry,rates,tile_out,counts", [
+    ((1, 6, 192), (48000, 8000), 2, (252, 1, 0, 333)), ((147, 160, 64), (48000, 44100), 16, (150, 1, 0, 333)),
+    ((160, 1, 32), (300, 48000), None, (60, 1, 0, 60))])
+def test_dense_tables_see_what_designed_tables_do_not(cm, geometry, rates, tile_out, counts):
+    """Three in-bounds mistakes at the ends of the filter, made in the emulation: with a dense table each of them
+    changes the output, so a kernel that made one would fail the GPU tests; whether the designed table of the same
+    geometry notices is printed.  (1, 6, 192) and (147, 160, 64) at forced small tiles, so that tiles after a run's
+    first stage history at all; (160, 1, 32) at the plan's 4096, where the second tile does.  A run begins at a
+    multiple of M after the history has filled, so that its first output meets the oldest history frame."""
+    L, M, T = geometry
+    tables = {"dense": TG.dense_table(L, T, L + T).astype(np.int64),
+              "designed": cm.src_design(*rates)[3].astype(np.int64)}
+    assert cm.src_design(*rates)[:3] == geometry
+    case = TG._case("faults", geometry, 2, [[n] for n in counts])
+    tile_out = tile_out or cm.plan_src(1, 2, L, M, T, 1).tile_out
+    for name, H in tables.items():
+        tiles, parts, differ, _, _ = _emulate_case(cm, case, tile_out, H)
+        assert not differ and any(q0 > 0 and npre > 0 for q0, npre, _ in parts)
+        assert any(run > 0 and j_lo == -(T - 1) for run, _, _, j_lo, _ in tiles)       # the oldest history frame, full
+        for fault in FAULTS:
+            differ = _emulate_case(cm, case, tile_out, H, fault)[2]
+            print("src fault", geometry, name, "table:", fault, "->", "noticed" if differ else "NOT noticed")
+            if name == "dense":
+                assert differ, fault
+
+
+def test_src_divmod_is_exact_for_every_l_below_2_22():
+    """src_divmod's t * inv >> 32 with inv = ceil(2^32 / L), for every L the library takes: right at every multiple
+    of L and just below it, and monotone in t -- so right for every t < 2^22"""
+    for L in range(2, 641):
+        inv = np.uint64(((1 << 32) + L - 1) // L)
+        assert int(inv) < 1 << 32                                # (the kernel multiplies 32 bits by 32 bits)
+        k = np.arange(1, -(-(1 << 22) // L), dtype=np.uint64)
+        t = k * np.uint64(L)
+        assert int(t[-1]) < 1 << 22 <= int(t[-1]) + L
+        assert np.array_equal((t * inv) >> np.uint64(32), k), L
+        assert np.array_equal(((t - np.uint64(1)) * inv) >> np.uint64(32), k - np.uint64(1)), L
 
 
 def test_headers_compile_as_c_and_cxx(tmp_path):
