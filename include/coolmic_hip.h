@@ -381,6 +381,80 @@ int      cmhip_src_design(unsigned int rate_in, unsigned int rate_out, unsigned 
                           int16_t *h, size_t cap /* entries */);
 uint32_t cmhip_src_out_frames(unsigned int L, unsigned int M, uint32_t r, uint32_t frames);
 
+/* ---- channel mixing, an object of its own beside the batch --------------------- */
+/* A mixer turns S streams of channels_in interleaved int16 channels into S streams of channels_out, frame by frame,
+ * in exact integers.  The signal is the raw int16 the caller hands in: no gain and no map, the batch does those.
+ *
+ * Arithmetic.  Every stream has a matrix W[channels_out][channels_in] of its own, int16 in units of 2^-14
+ *   (unity = 16384, as the resampler's table); negative weights are allowed.  Output channel o of frame f:
+ *       acc     = sum_{c<C_in} W[o][c] * x[f][c]             exact in int32
+ *       y[f][o] = saturate_int16((acc + 8192) >> 14)         arithmetic shift (floor): halves round towards +inf
+ * Validity.  channels_in and channels_out lie in 1..16 and may be equal (1 -> 1 is a signed gain, 2 -> 2 a balance or
+ *   a mid/side matrix); every row has sum_c |W[o][c]| <= 65535.  Then |acc + 8192| <= 65535*32768 + 8192 < 2^31: int32
+ *   never overflows and the result does not depend on the order of summation (the resampler's bound and argument).
+ *   Anything else is COOLMIC_ERROR_INVAL and changes nothing.
+ * Identity.  W = 16384 * I gives acc = 16384 * x, and (16384 * x + 8192) >> 14 = x: the input comes back bit for bit.
+ * State.  There is none: no history, nothing carried between runs.  A stream with 0 frames in a run touches nothing,
+ *   and the output does not depend on how a stream was cut into runs.
+ * The matrix at creation: W[o][o] = 16384 for o < min(C_in, C_out), zero elsewhere -- the leading channels are kept
+ *   and extra outputs are silent.
+ *
+ * cmhip_mix_run: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in samples as in a batch, both
+ *   device-accessible; asynchronous on the mixer's stream.  `frames` frames per stream, or frames_per_stream[s] <=
+ *   frames (host array of S entries, may be NULL).  COOLMIC_ERROR_INVAL, with nothing launched and nothing changed,
+ *   when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or smaller than frames * C_in (in) or
+ *   frames * C_out (out), frames > max_frames, a per-stream count is above frames, the run's grid would reach 2^31
+ *   workgroups, or the byte ranges of the input ([in, in + S * in_stride samples)) and of the output overlap at all
+ *   -- not only in == out: a narrower output written over the input would race between tiles.  COOLMIC_ERROR_FAULT for
+ *   NULL arrays.  Samples past a stream's count are neither read nor written.
+ * cmhip_mix_set_matrix (stream -1: all) is ordered with the runs: runs queued before it use the old matrix, runs
+ *   queued after it the new one, without the caller synchronising; W may be reused as soon as it returns.  A matrix
+ *   that fails the validity rules is refused and the old one stays.  cmhip_mix_get_matrix answers from the host's
+ *   mirror: what the last accepted set (or creation) left.
+ * Composition: as the resampler -- out = cmhip_batch_dev_in(b), out_stride = cmhip_batch_stride(b) of a batch with
+ *   channels = channels_out; with hip_stream = cmhip_batch_hip_stream(b) the order is the stream's.  The chain is
+ *   source -> rate (cmhip_src_t) -> width (cmhip_mix_t) -> batch (gain, VU, true peak, loudness).
+ * cmhip_mix_new returns NULL on failure; max_frames * max(C_in, C_out) may not pass 2^31 samples.
+ *
+ * Presets (cmhip_mix_preset; these integers are the specification; 5.1 is in the order L R C LFE Ls Rs):
+ *   CMHIP_MIX_MONO_TO_STEREO       1 -> 2   {16384}, {16384}
+ *   CMHIP_MIX_STEREO_TO_MONO       2 -> 1   {8192, 8192}
+ *   CMHIP_MIX_STEREO_TO_MS         2 -> 2   {8192, 8192}, {8192, -8192}
+ *   CMHIP_MIX_51_TO_STEREO         6 -> 2   {16384, 0, 11585, 0, 11585, 0}, {0, 16384, 11585, 0, 0, 11585}
+ *                                           ITU-R BS.775: 1, 1/sqrt(2), 1/sqrt(2); may saturate
+ *   CMHIP_MIX_51_TO_STEREO_NORM    6 -> 2   {6786, 0, 4799, 0, 4799, 0}, {0, 6786, 4799, 0, 0, 4799}
+ *                                           the same divided by 1 + sqrt(2): rows sum to exactly 16384, never saturates
+ *   W == NULL returns the geometry only (channels_in, channels_out may each be NULL); with W, cap counts its entries,
+ *   and a cap below C_out * C_in is COOLMIC_ERROR_INVAL with nothing written.  An unknown preset is
+ *   COOLMIC_ERROR_INVAL.  cmhip_mix_check: 0 for a valid matrix, COOLMIC_ERROR_INVAL for a channel count outside 1..16
+ *   or a row above the bound, COOLMIC_ERROR_FAULT for W == NULL. */
+#define CMHIP_MIX_MONO_TO_STEREO     0u
+#define CMHIP_MIX_STEREO_TO_MONO     1u
+#define CMHIP_MIX_STEREO_TO_MS       2u
+#define CMHIP_MIX_51_TO_STEREO       3u
+#define CMHIP_MIX_51_TO_STEREO_NORM  4u
+typedef struct cmhip_mix cmhip_mix_t;
+typedef struct cmhip_mix_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels_in;     /* 1..16 */
+    unsigned int channels_out;    /* 1..16 */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_mix_desc_t;
+cmhip_mix_t *cmhip_mix_new(const cmhip_mix_desc_t *d);
+void     cmhip_mix_free(cmhip_mix_t *m);
+int      cmhip_mix_set_matrix(cmhip_mix_t *m, long stream, const int16_t *W /* [C_out][C_in] */);
+int      cmhip_mix_get_matrix(const cmhip_mix_t *m, unsigned int stream, int16_t *W);
+int      cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_mix_sync(cmhip_mix_t *m);
+void    *cmhip_mix_hip_stream(cmhip_mix_t *m);
+/* host only, no device needed */
+int      cmhip_mix_check(unsigned int channels_in, unsigned int channels_out, const int16_t *W);
+int      cmhip_mix_preset(unsigned int preset, unsigned int *channels_in, unsigned int *channels_out, int16_t *W,
+                          size_t cap /* entries */);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

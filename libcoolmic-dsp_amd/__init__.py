@@ -91,6 +91,12 @@ class SrcDesc(C.Structure):
                 ("rate_out", C.c_uint), ("max_in_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class MixDesc(C.Structure):
+    """cmhip_mix_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels_in", C.c_uint), ("channels_out", C.c_uint),
+                ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
 class Placement(C.Structure):
     """cmhip_placement_t (include/coolmic_hip.h)"""
     _fields_ = [("searched", C.c_int), ("candidates", C.c_int), ("chosen_in", C.c_int),
@@ -191,6 +197,15 @@ SIGNATURES = {
     "cmhip_src_hip_stream": (_vp, [_vp]),
     "cmhip_src_design": (C.c_int, [C.c_uint, C.c_uint, _P(C.c_uint), _P(C.c_uint), _P(C.c_uint), _vp, C.c_size_t]),
     "cmhip_src_out_frames": (C.c_uint32, [C.c_uint, C.c_uint, C.c_uint32, C.c_uint32]),
+    "cmhip_mix_new": (_vp, [_P(MixDesc)]),
+    "cmhip_mix_free": (None, [_vp]),
+    "cmhip_mix_set_matrix": (C.c_int, [_vp, C.c_long, _vp]),
+    "cmhip_mix_get_matrix": (C.c_int, [_vp, C.c_uint, _vp]),
+    "cmhip_mix_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_mix_sync": (C.c_int, [_vp]),
+    "cmhip_mix_hip_stream": (_vp, [_vp]),
+    "cmhip_mix_check": (C.c_int, [C.c_uint, C.c_uint, _vp]),
+    "cmhip_mix_preset": (C.c_int, [C.c_uint, _P(C.c_uint), _P(C.c_uint), _vp, C.c_size_t]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -319,6 +334,9 @@ if hasattr(lib, "cmhip_test_plan_loud"):        # (not in builds older than loud
 if hasattr(lib, "cmhip_test_plan_src"):         # (not in builds older than sample-rate conversion)
     lib.cmhip_test_plan_src.restype = None
     lib.cmhip_test_plan_src.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
+if hasattr(lib, "cmhip_test_plan_mix"):         # (not in builds older than channel mixing)
+    lib.cmhip_test_plan_mix.restype = None
+    lib.cmhip_test_plan_mix.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -457,6 +475,40 @@ def src_design(rate_in, rate_out):
 def src_out_frames(L, M, r, frames):
     """output frames of a run of `frames` input frames for a stream at position r = (frames so far) mod M"""
     return lib.cmhip_src_out_frames(L, M, r, frames)
+
+
+class MixPlan(C.Structure):
+    """cmhip::MixPlan (csrc/cmhip_internal.h): what the mixer's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_frames",
+                                                               "lds_bytes")]
+
+
+def plan_mix(streams, channels_in, channels_out, frames):
+    """Test hook: the mixer launcher's plan for a run whose longest stream has `frames` frames (host logic, needs no
+    GPU)"""
+    p = MixPlan()
+    lib.cmhip_test_plan_mix(streams, channels_in, channels_out, frames, C.addressof(p))
+    return p
+
+
+MIX_MONO_TO_STEREO, MIX_STEREO_TO_MONO, MIX_STEREO_TO_MS, MIX_51_TO_STEREO, MIX_51_TO_STEREO_NORM = range(5)
+
+
+def mix_preset(preset):
+    """a preset matrix -> (channels_in, channels_out, int16 array [C_out][C_in]); CoolmicError for an unknown one"""
+    ci, co = C.c_uint(), C.c_uint()
+    _check("mix_preset", lib.cmhip_mix_preset(preset, C.byref(ci), C.byref(co), None, 0))
+    w = np.zeros(ci.value * co.value, dtype=np.int16)
+    _check("mix_preset", lib.cmhip_mix_preset(preset, None, None, w.ctypes.data, w.size))
+    return ci.value, co.value, w.reshape(co.value, ci.value)
+
+
+def mix_check(channels_in, channels_out, W):
+    """cmhip_mix_check as it is -> error number (0: the matrix is valid); W None is passed as NULL"""
+    if W is None:
+        return lib.cmhip_mix_check(channels_in, channels_out, None)
+    w = np.ascontiguousarray(W, dtype=np.int16)
+    return lib.cmhip_mix_check(channels_in, channels_out, w.ctypes.data)
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -835,6 +887,65 @@ class Resampler:
 
     def hip_stream(self):
         return lib.cmhip_src_hip_stream(self.h) or 0
+
+
+class Mixer:
+    """cmhip_mix_t: channel mixing of S streams beside a batch, one matrix int16 [C_out][C_in] (units of 2^-14) per
+    stream.  `matrix`: set for every stream at creation (default: the leading channels kept)."""
+
+    def __init__(self, streams, channels_in, channels_out, max_frames, matrix=None, device=0, hip_stream=None):
+        d = MixDesc(device, streams, channels_in, channels_out, max_frames, hip_stream)
+        self.h = lib.cmhip_mix_new(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_mix_new", ERROR_INVAL)
+        self.streams, self.channels_in, self.channels_out, self.max_frames = streams, channels_in, channels_out, max_frames
+        if matrix is not None:
+            self.set_matrix(-1, matrix)
+
+    def close(self):
+        if self.h:
+            lib.cmhip_mix_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_matrix_rc(self, stream, W):
+        """cmhip_mix_set_matrix as it is -> error number"""
+        w = np.ascontiguousarray(W, dtype=np.int16)
+        assert w.size == self.channels_out * self.channels_in
+        return lib.cmhip_mix_set_matrix(self.h, stream, w.ctypes.data)
+
+    def set_matrix(self, stream, W):
+        """stream -1: every stream.  Ordered with the runs on the mixer's stream."""
+        _check("mix_set_matrix", self.set_matrix_rc(stream, W))
+
+    def get_matrix(self, stream):
+        w = np.zeros((self.channels_out, self.channels_in), dtype=np.int16)
+        _check("mix_get_matrix", lib.cmhip_mix_get_matrix(self.h, stream, w.ctypes.data))
+        return w
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_mix_run as it is -> error number"""
+        fps = None
+        if frames_per_stream is not None:
+            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
+            assert fps.size == self.streams
+        return lib.cmhip_mix_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
+                                 out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers)"""
+        _check("mix_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def sync(self):
+        _check("mix_sync", lib.cmhip_mix_sync(self.h))
+
+    def hip_stream(self):
+        return lib.cmhip_mix_hip_stream(self.h) or 0
 
 
 class PinnedPcm:

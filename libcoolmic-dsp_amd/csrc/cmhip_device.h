@@ -1,6 +1,6 @@
 // cmhip_device.h -- device-side helpers shared by the kernel files: exact gain arithmetic on packed
 // int16, tile edges (a stream's extent, its ragged last vector), the VU window position, key and peak lookups,
-// DPP wave reductions.  (Included by k_block.hip, k_eq.hip, k_misc.hip, k_tpeak.hip, k_src.hip.)
+// DPP wave reductions.  (Included by k_block.hip, k_eq.hip, k_misc.hip, k_tpeak.hip, k_src.hip, k_mix.hip.)
 #ifndef CMHIP_DEVICE_H
 #define CMHIP_DEVICE_H
 

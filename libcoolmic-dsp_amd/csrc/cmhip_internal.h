@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip (the gfx950 kernels) and cmhip_batch.hip (the
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip (the gfx950 kernels) and cmhip_batch.hip (the
 // engine).
 #pragma once
 
@@ -200,6 +200,23 @@ struct SrcArgs {
     uint32_t       table_lds;      // the table is copied into LDS
 };
 
+// Channel mixing (k_mix.hip; the arithmetic: include/coolmic_hip.h): a mixer's run over S stream slots.
+struct MixArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    // [S][C_out][CP] the matrices in the kernel's form, CP = ceil(C_in / 2): dword k of row o is
+    // W[o][2k] | W[o][2k+1] << 16, an odd C_in padded with a zero weight
+    const uint32_t *wk;
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels_in, channels_out;
+    // (the launcher fills these in)
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_frames;    // frames per tile
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -268,6 +285,22 @@ struct SrcPlan {
 };
 SrcPlan plan_src(const SrcArgs &a, uint32_t out_frames);
 hipError_t launch_src(const SrcArgs &a, uint32_t out_frames, hipStream_t st);
+// Channel mixing (k_mix.hip): one workgroup per stream and tile of tile_frames frames.  fast: the kernel for mono /
+// stereo on both sides (one wave per workgroup, no LDS); otherwise the any-channel-count kernel (256 threads).
+struct MixPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   fast;
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+    uint32_t   chunks;             // MixArgs::chunks: tiles per stream
+    uint32_t   tile_frames;        // MixArgs::tile_frames (a multiple of 8)
+    uint32_t   lds_bytes;          // dynamic LDS of the launch
+};
+MixPlan plan_mix(const MixArgs &a);
+hipError_t launch_mix(const MixArgs &a, hipStream_t st);
+// (one matrix W[C_out][C_in] into the kernel-form rows of streams first .. first + count - 1, in stream order; the
+// matrix travels as a kernel argument, so W may change as soon as the call returns)
+hipError_t launch_mix_set(uint32_t *wk, uint32_t first, uint32_t count, uint32_t channels_in, uint32_t channels_out,
+                          const int16_t *W, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

@@ -1,0 +1,242 @@
+// cmhip_mix.hip -- channel mixing on the host side (include/coolmic_hip.h, "channel mixing"): the mixer object beside
+// the batch, its validation, the launch of k_mix.hip's kernels, the presets and the matrix check.
+//
+// Device state of a mixer: the streams' matrices in the kernel's form (MixArgs::wk), uint32 [S][C_out][CP].  That is
+// all: there is no history.  The host keeps a mirror of every matrix as the caller gave it (int16 [S][C_out][C_in]);
+// cmhip_mix_get_matrix answers from it.  A new matrix reaches the device inside a kernel's arguments (k_mix_set), so
+// it is ordered with the runs by the stream alone and no staging memory outlives the call.
+#include "cmhip_engine.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <new>
+
+constexpr uint64_t MIX_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
+
+struct cmhip_mix {
+    cmhip_mix_desc_t d;
+    hipStream_t stream;
+    bool own_stream;
+    uint32_t *d_wk;
+    uint32_t *d_nframes;
+    std::vector<int16_t> w;            // the mirror: [S][C_out][C_in]
+};
+
+static bool mix_channels_ok(unsigned ci, unsigned co) { return ci >= 1 && ci <= MAX_CH && co >= 1 && co <= MAX_CH; }
+
+extern "C" int cmhip_mix_check(unsigned channels_in, unsigned channels_out, const int16_t *W)
+{
+    if (!mix_channels_ok(channels_in, channels_out))
+        return fail(COOLMIC_ERROR_INVAL, "mix: %u -> %u channels: both must lie in 1..16", channels_in, channels_out);
+    if (!W)
+        return fail(COOLMIC_ERROR_FAULT, "mix: matrix is NULL");
+    for (unsigned o = 0; o < channels_out; o++) {
+        unsigned long sum = 0;
+        for (unsigned c = 0; c < channels_in; c++)
+            sum += (unsigned long)abs((int)W[(size_t)o * channels_in + c]);
+        if (sum > 65535)
+            return fail(COOLMIC_ERROR_INVAL, "mix: row %u has sum |w| = %lu above 65535", o, sum);
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+// the presets, as the header prints them
+static const int16_t MIX_P_MONO_TO_STEREO[] = {16384, 16384};
+static const int16_t MIX_P_STEREO_TO_MONO[] = {8192, 8192};
+static const int16_t MIX_P_STEREO_TO_MS[] = {8192, 8192, 8192, -8192};
+static const int16_t MIX_P_51_TO_STEREO[] = {16384, 0, 11585, 0, 11585, 0, 0, 16384, 11585, 0, 0, 11585};
+static const int16_t MIX_P_51_TO_STEREO_NORM[] = {6786, 0, 4799, 0, 4799, 0, 0, 6786, 4799, 0, 0, 4799};
+
+extern "C" int cmhip_mix_preset(unsigned preset, unsigned *channels_in, unsigned *channels_out, int16_t *W, size_t cap)
+{
+    unsigned ci, co;
+    const int16_t *w;
+    switch (preset) {
+    case CMHIP_MIX_MONO_TO_STEREO: ci = 1; co = 2; w = MIX_P_MONO_TO_STEREO; break;
+    case CMHIP_MIX_STEREO_TO_MONO: ci = 2; co = 1; w = MIX_P_STEREO_TO_MONO; break;
+    case CMHIP_MIX_STEREO_TO_MS: ci = 2; co = 2; w = MIX_P_STEREO_TO_MS; break;
+    case CMHIP_MIX_51_TO_STEREO: ci = 6; co = 2; w = MIX_P_51_TO_STEREO; break;
+    case CMHIP_MIX_51_TO_STEREO_NORM: ci = 6; co = 2; w = MIX_P_51_TO_STEREO_NORM; break;
+    default:
+        return fail(COOLMIC_ERROR_INVAL, "mix_preset: no preset %u", preset);
+    }
+    if (W) {
+        if (cap < (size_t)ci * co)
+            return fail(COOLMIC_ERROR_INVAL, "mix_preset: room for %zu entries, the matrix has %u", cap, ci * co);
+        memcpy(W, w, (size_t)ci * co * sizeof(int16_t));
+    }
+    if (channels_in)
+        *channels_in = ci;
+    if (channels_out)
+        *channels_out = co;
+    return COOLMIC_ERROR_NONE;
+}
+
+static int mix_init(cmhip_mix_t *m)
+{
+    const cmhip_mix_desc_t &d = m->d;
+    HIP_TRY(hipSetDevice(d.device));
+    if (d.hip_stream) {
+        m->stream = (hipStream_t)d.hip_stream;
+    } else {
+        HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        m->own_stream = true;
+    }
+    const size_t S = d.streams, CI = d.channels_in, CO = d.channels_out, n = CO * ((CI + 1) / 2);
+    HIP_TRY(hipMalloc((void **)&m->d_wk, S * n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_nframes, S * sizeof(uint32_t)));
+    // the matrix at creation: the leading channels kept, silence in extra outputs
+    std::vector<int16_t> w0(CO * CI, 0);
+    for (size_t o = 0; o < (CI < CO ? CI : CO); o++)
+        w0[o * CI + o] = 16384;
+    m->w.resize(S * CO * CI);
+    for (size_t s = 0; s < S; s++)
+        memcpy(&m->w[s * CO * CI], w0.data(), CO * CI * sizeof(int16_t));
+    const hipError_t e = launch_mix_set(m->d_wk, 0, d.streams, d.channels_in, d.channels_out, w0.data(), m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "mix_new: %s", hipGetErrorString(e));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void cmhip_mix_free(cmhip_mix_t *m)
+{
+    if (!m)
+        return;
+    (void)hipSetDevice(m->d.device);
+    if (m->stream)
+        (void)hipStreamSynchronize(m->stream);
+    (void)hipFree(m->d_wk);
+    (void)hipFree(m->d_nframes);
+    if (m->own_stream)
+        (void)hipStreamDestroy(m->stream);
+    delete m;
+}
+
+extern "C" cmhip_mix_t *cmhip_mix_new(const cmhip_mix_desc_t *d)
+{
+    if (!d) {
+        fail(COOLMIC_ERROR_FAULT, "mix_new: NULL argument");
+        return nullptr;
+    }
+    if (d->streams == 0 || !mix_channels_ok(d->channels_in, d->channels_out) || d->max_frames == 0) {
+        fail(COOLMIC_ERROR_INVAL, "mix_new: streams, channels_in, channels_out (1..16) and max_frames must be positive");
+        return nullptr;
+    }
+    const unsigned cmax = d->channels_in > d->channels_out ? d->channels_in : d->channels_out;
+    if (d->max_frames > MIX_MAX_SAMPLES / cmax) {
+        fail(COOLMIC_ERROR_INVAL, "mix_new: max_frames %zu: a slot of a run would pass 2^31 samples", d->max_frames);
+        return nullptr;
+    }
+    if ((uint64_t)d->streams * MAX_CH * (MAX_CH / 2) >= (1ull << 31)) {
+        fail(COOLMIC_ERROR_INVAL, "mix_new: %u streams: the matrix table would pass 2^31 entries", d->streams);
+        return nullptr;
+    }
+    cmhip_mix_t *m = new (std::nothrow) cmhip_mix();
+    if (!m) {
+        fail(COOLMIC_ERROR_NOMEM, "mix_new: out of memory");
+        return nullptr;
+    }
+    m->d = *d;
+    if (mix_init(m)) {
+        cmhip_mix_free(m);
+        return nullptr;
+    }
+    return m;
+}
+
+extern "C" int cmhip_mix_set_matrix(cmhip_mix_t *m, long stream, const int16_t *W)
+{
+    if (!m || !W)
+        return fail(COOLMIC_ERROR_FAULT, "mix_set_matrix: NULL argument");
+    if (stream >= (long)m->d.streams || stream < -1)
+        return fail(COOLMIC_ERROR_INVAL, "mix_set_matrix: stream %ld out of range", stream);
+    const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
+    const int rc = cmhip_mix_check(CI, CO, W);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(m->d.device));
+    const uint32_t lo = stream < 0 ? 0u : (uint32_t)stream, n = stream < 0 ? m->d.streams : 1u;
+    const hipError_t e = launch_mix_set(m->d_wk, lo, n, CI, CO, W, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "mix_set_matrix: %s", hipGetErrorString(e));
+    for (size_t s = lo; s < (size_t)lo + n; s++)
+        memcpy(&m->w[s * CO * CI], W, (size_t)CO * CI * sizeof(int16_t));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_mix_get_matrix(const cmhip_mix_t *m, unsigned stream, int16_t *W)
+{
+    if (!m || !W)
+        return fail(COOLMIC_ERROR_FAULT, "mix_get_matrix: NULL argument");
+    if (stream >= m->d.streams)
+        return fail(COOLMIC_ERROR_INVAL, "mix_get_matrix: stream %u out of range", stream);
+    const size_t n = (size_t)m->d.channels_out * m->d.channels_in;
+    memcpy(W, &m->w[stream * n], n * sizeof(int16_t));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void *cmhip_mix_hip_stream(cmhip_mix_t *m) { return m ? (void *)m->stream : nullptr; }
+
+extern "C" int cmhip_mix_sync(cmhip_mix_t *m)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "mix_sync: mixer is NULL");
+    HIP_TRY(hipSetDevice(m->d.device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, size_t frames,
+                             const uint32_t *frames_per_stream, void *out, size_t out_stride)
+{
+    if (!m || !in || !out)
+        return fail(COOLMIC_ERROR_FAULT, "mix_run: NULL argument");
+    const unsigned S = m->d.streams, CI = m->d.channels_in, CO = m->d.channels_out;
+    if (((uintptr_t)in | (uintptr_t)out) & 15u)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: in and out must be 16-byte aligned");
+    if ((in_stride | out_stride) & 7u)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: strides must be multiples of 8 samples");
+    if (frames > m->d.max_frames)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: %zu frames above max_frames %zu", frames, m->d.max_frames);
+    if (frames_per_stream)
+        for (unsigned s = 0; s < S; s++)
+            if (frames_per_stream[s] > frames)
+                return fail(COOLMIC_ERROR_INVAL, "mix_run: frames_per_stream[%u] above frames", s);
+    if (in_stride < frames * CI)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, CI);
+    if (out_stride < frames * CO)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: out_stride %zu below %zu frames of %u channels", out_stride, frames,
+                    CO);
+    // the byte ranges [in, in + S * in_stride) and [out, out + S * out_stride) may not share a byte: a narrower
+    // output written over the input would race between tiles
+    const uintptr_t ib = (uintptr_t)in, ie = ib + (uintptr_t)S * in_stride * sizeof(int16_t);
+    const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)S * out_stride * sizeof(int16_t);
+    if (ib < oe && ob < ie)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: the input and the output overlap");
+    // nothing was touched so far; from here on the run happens
+    if (frames == 0)
+        return COOLMIC_ERROR_NONE;
+    HIP_TRY(hipSetDevice(m->d.device));
+    MixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = (const int16_t *)in;
+    a.out = (int16_t *)out;
+    a.nframes = frames_per_stream ? m->d_nframes : nullptr;
+    a.wk = m->d_wk;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.frames = (uint32_t)frames;
+    a.streams = S;
+    a.channels_in = CI;
+    a.channels_out = CO;
+    if (plan_mix(a).err != hipSuccess)
+        return fail(COOLMIC_ERROR_INVAL, "mix_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
+                    frames);
+    if (frames_per_stream)
+        HIP_TRY(hipMemcpyAsync(m->d_nframes, frames_per_stream, S * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    const hipError_t e = launch_mix(a, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "mix_run: %s", hipGetErrorString(e));
+    return COOLMIC_ERROR_NONE;
+}

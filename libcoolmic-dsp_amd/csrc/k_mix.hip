@@ -1,0 +1,354 @@
+// k_mix.hip -- gfx950 (MI355X, wave64) channel-mixing kernels: S streams of C_in interleaved int16 channels become
+// S streams of C_out, frame by frame, by a matrix W[C_out][C_in] per stream in units of 2^-14 (include/coolmic_hip.h,
+// "channel mixing", has the arithmetic to the bit):
+//     acc = sum_{c<C_in} W[o][c] * x[f][c]      y[f][o] = saturate((acc + 8192) >> 14)
+//
+//   k_mix_fast<CI, CO>  CI, CO in {1, 2}: one short-lived wave per contiguous tile of one stream, the matrix in SGPRs
+//   k_mix_any           every other pair up to 16 -> 16: a workgroup stages a tile through LDS; no speed goal
+//   k_mix_set           writes one matrix, handed over as a kernel argument, into the rows of a range of streams
+//
+// The kernel form of a matrix (MixArgs::wk): per stream [C_out][CP] dwords, CP = ceil(C_in / 2), dword k of row o is
+// W[o][2k] | W[o][2k+1] << 16 (an odd C_in padded with a zero weight) -- the order v_dot2_i32_i16 meets the two
+// channels of an input dword in.  The accumulator starts at 8192, so rounding costs no instruction; then one shift,
+// and v_cvt_pk_i16_i32 clamps and packs two results.  No state: nothing is carried between runs.
+#include "cmhip_device.h"
+
+namespace cmhip {
+
+constexpr u32 MIX_BLOCK = 256;
+constexpr u32 MIX_LDS_LIMIT = 64u * 1024u;       // what a workgroup may take without raising the device's limit
+constexpr u32 MIX_TILE_MAX = 1024;               // frames of a k_mix_any tile at most: four per thread
+
+__host__ __device__ constexpr u32 mix_cp(u32 ci) { return (ci + 1u) / 2u; }
+// LDS of k_mix_any: the matrix (rounded up to whole 16-byte vectors), CP planes of tile dwords, the output tile
+__host__ __device__ constexpr u32 mix_wk_lds(u32 ci, u32 co) { return (co * mix_cp(ci) + 3u) & ~3u; }
+__host__ __device__ constexpr u32 mix_lds_bytes(u32 ci, u32 co, u32 tile)
+{
+    return 4u * mix_wk_lds(ci, co) + 4u * mix_cp(ci) * tile + 2u * co * tile;
+}
+
+__device__ __forceinline__ int mix_dot2(u32 x, u32 k, int acc)
+{
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, x), __builtin_bit_cast(v2s, k), acc, false);
+}
+// two accumulators (rounding included) -> one dword of output: shift, then clamp and pack
+__device__ __forceinline__ u32 mix_pack(int a0, int a1)
+{
+    return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(a0 >> 14, a1 >> 14));
+}
+
+// ---------------------------------------------------------------------------
+// Form 1: mono / stereo on both sides.  A lane works in UNITS of UF frames, the fewest that are whole 16-byte vectors
+// on both sides: VI input vectors and VO output vectors.  NU units per lane make four vectors on the wider side:
+//     1 -> 1   UF 8, 1 in, 1 out, NU 4: a tile of 2048 frames      2 -> 1   UF 8, 2 in, 1 out, NU 2: 1024 frames
+//     2 -> 2   UF 4, 1 in, 1 out, NU 4: 1024 frames                1 -> 2   UF 8, 1 in, 2 out, NU 2: 1024 frames
+// Unit j of a lane is unit n0 + 64 j + lane of the stream, so a wave's instruction covers 64 consecutive units.
+template <int CI, int CO>
+struct MixFast {
+    static constexpr u32 UF = 8u / (u32)(CI < CO ? CI : CO);
+    static constexpr u32 VI = UF * (u32)CI / 8u, VO = UF * (u32)CO / 8u;
+    static constexpr u32 NU = 4u / (VI > VO ? VI : VO);
+    static constexpr u32 TILE_FRAMES = 64u * NU * UF;
+};
+
+// Every output sample is ONE dot instruction on an input dword.  Stereo in: the dword is a frame, the weight dword
+// the row.  Mono in: the dword holds two frames, and the row's weight sits in the half of the frame it belongs to
+// (the other half is zero), so no sample is extracted from its dword.
+template <int CI, int CO, bool FULL>
+__device__ __forceinline__ void mix_fast_tile(const MixArgs &a, u32 s, u32 k, u32 F, const int16_t *a_in,
+                                              int16_t *a_out, u64 in_stride, u64 out_stride)
+{
+    using G = MixFast<CI, CO>;
+    constexpr u32 VI = G::VI, VO = G::VO, NU = G::NU;
+    const u32 lane = threadIdx.x & 63u;
+    const int16_t *ins = a_in + (u64)s * in_stride;
+    int16_t *outs = a_out + (u64)s * out_stride;
+    const u32 ns_in = F * (u32)CI, ns_out = F * (u32)CO;
+    const u32 nfull_in = ns_in >> 3, ntail_in = ns_in & 7u;
+    const u32 nfull_out = ns_out >> 3, ntail_out = ns_out & 7u;
+    const u32 n0 = k * 64u * NU;
+
+    // ---- load: every vector of the tile, before the matrix is read
+    u32 x[NU][VI][4];
+#pragma unroll
+    for (u32 j = 0; j < NU; j++) {
+#pragma unroll
+        for (u32 i = 0; i < VI; i++) {
+            const u32 v = (n0 + 64u * j + lane) * VI + i;
+            load_vec(x[j][i], ins, v, FULL || v < nfull_in, !FULL && ntail_in && v == nfull_in, ntail_in);
+        }
+    }
+
+    // ---- the stream's matrix, read only now (the tile's loads depend on kernel arguments alone and are on their
+    // way; the barrier keeps the scheduler from moving these reads back up).  One or two dwords at FIXED offsets
+    // from the row's address, which is computed in full: no scalar load with a register and an immediate offset.
+    __builtin_amdgcn_sched_barrier(0);
+    constexpr u32 NW = (u32)CO;                      // CP == 1: one dword per output channel
+    const u32 *wrow = a.wk + (u64)s * NW;
+    u32 wk[2];
+    wk[0] = uniform(wrow[0]);
+    wk[1] = NW > 1 ? uniform(wrow[NW - 1u]) : 0u;
+    u32 wlo[2], whi[2];                              // mono in: the weight in the low / the high half
+#pragma unroll
+    for (u32 o = 0; o < 2; o++) {
+        wlo[o] = wk[o] & 0xffffu;
+        whi[o] = wk[o] << 16;
+    }
+
+    // ---- arithmetic and stores
+    u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
+    // (output vector i of unit j.  Called once or twice per unit, not from a loop over i: around a loop of one
+    // iteration the optimiser promotes the store out of it and the copy it makes is an ordinary store, not "nt")
+    auto out_vec = [&](u32 j, auto ic) {
+        constexpr u32 i = decltype(ic)::value;
+        u32x4 ov;
+#pragma unroll
+        for (u32 d = 0; d < 4; d++) {
+            int acc[2];
+#pragma unroll
+            for (u32 h = 0; h < 2; h++) {
+                const u32 e = (i * 4u + d) * 2u + h;                 // output sample of the unit
+                const u32 f = e / (u32)CO, oc = e % (u32)CO;
+                const u32 dw = (f * (u32)CI) >> 1;                   // the input dword that holds frame f
+                const u32 xin = x[j][dw >> 2][dw & 3u];
+                const u32 w = CI == 2 ? wk[oc] : ((f & 1u) ? whi[oc] : wlo[oc]);
+                acc[h] = mix_dot2(xin, w, 8192);
+            }
+            ov[d] = mix_pack(acc[0], acc[1]);
+        }
+        const u32 v = (n0 + 64u * j + lane) * VO + i;
+        if (FULL || v < nfull_out) {
+            __builtin_nontemporal_store(ov, dst + v);
+        } else if (ntail_out && v == nfull_out) {
+            const u32 o[4] = {ov.x, ov.y, ov.z, ov.w};
+            store_tail(outs, v, o, ntail_out);
+        }
+    };
+#pragma unroll
+    for (u32 j = 0; j < NU; j++) {
+        out_vec(j, std::integral_constant<u32, 0>{});
+        if constexpr (VO == 2)
+            out_vec(j, std::integral_constant<u32, 1>{});
+    }
+}
+
+template <int CI, int CO>
+__global__ __launch_bounds__(64) void k_mix_fast(MixArgs a)
+{
+    using G = MixFast<CI, CO>;
+    // every kernel argument the tile's loads need is read here, with the first batch of scalar loads (k_run_fast)
+    const int16_t *a_in = a.in;
+    int16_t *a_out = a.out;
+    const u64 in_stride = a.in_stride, out_stride = a.out_stride;
+    const u32 a_frames = a.frames;
+    const u32 s = blockIdx.x / a.chunks;             // stream
+    const u32 k = blockIdx.x - s * a.chunks;         // tile inside the stream
+    const u32 F = a.nframes ? a.nframes[s] : a_frames;
+    const u32 f0 = k * G::TILE_FRAMES;
+    if (f0 >= F)                                     // (uniform)
+        return;
+    if (f0 + G::TILE_FRAMES <= F)
+        mix_fast_tile<CI, CO, true>(a, s, k, F, a_in, a_out, in_stride, out_stride);
+    else
+        mix_fast_tile<CI, CO, false>(a, s, k, F, a_in, a_out, in_stride, out_stride);
+}
+
+// ---------------------------------------------------------------------------
+// Form 2: any pair of channel counts.  A workgroup of 256 threads takes one stream and a tile of tile_frames frames
+// (a multiple of 8: tile edges are 16-byte edges on both sides for every channel count).
+//   1. the tile's interleaved input is loaded in 16-byte vectors and scattered into CP planes of dwords,
+//      plane[k][f] = x[f][2k] | x[f][2k+1] << 16: for an even C_in every loaded dword is such a pair, for an odd one
+//      the samples go in by halves (the unused half of the last plane is never written: it meets a zero weight, and
+//      in integers anything times zero is zero);
+//   2. a thread computes all C_out samples of its frames: lanes with consecutive frames read consecutive dwords of a
+//      plane (conflict-free, and exactly the operand of the dot instruction), the matrix is read from LDS at a
+//      wave-uniform address (a broadcast);
+//   3. the results go into an interleaved output tile in LDS and leave as whole 16-byte vectors, the ragged end of
+//      the stream sample by sample.
+__global__ __launch_bounds__(MIX_BLOCK) void k_mix_any(MixArgs a)
+{
+    extern __shared__ u32x4 mix_lds[];
+    const u32 CI = a.channels_in, CO = a.channels_out, CP = mix_cp(CI), tile = a.tile_frames;
+    const u32 tid = threadIdx.x;
+    const u32 s = blockIdx.x / a.chunks;             // stream
+    const u32 k = blockIdx.x - s * a.chunks;         // tile inside the stream
+    const u32 F = a.nframes ? a.nframes[s] : a.frames;
+    const u32 f0 = k * tile;
+    if (f0 >= F)                                     // (uniform)
+        return;
+    const u32 nt = min(tile, F - f0);                // the tile's frames
+    const int16_t *ins = a.in + (u64)s * a.in_stride;
+    int16_t *outs = a.out + (u64)s * a.out_stride;
+
+    u32 *wl = reinterpret_cast<u32 *>(mix_lds);
+    u32 *plane = wl + mix_wk_lds(CI, CO);
+    int16_t *plane16 = reinterpret_cast<int16_t *>(plane);
+    int16_t *ot = reinterpret_cast<int16_t *>(plane + CP * tile);
+
+    for (u32 i = tid; i < CO * CP; i += MIX_BLOCK)
+        wl[i] = a.wk[(u64)s * CO * CP + i];
+
+    // ---- stage the input: vectors vb .. vb + nv - 1 of the stream (f0 * CI is a multiple of 8)
+    {
+        const u32 ns = F * CI, nfull = ns >> 3, ntail = ns & 7u;
+        const u32 vb = (f0 * CI) >> 3, nv = (nt * CI + 7u) >> 3;
+        for (u32 w = tid; w < nv; w += MIX_BLOCK) {
+            const u32 v = vb + w;
+            u32 x[4];
+            load_vec(x, ins, v, v < nfull, v == nfull && ntail != 0, ntail);
+            if ((CI & 1u) == 0) {
+#pragma unroll
+                for (u32 i = 0; i < 4; i++) {
+                    const u32 e = w * 4u + i;                        // dword of the tile
+                    const u32 f = e / CP, kk = e - f * CP;
+                    if (f < nt)
+                        plane[kk * tile + f] = x[i];
+                }
+            } else {
+#pragma unroll
+                for (u32 i = 0; i < 8; i++) {
+                    const u32 e = w * 8u + i;                        // sample of the tile
+                    const u32 f = e / CI, c = e - f * CI;
+                    if (f < nt)
+                        plane16[((c >> 1) * tile + f) * 2u + (c & 1u)] = (int16_t)(x[i >> 1] >> (16u * (i & 1u)));
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- one thread per frame, all outputs of the frame
+    for (u32 f = tid; f < nt; f += MIX_BLOCK) {
+        for (u32 o = 0; o < CO; o++) {
+            int acc = 8192;
+            for (u32 kk = 0; kk < CP; kk++)
+                acc = mix_dot2(plane[kk * tile + f], wl[o * CP + kk], acc);
+            ot[f * CO + o] = (int16_t)min(max(acc >> 14, -32768), 32767);
+        }
+    }
+    __syncthreads();
+
+    // ---- the output tile: whole vectors, the stream's ragged end sample by sample (f0 * CO is a multiple of 8)
+    {
+        const u32 ns = F * CO, nfull = ns >> 3, ntail = ns & 7u;
+        const u32 vb = (f0 * CO) >> 3, nv = (nt * CO + 7u) >> 3;
+        u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
+        const u32x4 *otv = reinterpret_cast<const u32x4 *>(ot);
+        for (u32 w = tid; w < nv; w += MIX_BLOCK) {
+            const u32 v = vb + w;
+            if (v < nfull) {
+                __builtin_nontemporal_store(otv[w], dst + v);
+            } else if (v == nfull) {
+                for (u32 j = 0; j < ntail; j++)
+                    outs[(u64)v * 8 + j] = ot[w * 8u + j];
+            }
+        }
+    }
+}
+
+// one matrix in the kernel form (at most 16 x 8 dwords, a kernel argument: it travels with the launch, so nothing
+// the host owns is read later) into the rows of streams first .. first + count - 1
+struct MixSetArgs {
+    u32 *wk;
+    u32 first, count, n;                             // n = C_out * CP dwords per stream
+    u32 w[MAX_CH * (MAX_CH / 2u)];
+};
+__global__ __launch_bounds__(MIX_BLOCK) void k_mix_set(MixSetArgs a)
+{
+    const u64 i = (u64)blockIdx.x * MIX_BLOCK + threadIdx.x;
+    if (i >= (u64)a.count * a.n)
+        return;
+    const u32 e = (u32)(i % a.n);
+    u32 val = 0;
+    for (u32 j = 0; j < MAX_CH * (MAX_CH / 2u); j++)     // (selects: the argument stays in SGPRs)
+        if (j == e)
+            val = a.w[j];
+    a.wk[(u64)a.first * a.n + i] = val;
+}
+
+// ---------------------------------------------------------------------------
+// launcher
+
+MixPlan plan_mix(const MixArgs &a)
+{
+    MixPlan p{};
+    p.err = hipSuccess;
+    const u32 CI = a.channels_in, CO = a.channels_out;
+    if (a.streams == 0 || a.frames == 0 || CI == 0 || CI > MAX_CH || CO == 0 || CO > MAX_CH)
+        return p;
+    MixPlan refused{};
+    refused.err = hipErrorInvalidValue;
+    u32 tile, lds = 0;
+    const bool fast = CI <= 2 && CO <= 2;
+    if (fast) {
+        tile = CI == 1 && CO == 1 ? MixFast<1, 1>::TILE_FRAMES : MixFast<2, 2>::TILE_FRAMES;     // (2048 : 1024)
+    } else {
+        // the largest power-of-two tile whose planes and output fit beside the matrix
+        for (tile = MIX_TILE_MAX; mix_lds_bytes(CI, CO, tile) > MIX_LDS_LIMIT; tile >>= 1)
+            ;
+        lds = mix_lds_bytes(CI, CO, tile);
+    }
+    const u64 tiles = ((u64)a.frames + tile - 1u) / tile;
+    if (tiles * a.streams >= (1ull << 31))                   // (as plan_run: no grid of 2^31 workgroups)
+        return refused;
+    p.fast = fast ? 1u : 0u;
+    p.block = fast ? 64u : MIX_BLOCK;
+    p.tile_frames = tile;
+    p.lds_bytes = lds;
+    p.chunks = (u32)tiles;
+    p.grid = a.streams * p.chunks;
+    return p;
+}
+
+hipError_t launch_mix(const MixArgs &a, hipStream_t st)
+{
+    const MixPlan p = plan_mix(a);
+    if (p.grid == 0)
+        return p.err;
+    MixArgs b = a;
+    b.chunks = p.chunks;
+    b.tile_frames = p.tile_frames;
+    const u32 form = p.fast ? a.channels_in * 2u + a.channels_out : 0u;
+    switch (form) {
+    case 3: hipLaunchKernelGGL((k_mix_fast<1, 1>), dim3(p.grid), dim3(p.block), 0, st, b); break;
+    case 4: hipLaunchKernelGGL((k_mix_fast<1, 2>), dim3(p.grid), dim3(p.block), 0, st, b); break;
+    case 5: hipLaunchKernelGGL((k_mix_fast<2, 1>), dim3(p.grid), dim3(p.block), 0, st, b); break;
+    case 6: hipLaunchKernelGGL((k_mix_fast<2, 2>), dim3(p.grid), dim3(p.block), 0, st, b); break;
+    default: hipLaunchKernelGGL(k_mix_any, dim3(p.grid), dim3(p.block), p.lds_bytes, st, b); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_mix_set(uint32_t *wk, uint32_t first, uint32_t count, uint32_t channels_in, uint32_t channels_out,
+                          const int16_t *W, hipStream_t st)
+{
+    MixSetArgs a{};
+    const u32 CP = mix_cp(channels_in);
+    a.wk = wk;
+    a.first = first;
+    a.count = count;
+    a.n = channels_out * CP;
+    for (u32 o = 0; o < channels_out; o++)
+        for (u32 c = 0; c < channels_in; c++)
+            a.w[o * CP + (c >> 1)] |= (u32)(uint16_t)W[o * channels_in + c] << (16u * (c & 1u));
+    const u64 total = (u64)count * a.n;
+    if (total == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_mix_set, dim3((u32)((total + MIX_BLOCK - 1u) / MIX_BLOCK)), dim3(MIX_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+// test hook: the plan of a mixer run whose longest stream has `frames` frames (host logic, needs no GPU)
+extern "C" void cmhip_test_plan_mix(uint32_t streams, uint32_t channels_in, uint32_t channels_out, uint32_t frames,
+                                    MixPlan *plan)
+{
+    MixArgs a{};
+    a.streams = streams;
+    a.channels_in = channels_in;
+    a.channels_out = channels_out;
+    a.frames = frames;
+    if (plan)
+        *plan = plan_mix(a);
+}
+
+}  // namespace cmhip
