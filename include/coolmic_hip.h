@@ -455,6 +455,84 @@ int      cmhip_mix_check(unsigned int channels_in, unsigned int channels_out, co
 int      cmhip_mix_preset(unsigned int preset, unsigned int *channels_in, unsigned int *channels_out, int16_t *W,
                           size_t cap /* entries */);
 
+/* ---- mix bus, an object of its own beside the batch ------------------------------ */
+/* A bus object sums streams: `streams` input slots of channels_in interleaved int16 channels become `buses` output
+ * slots of channels_out, by a routing table of n SENDS.  Send j is (bus_j, stream_j, W_j[channels_out][channels_in]),
+ * W_j int16 in units of 2^-14 as the mixer's (unity = 16384, negative weights allowed).  A programme of several
+ * microphones, a conference room, the "everyone but me" return feed (mix-minus: one bus per participant) are tables.
+ *
+ * Arithmetic.  For bus b, frame f, output channel o:
+ *       p_j        = sum_{c<C_in} W_j[o][c] * x[stream_j][f][c]     exact in int32; 0 where f >= count(stream_j)
+ *       acc        = sum over the sends j of bus b of p_j            exact in int64, in any order
+ *       y[b][f][o] = saturate_int16((acc + 8192) >> 14)              arithmetic shift (floor); ONE rounding, after the sum
+ *   Sends are never rounded or saturated one by one, and their order does not matter.  A stream may feed several buses,
+ *   and may appear more than once in one bus: the weights simply add.
+ * Validity.  channels_in, channels_out in 1..16; streams, buses >= 1; every row of every send has
+ *   sum_c |W_j[o][c]| <= 65535 (the mixer's bound: |p_j| <= 65535 * 32768 < 2^31); bus_j < buses, stream_j < streams;
+ *   n <= max_sends, the capacity of the table fixed at creation (>= 1); max_frames * max(C_in, C_out) < 2^31; streams,
+ *   buses + 1 and max_sends * C_out * ceil(C_in / 2) each stay below 2^31.  Anything else is COOLMIC_ERROR_INVAL and
+ *   changes nothing.  The sum over a bus is not bounded by a rule: 2^31 sends of 2^31 each still fit an int64.
+ * Counts.  A bus's output count is the largest count among its sends' streams, 0 for a bus with no sends; such a bus
+ *   touches nothing.  Samples past a bus's count are not written.  A send whose stream is shorter than the bus
+ *   contributes silence beyond its own count: its slot is not read there.
+ * State.  There is none: nothing is carried between runs and the output does not depend on how the streams were cut
+ *   into runs.  A bus with one send equals cmhip_mix_run with the same matrix bit for bit.
+ *
+ * cmhip_bus_run: `in` is int16 [streams][in_stride], `out` int16 [buses][out_stride], strides in samples as in a
+ *   batch, both device-accessible; asynchronous on the object's stream.  `frames` frames per stream, or
+ *   frames_per_stream[s] <= frames (host array of `streams` entries, may be NULL; free on return).  The contract and
+ *   the refusals are cmhip_mix_run's: COOLMIC_ERROR_INVAL, with nothing launched and nothing changed, when a base is
+ *   not 16-byte aligned, a stride is not a multiple of 8 samples or smaller than frames * C_in (in) or frames * C_out
+ *   (out), frames > max_frames, a per-stream count is above frames, the run's grid would reach 2^31 workgroups, or the
+ *   byte ranges [in, in + streams * in_stride samples) and [out, out + buses * out_stride samples) overlap at all;
+ *   COOLMIC_ERROR_FAULT for NULL arrays.  out_frames[] (host, `buses` entries, may be NULL) receives every bus's count,
+ *   computed on the host from the mirror of the table before the call returns, without a device wait -- exactly the
+ *   frames_per_stream argument of a cmhip_batch_run on the result.
+ * cmhip_bus_set_routing replaces the whole table (n == 0 empties it; routing at creation: empty).  It is ordered with
+ *   the runs by the stream alone: runs queued before it use the old table, runs queued after it the new one, the
+ *   caller does not synchronise, and bus[], stream[], W[] are free on return.  The table travels from ONE pinned
+ *   staging area the object owns: a second cmhip_bus_set_routing may wait ON THE HOST until the first one's copy has
+ *   executed on the stream (likewise the fifth of five cmhip_bus_run with frames_per_stream queued back to back, for
+ *   the first one's counts).  A table that fails the validity rules is refused and the old one stays.
+ *   cmhip_bus_sends / cmhip_bus_get_routing answer from the host's mirror, in the caller's order; a cap below the
+ *   table's sends is COOLMIC_ERROR_INVAL with nothing written.
+ * Composition: as the mixer -- out = cmhip_batch_dev_in(b), out_stride = cmhip_batch_stride(b) of a batch with
+ *   streams = buses and channels = channels_out, frames_per_stream = out_frames; with hip_stream =
+ *   cmhip_batch_hip_stream(b) the order is the stream's.  The chain is source -> rate (cmhip_src_t) -> width
+ *   (cmhip_mix_t) -> bus (cmhip_bus_t) -> batch.
+ * cmhip_bus_new returns NULL on failure.
+ *
+ * Host only.  cmhip_bus_check: 0 for a valid table of n sends, else as above (COOLMIC_ERROR_FAULT for a NULL array
+ *   with n > 0); sizes are judged before an array is read.  cmhip_bus_mix_minus writes the table of n participants with
+ *   C_in == C_out == channels: bus b gets every stream != b with the matrix w * I, bus-major, n * (n - 1) sends; a
+ *   cap_sends below that is COOLMIC_ERROR_INVAL with nothing written (n == 1 is the empty table). */
+typedef struct cmhip_bus cmhip_bus_t;
+typedef struct cmhip_bus_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* input slots, >= 1 */
+    unsigned int buses;           /* output slots, >= 1 */
+    unsigned int channels_in;     /* 1..16 */
+    unsigned int channels_out;    /* 1..16 */
+    size_t       max_frames;      /* per run and slot */
+    size_t       max_sends;       /* capacity of the routing table, >= 1 */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_bus_desc_t;
+cmhip_bus_t *cmhip_bus_new(const cmhip_bus_desc_t *d);
+void     cmhip_bus_free(cmhip_bus_t *m);
+int      cmhip_bus_set_routing(cmhip_bus_t *m, size_t n, const uint32_t *bus, const uint32_t *stream,
+                               const int16_t *W /* [n][C_out][C_in] */);
+size_t   cmhip_bus_sends(const cmhip_bus_t *m);
+int      cmhip_bus_get_routing(const cmhip_bus_t *m, size_t cap, uint32_t *bus, uint32_t *stream, int16_t *W);
+int      cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride, uint32_t *out_frames);
+int      cmhip_bus_sync(cmhip_bus_t *m);
+void    *cmhip_bus_hip_stream(cmhip_bus_t *m);
+/* host only, no device needed */
+int      cmhip_bus_check(unsigned int buses, unsigned int streams, unsigned int channels_in, unsigned int channels_out,
+                         size_t n, const uint32_t *bus, const uint32_t *stream, const int16_t *W);
+int      cmhip_bus_mix_minus(unsigned int n, int16_t w, uint32_t *bus, uint32_t *stream, int16_t *W, size_t cap_sends,
+                             unsigned int channels);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

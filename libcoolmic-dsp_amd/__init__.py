@@ -97,6 +97,13 @@ class MixDesc(C.Structure):
                 ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class BusDesc(C.Structure):
+    """cmhip_bus_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("buses", C.c_uint), ("channels_in", C.c_uint),
+                ("channels_out", C.c_uint), ("max_frames", C.c_size_t), ("max_sends", C.c_size_t),
+                ("hip_stream", C.c_void_p)]
+
+
 class Placement(C.Structure):
     """cmhip_placement_t (include/coolmic_hip.h)"""
     _fields_ = [("searched", C.c_int), ("candidates", C.c_int), ("chosen_in", C.c_int),
@@ -206,6 +213,16 @@ SIGNATURES = {
     "cmhip_mix_hip_stream": (_vp, [_vp]),
     "cmhip_mix_check": (C.c_int, [C.c_uint, C.c_uint, _vp]),
     "cmhip_mix_preset": (C.c_int, [C.c_uint, _P(C.c_uint), _P(C.c_uint), _vp, C.c_size_t]),
+    "cmhip_bus_new": (_vp, [_P(BusDesc)]),
+    "cmhip_bus_free": (None, [_vp]),
+    "cmhip_bus_set_routing": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp]),
+    "cmhip_bus_sends": (C.c_size_t, [_vp]),
+    "cmhip_bus_get_routing": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp]),
+    "cmhip_bus_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "cmhip_bus_sync": (C.c_int, [_vp]),
+    "cmhip_bus_hip_stream": (_vp, [_vp]),
+    "cmhip_bus_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_size_t, _vp, _vp, _vp]),
+    "cmhip_bus_mix_minus": (C.c_int, [C.c_uint, C.c_int16, _vp, _vp, _vp, C.c_size_t, C.c_uint]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -337,6 +354,13 @@ if hasattr(lib, "cmhip_test_plan_src"):         # (not in builds older than samp
 if hasattr(lib, "cmhip_test_plan_mix"):         # (not in builds older than channel mixing)
     lib.cmhip_test_plan_mix.restype = None
     lib.cmhip_test_plan_mix.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
+if hasattr(lib, "cmhip_test_plan_bus"):         # (not in builds older than the mix bus)
+    lib.cmhip_test_plan_bus.restype = None
+    lib.cmhip_test_plan_bus.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
+    lib.cmhip_test_bus_compile.restype = C.c_int
+    lib.cmhip_test_bus_compile.argtypes = [C.c_uint] * 4 + [C.c_size_t] + [_vp] * 7
+    lib.cmhip_test_bus_nt_loads.restype = None
+    lib.cmhip_test_bus_nt_loads.argtypes = [_vp, C.c_int]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -509,6 +533,64 @@ def mix_check(channels_in, channels_out, W):
         return lib.cmhip_mix_check(channels_in, channels_out, None)
     w = np.ascontiguousarray(W, dtype=np.int16)
     return lib.cmhip_mix_check(channels_in, channels_out, w.ctypes.data)
+
+
+class BusPlan(C.Structure):
+    """cmhip::BusPlan (csrc/cmhip_internal.h): what the mix bus's launcher launches for a run"""
+    _fields_ = MixPlan._fields_
+
+
+def plan_bus(buses, channels_in, channels_out, frames):
+    """Test hook: the bus launcher's plan for a run whose longest stream has `frames` frames (host logic, needs no
+    GPU)"""
+    p = BusPlan()
+    lib.cmhip_test_plan_bus(buses, channels_in, channels_out, frames, C.addressof(p))
+    return p
+
+
+def _bus_table(bus, stream, W, channels_in, channels_out):
+    """a routing table as three contiguous arrays (uint32 [n], uint32 [n], int16 [n][C_out][C_in]) and n"""
+    b = np.ascontiguousarray(bus, dtype=np.uint32).reshape(-1)
+    s = np.ascontiguousarray(stream, dtype=np.uint32).reshape(-1)
+    w = np.ascontiguousarray(W, dtype=np.int16).reshape(-1, channels_out, channels_in)
+    assert b.size == s.size == w.shape[0]
+    return b, s, w, b.size
+
+
+def bus_check(buses, streams, channels_in, channels_out, bus, stream, W, n=None):
+    """cmhip_bus_check as it is -> error number (0: the table is valid).  n: the send count handed over when it is not
+    the arrays' (they are not read when the sizes alone decide)"""
+    if bus is None:
+        return lib.cmhip_bus_check(buses, streams, channels_in, channels_out, n or 0, None, None, None)
+    b, s, w = (np.ascontiguousarray(bus, dtype=np.uint32), np.ascontiguousarray(stream, dtype=np.uint32),
+               np.ascontiguousarray(W, dtype=np.int16))
+    return lib.cmhip_bus_check(buses, streams, channels_in, channels_out, b.size if n is None else n, b.ctypes.data,
+                               s.ctypes.data, w.ctypes.data)
+
+
+def bus_mix_minus(n, w, channels=1, cap_sends=None):
+    """cmhip_bus_mix_minus -> (bus uint32 [n(n-1)], stream uint32 [n(n-1)], W int16 [n(n-1)][channels][channels]);
+    CoolmicError when it is refused"""
+    sends = n * (n - 1) if cap_sends is None else cap_sends
+    b, s = np.zeros(max(sends, 1), dtype=np.uint32), np.zeros(max(sends, 1), dtype=np.uint32)
+    W = np.zeros((max(sends, 1), channels, channels), dtype=np.int16)
+    _check("bus_mix_minus", lib.cmhip_bus_mix_minus(n, w, b.ctypes.data, s.ctypes.data, W.ctypes.data, sends, channels))
+    k = n * (n - 1)
+    return b[:k], s[:k], W[:k]
+
+
+def bus_compile(buses, streams, channels_in, channels_out, bus, stream, W):
+    """Test hook: the routing compiler (csrc/bus_route.h) on a table -> (first uint32 [B+1], stream uint32 [n],
+    flag uint32 [n], wk uint32 [n][C_out][CP]); host logic, needs no GPU"""
+    b, s, w, n = _bus_table(bus, stream, W, channels_in, channels_out)
+    cp = (channels_in + 1) // 2
+    first = np.zeros(buses + 1, dtype=np.uint32)
+    so, fl = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    wk = np.zeros((max(n, 1), channels_out, cp), dtype=np.uint32)
+    _check("bus_compile", lib.cmhip_test_bus_compile(buses, streams, channels_in, channels_out, n, b.ctypes.data,
+                                                     s.ctypes.data, w.ctypes.data, first.ctypes.data, so.ctypes.data,
+                                                     fl.ctypes.data, wk.ctypes.data))
+    return first, so[:n], fl[:n], wk[:n]
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -946,6 +1028,70 @@ class Mixer:
 
     def hip_stream(self):
         return lib.cmhip_mix_hip_stream(self.h) or 0
+
+
+class Bus:
+    """cmhip_bus_t: a mix bus beside a batch -- `streams` input slots summed into `buses` output slots by a routing
+    table of sends (bus, stream, W int16 [C_out][C_in] in units of 2^-14).  Routing at creation: empty."""
+
+    def __init__(self, streams, buses, channels_in, channels_out, max_frames, max_sends, device=0, hip_stream=None):
+        d = BusDesc(device, streams, buses, channels_in, channels_out, max_frames, max_sends, hip_stream)
+        self.h = lib.cmhip_bus_new(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_bus_new", ERROR_INVAL)
+        self.streams, self.buses, self.channels_in, self.channels_out = streams, buses, channels_in, channels_out
+        self.max_frames, self.max_sends = max_frames, max_sends
+
+    def close(self):
+        if self.h:
+            lib.cmhip_bus_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_routing_rc(self, bus, stream, W):
+        """cmhip_bus_set_routing as it is -> error number"""
+        b, s, w, n = _bus_table(bus, stream, W, self.channels_in, self.channels_out)
+        return lib.cmhip_bus_set_routing(self.h, n, b.ctypes.data, s.ctypes.data, w.ctypes.data)
+
+    def set_routing(self, bus, stream, W):
+        """replaces the whole table; ordered with the runs on the object's stream"""
+        _check("bus_set_routing", self.set_routing_rc(bus, stream, W))
+
+    def sends(self):
+        return lib.cmhip_bus_sends(self.h)
+
+    def get_routing(self):
+        n = self.sends()
+        b, s = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        w = np.zeros((max(n, 1), self.channels_out, self.channels_in), dtype=np.int16)
+        _check("bus_get_routing", lib.cmhip_bus_get_routing(self.h, n, b.ctypes.data, s.ctypes.data, w.ctypes.data))
+        return b[:n], s[:n], w[:n]
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None, out_frames=None):
+        """cmhip_bus_run as it is -> error number; out_frames: a uint32 array of `buses` entries or None"""
+        fps = None
+        if frames_per_stream is not None:
+            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
+            assert fps.size == self.streams
+        return lib.cmhip_bus_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
+                                 out_stride, out_frames.ctypes.data if out_frames is not None else None)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers) -> every bus's frame count (uint32 [buses])"""
+        got = np.zeros(self.buses, dtype=np.uint32)
+        _check("bus_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream, got))
+        return got
+
+    def sync(self):
+        _check("bus_sync", lib.cmhip_bus_sync(self.h))
+
+    def hip_stream(self):
+        return lib.cmhip_bus_hip_stream(self.h) or 0
 
 
 class PinnedPcm:

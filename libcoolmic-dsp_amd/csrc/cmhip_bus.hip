@@ -1,0 +1,343 @@
+// cmhip_bus.hip -- the mix bus on the host side (include/coolmic_hip.h, "mix bus"): the bus object beside the batch,
+// its validation, the routing table's way to the device, the launch of k_bus.hip's kernels, the table check and the
+// mix-minus table.
+//
+// Device state of a bus: the routing table in the kernels' form (csrc/bus_route.h compiles it) -- first[B+1],
+// send[max_sends], wk[max_sends][C_out][CP] in one array -- and the counts of a run, [S] per stream and [B] per bus.
+// That is all: there is no history.  The host keeps the table as the caller gave it (cmhip_bus_get_routing) and as
+// compiled (a run's out_frames come from it without a device wait).
+//
+// Both travel by hipMemcpyAsync on the object's stream from PINNED memory the object owns, so they are ordered with the
+// runs by the stream alone and nothing the caller owns is read after a call returns: the table from one staging area
+// with an event (a second set waits on the host until the first one's copy has executed), a run's counts from a small
+// ring of slots with an event each (run RING + 1 waits for run 1's copy).
+#include "cmhip_engine.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <new>
+
+#include "bus_route.h"
+
+constexpr uint64_t BUS_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
+constexpr unsigned BUS_RING = 4;                     // runs whose counts may be on their way at once
+
+struct cmhip_bus {
+    cmhip_bus_desc_t d;
+    hipStream_t stream;
+    bool own_stream;
+    uint32_t *d_table;                 // first[B+1] | send[max_sends] | wk[max_sends * NW]
+    uint32_t *d_counts;                // [S] streams | [B] buses
+    uint32_t *h_table;                 // pinned, the same layout
+    hipEvent_t table_ev;
+    bool table_busy;                   // a copy from h_table was queued and not yet waited for
+    uint32_t *h_counts;                // pinned [BUS_RING][S + B]
+    hipEvent_t counts_ev[BUS_RING];
+    bool counts_busy[BUS_RING];
+    unsigned ring;
+    bool nt_loads;
+    std::vector<uint32_t> bus, strm;   // the mirror, in the caller's order
+    std::vector<int16_t> w;
+    BusTable t;                        // ... and compiled
+};
+
+static size_t bus_nw(const cmhip_bus_t *m) { return (size_t)m->d.channels_out * ((m->d.channels_in + 1) / 2); }
+
+static int bus_route_fail(const char *who, BusRouteError e, size_t where)
+{
+    switch (e) {
+    case BUS_ROUTE_OK: return COOLMIC_ERROR_NONE;
+    case BUS_ROUTE_GEOMETRY:
+        return fail(COOLMIC_ERROR_INVAL, "%s: buses and streams must be positive, both channel counts in 1..16", who);
+    case BUS_ROUTE_SIZE: return fail(COOLMIC_ERROR_INVAL, "%s: the table would reach 2^31 entries", who);
+    case BUS_ROUTE_NULL: return fail(COOLMIC_ERROR_FAULT, "%s: NULL argument", who);
+    case BUS_ROUTE_BUS: return fail(COOLMIC_ERROR_INVAL, "%s: send %zu: bus out of range", who, where);
+    case BUS_ROUTE_STREAM: return fail(COOLMIC_ERROR_INVAL, "%s: send %zu: stream out of range", who, where);
+    case BUS_ROUTE_ROW: return fail(COOLMIC_ERROR_INVAL, "%s: send %zu has a row with sum |w| above 65535", who, where);
+    }
+    return fail(COOLMIC_ERROR_GENERIC, "%s: unknown error", who);
+}
+
+extern "C" int cmhip_bus_check(unsigned buses, unsigned streams, unsigned channels_in, unsigned channels_out, size_t n,
+                               const uint32_t *bus, const uint32_t *stream, const int16_t *W)
+{
+    size_t where = 0;
+    return bus_route_fail("bus_check", bus_route_check(buses, streams, channels_in, channels_out, n, bus, stream, W, &where),
+                          where);
+}
+
+extern "C" int cmhip_bus_mix_minus(unsigned n, int16_t w, uint32_t *bus, uint32_t *stream, int16_t *W, size_t cap_sends,
+                                   unsigned channels)
+{
+    if (n == 0 || channels == 0 || channels > MAX_CH)
+        return fail(COOLMIC_ERROR_INVAL, "bus_mix_minus: %u participants of %u channels", n, channels);
+    const size_t sends = (size_t)n * (n - 1);
+    if (cap_sends < sends)
+        return fail(COOLMIC_ERROR_INVAL, "bus_mix_minus: room for %zu sends, the table has %zu", cap_sends, sends);
+    if (sends && (!bus || !stream || !W))
+        return fail(COOLMIC_ERROR_FAULT, "bus_mix_minus: NULL argument");
+    size_t j = 0;
+    for (unsigned b = 0; b < n; b++) {
+        for (unsigned s = 0; s < n; s++) {
+            if (s == b)
+                continue;
+            bus[j] = b;
+            stream[j] = s;
+            int16_t *m = W + j * channels * channels;
+            memset(m, 0, (size_t)channels * channels * sizeof(int16_t));
+            for (unsigned c = 0; c < channels; c++)
+                m[c * channels + c] = w;
+            j++;
+        }
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+// test hook: the compiled form of a table -- first [B+1], stream [n], flag [n], wk [n][C_out][CP] (host logic, no GPU)
+extern "C" int cmhip_test_bus_compile(unsigned buses, unsigned streams, unsigned channels_in, unsigned channels_out,
+                                      size_t n, const uint32_t *bus, const uint32_t *stream, const int16_t *W,
+                                      uint32_t *first, uint32_t *stream_out, uint32_t *flag, uint32_t *wk)
+{
+    const int rc = cmhip_bus_check(buses, streams, channels_in, channels_out, n, bus, stream, W);
+    if (rc)
+        return rc;
+    BusTable t;
+    bus_route_compile(buses, channels_in, channels_out, n, bus, stream, W, t);
+    memcpy(first, t.first.data(), t.first.size() * sizeof(uint32_t));
+    if (n) {
+        memcpy(stream_out, t.stream.data(), n * sizeof(uint32_t));
+        memcpy(flag, t.flag.data(), n * sizeof(uint32_t));
+        memcpy(wk, t.wk.data(), t.wk.size() * sizeof(uint32_t));
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+static int bus_init(cmhip_bus_t *m)
+{
+    const cmhip_bus_desc_t &d = m->d;
+    HIP_TRY(hipSetDevice(d.device));
+    if (d.hip_stream) {
+        m->stream = (hipStream_t)d.hip_stream;
+    } else {
+        HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        m->own_stream = true;
+    }
+    const size_t B = d.buses, S = d.streams, words = B + 1 + d.max_sends * (1 + bus_nw(m));
+    HIP_TRY(hipMalloc((void **)&m->d_table, words * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_counts, (S + B) * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void **)&m->h_table, words * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **)&m->h_counts, BUS_RING * (S + B) * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&m->table_ev, hipEventDisableTiming));
+    for (unsigned i = 0; i < BUS_RING; i++)
+        HIP_TRY(hipEventCreateWithFlags(&m->counts_ev[i], hipEventDisableTiming));
+    // routing at creation: empty
+    bus_route_compile(d.buses, d.channels_in, d.channels_out, 0, nullptr, nullptr, nullptr, m->t);
+    HIP_TRY(hipMemsetAsync(m->d_table, 0, (B + 1) * sizeof(uint32_t), m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void cmhip_bus_free(cmhip_bus_t *m)
+{
+    if (!m)
+        return;
+    (void)hipSetDevice(m->d.device);
+    if (m->stream)
+        (void)hipStreamSynchronize(m->stream);
+    (void)hipFree(m->d_table);
+    (void)hipFree(m->d_counts);
+    (void)hipHostFree(m->h_table);
+    (void)hipHostFree(m->h_counts);
+    if (m->table_ev)
+        (void)hipEventDestroy(m->table_ev);
+    for (unsigned i = 0; i < BUS_RING; i++)
+        if (m->counts_ev[i])
+            (void)hipEventDestroy(m->counts_ev[i]);
+    if (m->own_stream)
+        (void)hipStreamDestroy(m->stream);
+    delete m;
+}
+
+extern "C" cmhip_bus_t *cmhip_bus_new(const cmhip_bus_desc_t *d)
+{
+    if (!d) {
+        fail(COOLMIC_ERROR_FAULT, "bus_new: NULL argument");
+        return nullptr;
+    }
+    if (d->streams == 0 || d->buses == 0 || d->channels_in < 1 || d->channels_in > MAX_CH || d->channels_out < 1 ||
+        d->channels_out > MAX_CH || d->max_frames == 0 || d->max_sends == 0) {
+        fail(COOLMIC_ERROR_INVAL,
+             "bus_new: streams, buses, channels_in, channels_out (1..16), max_frames and max_sends must be positive");
+        return nullptr;
+    }
+    const unsigned cmax = d->channels_in > d->channels_out ? d->channels_in : d->channels_out;
+    if (d->max_frames >= BUS_MAX_SAMPLES || d->max_frames * cmax >= BUS_MAX_SAMPLES) {
+        fail(COOLMIC_ERROR_INVAL, "bus_new: max_frames %zu: a slot of a run would reach 2^31 samples", d->max_frames);
+        return nullptr;
+    }
+    if (bus_route_check(d->buses, d->streams, d->channels_in, d->channels_out, d->max_sends, nullptr, nullptr, nullptr,
+                        nullptr) == BUS_ROUTE_SIZE) {
+        fail(COOLMIC_ERROR_INVAL, "bus_new: %u streams, %u buses, %zu sends: the table would reach 2^31 entries",
+             d->streams, d->buses, d->max_sends);
+        return nullptr;
+    }
+    cmhip_bus_t *m = new (std::nothrow) cmhip_bus();
+    if (!m) {
+        fail(COOLMIC_ERROR_NOMEM, "bus_new: out of memory");
+        return nullptr;
+    }
+    m->d = *d;
+    if (bus_init(m)) {
+        cmhip_bus_free(m);
+        return nullptr;
+    }
+    return m;
+}
+
+extern "C" int cmhip_bus_set_routing(cmhip_bus_t *m, size_t n, const uint32_t *bus, const uint32_t *stream,
+                                     const int16_t *W)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "bus_set_routing: bus is NULL");
+    if (n > m->d.max_sends)
+        return fail(COOLMIC_ERROR_INVAL, "bus_set_routing: %zu sends above max_sends %zu", n, m->d.max_sends);
+    const unsigned B = m->d.buses, CI = m->d.channels_in, CO = m->d.channels_out;
+    size_t where = 0;
+    const BusRouteError e = bus_route_check(B, m->d.streams, CI, CO, n, bus, stream, W, &where);
+    if (e != BUS_ROUTE_OK)
+        return bus_route_fail("bus_set_routing", e, where);
+    HIP_TRY(hipSetDevice(m->d.device));
+    if (m->table_busy) {                             // the staging area is still the source of the last set's copy
+        HIP_TRY(hipEventSynchronize(m->table_ev));
+        m->table_busy = false;
+    }
+    // nothing was touched so far; from here on the table changes
+    bus_route_compile(B, CI, CO, n, bus, stream, W, m->t);
+    m->bus.assign(bus, bus + n);
+    m->strm.assign(stream, stream + n);
+    m->w.assign(W, W + n * CO * CI);
+    const size_t nw = bus_nw(m), send0 = (size_t)B + 1, wk0 = send0 + m->d.max_sends;
+    for (unsigned b = 0; b <= B; b++)
+        m->h_table[b] = bus_first_word(m->t, b);
+    for (size_t p = 0; p < n; p++)
+        m->h_table[send0 + p] = bus_send_word(m->t, p);
+    if (n)
+        memcpy(m->h_table + wk0, m->t.wk.data(), n * nw * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(m->d_table, m->h_table, (send0 + n) * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    m->table_busy = true;                            // (whatever follows: the area may be in use)
+    if (n)
+        HIP_TRY(hipMemcpyAsync(m->d_table + wk0, m->h_table + wk0, n * nw * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               m->stream));
+    HIP_TRY(hipEventRecord(m->table_ev, m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" size_t cmhip_bus_sends(const cmhip_bus_t *m) { return m ? m->bus.size() : 0; }
+
+extern "C" int cmhip_bus_get_routing(const cmhip_bus_t *m, size_t cap, uint32_t *bus, uint32_t *stream, int16_t *W)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "bus_get_routing: bus is NULL");
+    const size_t n = m->bus.size();
+    if (cap < n)
+        return fail(COOLMIC_ERROR_INVAL, "bus_get_routing: room for %zu sends, the table has %zu", cap, n);
+    if (n && (!bus || !stream || !W))
+        return fail(COOLMIC_ERROR_FAULT, "bus_get_routing: NULL argument");
+    if (n) {
+        memcpy(bus, m->bus.data(), n * sizeof(uint32_t));
+        memcpy(stream, m->strm.data(), n * sizeof(uint32_t));
+        memcpy(W, m->w.data(), m->w.size() * sizeof(int16_t));
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void *cmhip_bus_hip_stream(cmhip_bus_t *m) { return m ? (void *)m->stream : nullptr; }
+
+extern "C" int cmhip_bus_sync(cmhip_bus_t *m)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "bus_sync: bus is NULL");
+    HIP_TRY(hipSetDevice(m->d.device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+// test hook (tools/bench_bus.py): k_bus_fast's input loads non-temporal (on != 0) or plain (the default)
+extern "C" void cmhip_test_bus_nt_loads(cmhip_bus_t *m, int on)
+{
+    if (m)
+        m->nt_loads = on != 0;
+}
+
+extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, size_t frames,
+                             const uint32_t *frames_per_stream, void *out, size_t out_stride, uint32_t *out_frames)
+{
+    if (!m || !in || !out)
+        return fail(COOLMIC_ERROR_FAULT, "bus_run: NULL argument");
+    const unsigned S = m->d.streams, B = m->d.buses, CI = m->d.channels_in, CO = m->d.channels_out;
+    if (((uintptr_t)in | (uintptr_t)out) & 15u)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: in and out must be 16-byte aligned");
+    if ((in_stride | out_stride) & 7u)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: strides must be multiples of 8 samples");
+    if (frames > m->d.max_frames)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: %zu frames above max_frames %zu", frames, m->d.max_frames);
+    if (frames_per_stream)
+        for (unsigned s = 0; s < S; s++)
+            if (frames_per_stream[s] > frames)
+                return fail(COOLMIC_ERROR_INVAL, "bus_run: frames_per_stream[%u] above frames", s);
+    if (in_stride < frames * CI)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, CI);
+    if (out_stride < frames * CO)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: out_stride %zu below %zu frames of %u channels", out_stride, frames,
+                    CO);
+    // the byte ranges [in, in + S * in_stride) and [out, out + B * out_stride) may not share a byte
+    const uintptr_t ib = (uintptr_t)in, ie = ib + (uintptr_t)S * in_stride * sizeof(int16_t);
+    const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)B * out_stride * sizeof(int16_t);
+    if (ib < oe && ob < ie)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: the input and the output overlap");
+    BusArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = (const int16_t *)in;
+    a.out = (int16_t *)out;
+    a.nframes = frames_per_stream ? m->d_counts : nullptr;
+    a.bus_frames = m->d_counts + S;
+    a.first = m->d_table;
+    a.send = m->d_table + B + 1;
+    a.wk = a.send + m->d.max_sends;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.frames = (uint32_t)frames;
+    a.buses = B;
+    a.channels_in = CI;
+    a.channels_out = CO;
+    a.nt_loads = m->nt_loads ? 1u : 0u;
+    if (plan_bus(a).err != hipSuccess)
+        return fail(COOLMIC_ERROR_INVAL, "bus_run: %u buses of %zu frames: the grid would reach 2^31 workgroups", B,
+                    frames);
+    // nothing was touched so far; from here on the run happens
+    if (out_frames)
+        for (unsigned b = 0; b < B; b++)
+            out_frames[b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
+    if (frames == 0 || m->bus.empty())
+        return COOLMIC_ERROR_NONE;
+    HIP_TRY(hipSetDevice(m->d.device));
+    if (frames_per_stream) {
+        const unsigned r = m->ring;
+        if (m->counts_busy[r]) {                     // BUS_RING runs back: its counts have long been copied
+            HIP_TRY(hipEventSynchronize(m->counts_ev[r]));
+            m->counts_busy[r] = false;
+        }
+        uint32_t *h = m->h_counts + (size_t)r * (S + B);
+        memcpy(h, frames_per_stream, S * sizeof(uint32_t));
+        for (unsigned b = 0; b < B; b++)
+            h[S + b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
+        HIP_TRY(hipMemcpyAsync(m->d_counts, h, ((size_t)S + B) * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+        m->counts_busy[r] = true;
+        HIP_TRY(hipEventRecord(m->counts_ev[r], m->stream));
+        m->ring = (r + 1) % BUS_RING;
+    }
+    const hipError_t e = launch_bus(a, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "bus_run: %s", hipGetErrorString(e));
+    return COOLMIC_ERROR_NONE;
+}

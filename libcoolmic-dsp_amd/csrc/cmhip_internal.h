@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip (the gfx950 kernels) and cmhip_batch.hip (the
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip / k_bus.hip (the gfx950 kernels) and cmhip_batch.hip (the
 // engine).
 #pragma once
 
@@ -217,6 +217,26 @@ struct MixArgs {
     uint32_t       tile_frames;    // frames per tile
 };
 
+// Mix bus (k_bus.hip; the arithmetic: include/coolmic_hip.h): a run that sums S input slots into B bus slots by the
+// routing table csrc/bus_route.h compiled.
+struct BusArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [B][out_stride]
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    const uint32_t *bus_frames;    // per-bus frame counts (read when nframes != nullptr)
+    const uint32_t *first;         // [B+1] sends of bus b: first[b] .. first[b+1]-1; bit 31: the bus has several groups
+    const uint32_t *send;          // [n] the send's stream; bit 31: the send starts a group
+    const uint32_t *wk;            // [n][C_out][CP] the sends' matrices in the mixer's form (MixArgs::wk)
+    uint64_t       in_stride, out_stride;    // samples between slots (multiples of 8)
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       buses;
+    uint32_t       channels_in, channels_out;
+    uint32_t       nt_loads;       // k_bus_fast loads its input non-temporally (tools/bench_bus.py; default: plain)
+    // (the launcher fills these in)
+    uint32_t       chunks;         // tiles per bus
+    uint32_t       tile_frames;    // frames per tile
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -301,6 +321,18 @@ hipError_t launch_mix(const MixArgs &a, hipStream_t st);
 // matrix travels as a kernel argument, so W may change as soon as the call returns)
 hipError_t launch_mix_set(uint32_t *wk, uint32_t first, uint32_t count, uint32_t channels_in, uint32_t channels_out,
                           const int16_t *W, hipStream_t st);
+// Mix bus (k_bus.hip): one workgroup per bus and tile of tile_frames frames.  fast: the kernel for mono / stereo on
+// both sides (one wave per workgroup, no LDS); otherwise the any-channel-count kernel (256 threads).
+struct BusPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   fast;
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+    uint32_t   chunks;             // BusArgs::chunks: tiles per bus
+    uint32_t   tile_frames;        // BusArgs::tile_frames (a multiple of 8)
+    uint32_t   lds_bytes;          // dynamic LDS of the launch
+};
+BusPlan plan_bus(const BusArgs &a);
+hipError_t launch_bus(const BusArgs &a, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,
