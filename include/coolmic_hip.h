@@ -533,6 +533,82 @@ int      cmhip_bus_check(unsigned int buses, unsigned int streams, unsigned int 
 int      cmhip_bus_mix_minus(unsigned int n, int16_t w, uint32_t *bus, uint32_t *stream, int16_t *W, size_t cap_sends,
                              unsigned int channels);
 
+/* ---- peak limiter, an object of its own beside the batch -------------------------- */
+/* A limiter takes S streams of `channels` interleaved int16 channels in and gives the same out, delayed by a fixed
+ * number of frames and held under a ceiling: a brick-wall look-ahead limiter in exact integers.  It is what follows a
+ * bus (mix with headroom, drive up, hold a ceiling) and precedes the batch.
+ *
+ * Geometry, per object: lookahead_log2 = a in 3..9, A = 2^a; the delay is D = A - 1 frames; hold = H >= 0 frames with
+ *   W = A + H <= 2048; HIST = A + W - 2 is the number of earlier frames an output depends on.
+ * Parameters, per stream, settable between runs: threshold T in 1..32767, in sample units (at creation 32767); drive in
+ *   1..65535, in units of 2^-12 (unity 4096, at creation 4096).
+ * Arithmetic.  For frame n of a stream, counted over everything it was ever given; frames before the first (or before
+ *   a reset) are zero:
+ *       p12[n] = drive * max_c |x[n][c]|                   <= 65535 * 32768 < 2^31
+ *       pr[n]  = (p12[n] + 4095) >> 12                     peak after drive, rounded up to sample units
+ *       g[n]   = 32768                     if pr[n] <= T   (Q15, unity = 32768)
+ *                floor(T * 32768 / pr[n])  otherwise       (numerator < 2^30)
+ *       m[n]   = min(g[n-W+1 .. n])                        sliding minimum: attack look-ahead + hold
+ *       S[n]   = sum(m[n-A+1 .. n])                        <= 2^(15+a) <= 2^24
+ *       s[n]   = S[n] >> a                                 linear attack and release over A frames
+ *       c[n]   = drive * s[n]                              < 2^31
+ *       y[n][ch] = (x[n-D][ch] * c[n] + 2^26) >> 27        64-bit product, arithmetic shift
+ *   All channels of a frame share one gain (linked), so the stereo image does not move.
+ * Ceiling.  Every m[n-j], j < A, has g[n-D] in its window (0 <= D - j <= W - 1), so s[n] <= g[n-D]; with
+ *   |x[n-D][ch]| * drive <= 4096 * pr[n-D] this gives |x * c| <= T * 2^27: |y| <= T always.  Nothing is saturated, so
+ *   nothing can hide an error.
+ * Transparency.  Where pr <= T over the whole window, s = 32768, c = drive * 2^15 and y = (x * drive + 2^11) >> 12: at
+ *   unity drive the output is the input delayed by D frames, bit for bit.
+ * Cuts.  A run evaluates every frame it looks at with the parameters in force for that run, the HIST history frames
+ *   included: the history holds raw input frames, not gains.  Between parameter changes the concatenated output does
+ *   not depend on how a stream was cut into runs; a run that follows a change still holds the ceiling for the new T by
+ *   construction.  A stream given 0 frames keeps everything.
+ * Gain-reduction meter.  Per stream the minimum s[n] over the frames output since the last reset of the meter, Q15;
+ *   32768 when nothing was reduced.
+ *
+ * cmhip_lim_run has cmhip_mix_run's contract with C_in = C_out = channels: `in` is int16 [S][in_stride], `out` int16
+ *   [S][out_stride], strides in samples, both device-accessible; asynchronous on the limiter's stream.  `frames` frames
+ *   per stream, or frames_per_stream[s] <= frames (host array of S entries, may be NULL).  COOLMIC_ERROR_INVAL, with
+ *   nothing launched and nothing changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or
+ *   smaller than frames * channels, frames > max_frames, a per-stream count is above frames, the run's grid would reach
+ *   2^31 workgroups, or the byte ranges [in, in + S * in_stride samples) and [out, out + S * out_stride samples)
+ *   overlap at all.  COOLMIC_ERROR_FAULT for NULL arrays.  Samples past a stream's count are neither read nor written.
+ *   A stream produces as many output frames as it is given input frames; the first D after creation or a reset are
+ *   zeros from the history, and a caller flushes with D frames of silence.
+ * cmhip_lim_set (stream -1: all) is ordered with the runs by the stream alone: runs queued before it use the old
+ *   parameters, runs queued after it the new ones, without a host wait.  Invalid values are refused and the old ones
+ *   stay.  cmhip_lim_get answers from the host's mirror: what the last accepted set (or creation) left.
+ * cmhip_lim_reset (stream -1: all) zeroes the history and re-arms the meter, on the limiter's stream.
+ * cmhip_lim_min_gain waits for the stream and writes the S meters to out[]; reset != 0 re-arms them all afterwards.
+ * cmhip_lim_delay: D.  cmhip_lim_check (host only): 0 for a valid geometry and parameter pair, else COOLMIC_ERROR_INVAL.
+ * Composition: as the mixer -- out = cmhip_batch_dev_in(b), out_stride = cmhip_batch_stride(b) of a batch with the same
+ *   channels; with hip_stream = cmhip_batch_hip_stream(b) the order is the stream's.  The chain is source -> rate
+ *   (cmhip_src_t) -> width (cmhip_mix_t) -> sum (cmhip_bus_t) -> limit (cmhip_lim_t) -> batch.
+ * cmhip_lim_new returns NULL on failure; max_frames * channels may not pass 2^31 samples. */
+typedef struct cmhip_lim cmhip_lim_t;
+typedef struct cmhip_lim_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int lookahead_log2;  /* a in 3..9: A = 2^a, delay A - 1 frames */
+    unsigned int hold;            /* H frames, A + hold <= 2048 */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_lim_desc_t;
+cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d);
+void     cmhip_lim_free(cmhip_lim_t *m);
+unsigned int cmhip_lim_delay(const cmhip_lim_t *m);
+int      cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned int threshold, unsigned int drive);
+int      cmhip_lim_get(const cmhip_lim_t *m, unsigned int stream, unsigned int *threshold, unsigned int *drive);
+int      cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_lim_reset(cmhip_lim_t *m, long stream);
+int      cmhip_lim_min_gain(cmhip_lim_t *m, uint32_t *out /* [S] */, int reset);
+int      cmhip_lim_sync(cmhip_lim_t *m);
+void    *cmhip_lim_hip_stream(cmhip_lim_t *m);
+/* host only, no device needed */
+int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigned int threshold, unsigned int drive);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

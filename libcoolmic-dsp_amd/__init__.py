@@ -104,6 +104,12 @@ class BusDesc(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+class LimDesc(C.Structure):
+    """cmhip_lim_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("lookahead_log2", C.c_uint),
+                ("hold", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
 class Placement(C.Structure):
     """cmhip_placement_t (include/coolmic_hip.h)"""
     _fields_ = [("searched", C.c_int), ("candidates", C.c_int), ("chosen_in", C.c_int),
@@ -223,6 +229,17 @@ SIGNATURES = {
     "cmhip_bus_hip_stream": (_vp, [_vp]),
     "cmhip_bus_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_size_t, _vp, _vp, _vp]),
     "cmhip_bus_mix_minus": (C.c_int, [C.c_uint, C.c_int16, _vp, _vp, _vp, C.c_size_t, C.c_uint]),
+    "cmhip_lim_new": (_vp, [_P(LimDesc)]),
+    "cmhip_lim_free": (None, [_vp]),
+    "cmhip_lim_delay": (C.c_uint, [_vp]),
+    "cmhip_lim_set": (C.c_int, [_vp, C.c_long, C.c_uint, C.c_uint]),
+    "cmhip_lim_get": (C.c_int, [_vp, C.c_uint, _P(C.c_uint), _P(C.c_uint)]),
+    "cmhip_lim_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_lim_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_lim_min_gain": (C.c_int, [_vp, _vp, C.c_int]),
+    "cmhip_lim_sync": (C.c_int, [_vp]),
+    "cmhip_lim_hip_stream": (_vp, [_vp]),
+    "cmhip_lim_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -361,6 +378,9 @@ if hasattr(lib, "cmhip_test_plan_bus"):         # (not in builds older than the 
     lib.cmhip_test_bus_compile.argtypes = [C.c_uint] * 4 + [C.c_size_t] + [_vp] * 7
     lib.cmhip_test_bus_nt_loads.restype = None
     lib.cmhip_test_bus_nt_loads.argtypes = [_vp, C.c_int]
+if hasattr(lib, "cmhip_test_plan_lim"):         # (not in builds older than the peak limiter)
+    lib.cmhip_test_plan_lim.restype = None
+    lib.cmhip_test_plan_lim.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -591,6 +611,25 @@ def bus_compile(buses, streams, channels_in, channels_out, bus, stream, W):
                                                      s.ctypes.data, w.ctypes.data, first.ctypes.data, so.ctypes.data,
                                                      fl.ctypes.data, wk.ctypes.data))
     return first, so[:n], fl[:n], wk[:n]
+
+
+class LimPlan(C.Structure):
+    """cmhip::LimPlan (csrc/lim_plan.h): what the limiter's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_frames",
+                                                               "lds_bytes", "halo")]
+
+
+def plan_lim(streams, channels, lookahead_log2, hold, frames):
+    """Test hook: the limiter launcher's plan for a run whose longest stream has `frames` frames (host logic, needs no
+    GPU)"""
+    p = LimPlan()
+    lib.cmhip_test_plan_lim(streams, channels, lookahead_log2, hold, frames, C.addressof(p))
+    return p
+
+
+def lim_check(lookahead_log2, hold, threshold, drive):
+    """cmhip_lim_check as it is -> error number (0: valid)"""
+    return lib.cmhip_lim_check(lookahead_log2, hold, threshold, drive)
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -1092,6 +1131,76 @@ class Bus:
 
     def hip_stream(self):
         return lib.cmhip_bus_hip_stream(self.h) or 0
+
+
+class Limiter:
+    """cmhip_lim_t: a look-ahead peak limiter of S streams beside a batch; per stream a threshold (sample units) and a
+    drive (units of 2^-12).  The output is the input delayed by delay() frames and never above the threshold."""
+
+    def __init__(self, streams, channels, lookahead_log2, hold, max_frames, threshold=None, drive=None, device=0,
+                 hip_stream=None):
+        d = LimDesc(device, streams, channels, lookahead_log2, hold, max_frames, hip_stream)
+        self.h = lib.cmhip_lim_new(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_lim_new", ERROR_INVAL)
+        self.streams, self.channels, self.max_frames = streams, channels, max_frames
+        if threshold is not None or drive is not None:
+            self.set(-1, 32767 if threshold is None else threshold, 4096 if drive is None else drive)
+
+    def close(self):
+        if self.h:
+            lib.cmhip_lim_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def delay(self):
+        return lib.cmhip_lim_delay(self.h)
+
+    def set_rc(self, stream, threshold, drive):
+        """cmhip_lim_set as it is -> error number"""
+        return lib.cmhip_lim_set(self.h, stream, threshold, drive)
+
+    def set(self, stream, threshold, drive):
+        """stream -1: every stream.  Ordered with the runs on the limiter's stream."""
+        _check("lim_set", self.set_rc(stream, threshold, drive))
+
+    def get(self, stream):
+        t, d = C.c_uint(), C.c_uint()
+        _check("lim_get", lib.cmhip_lim_get(self.h, stream, C.byref(t), C.byref(d)))
+        return t.value, d.value
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_lim_run as it is -> error number"""
+        fps = None
+        if frames_per_stream is not None:
+            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
+            assert fps.size == self.streams
+        return lib.cmhip_lim_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
+                                 out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers)"""
+        _check("lim_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        _check("lim_reset", lib.cmhip_lim_reset(self.h, stream))
+
+    def min_gain(self, reset=False):
+        """waits for the stream -> the streams' gain-reduction meters, uint32 [S] in Q15"""
+        out = np.zeros(self.streams, dtype=np.uint32)
+        _check("lim_min_gain", lib.cmhip_lim_min_gain(self.h, out.ctypes.data, 1 if reset else 0))
+        return out
+
+    def sync(self):
+        _check("lim_sync", lib.cmhip_lim_sync(self.h))
+
+    def hip_stream(self):
+        return lib.cmhip_lim_hip_stream(self.h) or 0
 
 
 class PinnedPcm:

@@ -1,11 +1,13 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip / k_bus.hip (the gfx950 kernels) and cmhip_batch.hip (the
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip / k_bus.hip / k_lim.hip (the gfx950 kernels) and cmhip_batch.hip (the
 // engine).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+
+#include "lim_plan.h"
 
 namespace cmhip {
 
@@ -237,6 +239,29 @@ struct BusArgs {
     uint32_t       tile_frames;    // frames per tile
 };
 
+// Peak limiter (k_lim.hip; the arithmetic: include/coolmic_hip.h): a limiter's run over S stream slots.
+struct LimArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    const uint32_t *par;           // [S] threshold | drive << 16
+    // [2][S][halo * C] the last halo input frames per stream, interleaved, oldest first.  Two slots: a run reads slot
+    // `parity`, the stream's last tile (or its first, for a stream with 0 frames) writes slot `parity ^ 1`; the host
+    // flips parity (the mechanism of SrcArgs::hist).
+    int16_t       *hist;
+    uint32_t      *gmin;           // [S] the gain-reduction meter: minimum s[n], Q15
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       parity;
+    uint32_t       a, W;           // lookahead_log2, A + hold
+    // (the launcher fills these in)
+    uint32_t       halo;           // LimGeom::halo
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_frames;    // frames per tile
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -333,6 +358,11 @@ struct BusPlan {
 };
 BusPlan plan_bus(const BusArgs &a);
 hipError_t launch_bus(const BusArgs &a, hipStream_t st);
+// Peak limiter (k_lim.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/lim_plan.h's.
+hipError_t launch_lim(const LimArgs &a, hipStream_t st);
+// (threshold and drive into the parameter words of streams first .. first + count - 1; they travel as kernel arguments)
+hipError_t launch_lim_set(uint32_t *par, uint32_t first, uint32_t count, uint32_t threshold, uint32_t drive,
+                          hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

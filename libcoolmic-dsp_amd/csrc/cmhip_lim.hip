@@ -1,0 +1,245 @@
+// cmhip_lim.hip -- the peak limiter on the host side (include/coolmic_hip.h, "peak limiter"): the limiter object beside
+// the batch, its validation, the launch of k_lim.hip's kernels, parameters, reset and the gain-reduction meter.
+//
+// Device state of a limiter: one parameter word per stream (threshold | drive << 16), the streams' history, int16
+// [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
+// cmhip_src.hip's d_hist), and the meter, uint32 [S].  The host keeps a mirror of the parameters; cmhip_lim_get answers
+// from it.  New parameters reach the device inside a kernel's arguments (k_lim_set), so they are ordered with the runs
+// by the stream alone and no staging memory outlives the call.
+#include "cmhip_engine.h"
+
+#include <string.h>
+
+#include <new>
+
+constexpr uint64_t LIM_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
+
+struct cmhip_lim {
+    cmhip_lim_desc_t d;
+    LimGeom g;
+    hipStream_t stream;
+    bool own_stream;
+    uint32_t *d_par;
+    uint32_t *d_nframes;
+    uint32_t *d_gmin;
+    int16_t *d_hist;
+    unsigned parity;
+    std::vector<uint32_t> par;         // the mirror: threshold | drive << 16
+};
+
+static size_t lim_slot(const cmhip_lim_t *m) { return (size_t)m->g.halo * m->d.channels; }     // samples per stream
+
+extern "C" int cmhip_lim_check(unsigned lookahead_log2, unsigned hold, unsigned threshold, unsigned drive)
+{
+    if (!lim_geom(lookahead_log2, hold, nullptr))
+        return fail(COOLMIC_ERROR_INVAL, "lim: lookahead_log2 %u, hold %u: 3..9, and 2^lookahead_log2 + hold <= 2048",
+                    lookahead_log2, hold);
+    if (!lim_params_ok(threshold, drive))
+        return fail(COOLMIC_ERROR_INVAL, "lim: threshold %u, drive %u: 1..32767 and 1..65535", threshold, drive);
+    return COOLMIC_ERROR_NONE;
+}
+
+static int lim_init(cmhip_lim_t *m)
+{
+    const cmhip_lim_desc_t &d = m->d;
+    HIP_TRY(hipSetDevice(d.device));
+    if (d.hip_stream) {
+        m->stream = (hipStream_t)d.hip_stream;
+    } else {
+        HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        m->own_stream = true;
+    }
+    const size_t S = d.streams;
+    HIP_TRY(hipMalloc((void **)&m->d_par, S * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_nframes, S * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * lim_slot(m) * sizeof(int16_t)));
+    HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * lim_slot(m) * sizeof(int16_t), m->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)LIM_UNITY, S, m->stream));
+    m->par.assign(S, LIM_T_MAX | 4096u << 16);       // at creation: no limiting below full scale, unity drive
+    const hipError_t e = launch_lim_set(m->d_par, 0, d.streams, LIM_T_MAX, 4096u, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "lim_new: %s", hipGetErrorString(e));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void cmhip_lim_free(cmhip_lim_t *m)
+{
+    if (!m)
+        return;
+    (void)hipSetDevice(m->d.device);
+    if (m->stream)
+        (void)hipStreamSynchronize(m->stream);
+    (void)hipFree(m->d_par);
+    (void)hipFree(m->d_nframes);
+    (void)hipFree(m->d_gmin);
+    (void)hipFree(m->d_hist);
+    if (m->own_stream)
+        (void)hipStreamDestroy(m->stream);
+    delete m;
+}
+
+extern "C" cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d)
+{
+    if (!d) {
+        fail(COOLMIC_ERROR_FAULT, "lim_new: NULL argument");
+        return nullptr;
+    }
+    LimGeom g;
+    if (d->streams == 0 || d->channels == 0 || d->channels > MAX_CH || d->max_frames == 0 ||
+        !lim_geom(d->lookahead_log2, d->hold, &g)) {
+        fail(COOLMIC_ERROR_INVAL, "lim_new: streams, channels (1..16) and max_frames must be positive, lookahead_log2 "
+             "in 3..9 and 2^lookahead_log2 + hold <= 2048");
+        return nullptr;
+    }
+    if (d->max_frames > LIM_MAX_SAMPLES / d->channels) {
+        fail(COOLMIC_ERROR_INVAL, "lim_new: max_frames %zu: a slot of a run would pass 2^31 samples", d->max_frames);
+        return nullptr;
+    }
+    if ((uint64_t)d->streams * g.halo * d->channels >= (1ull << 31)) {
+        fail(COOLMIC_ERROR_INVAL, "lim_new: %u streams: the history would pass 2^31 samples", d->streams);
+        return nullptr;
+    }
+    cmhip_lim_t *m = new (std::nothrow) cmhip_lim();
+    if (!m) {
+        fail(COOLMIC_ERROR_NOMEM, "lim_new: out of memory");
+        return nullptr;
+    }
+    m->d = *d;
+    m->g = g;
+    if (lim_init(m)) {
+        cmhip_lim_free(m);
+        return nullptr;
+    }
+    return m;
+}
+
+extern "C" unsigned cmhip_lim_delay(const cmhip_lim_t *m) { return m ? m->g.D : 0u; }
+
+extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, unsigned drive)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "lim_set: limiter is NULL");
+    if (stream >= (long)m->d.streams || stream < -1)
+        return fail(COOLMIC_ERROR_INVAL, "lim_set: stream %ld out of range", stream);
+    const int rc = cmhip_lim_check(m->g.a, m->g.H, threshold, drive);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(m->d.device));
+    const uint32_t lo = stream < 0 ? 0u : (uint32_t)stream, n = stream < 0 ? m->d.streams : 1u;
+    const hipError_t e = launch_lim_set(m->d_par, lo, n, threshold, drive, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "lim_set: %s", hipGetErrorString(e));
+    for (size_t s = lo; s < (size_t)lo + n; s++)
+        m->par[s] = threshold | drive << 16;
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_lim_get(const cmhip_lim_t *m, unsigned stream, unsigned *threshold, unsigned *drive)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "lim_get: limiter is NULL");
+    if (stream >= m->d.streams)
+        return fail(COOLMIC_ERROR_INVAL, "lim_get: stream %u out of range", stream);
+    if (threshold)
+        *threshold = m->par[stream] & 0xffffu;
+    if (drive)
+        *drive = m->par[stream] >> 16;
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void *cmhip_lim_hip_stream(cmhip_lim_t *m) { return m ? (void *)m->stream : nullptr; }
+
+extern "C" int cmhip_lim_sync(cmhip_lim_t *m)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "lim_sync: limiter is NULL");
+    HIP_TRY(hipSetDevice(m->d.device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_lim_reset(cmhip_lim_t *m, long stream)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "lim_reset: limiter is NULL");
+    if (stream >= (long)m->d.streams || stream < -1)
+        return fail(COOLMIC_ERROR_INVAL, "lim_reset: stream %ld out of range", stream);
+    HIP_TRY(hipSetDevice(m->d.device));
+    const size_t lo = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? m->d.streams : 1, per = lim_slot(m);
+    // (the slot the next run reads; the other one is rewritten by that run)
+    HIP_TRY(hipMemsetAsync(m->d_hist + ((size_t)m->parity * m->d.streams + lo) * per, 0, n * per * sizeof(int16_t),
+                           m->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->d_gmin + lo), (int)LIM_UNITY, n, m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_lim_min_gain(cmhip_lim_t *m, uint32_t *out, int reset)
+{
+    if (!m || !out)
+        return fail(COOLMIC_ERROR_FAULT, "lim_min_gain: NULL argument");
+    HIP_TRY(hipSetDevice(m->d.device));
+    HIP_TRY(hipMemcpyAsync(out, m->d_gmin, m->d.streams * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (reset)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)LIM_UNITY, m->d.streams, m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, size_t frames,
+                             const uint32_t *frames_per_stream, void *out, size_t out_stride)
+{
+    if (!m || !in || !out)
+        return fail(COOLMIC_ERROR_FAULT, "lim_run: NULL argument");
+    const unsigned S = m->d.streams, C = m->d.channels;
+    if (((uintptr_t)in | (uintptr_t)out) & 15u)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: in and out must be 16-byte aligned");
+    if ((in_stride | out_stride) & 7u)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: strides must be multiples of 8 samples");
+    if (frames > m->d.max_frames)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: %zu frames above max_frames %zu", frames, m->d.max_frames);
+    if (frames_per_stream)
+        for (unsigned s = 0; s < S; s++)
+            if (frames_per_stream[s] > frames)
+                return fail(COOLMIC_ERROR_INVAL, "lim_run: frames_per_stream[%u] above frames", s);
+    if (in_stride < frames * C)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, C);
+    if (out_stride < frames * C)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: out_stride %zu below %zu frames of %u channels", out_stride, frames, C);
+    // the byte ranges [in, in + S * in_stride) and [out, out + S * out_stride) may not share a byte: a tile reads the
+    // frames in front of it again after its neighbour may have written them
+    const uintptr_t ib = (uintptr_t)in, ie = ib + (uintptr_t)S * in_stride * sizeof(int16_t);
+    const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)S * out_stride * sizeof(int16_t);
+    if (ib < oe && ob < ie)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: the input and the output overlap");
+    if (plan_lim(S, C, m->g.a, m->g.H, (uint32_t)frames).err)
+        return fail(COOLMIC_ERROR_INVAL, "lim_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
+                    frames);
+    // nothing was touched so far; from here on the run happens
+    if (frames == 0)
+        return COOLMIC_ERROR_NONE;
+    HIP_TRY(hipSetDevice(m->d.device));
+    LimArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = (const int16_t *)in;
+    a.out = (int16_t *)out;
+    a.nframes = frames_per_stream ? m->d_nframes : nullptr;
+    a.par = m->d_par;
+    a.hist = m->d_hist;
+    a.gmin = m->d_gmin;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.frames = (uint32_t)frames;
+    a.streams = S;
+    a.channels = C;
+    a.parity = m->parity;
+    a.a = m->g.a;
+    a.W = m->g.W;
+    if (frames_per_stream)
+        HIP_TRY(hipMemcpyAsync(m->d_nframes, frames_per_stream, S * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    const hipError_t e = launch_lim(a, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "lim_run: %s", hipGetErrorString(e));
+    m->parity ^= 1u;                         // the kernel wrote the other slots
+    return COOLMIC_ERROR_NONE;
+}

@@ -1,0 +1,95 @@
+// lim_plan.h -- the geometry and the launch plan of the peak limiter (include/coolmic_hip.h, "peak limiter").  Host
+// only, plain C++17, no HIP: tests/cpp/lim_plan_test.cpp compiles it with g++ alone.
+//
+//   a = lookahead_log2 in 3..9, A = 2^a, D = A - 1 (the delay), H = hold, W = A + H <= 2048,
+//   HIST = A + W - 2: the earlier frames an output depends on.
+//   halo = HIST rounded up to 8 frames: what a stream's history slot holds and what a tile evaluates in front of its own
+//   frames -- a multiple of 8 so that a slot is whole 16-byte vectors for every channel count and lines up with the
+//   stream's vectors (frame -1 of a run is the slot's last frame).
+//   A workgroup of 256 threads takes one stream and a tile of tile_frames frames: the largest power of two <= 4096 that
+//   is >= halo (so the frames in front of a tile never reach past the previous tile) and whose per-frame dwords,
+//   (tile_frames + halo) * 4 bytes of dynamic LDS, fit 64 KiB (no per-device limit is raised).
+#ifndef CMHIP_LIM_PLAN_H
+#define CMHIP_LIM_PLAN_H
+
+#include <stdint.h>
+
+namespace cmhip {
+
+constexpr uint32_t LIM_BLOCK = 256;
+constexpr uint32_t LIM_TILE_MAX = 4096;
+constexpr uint32_t LIM_LDS_LIMIT = 64u * 1024u;
+constexpr uint32_t LIM_MAX_CH = 16;
+constexpr uint32_t LIM_A_MIN = 3, LIM_A_MAX = 9;
+constexpr uint32_t LIM_W_MAX = 2048;
+constexpr uint32_t LIM_HALO_MAX = 2560;              // a = 9, W = 2048: HIST = 2558
+constexpr uint32_t LIM_T_MAX = 32767;
+constexpr uint32_t LIM_DRIVE_MAX = 65535;
+constexpr uint32_t LIM_UNITY = 32768;                // Q15
+
+struct LimGeom {
+    uint32_t a, A, D, H, W, hist, halo;
+};
+
+// false: lookahead_log2 or hold out of range (g is not written)
+inline bool lim_geom(uint32_t lookahead_log2, uint32_t hold, LimGeom *g)
+{
+    if (lookahead_log2 < LIM_A_MIN || lookahead_log2 > LIM_A_MAX)
+        return false;
+    const uint32_t A = 1u << lookahead_log2;
+    if (hold > LIM_W_MAX - A)
+        return false;
+    if (g) {
+        g->a = lookahead_log2;
+        g->A = A;
+        g->D = A - 1u;
+        g->H = hold;
+        g->W = A + hold;
+        g->hist = A + g->W - 2u;
+        g->halo = (g->hist + 7u) & ~7u;
+    }
+    return true;
+}
+
+inline bool lim_params_ok(uint32_t threshold, uint32_t drive)
+{
+    return threshold >= 1u && threshold <= LIM_T_MAX && drive >= 1u && drive <= LIM_DRIVE_MAX;
+}
+
+struct LimPlan {
+    int      err;                  // 1: refused, the grid would reach 2^31 workgroups
+    uint32_t fast;                 // the mono / stereo kernel; otherwise the any-channel-count kernel
+    uint32_t grid, block;          // grid 0: nothing to launch (or refused, or bad geometry)
+    uint32_t chunks;               // tiles per stream
+    uint32_t tile_frames;
+    uint32_t lds_bytes;            // dynamic LDS of the launch
+    uint32_t halo;
+};
+
+// the plan of a run whose longest stream has `frames` frames
+inline LimPlan plan_lim(uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold, uint32_t frames)
+{
+    LimPlan p{};
+    LimGeom g;
+    if (streams == 0 || frames == 0 || channels == 0 || channels > LIM_MAX_CH || !lim_geom(lookahead_log2, hold, &g))
+        return p;
+    uint32_t tile = LIM_TILE_MAX;
+    while (tile / 2u >= g.halo && tile / 2u >= 8u && (tile + g.halo) * 4u > LIM_LDS_LIMIT)
+        tile >>= 1;                                   // (never taken today: 4096 + 2560 frames are 26 KiB)
+    const uint64_t tiles = ((uint64_t)frames + tile - 1u) / tile;
+    if (tiles * streams >= (1ull << 31)) {
+        p.err = 1;
+        return p;
+    }
+    p.fast = channels <= 2u ? 1u : 0u;
+    p.block = LIM_BLOCK;
+    p.tile_frames = tile;
+    p.lds_bytes = (tile + g.halo) * 4u;
+    p.halo = g.halo;
+    p.chunks = (uint32_t)tiles;
+    p.grid = streams * p.chunks;
+    return p;
+}
+
+}  // namespace cmhip
+#endif
