@@ -455,6 +455,57 @@ int      cmhip_mix_check(unsigned int channels_in, unsigned int channels_out, co
 int      cmhip_mix_preset(unsigned int preset, unsigned int *channels_in, unsigned int *channels_out, int16_t *W,
                           size_t cap /* entries */);
 
+/* ---- matrix ramps: a mixer's matrix moves without a click ------------------------ */
+/* cmhip_mix_set_matrix is a step between two frames, and a step in a gain is a click.  A ramp takes a stream's matrix
+ * from W0, the matrix in force, to W1 over R frames of that stream, every frame with a matrix of its own, still in
+ * exact integers.  A fader, a fade in or out, a crossfade between two downmixes are ramps.
+ *
+ * Arithmetic.  Frames are counted per stream, by the frames the stream is actually given.  Frame n = 1..R of the ramp
+ *   uses the weights below, frame R + 1 and every later one W1.  R lies in 2..2^20.
+ *       inc   = ceil(2^32 / R)                              uint32 (R >= 2: inc <= 2^31)
+ *       p(n)  = min(32768, (n * inc) >> 17)                 64-bit product; the position in units of 2^-15, p(0) = 0
+ *       N     = w0 * (32768 - p) + w1 * p                   per matrix entry, exact in int32 (|N| <= 2^30)
+ *       w(p)  = N / 32768 truncated TOWARDS ZERO            sgn(N) * (|N| >> 15) -- not an arithmetic shift
+ *       acc   = sum_c w(p(n))[o][c] * x[f][c]               y = saturate_int16((acc + 8192) >> 14), the mixer's own tail
+ * Properties.
+ *   End point: R * inc >= 2^32, so p(R) = 32768 for every R: frame R already uses exactly W1.
+ *   Shape: p is non-decreasing and never behind the ideal line: inc exceeds 2^32 / R by less than 1, so
+ *     0 <= p(n) - floor(32768 * n / R) <= ceil(n / 2^17) -- at most 1 for R <= 2^17 (2.7 s at 48 kHz), at most 8 at 2^20,
+ *     where a ramp whose R is not a power of two arrives up to R / 4096 frames early.
+ *   Start: p = 0 gives N = 32768 * w0, so w = w0.       Constant: W0 = W1 gives N = 32768 * w0 at every p.
+ *   Monotone: N is linear in p and truncation is monotone, so every entry moves monotonically from w0 to w1.
+ *   Row bound: truncation towards zero gives |w(p)| <= |N| / 32768 <= (|w0| (32768 - p) + |w1| p) / 32768.  Summed
+ *     over a row this is the convex combination of the two ends' row sums, so sum_c |w(p)[o][c]| <= 65535 at every
+ *     position, and the mixer's int32 argument holds for every frame of every ramp.  Neither floor nor
+ *     round-to-nearest has this property: either can pass the bound by up to C_in, and 65543 * 32768 overflows.
+ * Retargeting.  A ramp requested while one is running starts from the matrix in force, cur = w(p(done)), where done
+ *   counts the ramp's frames already produced (W0 when done = 0); n restarts at 1.  cur obeys the row bound, so this
+ *   is closed under repetition.
+ * Cancelling.  cmhip_mix_set_matrix during a ramp ends it and steps; its contract is otherwise unchanged.
+ * Zero frames.  A stream given 0 frames in a run keeps its position.
+ * Cuts.  The concatenated output does not depend on how a stream was cut into runs, with ramps and retargets at the
+ *   same frames.
+ * Read-back.  cmhip_mix_get_matrix keeps answering with the last accepted matrix, which for a ramp is its target.
+ *
+ * cmhip_mix_ramp_matrix (stream -1: all streams, each from its own matrix in force) is ordered with the runs by the
+ *   mixer's stream alone, as cmhip_mix_set_matrix: no host wait and no synchronisation, in it or in cmhip_mix_run; W
+ *   may be reused as soon as it returns.  ramp_frames 0 or 1 is exactly cmhip_mix_set_matrix.  COOLMIC_ERROR_INVAL for
+ *   ramp_frames above 2^20, a matrix that fails cmhip_mix_check or a stream out of range, COOLMIC_ERROR_FAULT for NULL;
+ *   a refused call changes nothing, a running ramp included.  The ramps' state is allocated by the first ramp;
+ *   COOLMIC_ERROR_NOMEM then leaves the mixer usable.  A mixer that never ramps runs exactly as before, and so does
+ *   every run at which no stream is inside a ramp.
+ * cmhip_mix_ramp_state answers from the host's mirror (the host sees every run's counts and advances the positions the
+ *   device advances): while the stream ramps 0 <= *done < *ramp_frames and W_now = w(p(done)); otherwise 0, 0 and
+ *   the stream's matrix.  W_now may be NULL; COOLMIC_ERROR_FAULT for the other pointers, COOLMIC_ERROR_INVAL for a
+ *   stream out of range.
+ * cmhip_mix_ramp_position and cmhip_mix_ramp_weight are the specification as code, on the host. */
+int      cmhip_mix_ramp_matrix(cmhip_mix_t *m, long stream, const int16_t *W /* [C_out][C_in] */, uint32_t ramp_frames);
+int      cmhip_mix_ramp_state(const cmhip_mix_t *m, unsigned int stream, uint32_t *done, uint32_t *ramp_frames,
+                              int16_t *W_now /* [C_out][C_in], may be NULL */);
+/* host only, no device needed */
+uint32_t cmhip_mix_ramp_position(uint32_t n, uint32_t ramp_frames);   /* p(n); n > ramp_frames counts as ramp_frames */
+int16_t  cmhip_mix_ramp_weight(int16_t w0, int16_t w1, uint32_t p);   /* p above 32768 counts as 32768 */
+
 /* ---- mix bus, an object of its own beside the batch ------------------------------ */
 /* A bus object sums streams: `streams` input slots of channels_in interleaved int16 channels become `buses` output
  * slots of channels_out, by a routing table of n SENDS.  Send j is (bus_j, stream_j, W_j[channels_out][channels_in]),

@@ -219,6 +219,10 @@ SIGNATURES = {
     "cmhip_mix_hip_stream": (_vp, [_vp]),
     "cmhip_mix_check": (C.c_int, [C.c_uint, C.c_uint, _vp]),
     "cmhip_mix_preset": (C.c_int, [C.c_uint, _P(C.c_uint), _P(C.c_uint), _vp, C.c_size_t]),
+    "cmhip_mix_ramp_matrix": (C.c_int, [_vp, C.c_long, _vp, C.c_uint32]),
+    "cmhip_mix_ramp_state": (C.c_int, [_vp, C.c_uint, _P(C.c_uint32), _P(C.c_uint32), _vp]),
+    "cmhip_mix_ramp_position": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "cmhip_mix_ramp_weight": (C.c_int16, [C.c_int16, C.c_int16, C.c_uint32]),
     "cmhip_bus_new": (_vp, [_P(BusDesc)]),
     "cmhip_bus_free": (None, [_vp]),
     "cmhip_bus_set_routing": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp]),
@@ -553,6 +557,16 @@ def mix_check(channels_in, channels_out, W):
         return lib.cmhip_mix_check(channels_in, channels_out, None)
     w = np.ascontiguousarray(W, dtype=np.int16)
     return lib.cmhip_mix_check(channels_in, channels_out, w.ctypes.data)
+
+
+def mix_ramp_position(n, ramp_frames):
+    """cmhip_mix_ramp_position: p(n) of a ramp of ramp_frames frames, in units of 2^-15"""
+    return lib.cmhip_mix_ramp_position(n, ramp_frames)
+
+
+def mix_ramp_weight(w0, w1, p):
+    """cmhip_mix_ramp_weight: the entry between w0 and w1 at position p"""
+    return lib.cmhip_mix_ramp_weight(w0, w1, p)
 
 
 class BusPlan(C.Structure):
@@ -1048,6 +1062,24 @@ class Mixer:
         w = np.zeros((self.channels_out, self.channels_in), dtype=np.int16)
         _check("mix_get_matrix", lib.cmhip_mix_get_matrix(self.h, stream, w.ctypes.data))
         return w
+
+    def ramp_matrix_rc(self, stream, W, ramp_frames):
+        """cmhip_mix_ramp_matrix as it is -> error number"""
+        w = np.ascontiguousarray(W, dtype=np.int16)
+        assert w.size == self.channels_out * self.channels_in
+        return lib.cmhip_mix_ramp_matrix(self.h, stream, w.ctypes.data, ramp_frames)
+
+    def ramp_matrix(self, stream, W, ramp_frames):
+        """a click-free move to W over ramp_frames of the stream's frames (stream -1: every stream, each from its own
+        matrix in force).  Ordered with the runs on the mixer's stream."""
+        _check("mix_ramp_matrix", self.ramp_matrix_rc(stream, W, ramp_frames))
+
+    def ramp_state(self, stream):
+        """-> (done, ramp_frames, the matrix in force int16 [C_out][C_in]); (0, 0, the matrix) when nothing ramps"""
+        done, total = C.c_uint32(0), C.c_uint32(0)
+        w = np.zeros((self.channels_out, self.channels_in), dtype=np.int16)
+        _check("mix_ramp_state", lib.cmhip_mix_ramp_state(self.h, stream, C.byref(done), C.byref(total), w.ctypes.data))
+        return done.value, total.value, w
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """cmhip_mix_run as it is -> error number"""

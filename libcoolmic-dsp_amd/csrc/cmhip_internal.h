@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip / k_bus.hip / k_lim.hip (the gfx950 kernels) and cmhip_batch.hip (the
+// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip / k_mixramp.hip / k_bus.hip / k_lim.hip (the gfx950 kernels) and cmhip_batch.hip (the
 // engine).
 #pragma once
 
@@ -219,6 +219,17 @@ struct MixArgs {
     uint32_t       tile_frames;    // frames per tile
 };
 
+// Matrix ramps (k_mixramp.hip; the arithmetic: include/coolmic_hip.h, csrc/mix_ramp.h): a mixer's run while at least
+// one stream ramps.  Per stream a record of MIXR_HDR + 2 n dwords, n = C_out * CP:
+//     inc, R, done, 0,  W0[n], W1[n]       (the matrices in the kernel's form, MixArgs::wk)
+// The stream ramps while done < R; frame f of the run uses w(p(done + f + 1)).  MixArgs::wk holds the targets.
+constexpr uint32_t MIXR_HDR = 4;
+constexpr uint32_t MIXR_INC = 0, MIXR_R = 1, MIXR_DONE = 2;
+struct MixRampArgs {
+    MixArgs         m;
+    const uint32_t *ramp;          // [S][MIXR_HDR + 2 n]
+};
+
 // Mix bus (k_bus.hip; the arithmetic: include/coolmic_hip.h): a run that sums S input slots into B bus slots by the
 // routing table csrc/bus_route.h compiled.
 struct BusArgs {
@@ -346,6 +357,20 @@ hipError_t launch_mix(const MixArgs &a, hipStream_t st);
 // matrix travels as a kernel argument, so W may change as soon as the call returns)
 hipError_t launch_mix_set(uint32_t *wk, uint32_t first, uint32_t count, uint32_t channels_in, uint32_t channels_out,
                           const int16_t *W, hipStream_t st);
+// Matrix ramps (k_mixramp.hip).  launch_mixramp: a run with plan_mix's own grid and tile (lds_bytes: the dynamic LDS
+// of the any-channel-count ramp kernel, two matrices beside the target); the caller launches it only while a stream
+// ramps.  The small kernels, all in stream order: start (or retarget) a ramp of R >= 2 frames to W for streams first
+// .. first + count - 1, each from its own matrix in force; advance every stream's position by its count of the run
+// (nframes nullptr: by frames); cancel the ramps of a range of streams.
+uint32_t mixramp_record_dwords(uint32_t channels_in, uint32_t channels_out);
+uint32_t mixramp_lds_bytes(uint32_t channels_in, uint32_t channels_out, uint32_t tile_frames);
+hipError_t launch_mixramp(const MixRampArgs &a, hipStream_t st);
+hipError_t launch_mixramp_start(uint32_t *ramp, uint32_t *wk, uint32_t first, uint32_t count, uint32_t channels_in,
+                                uint32_t channels_out, const int16_t *W, uint32_t R, hipStream_t st);
+hipError_t launch_mixramp_advance(uint32_t *ramp, const uint32_t *nframes, uint32_t frames, uint32_t streams,
+                                  uint32_t channels_in, uint32_t channels_out, hipStream_t st);
+hipError_t launch_mixramp_cancel(uint32_t *ramp, uint32_t first, uint32_t count, uint32_t channels_in,
+                                 uint32_t channels_out, hipStream_t st);
 // Mix bus (k_bus.hip): one workgroup per bus and tile of tile_frames frames.  fast: the kernel for mono / stereo on
 // both sides (one wave per workgroup, no LDS); otherwise the any-channel-count kernel (256 threads).
 struct BusPlan {

@@ -5,7 +5,13 @@
 // all: there is no history.  The host keeps a mirror of every matrix as the caller gave it (int16 [S][C_out][C_in]);
 // cmhip_mix_get_matrix answers from it.  A new matrix reaches the device inside a kernel's arguments (k_mix_set), so
 // it is ordered with the runs by the stream alone and no staging memory outlives the call.
+//
+// Matrix ramps (include/coolmic_hip.h, "matrix ramps"): the first cmhip_mix_ramp_matrix allocates a record per stream
+// on the device (MixRampArgs::ramp) and the host's mirror of it (csrc/mix_ramp.h).  The host sees every run's counts,
+// so the mirror advances as the device does and knows whether any stream ramps: only then does cmhip_mix_run launch
+// k_mixramp.hip's kernels, and a mixer that never ramps launches what it always did.
 #include "cmhip_engine.h"
+#include "mix_ramp.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -21,6 +27,8 @@ struct cmhip_mix {
     uint32_t *d_wk;
     uint32_t *d_nframes;
     std::vector<int16_t> w;            // the mirror: [S][C_out][C_in]
+    uint32_t *d_ramp;                  // the streams' ramp records, allocated by the first ramp
+    MixRampMirror *ramp;               // ... and their mirror
 };
 
 static bool mix_channels_ok(unsigned ci, unsigned co) { return ci >= 1 && ci <= MAX_CH && co >= 1 && co <= MAX_CH; }
@@ -108,6 +116,8 @@ extern "C" void cmhip_mix_free(cmhip_mix_t *m)
         (void)hipStreamSynchronize(m->stream);
     (void)hipFree(m->d_wk);
     (void)hipFree(m->d_nframes);
+    (void)hipFree(m->d_ramp);
+    delete m->ramp;
     if (m->own_stream)
         (void)hipStreamDestroy(m->stream);
     delete m;
@@ -160,10 +170,104 @@ extern "C" int cmhip_mix_set_matrix(cmhip_mix_t *m, long stream, const int16_t *
     const hipError_t e = launch_mix_set(m->d_wk, lo, n, CI, CO, W, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "mix_set_matrix: %s", hipGetErrorString(e));
+    if (m->ramp) {                     // a step ends whatever ramp runs
+        const hipError_t ec = launch_mixramp_cancel(m->d_ramp, lo, n, CI, CO, m->stream);
+        if (ec != hipSuccess)
+            return fail(COOLMIC_ERROR_GENERIC, "mix_set_matrix: %s", hipGetErrorString(ec));
+        for (size_t s = lo; s < (size_t)lo + n; s++)
+            m->ramp->cancel(s, W);
+    }
     for (size_t s = lo; s < (size_t)lo + n; s++)
         memcpy(&m->w[s * CO * CI], W, (size_t)CO * CI * sizeof(int16_t));
     return COOLMIC_ERROR_NONE;
 }
+
+// the ramp records and their mirror, on first use: every stream at rest (R = 0) on its matrix
+static int mix_ramp_alloc(cmhip_mix_t *m)
+{
+    const size_t S = m->d.streams, n = (size_t)m->d.channels_out * m->d.channels_in;
+    const size_t bytes = S * mixramp_record_dwords(m->d.channels_in, m->d.channels_out) * sizeof(uint32_t);
+    MixRampMirror *mirror = new (std::nothrow) MixRampMirror();
+    if (!mirror)
+        return fail(COOLMIC_ERROR_NOMEM, "mix_ramp_matrix: out of memory");
+    try {
+        mirror->init(S, n, m->w.data());
+    } catch (const std::bad_alloc &) {
+        delete mirror;
+        return fail(COOLMIC_ERROR_NOMEM, "mix_ramp_matrix: out of memory");
+    }
+    uint32_t *d = nullptr;
+    if (hipMalloc((void **)&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        delete mirror;
+        return fail(COOLMIC_ERROR_NOMEM, "mix_ramp_matrix: no device memory for %zu bytes of ramp state", bytes);
+    }
+    const hipError_t e = hipMemsetAsync(d, 0, bytes, m->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        delete mirror;
+        return fail(COOLMIC_ERROR_GENERIC, "mix_ramp_matrix: %s", hipGetErrorString(e));
+    }
+    m->d_ramp = d;
+    m->ramp = mirror;
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_mix_ramp_matrix(cmhip_mix_t *m, long stream, const int16_t *W, uint32_t ramp_frames)
+{
+    if (!m || !W)
+        return fail(COOLMIC_ERROR_FAULT, "mix_ramp_matrix: NULL argument");
+    if (stream >= (long)m->d.streams || stream < -1)
+        return fail(COOLMIC_ERROR_INVAL, "mix_ramp_matrix: stream %ld out of range", stream);
+    if (ramp_frames > MIX_RAMP_MAX)
+        return fail(COOLMIC_ERROR_INVAL, "mix_ramp_matrix: %u frames above %u", ramp_frames, MIX_RAMP_MAX);
+    if (ramp_frames < 2)
+        return cmhip_mix_set_matrix(m, stream, W);
+    const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
+    const int rc = cmhip_mix_check(CI, CO, W);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(m->d.device));
+    if (!m->ramp) {
+        const int ra = mix_ramp_alloc(m);
+        if (ra)
+            return ra;
+    }
+    const uint32_t lo = stream < 0 ? 0u : (uint32_t)stream, n = stream < 0 ? m->d.streams : 1u;
+    const hipError_t e = launch_mixramp_start(m->d_ramp, m->d_wk, lo, n, CI, CO, W, ramp_frames, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "mix_ramp_matrix: %s", hipGetErrorString(e));
+    for (size_t s = lo; s < (size_t)lo + n; s++) {
+        m->ramp->start(s, W, ramp_frames);
+        memcpy(&m->w[s * CO * CI], W, (size_t)CO * CI * sizeof(int16_t));
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_mix_ramp_state(const cmhip_mix_t *m, unsigned stream, uint32_t *done, uint32_t *ramp_frames,
+                                    int16_t *W_now)
+{
+    if (!m || !done || !ramp_frames)
+        return fail(COOLMIC_ERROR_FAULT, "mix_ramp_state: NULL argument");
+    if (stream >= m->d.streams)
+        return fail(COOLMIC_ERROR_INVAL, "mix_ramp_state: stream %u out of range", stream);
+    const size_t n = (size_t)m->d.channels_out * m->d.channels_in;
+    if (m->ramp && m->ramp->ramping(stream)) {
+        *done = m->ramp->done[stream];
+        *ramp_frames = m->ramp->R[stream];
+        if (W_now)
+            m->ramp->now(stream, W_now);
+    } else {
+        *done = *ramp_frames = 0;
+        if (W_now)
+            memcpy(W_now, &m->w[stream * n], n * sizeof(int16_t));
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" uint32_t cmhip_mix_ramp_position(uint32_t n, uint32_t ramp_frames) { return mix_ramp_position(n, ramp_frames); }
+
+extern "C" int16_t cmhip_mix_ramp_weight(int16_t w0, int16_t w1, uint32_t p) { return mix_ramp_weight(w0, w1, p); }
 
 extern "C" int cmhip_mix_get_matrix(const cmhip_mix_t *m, unsigned stream, int16_t *W)
 {
@@ -235,8 +339,22 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
                     frames);
     if (frames_per_stream)
         HIP_TRY(hipMemcpyAsync(m->d_nframes, frames_per_stream, S * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-    const hipError_t e = launch_mix(a, m->stream);
+    if (!m->ramp || !m->ramp->any()) {               // nobody ramps: the plain kernels, as ever
+        const hipError_t e = launch_mix(a, m->stream);
+        if (e != hipSuccess)
+            return fail(COOLMIC_ERROR_GENERIC, "mix_run: %s", hipGetErrorString(e));
+        return COOLMIC_ERROR_NONE;
+    }
+    // somebody ramps: the ramp kernels, then every stream's position moves on by its count, there and here
+    MixRampArgs ra;
+    ra.m = a;
+    ra.ramp = m->d_ramp;
+    hipError_t e = launch_mixramp(ra, m->stream);
+    if (e == hipSuccess)
+        e = launch_mixramp_advance(m->d_ramp, a.nframes, a.frames, S, CI, CO, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "mix_run: %s", hipGetErrorString(e));
+    for (unsigned s = 0; s < S; s++)
+        m->ramp->advance(s, frames_per_stream ? frames_per_stream[s] : (uint32_t)frames);
     return COOLMIC_ERROR_NONE;
 }

@@ -11,31 +11,9 @@
 // W[o][2k] | W[o][2k+1] << 16 (an odd C_in padded with a zero weight) -- the order v_dot2_i32_i16 meets the two
 // channels of an input dword in.  The accumulator starts at 8192, so rounding costs no instruction; then one shift,
 // and v_cvt_pk_i16_i32 clamps and packs two results.  No state: nothing is carried between runs.
-#include "cmhip_device.h"
+#include "k_mix.h"
 
 namespace cmhip {
-
-constexpr u32 MIX_BLOCK = 256;
-constexpr u32 MIX_LDS_LIMIT = 64u * 1024u;       // what a workgroup may take without raising the device's limit
-constexpr u32 MIX_TILE_MAX = 1024;               // frames of a k_mix_any tile at most: four per thread
-
-__host__ __device__ constexpr u32 mix_cp(u32 ci) { return (ci + 1u) / 2u; }
-// LDS of k_mix_any: the matrix (rounded up to whole 16-byte vectors), CP planes of tile dwords, the output tile
-__host__ __device__ constexpr u32 mix_wk_lds(u32 ci, u32 co) { return (co * mix_cp(ci) + 3u) & ~3u; }
-__host__ __device__ constexpr u32 mix_lds_bytes(u32 ci, u32 co, u32 tile)
-{
-    return 4u * mix_wk_lds(ci, co) + 4u * mix_cp(ci) * tile + 2u * co * tile;
-}
-
-__device__ __forceinline__ int mix_dot2(u32 x, u32 k, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, x), __builtin_bit_cast(v2s, k), acc, false);
-}
-// two accumulators (rounding included) -> one dword of output: shift, then clamp and pack
-__device__ __forceinline__ u32 mix_pack(int a0, int a1)
-{
-    return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(a0 >> 14, a1 >> 14));
-}
 
 // ---------------------------------------------------------------------------
 // Form 1: mono / stereo on both sides.  A lane works in UNITS of UF frames, the fewest that are whole 16-byte vectors
@@ -43,13 +21,6 @@ __device__ __forceinline__ u32 mix_pack(int a0, int a1)
 //     1 -> 1   UF 8, 1 in, 1 out, NU 4: a tile of 2048 frames      2 -> 1   UF 8, 2 in, 1 out, NU 2: 1024 frames
 //     2 -> 2   UF 4, 1 in, 1 out, NU 4: 1024 frames                1 -> 2   UF 8, 1 in, 2 out, NU 2: 1024 frames
 // Unit j of a lane is unit n0 + 64 j + lane of the stream, so a wave's instruction covers 64 consecutive units.
-template <int CI, int CO>
-struct MixFast {
-    static constexpr u32 UF = 8u / (u32)(CI < CO ? CI : CO);
-    static constexpr u32 VI = UF * (u32)CI / 8u, VO = UF * (u32)CO / 8u;
-    static constexpr u32 NU = 4u / (VI > VO ? VI : VO);
-    static constexpr u32 TILE_FRAMES = 64u * NU * UF;
-};
 
 // Every output sample is ONE dot instruction on an input dword.  Stereo in: the dword is a frame, the weight dword
 // the row.  Mono in: the dword holds two frames, and the row's weight sits in the half of the frame it belongs to
