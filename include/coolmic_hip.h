@@ -156,7 +156,11 @@ int cmhip_batch_generate(cmhip_batch_t *b, int mode, uint32_t seed, size_t frame
 
 /* ---- the hot path --------------------------------------------------------- */
 /* process `frames` frames of every stream (frames_per_stream, if not NULL, gives each
- * stream its own count <= frames; host array of S entries).  Asynchronous. */
+ * stream its own count <= frames; host array of S entries, pageable or pinned, free on return:
+ * the batch copies it into a small ring of pinned blocks it owns, so a host loop may refill ONE
+ * array for the next run at once.  The fifth of five runs with frames_per_stream queued back to
+ * back may wait ON THE HOST until the first one's counts have been copied on the stream).
+ * Asynchronous.  cmhip_batch_run_slots takes its counts the same way. */
 int cmhip_batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per_stream);
 /* the same pass over PCM arrays named for this run: device-accessible memory laid out like the
  * batch's own, int16 [S][cmhip_batch_stride()] (slots_out NULL exactly when the batch writes no
@@ -342,8 +346,11 @@ int    cmhip_loud_integrate(const double *z, size_t n, double *integrated, doubl
  *
  * cmhip_src_run: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in samples as in a batch, both
  *   device-accessible; asynchronous on the resampler's stream.  `frames` input frames per stream, or
- *   frames_per_stream[s] <= frames (host array of S entries, may be NULL).  COOLMIC_ERROR_INVAL, with nothing launched
- *   and nothing changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or smaller than
+ *   frames_per_stream[s] <= frames (host array of S entries, may be NULL; free on return: the resampler copies it
+ *   into a small ring of pinned blocks it owns, and the fifth of five cmhip_src_run with frames_per_stream queued back
+ *   to back may wait ON THE HOST until the first one's counts have been copied on the stream).  COOLMIC_ERROR_INVAL,
+ *   with nothing launched and nothing changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples
+ *   or smaller than
  *   the run needs (frames * C in; the run's largest output count * C out -- cmhip_src_max_out_frames() * C always
  *   suffices), frames > max_in_frames, a per-stream count is above frames, or in == out; COOLMIC_ERROR_FAULT for NULL
  *   arrays.  out_frames[] (host, S entries, may be NULL) receives every stream's output count, computed on the host
@@ -401,7 +408,10 @@ uint32_t cmhip_src_out_frames(unsigned int L, unsigned int M, uint32_t r, uint32
  *
  * cmhip_mix_run: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in samples as in a batch, both
  *   device-accessible; asynchronous on the mixer's stream.  `frames` frames per stream, or frames_per_stream[s] <=
- *   frames (host array of S entries, may be NULL).  COOLMIC_ERROR_INVAL, with nothing launched and nothing changed,
+ *   frames (host array of S entries, may be NULL; free on return: the mixer copies it into a small ring of pinned
+ *   blocks it owns, and the fifth of five cmhip_mix_run with frames_per_stream queued back to back may wait ON THE HOST
+ *   until the first one's counts have been copied on the stream).  COOLMIC_ERROR_INVAL, with nothing launched and
+ *   nothing changed,
  *   when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or smaller than frames * C_in (in) or
  *   frames * C_out (out), frames > max_frames, a per-stream count is above frames, the run's grid would reach 2^31
  *   workgroups, or the byte ranges of the input ([in, in + S * in_stride samples)) and of the output overlap at all
@@ -619,7 +629,8 @@ int      cmhip_bus_mix_minus(unsigned int n, int16_t w, uint32_t *bus, uint32_t 
  *
  * cmhip_lim_run has cmhip_mix_run's contract with C_in = C_out = channels: `in` is int16 [S][in_stride], `out` int16
  *   [S][out_stride], strides in samples, both device-accessible; asynchronous on the limiter's stream.  `frames` frames
- *   per stream, or frames_per_stream[s] <= frames (host array of S entries, may be NULL).  COOLMIC_ERROR_INVAL, with
+ *   per stream, or frames_per_stream[s] <= frames (host array of S entries, may be NULL; free on return, with
+ *   cmhip_mix_run's possible wait on the host for the fifth run queued back to back).  COOLMIC_ERROR_INVAL, with
  *   nothing launched and nothing changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or
  *   smaller than frames * channels, frames > max_frames, a per-stream count is above frames, the run's grid would reach
  *   2^31 workgroups, or the byte ranges [in, in + S * in_stride samples) and [out, out + S * out_stride samples)

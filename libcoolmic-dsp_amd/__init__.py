@@ -809,8 +809,10 @@ class Batch:
         """one pass over PCM arrays named for this run (device pointers; MappedPcm.dev)"""
         fps = None
         if frames_per_stream is not None:
-            fps = (C.c_uint32 * self.streams)(*frames_per_stream)
-        _check("run_slots", lib.cmhip_batch_run_slots(self.h, frames, fps, slots_in, slots_out))
+            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
+            assert fps.size == self.streams
+        _check("run_slots", lib.cmhip_batch_run_slots(self.h, frames, fps.ctypes.data if fps is not None else None,
+                                                      slots_in, slots_out))
 
     def hip_stream(self):
         """the hipStream_t (as an integer) this batch launches on"""

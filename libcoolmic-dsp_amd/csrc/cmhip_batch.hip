@@ -207,6 +207,7 @@ extern "C" void cmhip_batch_free(cmhip_batch_t *b)
         (void)hipStreamDestroy(b->copy_stream);
     }
     (void)hipFree(b->d_nframes);
+    b->counts.destroy();
     (void)hipFree(b->d_eq);
     (void)hipFree(b->d_eqstate);
     (void)hipFree(b->d_sink);
@@ -305,6 +306,7 @@ static int batch_init(cmhip_batch_t *b)
     for (int i = 0; i < 4; i++)
         HIP_TRY(hipEventCreate(&b->ev_done[i]));
     HIP_TRY(hipMalloc((void **)&b->d_nframes, S * sizeof(uint32_t)));
+    HIP_TRY(b->counts.init(S));
     HIP_TRY(hipMalloc((void **)&b->d_sink, sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(b->d_sink, 0, sizeof(unsigned long long), b->stream));
     if (d.flags & CMHIP_EQ) {
@@ -886,8 +888,7 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
         for (unsigned s = 0; s < b->d.streams; s++)
             if (frames_per_stream[s] > frames)
                 return fail(COOLMIC_ERROR_INVAL, "run: frames_per_stream[%u] above frames", s);
-        HIP_TRY(hipMemcpyAsync(b->d_nframes, frames_per_stream, b->d.streams * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(b->counts.upload(b->d_nframes, frames_per_stream, b->d.streams, b->stream));
     }
     if (cmhip_engine_flush_params(b) || cmhip_engine_settle_node(b))
         return COOLMIC_ERROR_GENERIC;

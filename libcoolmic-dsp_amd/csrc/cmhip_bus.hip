@@ -10,7 +10,7 @@
 // Both travel by hipMemcpyAsync on the object's stream from PINNED memory the object owns, so they are ordered with the
 // runs by the stream alone and nothing the caller owns is read after a call returns: the table from one staging area
 // with an event (a second set waits on the host until the first one's copy has executed), a run's counts from a small
-// ring of slots with an event each (run RING + 1 waits for run 1's copy).
+// ring of blocks with an event each (CountsRing, csrc/cmhip_internal.h: run COUNTS_RING + 1 waits for run 1's copy).
 #include "cmhip_engine.h"
 
 #include <stdlib.h>
@@ -21,7 +21,6 @@
 #include "bus_route.h"
 
 constexpr uint64_t BUS_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
-constexpr unsigned BUS_RING = 4;                     // runs whose counts may be on their way at once
 
 struct cmhip_bus {
     cmhip_bus_desc_t d;
@@ -32,10 +31,7 @@ struct cmhip_bus {
     uint32_t *h_table;                 // pinned, the same layout
     hipEvent_t table_ev;
     bool table_busy;                   // a copy from h_table was queued and not yet waited for
-    uint32_t *h_counts;                // pinned [BUS_RING][S + B]
-    hipEvent_t counts_ev[BUS_RING];
-    bool counts_busy[BUS_RING];
-    unsigned ring;
+    CountsRing counts;                 // a run's [S + B] on their way to d_counts
     bool nt_loads;
     std::vector<uint32_t> bus, strm;   // the mirror, in the caller's order
     std::vector<int16_t> w;
@@ -127,10 +123,8 @@ static int bus_init(cmhip_bus_t *m)
     HIP_TRY(hipMalloc((void **)&m->d_table, words * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&m->d_counts, (S + B) * sizeof(uint32_t)));
     HIP_TRY(hipHostMalloc((void **)&m->h_table, words * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&m->h_counts, BUS_RING * (S + B) * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(m->counts.init(S + B));
     HIP_TRY(hipEventCreateWithFlags(&m->table_ev, hipEventDisableTiming));
-    for (unsigned i = 0; i < BUS_RING; i++)
-        HIP_TRY(hipEventCreateWithFlags(&m->counts_ev[i], hipEventDisableTiming));
     // routing at creation: empty
     bus_route_compile(d.buses, d.channels_in, d.channels_out, 0, nullptr, nullptr, nullptr, m->t);
     HIP_TRY(hipMemsetAsync(m->d_table, 0, (B + 1) * sizeof(uint32_t), m->stream));
@@ -147,12 +141,9 @@ extern "C" void cmhip_bus_free(cmhip_bus_t *m)
     (void)hipFree(m->d_table);
     (void)hipFree(m->d_counts);
     (void)hipHostFree(m->h_table);
-    (void)hipHostFree(m->h_counts);
+    m->counts.destroy();
     if (m->table_ev)
         (void)hipEventDestroy(m->table_ev);
-    for (unsigned i = 0; i < BUS_RING; i++)
-        if (m->counts_ev[i])
-            (void)hipEventDestroy(m->counts_ev[i]);
     if (m->own_stream)
         (void)hipStreamDestroy(m->stream);
     delete m;
@@ -322,19 +313,12 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
         return COOLMIC_ERROR_NONE;
     HIP_TRY(hipSetDevice(m->d.device));
     if (frames_per_stream) {
-        const unsigned r = m->ring;
-        if (m->counts_busy[r]) {                     // BUS_RING runs back: its counts have long been copied
-            HIP_TRY(hipEventSynchronize(m->counts_ev[r]));
-            m->counts_busy[r] = false;
-        }
-        uint32_t *h = m->h_counts + (size_t)r * (S + B);
+        uint32_t *h;
+        HIP_TRY(m->counts.take(&h));
         memcpy(h, frames_per_stream, S * sizeof(uint32_t));
         for (unsigned b = 0; b < B; b++)
             h[S + b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
-        HIP_TRY(hipMemcpyAsync(m->d_counts, h, ((size_t)S + B) * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-        m->counts_busy[r] = true;
-        HIP_TRY(hipEventRecord(m->counts_ev[r], m->stream));
-        m->ring = (r + 1) % BUS_RING;
+        HIP_TRY(m->counts.send(m->d_counts, (size_t)S + B, m->stream));
     }
     const hipError_t e = launch_bus(a, m->stream);
     if (e != hipSuccess)

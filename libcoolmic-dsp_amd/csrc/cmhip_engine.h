@@ -75,6 +75,7 @@ struct cmhip_batch {
     bool reset_pending[3];
     struct WorkPool *pool;
     uint32_t *d_nframes;
+    CountsRing counts;                 // a run's counts on their way to d_nframes
     EqParam *d_eq;
     EqState *d_eqstate;
     unsigned long long *d_sink;

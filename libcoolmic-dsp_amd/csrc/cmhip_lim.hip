@@ -21,6 +21,7 @@ struct cmhip_lim {
     bool own_stream;
     uint32_t *d_par;
     uint32_t *d_nframes;
+    CountsRing counts;                 // a run's counts on their way to d_nframes
     uint32_t *d_gmin;
     int16_t *d_hist;
     unsigned parity;
@@ -52,6 +53,7 @@ static int lim_init(cmhip_lim_t *m)
     const size_t S = d.streams;
     HIP_TRY(hipMalloc((void **)&m->d_par, S * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&m->d_nframes, S * sizeof(uint32_t)));
+    HIP_TRY(m->counts.init(S));
     HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * lim_slot(m) * sizeof(int16_t)));
     HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * lim_slot(m) * sizeof(int16_t), m->stream));
@@ -72,6 +74,7 @@ extern "C" void cmhip_lim_free(cmhip_lim_t *m)
         (void)hipStreamSynchronize(m->stream);
     (void)hipFree(m->d_par);
     (void)hipFree(m->d_nframes);
+    m->counts.destroy();
     (void)hipFree(m->d_gmin);
     (void)hipFree(m->d_hist);
     if (m->own_stream)
@@ -236,7 +239,7 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     a.a = m->g.a;
     a.W = m->g.W;
     if (frames_per_stream)
-        HIP_TRY(hipMemcpyAsync(m->d_nframes, frames_per_stream, S * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(m->counts.upload(m->d_nframes, frames_per_stream, S, m->stream));
     const hipError_t e = launch_lim(a, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "lim_run: %s", hipGetErrorString(e));

@@ -26,6 +26,7 @@ struct cmhip_mix {
     bool own_stream;
     uint32_t *d_wk;
     uint32_t *d_nframes;
+    CountsRing counts;                 // a run's counts on their way to d_nframes
     std::vector<int16_t> w;            // the mirror: [S][C_out][C_in]
     uint32_t *d_ramp;                  // the streams' ramp records, allocated by the first ramp
     MixRampMirror *ramp;               // ... and their mirror
@@ -94,6 +95,7 @@ static int mix_init(cmhip_mix_t *m)
     const size_t S = d.streams, CI = d.channels_in, CO = d.channels_out, n = CO * ((CI + 1) / 2);
     HIP_TRY(hipMalloc((void **)&m->d_wk, S * n * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&m->d_nframes, S * sizeof(uint32_t)));
+    HIP_TRY(m->counts.init(S));
     // the matrix at creation: the leading channels kept, silence in extra outputs
     std::vector<int16_t> w0(CO * CI, 0);
     for (size_t o = 0; o < (CI < CO ? CI : CO); o++)
@@ -116,6 +118,7 @@ extern "C" void cmhip_mix_free(cmhip_mix_t *m)
         (void)hipStreamSynchronize(m->stream);
     (void)hipFree(m->d_wk);
     (void)hipFree(m->d_nframes);
+    m->counts.destroy();
     (void)hipFree(m->d_ramp);
     delete m->ramp;
     if (m->own_stream)
@@ -338,7 +341,7 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
         return fail(COOLMIC_ERROR_INVAL, "mix_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
     if (frames_per_stream)
-        HIP_TRY(hipMemcpyAsync(m->d_nframes, frames_per_stream, S * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(m->counts.upload(m->d_nframes, frames_per_stream, S, m->stream));
     if (!m->ramp || !m->ramp->any()) {               // nobody ramps: the plain kernels, as ever
         const hipError_t e = launch_mix(a, m->stream);
         if (e != hipSuccess)

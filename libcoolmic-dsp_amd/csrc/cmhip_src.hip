@@ -28,6 +28,7 @@ struct cmhip_src {
     int16_t *d_hist;
     uint32_t *d_rpos;
     uint32_t *d_nframes;
+    CountsRing counts;                 // a run's counts on their way to d_nframes
     unsigned parity;
     std::vector<uint32_t> r;           // the mirror of the device's current r per stream
 };
@@ -165,6 +166,7 @@ static int src_init(cmhip_src_t *r, const int16_t *h)
     HIP_TRY(hipMalloc((void **)&r->d_hist, 2 * src_hist_words(r) * sizeof(int16_t)));
     HIP_TRY(hipMalloc((void **)&r->d_rpos, 2 * S * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&r->d_nframes, S * sizeof(uint32_t)));
+    HIP_TRY(r->counts.init(S));
     HIP_TRY(hipMemcpy(r->d_table, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(r->d_hist, 0, 2 * src_hist_words(r) * sizeof(int16_t), r->stream));
     HIP_TRY(hipMemsetAsync(r->d_rpos, 0, 2 * S * sizeof(uint32_t), r->stream));
@@ -183,6 +185,7 @@ extern "C" void cmhip_src_free(cmhip_src_t *r)
     (void)hipFree(r->d_hist);
     (void)hipFree(r->d_rpos);
     (void)hipFree(r->d_nframes);
+    r->counts.destroy();
     if (r->own_stream)
         (void)hipStreamDestroy(r->stream);
     delete r;
@@ -297,8 +300,7 @@ extern "C" int cmhip_src_run(cmhip_src_t *r, const void *in, size_t in_stride, s
     HIP_TRY(hipSetDevice(r->d.device));
     if (frames > 0) {
         if (frames_per_stream)
-            HIP_TRY(hipMemcpyAsync(r->d_nframes, frames_per_stream, S * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                   r->stream));
+            HIP_TRY(r->counts.upload(r->d_nframes, frames_per_stream, S, r->stream));
         SrcArgs a;
         memset(&a, 0, sizeof(a));
         a.in = (const int16_t *)in;
