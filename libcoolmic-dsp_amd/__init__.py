@@ -963,9 +963,43 @@ class Batch:
         return lib.cmhip_batch_dev_out(self.h)
 
 
-class Resampler:
+class _Stage:
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Limiter): the end of the handle `h`, its
+    stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
+
+    _stem = None
+
+    def close(self):
+        if self.h:
+            getattr(lib, "cmhip_%s_free" % self._stem)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sync(self):
+        _check(self._stem + "_sync", getattr(lib, "cmhip_%s_sync" % self._stem)(self.h))
+
+    def hip_stream(self):
+        return getattr(lib, "cmhip_%s_hip_stream" % self._stem)(self.h) or 0
+
+    def _counts(self, frames_per_stream):
+        """-> the run's frames_per_stream argument: None, or the uint32 array as ctypes passes it (it holds the array)"""
+        if frames_per_stream is None:
+            return None
+        fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
+        assert fps.size == self.streams
+        return fps.ctypes
+
+
+class Resampler(_Stage):
     """cmhip_src_t: sample-rate conversion of S streams beside a batch.  Without `table` the library designs one for
     the rates; with it, table = (L, M, int16 array [L][T])."""
+
+    _stem = "src"
 
     def __init__(self, streams, channels, rate_in, rate_out, max_in_frames, table=None, device=0, hip_stream=None):
         d = SrcDesc(device, streams, channels, rate_in, rate_out, max_in_frames, hip_stream)
@@ -980,17 +1014,6 @@ class Resampler:
             raise CoolmicError("cmhip_src_new", ERROR_INVAL)
         self.streams, self.channels, self.max_in_frames = streams, channels, max_in_frames
 
-    def close(self):
-        if self.h:
-            lib.cmhip_src_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def geometry(self):
         L, M, T = C.c_uint(), C.c_uint(), C.c_uint()
         _check("src_geometry", lib.cmhip_src_geometry(self.h, C.byref(L), C.byref(M), C.byref(T)))
@@ -1001,13 +1024,9 @@ class Resampler:
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """cmhip_src_run as it is -> (error number, uint32 array of the streams' output counts)"""
-        fps = None
-        if frames_per_stream is not None:
-            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
-            assert fps.size == self.streams
         got = np.zeros(self.streams, dtype=np.uint32)
-        rc = lib.cmhip_src_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
-                               out_stride, got.ctypes.data)
+        rc = lib.cmhip_src_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride,
+                               got.ctypes.data)
         return rc, got
 
     def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
@@ -1019,16 +1038,12 @@ class Resampler:
     def reset(self, stream=-1):
         _check("src_reset", lib.cmhip_src_reset(self.h, stream))
 
-    def sync(self):
-        _check("src_sync", lib.cmhip_src_sync(self.h))
 
-    def hip_stream(self):
-        return lib.cmhip_src_hip_stream(self.h) or 0
-
-
-class Mixer:
+class Mixer(_Stage):
     """cmhip_mix_t: channel mixing of S streams beside a batch, one matrix int16 [C_out][C_in] (units of 2^-14) per
     stream.  `matrix`: set for every stream at creation (default: the leading channels kept)."""
+
+    _stem = "mix"
 
     def __init__(self, streams, channels_in, channels_out, max_frames, matrix=None, device=0, hip_stream=None):
         d = MixDesc(device, streams, channels_in, channels_out, max_frames, hip_stream)
@@ -1038,17 +1053,6 @@ class Mixer:
         self.streams, self.channels_in, self.channels_out, self.max_frames = streams, channels_in, channels_out, max_frames
         if matrix is not None:
             self.set_matrix(-1, matrix)
-
-    def close(self):
-        if self.h:
-            lib.cmhip_mix_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_matrix_rc(self, stream, W):
         """cmhip_mix_set_matrix as it is -> error number"""
@@ -1085,27 +1089,18 @@ class Mixer:
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """cmhip_mix_run as it is -> error number"""
-        fps = None
-        if frames_per_stream is not None:
-            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
-            assert fps.size == self.streams
-        return lib.cmhip_mix_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
-                                 out_stride)
+        return lib.cmhip_mix_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
 
     def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """one run over device arrays (src, dst: device pointers)"""
         _check("mix_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
 
-    def sync(self):
-        _check("mix_sync", lib.cmhip_mix_sync(self.h))
 
-    def hip_stream(self):
-        return lib.cmhip_mix_hip_stream(self.h) or 0
-
-
-class Bus:
+class Bus(_Stage):
     """cmhip_bus_t: a mix bus beside a batch -- `streams` input slots summed into `buses` output slots by a routing
     table of sends (bus, stream, W int16 [C_out][C_in] in units of 2^-14).  Routing at creation: empty."""
+
+    _stem = "bus"
 
     def __init__(self, streams, buses, channels_in, channels_out, max_frames, max_sends, device=0, hip_stream=None):
         d = BusDesc(device, streams, buses, channels_in, channels_out, max_frames, max_sends, hip_stream)
@@ -1114,17 +1109,6 @@ class Bus:
             raise CoolmicError("cmhip_bus_new", ERROR_INVAL)
         self.streams, self.buses, self.channels_in, self.channels_out = streams, buses, channels_in, channels_out
         self.max_frames, self.max_sends = max_frames, max_sends
-
-    def close(self):
-        if self.h:
-            lib.cmhip_bus_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_routing_rc(self, bus, stream, W):
         """cmhip_bus_set_routing as it is -> error number"""
@@ -1147,12 +1131,8 @@ class Bus:
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None, out_frames=None):
         """cmhip_bus_run as it is -> error number; out_frames: a uint32 array of `buses` entries or None"""
-        fps = None
-        if frames_per_stream is not None:
-            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
-            assert fps.size == self.streams
-        return lib.cmhip_bus_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
-                                 out_stride, out_frames.ctypes.data if out_frames is not None else None)
+        return lib.cmhip_bus_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride,
+                                 out_frames.ctypes.data if out_frames is not None else None)
 
     def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """one run over device arrays (src, dst: device pointers) -> every bus's frame count (uint32 [buses])"""
@@ -1160,16 +1140,12 @@ class Bus:
         _check("bus_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream, got))
         return got
 
-    def sync(self):
-        _check("bus_sync", lib.cmhip_bus_sync(self.h))
 
-    def hip_stream(self):
-        return lib.cmhip_bus_hip_stream(self.h) or 0
-
-
-class Limiter:
+class Limiter(_Stage):
     """cmhip_lim_t: a look-ahead peak limiter of S streams beside a batch; per stream a threshold (sample units) and a
     drive (units of 2^-12).  The output is the input delayed by delay() frames and never above the threshold."""
+
+    _stem = "lim"
 
     def __init__(self, streams, channels, lookahead_log2, hold, max_frames, threshold=None, drive=None, device=0,
                  hip_stream=None):
@@ -1180,17 +1156,6 @@ class Limiter:
         self.streams, self.channels, self.max_frames = streams, channels, max_frames
         if threshold is not None or drive is not None:
             self.set(-1, 32767 if threshold is None else threshold, 4096 if drive is None else drive)
-
-    def close(self):
-        if self.h:
-            lib.cmhip_lim_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def delay(self):
         return lib.cmhip_lim_delay(self.h)
@@ -1210,12 +1175,7 @@ class Limiter:
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """cmhip_lim_run as it is -> error number"""
-        fps = None
-        if frames_per_stream is not None:
-            fps = np.ascontiguousarray(frames_per_stream, dtype=np.uint32)
-            assert fps.size == self.streams
-        return lib.cmhip_lim_run(self.h, src, in_stride, frames, fps.ctypes.data if fps is not None else None, dst,
-                                 out_stride)
+        return lib.cmhip_lim_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
 
     def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """one run over device arrays (src, dst: device pointers)"""
@@ -1229,12 +1189,6 @@ class Limiter:
         out = np.zeros(self.streams, dtype=np.uint32)
         _check("lim_min_gain", lib.cmhip_lim_min_gain(self.h, out.ctypes.data, 1 if reset else 0))
         return out
-
-    def sync(self):
-        _check("lim_sync", lib.cmhip_lim_sync(self.h))
-
-    def hip_stream(self):
-        return lib.cmhip_lim_hip_stream(self.h) or 0
 
 
 class PinnedPcm:

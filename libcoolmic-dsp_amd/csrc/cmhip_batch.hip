@@ -421,12 +421,11 @@ extern "C" int cmhip_batch_set_gain(cmhip_batch_t *b, long stream, unsigned int 
 {
     if (!b)
         return fail(COOLMIC_ERROR_FAULT, "set_gain: batch is NULL");
-    if (stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "set_gain: stream %ld out of range", stream);
-    if (stream >= 0)
-        return set_gain_one(b, (unsigned)stream, channels, scale, gain);
     int rc = COOLMIC_ERROR_NONE;
-    for (unsigned s = 0; s < b->d.streams && rc == COOLMIC_ERROR_NONE; s++)
+    for (unsigned s = sr.lo; s < sr.lo + sr.n && rc == COOLMIC_ERROR_NONE; s++)
         rc = set_gain_one(b, s, channels, scale, gain);
     return rc;
 }
@@ -435,15 +434,14 @@ extern "C" int cmhip_batch_set_chmap(cmhip_batch_t *b, long stream, const uint8_
 {
     if (!b)
         return fail(COOLMIC_ERROR_FAULT, "set_chmap: batch is NULL");
-    if (stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "set_chmap: stream %ld out of range", stream);
     if (map)
         for (unsigned c = 0; c < b->d.channels; c++)
             if (map[c] >= b->d.channels)
                 return fail(COOLMIC_ERROR_INVAL, "set_chmap: map[%u]=%u >= channels", c, map[c]);
-    const unsigned lo = stream < 0 ? 0 : (unsigned)stream;
-    const unsigned hi = stream < 0 ? b->d.streams : (unsigned)stream + 1;
-    for (unsigned s = lo; s < hi; s++) {
+    for (unsigned s = sr.lo; s < sr.lo + sr.n; s++) {
         for (unsigned c = 0; c < b->d.channels; c++)
             b->h_param[s].chmap[c] = map ? map[c] : (uint8_t)c;
         rebuild_param(b, s);
@@ -460,7 +458,8 @@ extern "C" int cmhip_batch_set_eq(cmhip_batch_t *b, long stream, unsigned int ns
         return fail(COOLMIC_ERROR_INVAL, "set_eq: batch was created without CMHIP_EQ");
     if (nsec > MAX_EQ || (nsec && !coef))
         return fail(COOLMIC_ERROR_INVAL, "set_eq: at most %u sections", MAX_EQ);
-    if (stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "set_eq: stream %ld out of range", stream);
     if (nsec && b->tp_on)
         return fail(COOLMIC_ERROR_INVAL, "set_eq: true peak is on, and it does not measure the equaliser's result");
@@ -470,9 +469,7 @@ extern "C" int cmhip_batch_set_eq(cmhip_batch_t *b, long stream, unsigned int ns
         return fail(COOLMIC_ERROR_INVAL,
                     "set_eq: the section count is a batch property (%u); set it with stream -1",
                     b->nsec);
-    const unsigned lo = stream < 0 ? 0 : (unsigned)stream;
-    const unsigned hi = stream < 0 ? b->d.streams : (unsigned)stream + 1;
-    for (unsigned s = lo; s < hi; s++) {
+    for (unsigned s = sr.lo; s < sr.lo + sr.n; s++) {
         b->h_eq[s].nsec = nsec;
         for (unsigned i = 0; i < nsec; i++)
             for (unsigned j = 0; j < 5; j++)
@@ -487,15 +484,13 @@ extern "C" int cmhip_batch_eq_reset(cmhip_batch_t *b, long stream)
 {
     if (!b || !(b->d.flags & CMHIP_EQ))
         return fail(COOLMIC_ERROR_INVAL, "eq_reset: no EQ in this batch");
-    if (stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "eq_reset: stream %ld out of range", stream);
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
     const size_t per_stream = b->d.channels * sizeof(EqState);
-    if (stream < 0)
-        HIP_TRY(hipMemsetAsync(b->d_eqstate, 0, b->d.streams * per_stream, b->stream));
-    else
-        HIP_TRY(hipMemsetAsync(b->d_eqstate + (size_t)stream * b->d.channels, 0, per_stream, b->stream));
+    HIP_TRY(hipMemsetAsync(b->d_eqstate + (size_t)sr.lo * b->d.channels, 0, sr.n * per_stream, b->stream));
     return COOLMIC_ERROR_NONE;
 }
 

@@ -10,7 +10,7 @@
 // Both travel by hipMemcpyAsync on the object's stream from PINNED memory the object owns, so they are ordered with the
 // runs by the stream alone and nothing the caller owns is read after a call returns: the table from one staging area
 // with an event (a second set waits on the host until the first one's copy has executed), a run's counts from a small
-// ring of blocks with an event each (CountsRing, csrc/cmhip_internal.h: run COUNTS_RING + 1 waits for run 1's copy).
+// ring of blocks with an event each (CountsRing, csrc/cmhip_stage.h: run COUNTS_RING + 1 waits for run 1's copy).
 #include "cmhip_engine.h"
 
 #include <stdlib.h>
@@ -22,16 +22,12 @@
 
 constexpr uint64_t BUS_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
-struct cmhip_bus {
+struct cmhip_bus : StageBase {         // d_counts and its ring hold [S] streams | [B] buses
     cmhip_bus_desc_t d;
-    hipStream_t stream;
-    bool own_stream;
     uint32_t *d_table;                 // first[B+1] | send[max_sends] | wk[max_sends * NW]
-    uint32_t *d_counts;                // [S] streams | [B] buses
     uint32_t *h_table;                 // pinned, the same layout
     hipEvent_t table_ev;
     bool table_busy;                   // a copy from h_table was queued and not yet waited for
-    CountsRing counts;                 // a run's [S + B] on their way to d_counts
     bool nt_loads;
     std::vector<uint32_t> bus, strm;   // the mirror, in the caller's order
     std::vector<int16_t> w;
@@ -112,18 +108,11 @@ extern "C" int cmhip_test_bus_compile(unsigned buses, unsigned streams, unsigned
 static int bus_init(cmhip_bus_t *m)
 {
     const cmhip_bus_desc_t &d = m->d;
-    HIP_TRY(hipSetDevice(d.device));
-    if (d.hip_stream) {
-        m->stream = (hipStream_t)d.hip_stream;
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->own_stream = true;
-    }
     const size_t B = d.buses, S = d.streams, words = B + 1 + d.max_sends * (1 + bus_nw(m));
+    if (m->open(d.device, d.hip_stream, S + B))
+        return COOLMIC_ERROR_GENERIC;
     HIP_TRY(hipMalloc((void **)&m->d_table, words * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_counts, (S + B) * sizeof(uint32_t)));
     HIP_TRY(hipHostMalloc((void **)&m->h_table, words * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(m->counts.init(S + B));
     HIP_TRY(hipEventCreateWithFlags(&m->table_ev, hipEventDisableTiming));
     // routing at creation: empty
     bus_route_compile(d.buses, d.channels_in, d.channels_out, 0, nullptr, nullptr, nullptr, m->t);
@@ -135,17 +124,11 @@ extern "C" void cmhip_bus_free(cmhip_bus_t *m)
 {
     if (!m)
         return;
-    (void)hipSetDevice(m->d.device);
-    if (m->stream)
-        (void)hipStreamSynchronize(m->stream);
+    m->close();
     (void)hipFree(m->d_table);
-    (void)hipFree(m->d_counts);
     (void)hipHostFree(m->h_table);
-    m->counts.destroy();
     if (m->table_ev)
         (void)hipEventDestroy(m->table_ev);
-    if (m->own_stream)
-        (void)hipStreamDestroy(m->stream);
     delete m;
 }
 
@@ -244,14 +227,7 @@ extern "C" int cmhip_bus_get_routing(const cmhip_bus_t *m, size_t cap, uint32_t 
 
 extern "C" void *cmhip_bus_hip_stream(cmhip_bus_t *m) { return m ? (void *)m->stream : nullptr; }
 
-extern "C" int cmhip_bus_sync(cmhip_bus_t *m)
-{
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "bus_sync: bus is NULL");
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return COOLMIC_ERROR_NONE;
-}
+extern "C" int cmhip_bus_sync(cmhip_bus_t *m) { return stage_sync(m, "bus_sync"); }
 
 // test hook (tools/bench_bus.py): k_bus_fast's input loads non-temporal (on != 0) or plain (the default)
 extern "C" void cmhip_test_bus_nt_loads(cmhip_bus_t *m, int on)
@@ -263,29 +239,14 @@ extern "C" void cmhip_test_bus_nt_loads(cmhip_bus_t *m, int on)
 extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, size_t frames,
                              const uint32_t *frames_per_stream, void *out, size_t out_stride, uint32_t *out_frames)
 {
-    if (!m || !in || !out)
+    if (!m)
         return fail(COOLMIC_ERROR_FAULT, "bus_run: NULL argument");
     const unsigned S = m->d.streams, B = m->d.buses, CI = m->d.channels_in, CO = m->d.channels_out;
-    if (((uintptr_t)in | (uintptr_t)out) & 15u)
-        return fail(COOLMIC_ERROR_INVAL, "bus_run: in and out must be 16-byte aligned");
-    if ((in_stride | out_stride) & 7u)
-        return fail(COOLMIC_ERROR_INVAL, "bus_run: strides must be multiples of 8 samples");
-    if (frames > m->d.max_frames)
-        return fail(COOLMIC_ERROR_INVAL, "bus_run: %zu frames above max_frames %zu", frames, m->d.max_frames);
-    if (frames_per_stream)
-        for (unsigned s = 0; s < S; s++)
-            if (frames_per_stream[s] > frames)
-                return fail(COOLMIC_ERROR_INVAL, "bus_run: frames_per_stream[%u] above frames", s);
-    if (in_stride < frames * CI)
-        return fail(COOLMIC_ERROR_INVAL, "bus_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, CI);
-    if (out_stride < frames * CO)
-        return fail(COOLMIC_ERROR_INVAL, "bus_run: out_stride %zu below %zu frames of %u channels", out_stride, frames,
-                    CO);
-    // the byte ranges [in, in + S * in_stride) and [out, out + B * out_stride) may not share a byte
-    const uintptr_t ib = (uintptr_t)in, ie = ib + (uintptr_t)S * in_stride * sizeof(int16_t);
-    const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)B * out_stride * sizeof(int16_t);
-    if (ib < oe && ob < ie)
-        return fail(COOLMIC_ERROR_INVAL, "bus_run: the input and the output overlap");
+    const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, B, CI, frames, CO,
+                        STAGE_APART};
+    const int refused = stage_run_refusal("bus_run", r);
+    if (refused)
+        return refused;
     BusArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;

@@ -4,9 +4,13 @@
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
 //   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
 //   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
-//   cmhip_src.hip      sample-rate conversion: the resampler object beside the batch (uses fail / HIP_TRY only)
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
+// and the stage objects beside the batch, which use fail, HIP_TRY and csrc/cmhip_stage.h only:
+//   cmhip_src.hip      sample-rate conversion
+//   cmhip_mix.hip      channel mixing and matrix ramps
+//   cmhip_bus.hip      the mix bus
+//   cmhip_lim.hip      the peak limiter
 #pragma once
 
 #include "cmhip_internal.h"
@@ -32,6 +36,8 @@ CMHIP_INTERNAL int cmhip_fail(int code, const char *fmt, ...) __attribute__((for
             return fail(COOLMIC_ERROR_GENERIC, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                         __FILE__, __LINE__);                                                \
     } while (0)
+
+#include "cmhip_stage.h"
 
 constexpr unsigned STAGE_SLOTS = 4;
 constexpr size_t STAGE_BYTES = 64 * 1024;

@@ -1,6 +1,6 @@
-// cmhip_internal.h -- device-side records and launcher prototypes shared by
-// k_block.hip / k_eq.hip / k_misc.hip / k_tpeak.hip / k_loud.hip / k_src.hip / k_mix.hip / k_mixramp.hip / k_bus.hip / k_lim.hip (the gfx950 kernels) and cmhip_batch.hip (the
-// engine).
+// cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
+// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_lim.hip) and the host code that
+// launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -271,75 +271,6 @@ struct LimArgs {
     uint32_t       halo;           // LimGeom::halo
     uint32_t       chunks;         // tiles per stream
     uint32_t       tile_frames;    // frames per tile
-};
-
-// A run's per-stream counts on their way to the device (cmhip_batch_run, cmhip_src_run, cmhip_mix_run, cmhip_bus_run,
-// cmhip_lim_run): hipMemcpyAsync from pinned memory reads the host array when the stream reaches the copy, not when it
-// is queued, so the copy never starts at memory the caller owns.  The object owns a small ring of pinned blocks with an
-// event each; a run takes the next block (waiting on the host only when run COUNTS_RING + 1 finds run 1's copy not yet
-// executed), fills it, and sends it.  The caller's array is free when the call returns.  The blocks are made with
-// the object, not by its first ragged run: nothing on the hot path allocates.
-constexpr unsigned COUNTS_RING = 4;                  // runs whose counts may be on their way at once
-struct CountsRing {
-    uint32_t  *h = nullptr;                          // pinned [COUNTS_RING][words]
-    size_t     words = 0;
-    hipEvent_t ev[COUNTS_RING] = {};
-    bool       busy[COUNTS_RING] = {};
-    unsigned   next = 0;
-
-    hipError_t init(size_t words_per_run)            // (on the object's device, which the caller has made current)
-    {
-        words = words_per_run;
-        hipError_t e = hipHostMalloc((void **)&h, COUNTS_RING * words * sizeof(uint32_t), hipHostMallocDefault);
-        for (unsigned i = 0; i < COUNTS_RING && e == hipSuccess; i++)
-            e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        return e;
-    }
-    void destroy()
-    {
-        if (h)
-            (void)hipHostFree(h);
-        h = nullptr;
-        for (unsigned i = 0; i < COUNTS_RING; i++) {
-            if (ev[i])
-                (void)hipEventDestroy(ev[i]);
-            ev[i] = nullptr;
-        }
-    }
-    // the block of the next run, free to be written
-    hipError_t take(uint32_t **block)
-    {
-        if (busy[next]) {                            // COUNTS_RING runs back: its counts have long been copied
-            const hipError_t e = hipEventSynchronize(ev[next]);
-            if (e != hipSuccess)
-                return e;
-            busy[next] = false;
-        }
-        *block = h + (size_t)next * words;
-        return hipSuccess;
-    }
-    // the block take() gave, filled: `n` words of it to dst, in stream order
-    hipError_t send(uint32_t *dst, size_t n, hipStream_t st)
-    {
-        hipError_t e = hipMemcpyAsync(dst, h + (size_t)next * words, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess)
-            return e;
-        busy[next] = true;                           // (whatever follows: the block may be in use)
-        e = hipEventRecord(ev[next], st);
-        next = (next + 1) % COUNTS_RING;
-        return e;
-    }
-    // counts[n] as they are: take, fill, send
-    hipError_t upload(uint32_t *dst, const uint32_t *counts, size_t n, hipStream_t st)
-    {
-        uint32_t *block;
-        const hipError_t e = take(&block);
-        if (e != hipSuccess)
-            return e;
-        for (size_t i = 0; i < n; i++)
-            block[i] = counts[i];
-        return send(dst, n, st);
-    }
 };
 
 struct GenArgs {

@@ -14,14 +14,10 @@
 
 constexpr uint64_t LIM_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
-struct cmhip_lim {
+struct cmhip_lim : StageBase {
     cmhip_lim_desc_t d;
     LimGeom g;
-    hipStream_t stream;
-    bool own_stream;
     uint32_t *d_par;
-    uint32_t *d_nframes;
-    CountsRing counts;                 // a run's counts on their way to d_nframes
     uint32_t *d_gmin;
     int16_t *d_hist;
     unsigned parity;
@@ -43,17 +39,10 @@ extern "C" int cmhip_lim_check(unsigned lookahead_log2, unsigned hold, unsigned 
 static int lim_init(cmhip_lim_t *m)
 {
     const cmhip_lim_desc_t &d = m->d;
-    HIP_TRY(hipSetDevice(d.device));
-    if (d.hip_stream) {
-        m->stream = (hipStream_t)d.hip_stream;
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->own_stream = true;
-    }
     const size_t S = d.streams;
+    if (m->open(d.device, d.hip_stream, S))
+        return COOLMIC_ERROR_GENERIC;
     HIP_TRY(hipMalloc((void **)&m->d_par, S * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_nframes, S * sizeof(uint32_t)));
-    HIP_TRY(m->counts.init(S));
     HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * lim_slot(m) * sizeof(int16_t)));
     HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * lim_slot(m) * sizeof(int16_t), m->stream));
@@ -69,16 +58,10 @@ extern "C" void cmhip_lim_free(cmhip_lim_t *m)
 {
     if (!m)
         return;
-    (void)hipSetDevice(m->d.device);
-    if (m->stream)
-        (void)hipStreamSynchronize(m->stream);
+    m->close();
     (void)hipFree(m->d_par);
-    (void)hipFree(m->d_nframes);
-    m->counts.destroy();
     (void)hipFree(m->d_gmin);
     (void)hipFree(m->d_hist);
-    if (m->own_stream)
-        (void)hipStreamDestroy(m->stream);
     delete m;
 }
 
@@ -123,17 +106,17 @@ extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, un
 {
     if (!m)
         return fail(COOLMIC_ERROR_FAULT, "lim_set: limiter is NULL");
-    if (stream >= (long)m->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "lim_set: stream %ld out of range", stream);
     const int rc = cmhip_lim_check(m->g.a, m->g.H, threshold, drive);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    const uint32_t lo = stream < 0 ? 0u : (uint32_t)stream, n = stream < 0 ? m->d.streams : 1u;
-    const hipError_t e = launch_lim_set(m->d_par, lo, n, threshold, drive, m->stream);
+    const hipError_t e = launch_lim_set(m->d_par, sr.lo, sr.n, threshold, drive, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "lim_set: %s", hipGetErrorString(e));
-    for (size_t s = lo; s < (size_t)lo + n; s++)
+    for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
         m->par[s] = threshold | drive << 16;
     return COOLMIC_ERROR_NONE;
 }
@@ -153,23 +136,17 @@ extern "C" int cmhip_lim_get(const cmhip_lim_t *m, unsigned stream, unsigned *th
 
 extern "C" void *cmhip_lim_hip_stream(cmhip_lim_t *m) { return m ? (void *)m->stream : nullptr; }
 
-extern "C" int cmhip_lim_sync(cmhip_lim_t *m)
-{
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "lim_sync: limiter is NULL");
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return COOLMIC_ERROR_NONE;
-}
+extern "C" int cmhip_lim_sync(cmhip_lim_t *m) { return stage_sync(m, "lim_sync"); }
 
 extern "C" int cmhip_lim_reset(cmhip_lim_t *m, long stream)
 {
     if (!m)
         return fail(COOLMIC_ERROR_FAULT, "lim_reset: limiter is NULL");
-    if (stream >= (long)m->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "lim_reset: stream %ld out of range", stream);
     HIP_TRY(hipSetDevice(m->d.device));
-    const size_t lo = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? m->d.streams : 1, per = lim_slot(m);
+    const size_t lo = sr.lo, n = sr.n, per = lim_slot(m);
     // (the slot the next run reads; the other one is rewritten by that run)
     HIP_TRY(hipMemsetAsync(m->d_hist + ((size_t)m->parity * m->d.streams + lo) * per, 0, n * per * sizeof(int16_t),
                            m->stream));
@@ -192,29 +169,16 @@ extern "C" int cmhip_lim_min_gain(cmhip_lim_t *m, uint32_t *out, int reset)
 extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, size_t frames,
                              const uint32_t *frames_per_stream, void *out, size_t out_stride)
 {
-    if (!m || !in || !out)
+    if (!m)
         return fail(COOLMIC_ERROR_FAULT, "lim_run: NULL argument");
     const unsigned S = m->d.streams, C = m->d.channels;
-    if (((uintptr_t)in | (uintptr_t)out) & 15u)
-        return fail(COOLMIC_ERROR_INVAL, "lim_run: in and out must be 16-byte aligned");
-    if ((in_stride | out_stride) & 7u)
-        return fail(COOLMIC_ERROR_INVAL, "lim_run: strides must be multiples of 8 samples");
-    if (frames > m->d.max_frames)
-        return fail(COOLMIC_ERROR_INVAL, "lim_run: %zu frames above max_frames %zu", frames, m->d.max_frames);
-    if (frames_per_stream)
-        for (unsigned s = 0; s < S; s++)
-            if (frames_per_stream[s] > frames)
-                return fail(COOLMIC_ERROR_INVAL, "lim_run: frames_per_stream[%u] above frames", s);
-    if (in_stride < frames * C)
-        return fail(COOLMIC_ERROR_INVAL, "lim_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, C);
-    if (out_stride < frames * C)
-        return fail(COOLMIC_ERROR_INVAL, "lim_run: out_stride %zu below %zu frames of %u channels", out_stride, frames, C);
-    // the byte ranges [in, in + S * in_stride) and [out, out + S * out_stride) may not share a byte: a tile reads the
-    // frames in front of it again after its neighbour may have written them
-    const uintptr_t ib = (uintptr_t)in, ie = ib + (uintptr_t)S * in_stride * sizeof(int16_t);
-    const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)S * out_stride * sizeof(int16_t);
-    if (ib < oe && ob < ie)
-        return fail(COOLMIC_ERROR_INVAL, "lim_run: the input and the output overlap");
+    // (the two arrays may not share a byte: a tile reads the frames in front of it again after its neighbour may have
+    // written them)
+    const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
+                        STAGE_APART};
+    const int refused = stage_run_refusal("lim_run", r);
+    if (refused)
+        return refused;
     if (plan_lim(S, C, m->g.a, m->g.H, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "lim_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
@@ -226,7 +190,7 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_nframes : nullptr;
+    a.nframes = frames_per_stream ? m->d_counts : nullptr;
     a.par = m->d_par;
     a.hist = m->d_hist;
     a.gmin = m->d_gmin;
@@ -239,7 +203,7 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     a.a = m->g.a;
     a.W = m->g.W;
     if (frames_per_stream)
-        HIP_TRY(m->counts.upload(m->d_nframes, frames_per_stream, S, m->stream));
+        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
     const hipError_t e = launch_lim(a, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "lim_run: %s", hipGetErrorString(e));

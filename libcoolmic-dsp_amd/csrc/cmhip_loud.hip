@@ -352,13 +352,14 @@ extern "C" int cmhip_batch_loud_set_weights(cmhip_batch_t *b, long stream, const
 {
     if (!b || !w)
         return fail(COOLMIC_ERROR_FAULT, "loud_set_weights: NULL argument");
-    if (!b->loud_on || stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!b->loud_on || !sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "loud_set_weights: stream %ld out of range or batch without loudness", stream);
-    const size_t S = b->d.streams, C = b->d.channels;
+    const size_t C = b->d.channels;
     for (size_t c = 0; c < C; c++)
         if (!(w[c] >= 0.0) || !isfinite(w[c]))
             return fail(COOLMIC_ERROR_INVAL, "loud_set_weights: weight %zu is negative or not finite", c);
-    const size_t lo = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? S : 1;
+    const size_t lo = sr.lo, n = sr.n;
     for (size_t s = lo; s < lo + n; s++)
         if (loud_completed(b, s))
             return fail(COOLMIC_ERROR_BUSY, "loud_set_weights: stream %zu holds completed sub-blocks (reset first)", s);
@@ -371,12 +372,12 @@ extern "C" int cmhip_batch_loud_reset(cmhip_batch_t *b, long stream)
 {
     if (!b)
         return fail(COOLMIC_ERROR_FAULT, "loud_reset: batch is NULL");
-    if (!b->loud_on || stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!b->loud_on || !sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "loud_reset: stream %ld out of range or batch without loudness", stream);
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
-    const size_t S = b->d.streams, C = b->d.channels;
-    const size_t lo = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? S : 1;
+    const size_t C = b->d.channels, lo = sr.lo, n = sr.n;
     HIP_TRY(hipMemsetAsync(b->d_loud + lo * C, 0, n * C * sizeof(LoudState), b->stream));
     loud_clear_host(b, lo, n);
     return COOLMIC_ERROR_NONE;

@@ -20,13 +20,9 @@
 
 constexpr uint64_t MIX_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
-struct cmhip_mix {
+struct cmhip_mix : StageBase {
     cmhip_mix_desc_t d;
-    hipStream_t stream;
-    bool own_stream;
     uint32_t *d_wk;
-    uint32_t *d_nframes;
-    CountsRing counts;                 // a run's counts on their way to d_nframes
     std::vector<int16_t> w;            // the mirror: [S][C_out][C_in]
     uint32_t *d_ramp;                  // the streams' ramp records, allocated by the first ramp
     MixRampMirror *ramp;               // ... and their mirror
@@ -85,17 +81,10 @@ extern "C" int cmhip_mix_preset(unsigned preset, unsigned *channels_in, unsigned
 static int mix_init(cmhip_mix_t *m)
 {
     const cmhip_mix_desc_t &d = m->d;
-    HIP_TRY(hipSetDevice(d.device));
-    if (d.hip_stream) {
-        m->stream = (hipStream_t)d.hip_stream;
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->own_stream = true;
-    }
     const size_t S = d.streams, CI = d.channels_in, CO = d.channels_out, n = CO * ((CI + 1) / 2);
+    if (m->open(d.device, d.hip_stream, S))
+        return COOLMIC_ERROR_GENERIC;
     HIP_TRY(hipMalloc((void **)&m->d_wk, S * n * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_nframes, S * sizeof(uint32_t)));
-    HIP_TRY(m->counts.init(S));
     // the matrix at creation: the leading channels kept, silence in extra outputs
     std::vector<int16_t> w0(CO * CI, 0);
     for (size_t o = 0; o < (CI < CO ? CI : CO); o++)
@@ -113,16 +102,10 @@ extern "C" void cmhip_mix_free(cmhip_mix_t *m)
 {
     if (!m)
         return;
-    (void)hipSetDevice(m->d.device);
-    if (m->stream)
-        (void)hipStreamSynchronize(m->stream);
+    m->close();
     (void)hipFree(m->d_wk);
-    (void)hipFree(m->d_nframes);
-    m->counts.destroy();
     (void)hipFree(m->d_ramp);
     delete m->ramp;
-    if (m->own_stream)
-        (void)hipStreamDestroy(m->stream);
     delete m;
 }
 
@@ -162,14 +145,15 @@ extern "C" int cmhip_mix_set_matrix(cmhip_mix_t *m, long stream, const int16_t *
 {
     if (!m || !W)
         return fail(COOLMIC_ERROR_FAULT, "mix_set_matrix: NULL argument");
-    if (stream >= (long)m->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "mix_set_matrix: stream %ld out of range", stream);
     const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
     const int rc = cmhip_mix_check(CI, CO, W);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    const uint32_t lo = stream < 0 ? 0u : (uint32_t)stream, n = stream < 0 ? m->d.streams : 1u;
+    const uint32_t lo = sr.lo, n = sr.n;
     const hipError_t e = launch_mix_set(m->d_wk, lo, n, CI, CO, W, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "mix_set_matrix: %s", hipGetErrorString(e));
@@ -220,7 +204,8 @@ extern "C" int cmhip_mix_ramp_matrix(cmhip_mix_t *m, long stream, const int16_t 
 {
     if (!m || !W)
         return fail(COOLMIC_ERROR_FAULT, "mix_ramp_matrix: NULL argument");
-    if (stream >= (long)m->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "mix_ramp_matrix: stream %ld out of range", stream);
     if (ramp_frames > MIX_RAMP_MAX)
         return fail(COOLMIC_ERROR_INVAL, "mix_ramp_matrix: %u frames above %u", ramp_frames, MIX_RAMP_MAX);
@@ -236,7 +221,7 @@ extern "C" int cmhip_mix_ramp_matrix(cmhip_mix_t *m, long stream, const int16_t 
         if (ra)
             return ra;
     }
-    const uint32_t lo = stream < 0 ? 0u : (uint32_t)stream, n = stream < 0 ? m->d.streams : 1u;
+    const uint32_t lo = sr.lo, n = sr.n;
     const hipError_t e = launch_mixramp_start(m->d_ramp, m->d_wk, lo, n, CI, CO, W, ramp_frames, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "mix_ramp_matrix: %s", hipGetErrorString(e));
@@ -285,42 +270,20 @@ extern "C" int cmhip_mix_get_matrix(const cmhip_mix_t *m, unsigned stream, int16
 
 extern "C" void *cmhip_mix_hip_stream(cmhip_mix_t *m) { return m ? (void *)m->stream : nullptr; }
 
-extern "C" int cmhip_mix_sync(cmhip_mix_t *m)
-{
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "mix_sync: mixer is NULL");
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return COOLMIC_ERROR_NONE;
-}
+extern "C" int cmhip_mix_sync(cmhip_mix_t *m) { return stage_sync(m, "mix_sync"); }
 
 extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, size_t frames,
                              const uint32_t *frames_per_stream, void *out, size_t out_stride)
 {
-    if (!m || !in || !out)
+    if (!m)
         return fail(COOLMIC_ERROR_FAULT, "mix_run: NULL argument");
     const unsigned S = m->d.streams, CI = m->d.channels_in, CO = m->d.channels_out;
-    if (((uintptr_t)in | (uintptr_t)out) & 15u)
-        return fail(COOLMIC_ERROR_INVAL, "mix_run: in and out must be 16-byte aligned");
-    if ((in_stride | out_stride) & 7u)
-        return fail(COOLMIC_ERROR_INVAL, "mix_run: strides must be multiples of 8 samples");
-    if (frames > m->d.max_frames)
-        return fail(COOLMIC_ERROR_INVAL, "mix_run: %zu frames above max_frames %zu", frames, m->d.max_frames);
-    if (frames_per_stream)
-        for (unsigned s = 0; s < S; s++)
-            if (frames_per_stream[s] > frames)
-                return fail(COOLMIC_ERROR_INVAL, "mix_run: frames_per_stream[%u] above frames", s);
-    if (in_stride < frames * CI)
-        return fail(COOLMIC_ERROR_INVAL, "mix_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, CI);
-    if (out_stride < frames * CO)
-        return fail(COOLMIC_ERROR_INVAL, "mix_run: out_stride %zu below %zu frames of %u channels", out_stride, frames,
-                    CO);
-    // the byte ranges [in, in + S * in_stride) and [out, out + S * out_stride) may not share a byte: a narrower
-    // output written over the input would race between tiles
-    const uintptr_t ib = (uintptr_t)in, ie = ib + (uintptr_t)S * in_stride * sizeof(int16_t);
-    const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)S * out_stride * sizeof(int16_t);
-    if (ib < oe && ob < ie)
-        return fail(COOLMIC_ERROR_INVAL, "mix_run: the input and the output overlap");
+    // (the two arrays may not share a byte: a narrower output written over the input would race between tiles)
+    const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, CI, frames, CO,
+                        STAGE_APART};
+    const int refused = stage_run_refusal("mix_run", r);
+    if (refused)
+        return refused;
     // nothing was touched so far; from here on the run happens
     if (frames == 0)
         return COOLMIC_ERROR_NONE;
@@ -329,7 +292,7 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_nframes : nullptr;
+    a.nframes = frames_per_stream ? m->d_counts : nullptr;
     a.wk = m->d_wk;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
@@ -341,7 +304,7 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
         return fail(COOLMIC_ERROR_INVAL, "mix_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
     if (frames_per_stream)
-        HIP_TRY(m->counts.upload(m->d_nframes, frames_per_stream, S, m->stream));
+        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
     if (!m->ramp || !m->ramp->any()) {               // nobody ramps: the plain kernels, as ever
         const hipError_t e = launch_mix(a, m->stream);
         if (e != hipSuccess)

@@ -18,17 +18,13 @@
 constexpr unsigned SRC_MAX_LM = 640, SRC_MAX_T = 192;
 constexpr uint64_t SRC_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
-struct cmhip_src {
+struct cmhip_src : StageBase {
     cmhip_src_desc_t d;
-    hipStream_t stream;
-    bool own_stream;
     unsigned L, M, T;
     size_t max_out;                    // floor(max_in_frames * L / M) + 1
     int16_t *d_table;
     int16_t *d_hist;
     uint32_t *d_rpos;
-    uint32_t *d_nframes;
-    CountsRing counts;                 // a run's counts on their way to d_nframes
     unsigned parity;
     std::vector<uint32_t> r;           // the mirror of the device's current r per stream
 };
@@ -146,13 +142,8 @@ extern "C" int cmhip_src_design(unsigned rate_in, unsigned rate_out, unsigned *L
 static int src_init(cmhip_src_t *r, const int16_t *h)
 {
     const cmhip_src_desc_t &d = r->d;
-    HIP_TRY(hipSetDevice(d.device));
-    if (d.hip_stream) {
-        r->stream = (hipStream_t)d.hip_stream;
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-        r->own_stream = true;
-    }
+    if (r->open(d.device, d.hip_stream, d.streams))
+        return COOLMIC_ERROR_GENERIC;
     // the table as the kernel reads it (SrcArgs::table)
     const unsigned T8 = (r->T + 7u) & ~7u, krow = T8 + 8u;
     std::vector<int16_t> tab((size_t)r->L * krow, 0);
@@ -165,8 +156,6 @@ static int src_init(cmhip_src_t *r, const int16_t *h)
     HIP_TRY(hipMalloc((void **)&r->d_table, tab.size() * sizeof(int16_t)));
     HIP_TRY(hipMalloc((void **)&r->d_hist, 2 * src_hist_words(r) * sizeof(int16_t)));
     HIP_TRY(hipMalloc((void **)&r->d_rpos, 2 * S * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&r->d_nframes, S * sizeof(uint32_t)));
-    HIP_TRY(r->counts.init(S));
     HIP_TRY(hipMemcpy(r->d_table, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(r->d_hist, 0, 2 * src_hist_words(r) * sizeof(int16_t), r->stream));
     HIP_TRY(hipMemsetAsync(r->d_rpos, 0, 2 * S * sizeof(uint32_t), r->stream));
@@ -178,16 +167,10 @@ extern "C" void cmhip_src_free(cmhip_src_t *r)
 {
     if (!r)
         return;
-    (void)hipSetDevice(r->d.device);
-    if (r->stream)
-        (void)hipStreamSynchronize(r->stream);
+    r->close();
     (void)hipFree(r->d_table);
     (void)hipFree(r->d_hist);
     (void)hipFree(r->d_rpos);
-    (void)hipFree(r->d_nframes);
-    r->counts.destroy();
-    if (r->own_stream)
-        (void)hipStreamDestroy(r->stream);
     delete r;
 }
 
@@ -257,35 +240,15 @@ extern "C" int cmhip_src_geometry(const cmhip_src_t *r, unsigned *L, unsigned *M
 extern "C" size_t cmhip_src_max_out_frames(const cmhip_src_t *r) { return r ? r->max_out : 0; }
 extern "C" void *cmhip_src_hip_stream(cmhip_src_t *r) { return r ? (void *)r->stream : nullptr; }
 
-extern "C" int cmhip_src_sync(cmhip_src_t *r)
-{
-    if (!r)
-        return fail(COOLMIC_ERROR_FAULT, "src_sync: resampler is NULL");
-    HIP_TRY(hipSetDevice(r->d.device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return COOLMIC_ERROR_NONE;
-}
+extern "C" int cmhip_src_sync(cmhip_src_t *r) { return stage_sync(r, "src_sync"); }
 
 extern "C" int cmhip_src_run(cmhip_src_t *r, const void *in, size_t in_stride, size_t frames,
                              const uint32_t *frames_per_stream, void *out, size_t out_stride, uint32_t *out_frames)
 {
-    if (!r || !in || !out)
+    if (!r)
         return fail(COOLMIC_ERROR_FAULT, "src_run: NULL argument");
     const unsigned S = r->d.streams, C = r->d.channels;
-    if (((uintptr_t)in | (uintptr_t)out) & 15u)
-        return fail(COOLMIC_ERROR_INVAL, "src_run: in and out must be 16-byte aligned");
-    if ((in_stride | out_stride) & 7u)
-        return fail(COOLMIC_ERROR_INVAL, "src_run: strides must be multiples of 8 samples");
-    if (in == out)
-        return fail(COOLMIC_ERROR_INVAL, "src_run: in == out");
-    if (frames > r->d.max_in_frames)
-        return fail(COOLMIC_ERROR_INVAL, "src_run: %zu frames above max_in_frames %zu", frames, r->d.max_in_frames);
-    if (frames_per_stream)
-        for (unsigned s = 0; s < S; s++)
-            if (frames_per_stream[s] > frames)
-                return fail(COOLMIC_ERROR_INVAL, "src_run: frames_per_stream[%u] above frames", s);
-    if (in_stride < frames * C)
-        return fail(COOLMIC_ERROR_INVAL, "src_run: in_stride %zu below %zu frames of %u channels", in_stride, frames, C);
+    // what the run gives its longest stream (pure arithmetic on counts the check below has yet to judge)
     uint32_t most = 0;
     for (unsigned s = 0; s < S; s++) {
         const uint32_t f = frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
@@ -293,19 +256,21 @@ extern "C" int cmhip_src_run(cmhip_src_t *r, const void *in, size_t in_stride, s
         if (k > most)
             most = k;
     }
-    if (out_stride < (size_t)most * C)
-        return fail(COOLMIC_ERROR_INVAL, "src_run: out_stride %zu below the run's %u frames of %u channels", out_stride,
-                    most, C);
+    const StageRun run = {in, out, in_stride, out_stride, frames, r->d.max_in_frames, frames_per_stream, S, S, C, most, C,
+                          STAGE_NOT_IN_PLACE};
+    const int refused = stage_run_refusal("src_run", run);
+    if (refused)
+        return refused;
     // nothing was touched so far; from here on the run happens
     HIP_TRY(hipSetDevice(r->d.device));
     if (frames > 0) {
         if (frames_per_stream)
-            HIP_TRY(r->counts.upload(r->d_nframes, frames_per_stream, S, r->stream));
+            HIP_TRY(r->counts.upload(r->d_counts, frames_per_stream, S, r->stream));
         SrcArgs a;
         memset(&a, 0, sizeof(a));
         a.in = (const int16_t *)in;
         a.out = (int16_t *)out;
-        a.nframes = frames_per_stream ? r->d_nframes : nullptr;
+        a.nframes = frames_per_stream ? r->d_counts : nullptr;
         a.table = r->d_table;
         a.hist = r->d_hist;
         a.rpos = r->d_rpos;
@@ -337,11 +302,12 @@ extern "C" int cmhip_src_reset(cmhip_src_t *r, long stream)
 {
     if (!r)
         return fail(COOLMIC_ERROR_FAULT, "src_reset: resampler is NULL");
-    if (stream >= (long)r->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, r->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "src_reset: stream %ld out of range", stream);
     HIP_TRY(hipSetDevice(r->d.device));
     const size_t S = r->d.streams, per = (size_t)r->d.channels * (r->T - 1);
-    const size_t lo = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? S : 1;
+    const size_t lo = sr.lo, n = sr.n;
     for (unsigned slot = 0; slot < 2; slot++) {
         HIP_TRY(hipMemsetAsync(r->d_hist + slot * src_hist_words(r) + lo * per, 0, n * per * sizeof(int16_t), r->stream));
         HIP_TRY(hipMemsetAsync(r->d_rpos + slot * S + lo, 0, n * sizeof(uint32_t), r->stream));

@@ -161,12 +161,12 @@ extern "C" int cmhip_batch_tp_reset(cmhip_batch_t *b, long stream)
 {
     if (!b)
         return fail(COOLMIC_ERROR_FAULT, "tp_reset: batch is NULL");
-    if (!b->tp_on || stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!b->tp_on || !sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "tp_reset: stream %ld out of range or batch without true peak", stream);
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
-    const size_t S = b->d.streams;
-    const size_t lo = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? S : 1;
+    const size_t lo = sr.lo, n = sr.n;
     HIP_TRY(hipMemsetAsync(b->d_tp_peak + lo * MAX_CH, 0, n * MAX_CH * sizeof(uint32_t), b->stream));
     for (unsigned slot = 0; slot < 2; slot++)
         HIP_TRY(hipMemsetAsync(b->d_tp_hist + slot * tp_hist_words(b) + lo * MAX_CH * TP_HIST, 0,

@@ -302,17 +302,15 @@ extern "C" int cmhip_batch_vu_reset(cmhip_batch_t *b, long stream)
 {
     if (!b)
         return fail(COOLMIC_ERROR_FAULT, "vu_reset: batch is NULL");
-    if (stream >= (long)b->d.streams || stream < -1)
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "vu_reset: stream %ld out of range", stream);
     if (use(b))
         return COOLMIC_ERROR_GENERIC;
     b->last_done = nullptr;                  // main-stream work on the windows follows the last run
     if (cmhip_engine_settle_node(b))
         return COOLMIC_ERROR_GENERIC;
-    if (stream < 0)
-        HIP_TRY(hipMemsetAsync(b->d_vu, 0, b->d.streams * sizeof(VuState), b->stream));
-    else
-        HIP_TRY(hipMemsetAsync(b->d_vu + stream, 0, sizeof(VuState), b->stream));
+    HIP_TRY(hipMemsetAsync(b->d_vu + sr.lo, 0, sr.n * sizeof(VuState), b->stream));
     return COOLMIC_ERROR_NONE;
 }
 
