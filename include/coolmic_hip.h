@@ -160,7 +160,10 @@ int cmhip_batch_generate(cmhip_batch_t *b, int mode, uint32_t seed, size_t frame
  * the batch copies it into a small ring of pinned blocks it owns, so a host loop may refill ONE
  * array for the next run at once.  The fifth of five runs with frames_per_stream queued back to
  * back may wait ON THE HOST until the first one's counts have been copied on the stream).
- * Asynchronous.  cmhip_batch_run_slots takes its counts the same way. */
+ * Asynchronous.  cmhip_batch_run_slots takes its counts the same way.
+ * A run with the equaliser (CMHIP_EQ with sections set) writes nothing past a stream's count: samples from
+ * count * channels on in its PCM slot (in place: the input there) and frames from count on in its float planes
+ * keep what they held. */
 int cmhip_batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per_stream);
 /* the same pass over PCM arrays named for this run: device-accessible memory laid out like the
  * batch's own, int16 [S][cmhip_batch_stride()] (slots_out NULL exactly when the batch writes no

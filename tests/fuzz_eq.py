@@ -19,7 +19,7 @@ seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
 bad = 0
 for case in range(cases):
-    C = int(rng.choice([1, 1, 2, 2, 3, 5, 6, 8, 16]))
+    C = int(rng.choice([1, 1, 2, 2, 3, 4, 5, 6, 7, 8, 12, 15, 16]))
     S = int(rng.integers(1, 40))
     T = int(rng.choice([1, 63, 64, 65, 300, 1000]))
     nsec = int(rng.integers(0, 5))
