@@ -597,6 +597,52 @@ int      cmhip_bus_check(unsigned int buses, unsigned int streams, unsigned int 
 int      cmhip_bus_mix_minus(unsigned int n, int16_t w, uint32_t *bus, uint32_t *stream, int16_t *W, size_t cap_sends,
                              unsigned int channels);
 
+/* ---- send ramps: a bus's sends move without a click ------------------------------- */
+/* cmhip_bus_set_routing replaces the whole table between two frames: every fader move, mute or mix-minus change on a
+ * bus is a step in a gain, and a step is a click.  A send of the table in force can instead move from its matrix in
+ * force to a target over R frames, every frame with a matrix of its own, still in exact integers.
+ *
+ * Arithmetic.  The ramp is the mixer's to the bit ("matrix ramps" above): inc = ceil(2^32 / R), p(n) = min(32768,
+ *   (n * inc) >> 17), N = w0 * (32768 - p) + w1 * p, w(p) = sgn(N) * (|N| >> 15), R in 2..2^20.  cmhip_mix_ramp_position
+ *   and cmhip_mix_ramp_weight remain the specification as code.  Everything else is the bus's own: p_j per send exact
+ *   in int32 with the send's matrix of that frame, the sum over a bus's sends exact in int64, ONE rounding
+ *   saturate_int16((acc + 8192) >> 14) after the sum.  The row bound of a ramp (every interpolated row stays within the
+ *   convex combination of its two ends) is what keeps p_j in int32 at every frame of every ramp.
+ * State.  Each send has its own (W0, W1, R, done) and ramps while done < R; different sends of one bus may be at
+ *   different positions of different ramps.
+ * Clock.  A send's ramp counts the OUTPUT frames of its bus.  In a run, frame f (from 0) of bus b uses
+ *   w(p(done_j + f + 1)) for send j while that number is <= R_j, later frames W1_j.  After the run done_j has advanced
+ *   by the bus's output count of that run, capped at R_j; a bus that produced 0 frames keeps its sends' positions.  A
+ *   send whose stream is shorter than the bus contributes silence beyond its own count, as ever; its ramp moves on all
+ *   the same.
+ * Retarget.  A ramp requested for a send that is ramping starts from the matrix in force, w(p(done)); n restarts at 1.
+ * Step.  ramp_frames 0 or 1 sets the named sends' matrices between two frames and ends their ramps -- one send can be
+ *   changed without replacing the table.
+ * cmhip_bus_set_routing ends every ramp and steps; its contract is otherwise untouched.  Topology changes only through
+ *   it: to fade a send in, put it into the table with a zero matrix and ramp it; to fade it out, ramp it to zero, then
+ *   drop it.  A zero-matrix send adds nothing to the sum but does count for its bus's frame count.
+ * Read-back.  cmhip_bus_get_routing answers with the last accepted matrices; for a ramping send that is its target.
+ * Cuts.  With ramps requested at the same output frames, the concatenated output does not depend on how the run
+ *   sequence is cut.
+ *
+ * cmhip_bus_ramp_sends moves sends first .. first + count - 1, indexed in the caller's order of the last accepted
+ *   cmhip_bus_set_routing, to W[0] .. W[count - 1].  It is ordered with the runs by the object's stream alone, as
+ *   cmhip_bus_set_routing: W is free on return and there is no host wait for the device's runs, in it or in
+ *   cmhip_bus_run; the one host wait it may make is cmhip_bus_set_routing's own, for the object's single pinned staging
+ *   area still being the source of the previous table copy.  count == 0 is accepted and does nothing.
+ *   COOLMIC_ERROR_INVAL for first + count above cmhip_bus_sends, ramp_frames above 2^20 or a row of a target with
+ *   sum |w| > 65535; COOLMIC_ERROR_FAULT for a NULL bus, or NULL W with count > 0.  A refused call changes nothing, a
+ *   running ramp included.  Ramp state is allocated by the first ramp; COOLMIC_ERROR_NOMEM there leaves the bus usable.
+ *   A bus that never ramps launches exactly what it did before, and so does every run at which no send is inside a
+ *   ramp.
+ * cmhip_bus_ramp_state answers from the host's mirror, which advances by the counts every cmhip_bus_run sees: while the
+ *   send ramps 0 <= *done < *ramp_frames and W_now = w(p(done)); otherwise 0, 0 and the send's matrix.  W_now may be
+ *   NULL; COOLMIC_ERROR_FAULT for the other pointers, COOLMIC_ERROR_INVAL for a send out of range. */
+int      cmhip_bus_ramp_sends(cmhip_bus_t *m, size_t first, size_t count,
+                              const int16_t *W /* [count][C_out][C_in] */, uint32_t ramp_frames);
+int      cmhip_bus_ramp_state(const cmhip_bus_t *m, size_t send, uint32_t *done, uint32_t *ramp_frames,
+                              int16_t *W_now /* [C_out][C_in], may be NULL */);
+
 /* ---- peak limiter, an object of its own beside the batch -------------------------- */
 /* A limiter takes S streams of `channels` interleaved int16 channels in and gives the same out, delayed by a fixed
  * number of frames and held under a ceiling: a brick-wall look-ahead limiter in exact integers.  It is what follows a

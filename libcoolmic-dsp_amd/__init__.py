@@ -233,6 +233,8 @@ SIGNATURES = {
     "cmhip_bus_hip_stream": (_vp, [_vp]),
     "cmhip_bus_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_size_t, _vp, _vp, _vp]),
     "cmhip_bus_mix_minus": (C.c_int, [C.c_uint, C.c_int16, _vp, _vp, _vp, C.c_size_t, C.c_uint]),
+    "cmhip_bus_ramp_sends": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32]),
+    "cmhip_bus_ramp_state": (C.c_int, [_vp, C.c_size_t, _P(C.c_uint32), _P(C.c_uint32), _vp]),
     "cmhip_lim_new": (_vp, [_P(LimDesc)]),
     "cmhip_lim_free": (None, [_vp]),
     "cmhip_lim_delay": (C.c_uint, [_vp]),
@@ -382,6 +384,9 @@ if hasattr(lib, "cmhip_test_plan_bus"):         # (not in builds older than the 
     lib.cmhip_test_bus_compile.argtypes = [C.c_uint] * 4 + [C.c_size_t] + [_vp] * 7
     lib.cmhip_test_bus_nt_loads.restype = None
     lib.cmhip_test_bus_nt_loads.argtypes = [_vp, C.c_int]
+if hasattr(lib, "cmhip_test_plan_busramp"):     # (not in builds older than the send ramps)
+    lib.cmhip_test_plan_busramp.restype = None
+    lib.cmhip_test_plan_busramp.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
 if hasattr(lib, "cmhip_test_plan_lim"):         # (not in builds older than the peak limiter)
     lib.cmhip_test_plan_lim.restype = None
     lib.cmhip_test_plan_lim.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
@@ -579,6 +584,13 @@ def plan_bus(buses, channels_in, channels_out, frames):
     GPU)"""
     p = BusPlan()
     lib.cmhip_test_plan_bus(buses, channels_in, channels_out, frames, C.addressof(p))
+    return p
+
+
+def plan_busramp(buses, channels_in, channels_out, frames):
+    """Test hook: the plan of a bus run at which a send ramps (host logic, needs no GPU) -> BusPlan"""
+    p = BusPlan()
+    lib.cmhip_test_plan_busramp(buses, channels_in, channels_out, frames, C.addressof(p))
     return p
 
 
@@ -1128,6 +1140,23 @@ class Bus(_Stage):
         w = np.zeros((max(n, 1), self.channels_out, self.channels_in), dtype=np.int16)
         _check("bus_get_routing", lib.cmhip_bus_get_routing(self.h, n, b.ctypes.data, s.ctypes.data, w.ctypes.data))
         return b[:n], s[:n], w[:n]
+
+    def ramp_sends_rc(self, first, W, ramp_frames):
+        """cmhip_bus_ramp_sends as it is -> error number; W int16 [count][C_out][C_in]"""
+        w = np.ascontiguousarray(W, dtype=np.int16).reshape(-1, self.channels_out, self.channels_in)
+        return lib.cmhip_bus_ramp_sends(self.h, first, w.shape[0], w.ctypes.data, ramp_frames)
+
+    def ramp_sends(self, first, W, ramp_frames):
+        """a click-free move of sends first .. (the caller's order) to W over ramp_frames output frames of their buses;
+        ramp_frames 0 or 1: a step.  Ordered with the runs on the object's stream."""
+        _check("bus_ramp_sends", self.ramp_sends_rc(first, W, ramp_frames))
+
+    def ramp_state(self, send):
+        """-> (done, ramp_frames, the matrix in force int16 [C_out][C_in]); (0, 0, the matrix) when the send is at rest"""
+        done, total = C.c_uint32(0), C.c_uint32(0)
+        w = np.zeros((self.channels_out, self.channels_in), dtype=np.int16)
+        _check("bus_ramp_state", lib.cmhip_bus_ramp_state(self.h, send, C.byref(done), C.byref(total), w.ctypes.data))
+        return done.value, total.value, w
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None, out_frames=None):
         """cmhip_bus_run as it is -> error number; out_frames: a uint32 array of `buses` entries or None"""

@@ -112,6 +112,41 @@ inline void bus_route_compile(uint32_t buses, uint32_t ci, uint32_t co, size_t n
     }
 }
 
+// The same table with the group split taken from BOUNDS instead of from W (send ramps, csrc/bus_ramp.h): bound[j][o]
+// is what row o of the caller's send j may reach while its matrix moves -- the larger of its two ends' sums for a
+// send that ramps, its own sum for one at rest -- and the greedy split above runs on these.  first, stream and wk
+// are bus_route_compile's own (wk holds W, the targets); only flag and groups differ, and with bounds equal to the
+// rows' sums not even they.  pos (may be nullptr) receives the compiled position of every send of the caller's order.
+inline void bus_route_compile_bounds(uint32_t buses, uint32_t ci, uint32_t co, size_t n, const uint32_t *bus,
+                                     const uint32_t *stream, const int16_t *W, const uint32_t *bound, BusTable &t,
+                                     std::vector<uint32_t> *pos)
+{
+    bus_route_compile(buses, ci, co, n, bus, stream, W, t);
+    std::vector<uint32_t> next(t.first.begin(), t.first.end() - 1);
+    std::vector<size_t> from(n);
+    for (size_t j = 0; j < n; j++)                   // (the same stable counting sort)
+        from[next[bus[j]]++] = j;
+    if (pos) {
+        pos->assign(n, 0);
+        for (size_t p = 0; p < n; p++)
+            (*pos)[from[p]] = (uint32_t)p;
+    }
+    uint32_t run[BUS_MAX_CH] = {0};
+    for (uint32_t b = 0; b < buses; b++) {
+        t.groups[b] = 0;
+        for (uint32_t p = t.first[b]; p < t.first[b + 1]; p++) {
+            const uint32_t *row = bound + from[p] * co;
+            bool fits = p != t.first[b];
+            for (uint32_t o = 0; o < co && fits; o++)
+                fits = run[o] + row[o] <= BUS_ROW_MAX;
+            for (uint32_t o = 0; o < co; o++)
+                run[o] = fits ? run[o] + row[o] : row[o];
+            t.flag[p] = fits ? 0u : 1u;
+            t.groups[b] += t.flag[p];
+        }
+    }
+}
+
 // the words the kernels read: bit 31 of first[b] says that bus b has more than one group, bit 31 of a send's word
 // that it starts a group (both indices stay below 2^31)
 constexpr uint32_t BUS_BIT = 0x80000000u;

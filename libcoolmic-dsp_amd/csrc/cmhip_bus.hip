@@ -11,6 +11,14 @@
 // runs by the stream alone and nothing the caller owns is read after a call returns: the table from one staging area
 // with an event (a second set waits on the host until the first one's copy has executed), a run's counts from a small
 // ring of blocks with an event each (CountsRing, csrc/cmhip_stage.h: run COUNTS_RING + 1 waits for run 1's copy).
+//
+// Send ramps (include/coolmic_hip.h, "send ramps"): the first cmhip_bus_ramp_sends that ramps allocates a record per
+// send on the device (BusRampArgs::ramp), a pinned copy of them beside the table's staging area, and the host's
+// mirror (csrc/bus_ramp.h).  Every cmhip_bus_ramp_sends compiles the table again -- the group split from both ends of
+// every running ramp -- and sends the WHOLE table and every record through the staging path: the split of a bus may
+// move at any of its sends, and one copy of the whole is simpler to order than patches (DESIGN 4.12 has the size).
+// The host sees every run's counts, so the mirror advances as the device does and knows whether any send ramps: only
+// then does cmhip_bus_run launch k_busramp.hip's kernels, and a bus that never ramps launches what it always did.
 #include "cmhip_engine.h"
 
 #include <stdlib.h>
@@ -18,6 +26,7 @@
 
 #include <new>
 
+#include "bus_ramp.h"
 #include "bus_route.h"
 
 constexpr uint64_t BUS_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
@@ -32,6 +41,12 @@ struct cmhip_bus : StageBase {         // d_counts and its ring hold [S] streams
     std::vector<uint32_t> bus, strm;   // the mirror, in the caller's order
     std::vector<int16_t> w;
     BusTable t;                        // ... and compiled
+    uint32_t *d_ramp;                  // the sends' ramp records in compiled order, allocated by the first ramp
+    uint32_t *h_ramp;                  // pinned, the same layout: staged with the table, under table_ev
+    BusRampMirror *ramp;               // ... and their mirror, in the caller's order
+    std::vector<uint32_t> pos;         // compiled position of the caller's send j (while ramp != nullptr)
+    std::vector<uint32_t> bound;       // the split's bounds [n][C_out] (scratch of a compile)
+    std::vector<uint32_t> bus_count;   // a ramp run's count per bus (scratch of a run)
 };
 
 static size_t bus_nw(const cmhip_bus_t *m) { return (size_t)m->d.channels_out * ((m->d.channels_in + 1) / 2); }
@@ -114,6 +129,7 @@ static int bus_init(cmhip_bus_t *m)
     HIP_TRY(hipMalloc((void **)&m->d_table, words * sizeof(uint32_t)));
     HIP_TRY(hipHostMalloc((void **)&m->h_table, words * sizeof(uint32_t), hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&m->table_ev, hipEventDisableTiming));
+    m->bus_count.assign(B, 0);
     // routing at creation: empty
     bus_route_compile(d.buses, d.channels_in, d.channels_out, 0, nullptr, nullptr, nullptr, m->t);
     HIP_TRY(hipMemsetAsync(m->d_table, 0, (B + 1) * sizeof(uint32_t), m->stream));
@@ -127,6 +143,9 @@ extern "C" void cmhip_bus_free(cmhip_bus_t *m)
     m->close();
     (void)hipFree(m->d_table);
     (void)hipHostFree(m->h_table);
+    (void)hipFree(m->d_ramp);
+    (void)hipHostFree(m->h_ramp);
+    delete m->ramp;
     if (m->table_ev)
         (void)hipEventDestroy(m->table_ev);
     delete m;
@@ -168,6 +187,41 @@ extern "C" cmhip_bus_t *cmhip_bus_new(const cmhip_bus_desc_t *d)
     return m;
 }
 
+// The table in force (m->bus, m->strm, m->w) compiled and on its way to the device; the caller has waited for the
+// staging area.  With ramp state the group split comes from the mirror's bounds -- for sends at rest these are their
+// own row sums, and the result is bus_route_compile's -- and `records` sends every send's record behind the table.
+static int bus_upload(cmhip_bus_t *m, bool records)
+{
+    const unsigned B = m->d.buses, CI = m->d.channels_in, CO = m->d.channels_out;
+    const size_t n = m->bus.size();
+    if (m->ramp) {
+        bus_ramp_bounds(*m->ramp, CI, CO, m->bound);
+        bus_route_compile_bounds(B, CI, CO, n, m->bus.data(), m->strm.data(), m->w.data(), m->bound.data(), m->t, &m->pos);
+    } else {
+        bus_route_compile(B, CI, CO, n, m->bus.data(), m->strm.data(), m->w.data(), m->t);
+    }
+    const size_t nw = bus_nw(m), send0 = (size_t)B + 1, wk0 = send0 + m->d.max_sends;
+    for (unsigned b = 0; b <= B; b++)
+        m->h_table[b] = bus_first_word(m->t, b);
+    for (size_t p = 0; p < n; p++)
+        m->h_table[send0 + p] = bus_send_word(m->t, p);
+    if (n)
+        memcpy(m->h_table + wk0, m->t.wk.data(), n * nw * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(m->d_table, m->h_table, (send0 + n) * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    m->table_busy = true;                            // (whatever follows: the area may be in use)
+    if (n)
+        HIP_TRY(hipMemcpyAsync(m->d_table + wk0, m->h_table + wk0, n * nw * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               m->stream));
+    if (records && n) {
+        const size_t recw = bus_ramp_record_dwords(CI, CO);
+        for (size_t j = 0; j < n; j++)
+            m->ramp->record(j, CI, CO, m->h_ramp + m->pos[j] * recw);
+        HIP_TRY(hipMemcpyAsync(m->d_ramp, m->h_ramp, n * recw * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    }
+    HIP_TRY(hipEventRecord(m->table_ev, m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
 extern "C" int cmhip_bus_set_routing(cmhip_bus_t *m, size_t n, const uint32_t *bus, const uint32_t *stream,
                                      const int16_t *W)
 {
@@ -185,25 +239,18 @@ extern "C" int cmhip_bus_set_routing(cmhip_bus_t *m, size_t n, const uint32_t *b
         HIP_TRY(hipEventSynchronize(m->table_ev));
         m->table_busy = false;
     }
-    // nothing was touched so far; from here on the table changes
-    bus_route_compile(B, CI, CO, n, bus, stream, W, m->t);
+    if (m->ramp) {                                   // every ramp ends: all sends at rest on the new table
+        try {
+            m->ramp->init(n, (size_t)CO * CI, bus, W);
+        } catch (const std::bad_alloc &) {
+            return fail(COOLMIC_ERROR_NOMEM, "bus_set_routing: out of memory");
+        }
+    }
+    // nothing of the table was touched so far; from here on it changes
     m->bus.assign(bus, bus + n);
     m->strm.assign(stream, stream + n);
     m->w.assign(W, W + n * CO * CI);
-    const size_t nw = bus_nw(m), send0 = (size_t)B + 1, wk0 = send0 + m->d.max_sends;
-    for (unsigned b = 0; b <= B; b++)
-        m->h_table[b] = bus_first_word(m->t, b);
-    for (size_t p = 0; p < n; p++)
-        m->h_table[send0 + p] = bus_send_word(m->t, p);
-    if (n)
-        memcpy(m->h_table + wk0, m->t.wk.data(), n * nw * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(m->d_table, m->h_table, (send0 + n) * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-    m->table_busy = true;                            // (whatever follows: the area may be in use)
-    if (n)
-        HIP_TRY(hipMemcpyAsync(m->d_table + wk0, m->h_table + wk0, n * nw * sizeof(uint32_t), hipMemcpyHostToDevice,
-                               m->stream));
-    HIP_TRY(hipEventRecord(m->table_ev, m->stream));
-    return COOLMIC_ERROR_NONE;
+    return bus_upload(m, false);
 }
 
 extern "C" size_t cmhip_bus_sends(const cmhip_bus_t *m) { return m ? m->bus.size() : 0; }
@@ -221,6 +268,105 @@ extern "C" int cmhip_bus_get_routing(const cmhip_bus_t *m, size_t cap, uint32_t 
         memcpy(bus, m->bus.data(), n * sizeof(uint32_t));
         memcpy(stream, m->strm.data(), n * sizeof(uint32_t));
         memcpy(W, m->w.data(), m->w.size() * sizeof(int16_t));
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+// the ramp records, their staging copy and the mirror, on first use: every send at rest on its matrix
+static int bus_ramp_alloc(cmhip_bus_t *m)
+{
+    const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
+    const size_t bytes = m->d.max_sends * bus_ramp_record_dwords(CI, CO) * sizeof(uint32_t);
+    BusRampMirror *mirror = new (std::nothrow) BusRampMirror();
+    if (!mirror)
+        return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: out of memory");
+    try {
+        mirror->init(m->bus.size(), (size_t)CO * CI, m->bus.data(), m->w.data());
+    } catch (const std::bad_alloc &) {
+        delete mirror;
+        return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: out of memory");
+    }
+    uint32_t *d = nullptr, *h = nullptr;
+    if (hipMalloc((void **)&d, bytes) != hipSuccess || hipHostMalloc((void **)&h, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d);
+        delete mirror;
+        return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: no memory for %zu bytes of ramp state", bytes);
+    }
+    const hipError_t e = hipMemsetAsync(d, 0, bytes, m->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        (void)hipHostFree(h);
+        delete mirror;
+        return fail(COOLMIC_ERROR_GENERIC, "bus_ramp_sends: %s", hipGetErrorString(e));
+    }
+    m->d_ramp = d;
+    m->h_ramp = h;
+    m->ramp = mirror;
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_bus_ramp_sends(cmhip_bus_t *m, size_t first, size_t count, const int16_t *W, uint32_t ramp_frames)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "bus_ramp_sends: bus is NULL");
+    if (count && !W)
+        return fail(COOLMIC_ERROR_FAULT, "bus_ramp_sends: NULL argument");
+    const size_t n = m->bus.size();
+    if (first > n || count > n - first)
+        return fail(COOLMIC_ERROR_INVAL, "bus_ramp_sends: sends %zu .. %zu + %zu: the table has %zu", first, first, count, n);
+    if (ramp_frames > MIX_RAMP_MAX)
+        return fail(COOLMIC_ERROR_INVAL, "bus_ramp_sends: %u frames above %u", ramp_frames, MIX_RAMP_MAX);
+    if (count == 0)
+        return COOLMIC_ERROR_NONE;
+    const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
+    const size_t e = (size_t)CO * CI;
+    for (size_t j = 0; j < count; j++)
+        for (unsigned o = 0; o < CO; o++) {
+            uint32_t sum = 0;
+            for (unsigned c = 0; c < CI; c++)
+                sum += bus_abs16(W[j * e + o * CI + c]);
+            if (sum > BUS_ROW_MAX)
+                return fail(COOLMIC_ERROR_INVAL, "bus_ramp_sends: send %zu has a row with sum |w| above 65535", first + j);
+        }
+    HIP_TRY(hipSetDevice(m->d.device));
+    if (ramp_frames >= 2 && !m->ramp) {
+        const int ra = bus_ramp_alloc(m);
+        if (ra)
+            return ra;
+    }
+    if (m->table_busy) {                             // the staging area is still the source of the last table's copy
+        HIP_TRY(hipEventSynchronize(m->table_ev));
+        m->table_busy = false;
+    }
+    // nothing of the table was touched so far; from here on it changes
+    for (size_t j = 0; j < count; j++) {
+        if (ramp_frames >= 2)
+            m->ramp->start(first + j, W + j * e, ramp_frames);
+        else if (m->ramp)
+            m->ramp->step(first + j, W + j * e);
+        memcpy(&m->w[(first + j) * e], W + j * e, e * sizeof(int16_t));
+    }
+    return bus_upload(m, m->ramp != nullptr);
+}
+
+extern "C" int cmhip_bus_ramp_state(const cmhip_bus_t *m, size_t send, uint32_t *done, uint32_t *ramp_frames,
+                                    int16_t *W_now)
+{
+    if (!m || !done || !ramp_frames)
+        return fail(COOLMIC_ERROR_FAULT, "bus_ramp_state: NULL argument");
+    if (send >= m->bus.size())
+        return fail(COOLMIC_ERROR_INVAL, "bus_ramp_state: send %zu out of range", send);
+    const size_t e = (size_t)m->d.channels_out * m->d.channels_in;
+    if (m->ramp && m->ramp->ramping(send)) {
+        *done = m->ramp->r.done[send];
+        *ramp_frames = m->ramp->r.R[send];
+        if (W_now)
+            m->ramp->now(send, W_now);
+    } else {
+        *done = *ramp_frames = 0;
+        if (W_now)
+            memcpy(W_now, &m->w[send * e], e * sizeof(int16_t));
     }
     return COOLMIC_ERROR_NONE;
 }
@@ -263,7 +409,8 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
     a.channels_in = CI;
     a.channels_out = CO;
     a.nt_loads = m->nt_loads ? 1u : 0u;
-    if (plan_bus(a).err != hipSuccess)
+    const bool ramps = m->ramp && m->ramp->any();    // (the ramp kernels' tile may be the finer one)
+    if ((ramps ? plan_busramp(a) : plan_bus(a)).err != hipSuccess)
         return fail(COOLMIC_ERROR_INVAL, "bus_run: %u buses of %zu frames: the grid would reach 2^31 workgroups", B,
                     frames);
     // nothing was touched so far; from here on the run happens
@@ -281,8 +428,24 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
             h[S + b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
         HIP_TRY(m->counts.send(m->d_counts, (size_t)S + B, m->stream));
     }
-    const hipError_t e = launch_bus(a, m->stream);
+    if (!ramps) {                                    // nobody ramps: the plain kernels, as ever
+        const hipError_t e = launch_bus(a, m->stream);
+        if (e != hipSuccess)
+            return fail(COOLMIC_ERROR_GENERIC, "bus_run: %s", hipGetErrorString(e));
+        return COOLMIC_ERROR_NONE;
+    }
+    // somebody ramps: the ramp kernels, then every ramping send moves on by its bus's count, there and here
+    BusRampArgs ra;
+    ra.b = a;
+    ra.ramp = m->d_ramp;
+    hipError_t e = launch_busramp(ra, m->stream);
+    if (e == hipSuccess)
+        e = launch_busramp_advance(m->d_ramp, a.nframes ? a.bus_frames : nullptr, a.frames, (uint32_t)m->bus.size(), CI,
+                                   CO, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "bus_run: %s", hipGetErrorString(e));
+    for (unsigned b = 0; b < B; b++)
+        m->bus_count[b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
+    m->ramp->advance(m->bus_count.data());
     return COOLMIC_ERROR_NONE;
 }

@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_lim.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -250,6 +250,15 @@ struct BusArgs {
     uint32_t       tile_frames;    // frames per tile
 };
 
+// Send ramps (k_busramp.hip; the arithmetic: include/coolmic_hip.h, "send ramps"): a bus's run while at least one send
+// ramps.  Per send, in the table's compiled order, a record of BUSR_HDR + 2 n dwords, n = C_out * CP, whose layout
+// csrc/bus_ramp.h states: inc, R, done, bus, W0[n], W1[n].  The send ramps while done < R; frame f of its bus uses
+// w(p(done + f + 1)).  BusArgs::wk holds the targets.
+struct BusRampArgs {
+    BusArgs         b;
+    const uint32_t *ramp;          // [n sends][BUSR_HDR + 2 n]
+};
+
 // Peak limiter (k_lim.hip; the arithmetic: include/coolmic_hip.h): a limiter's run over S stream slots.
 struct LimArgs {
     const int16_t *in;             // int16 [S][in_stride]
@@ -383,6 +392,14 @@ struct BusPlan {
 };
 BusPlan plan_bus(const BusArgs &a);
 hipError_t launch_bus(const BusArgs &a, hipStream_t st);
+// Send ramps (k_busramp.hip).  plan_busramp: plan_bus's grid and block; the mono / stereo forms keep its tile, the
+// any-channel-count form chooses its own with W0 and W1 counted beside the send's matrix in LDS.  launch_busramp: a run;
+// the caller launches it only while a send ramps.  launch_busramp_advance, behind it on the stream: every ramping
+// send's position moves on by its bus's count of the run (bus_frames nullptr: by frames), capped at R.
+BusPlan plan_busramp(const BusArgs &a);
+hipError_t launch_busramp(const BusRampArgs &a, hipStream_t st);
+hipError_t launch_busramp_advance(uint32_t *ramp, const uint32_t *bus_frames, uint32_t frames, uint32_t sends,
+                                  uint32_t channels_in, uint32_t channels_out, hipStream_t st);
 // Peak limiter (k_lim.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/lim_plan.h's.
 hipError_t launch_lim(const LimArgs &a, hipStream_t st);
 // (threshold and drive into the parameter words of streams first .. first + count - 1; they travel as kernel arguments)

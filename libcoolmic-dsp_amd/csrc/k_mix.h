@@ -1,4 +1,4 @@
-// k_mix.h -- what the mixer's kernel files share (k_mix.hip, k_mixramp.hip): the workgroup and LDS geometry of the
+// k_mix.h -- what the mixer's kernel files share (k_mix.hip, k_mixramp.hip; k_busramp.hip takes the ramp's steps from here): the workgroup and LDS geometry of the
 // any-channel-count form, the dot and pack steps, and the tile geometry of the mono / stereo form.
 #ifndef CMHIP_K_MIX_H
 #define CMHIP_K_MIX_H
@@ -27,6 +27,27 @@ __device__ __forceinline__ int mix_dot2(u32 x, u32 k, int acc)
 __device__ __forceinline__ u32 mix_pack(int a0, int a1)
 {
     return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pk_i16(a0 >> 14, a1 >> 14));
+}
+
+// ---- a ramp's position and weights (k_mixramp.hip, k_busramp.hip; csrc/mix_ramp.h is the same on the host)
+// n is clamped to R first: then n * inc <= R * ceil(2^32 / R) < 2^32 + R, and the shifted product fits 32 bits
+__device__ __forceinline__ u32 mixr_pos(u32 n, u32 R, u32 inc)
+{
+    const u64 q = (u64)min(n, R) * inc;
+    return min((u32)(q >> 17), 32768u);
+}
+// one entry: |N| <= 2^30; adding 32767 to a negative N turns the arithmetic shift into truncation towards zero
+__device__ __forceinline__ int mixr_w(int w0, int w1, u32 p)
+{
+    const int N = w0 * (int)(32768u - p) + w1 * (int)p;
+    return (N + ((N >> 31) & 32767)) >> 15;
+}
+// both halves of a kernel-form dword
+__device__ __forceinline__ u32 mixr_wk(u32 k0, u32 k1, u32 p)
+{
+    const int lo = mixr_w((int)(short)k0, (int)(short)k1, p);
+    const int hi = mixr_w((int)k0 >> 16, (int)k1 >> 16, p);
+    return ((u32)lo & 0xffffu) | ((u32)hi << 16);
 }
 
 // the mono / stereo form's geometry (k_mix.hip, "Form 1", explains the units)

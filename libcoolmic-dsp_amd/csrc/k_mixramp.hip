@@ -19,26 +19,6 @@
 
 namespace cmhip {
 
-// n is clamped to R first: then n * inc <= R * ceil(2^32 / R) < 2^32 + R, and the shifted product fits 32 bits
-__device__ __forceinline__ u32 mixr_pos(u32 n, u32 R, u32 inc)
-{
-    const u64 q = (u64)min(n, R) * inc;
-    return min((u32)(q >> 17), 32768u);
-}
-// one entry: |N| <= 2^30; adding 32767 to a negative N turns the arithmetic shift into truncation towards zero
-__device__ __forceinline__ int mixr_w(int w0, int w1, u32 p)
-{
-    const int N = w0 * (int)(32768u - p) + w1 * (int)p;
-    return (N + ((N >> 31) & 32767)) >> 15;
-}
-// both halves of a kernel-form dword
-__device__ __forceinline__ u32 mixr_wk(u32 k0, u32 k1, u32 p)
-{
-    const int lo = mixr_w((int)(short)k0, (int)(short)k1, p);
-    const int hi = mixr_w((int)k0 >> 16, (int)k1 >> 16, p);
-    return ((u32)lo & 0xffffu) | ((u32)hi << 16);
-}
-
 // ---------------------------------------------------------------------------
 // Form 1: k_mix_fast's tile (k_mix.hip explains units and vectors).  RAMP: per frame of a unit one position (a 32 x 32
 // -> 64 multiply, a funnel shift, two mins), per matrix entry two multiply-adds and the shift, and the row's dword is

@@ -11,8 +11,16 @@ mono batch: cmhip_batch_ceiling's plain read and plain copy.  The fast forms run
 input loads (cmhip_test_bus_nt_loads); the library's default is the first.
 
     python tools/bench_bus.py [--steps N] [--shapes a,b]      one JSON line per shape
+    python tools/bench_bus.py --ramp [--steps N] [--shapes a,b]   beside it, send ramps (cmhip_bus_ramp_sends, csrc/
+                                                              k_busramp.hip) with plain loads: every send mid-ramp, one
+                                                              send in 64 mid-ramp, and no send ramping once ramps have
+                                                              been used (the plain kernels again)
     python tools/bench_bus.py --count-asm                     VALU instructions per output sample and send of each
                                                               kernel, from build/k_bus.s (`make asm`; no GPU needed)
+
+--ramp: a ramp lasts 2^20 frames at most, 16 runs of these shapes, so the ramp modes warm up with 3 runs and time 10 at
+the most: every timed run lies inside the ramps.  The timed span holds the ramp kernel and the small kernel that
+advances the positions behind it, not the table's upload (queued before the first event).
 """
 import argparse
 import ctypes as C
@@ -76,6 +84,45 @@ def count_asm():
     return out
 
 
+# frames a lane makes per send of the mono / stereo kernels (TILE_FRAMES / 64)
+FAST_FRAMES = {(1, 1): 32, (1, 2): 16, (2, 1): 16, (2, 2): 16}
+
+
+def count_asm_ramp():
+    """k_busr_fast, from build/k_busramp.s: the straight-line block of one send of a whole tile INSIDE its ramp (the one
+    with the position's wide multiply and the dots) and the one outside it -> VALU instructions per frame and send"""
+    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", "k_busramp.s")
+    if not os.path.exists(path):
+        return None
+    text = open(path).read()
+    out = {}
+    for m in re.finditer(r"^(_ZN5cmhip\w*k_busr_fast\w*):.*?^\s*s_endpgm", text, flags=re.S | re.M):
+        f = re.search(r"k_busr_fastILi(\d)ELi(\d)ELb(\d)E", m.group(1))
+        blocks, cur = [], []
+        for ln in m.group(0).splitlines():
+            ln = ln.split(";")[0].strip()
+            if not ln or ln.startswith("."):
+                if ln.startswith(".LBB") and cur:
+                    blocks.append(cur)
+                    cur = []
+                continue
+            cur.append(ln.split()[0])
+            if ln.startswith(("s_cbranch", "s_branch")):
+                blocks.append(cur)
+                cur = []
+        blocks.append(cur)
+        n = lambda b, pre: sum(op.startswith(pre) for op in b)
+        wide = lambda b: n(b, "v_mul_hi_u32") + n(b, "v_mad_u64_u32")
+        ramp = [b for b in blocks if wide(b) and n(b, "v_dot2")]
+        plain = [b for b in blocks if not wide(b) and n(b, "v_dot2") >= 16]
+        frames = FAST_FRAMES[(int(f.group(1)), int(f.group(2)))]
+        out["k_busr_fast<%s, %s, nt=%s>" % f.groups()] = {
+            "frames_per_lane": frames,
+            "ramp_valu_per_frame_and_send": round(max(n(b, "v_") for b in ramp) / frames, 2) if ramp else None,
+            "plain_valu_per_frame_and_send": round(max(n(b, "v_") for b in plain) / frames, 2) if plain else None}
+    return out
+
+
 def hip_runtime():
     """the HIP runtime the engine is bound to, for the events"""
     for ln in open("/proc/self/maps"):
@@ -89,9 +136,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--count-asm", action="store_true")
+    ap.add_argument("--ramp", action="store_true")
     a = ap.parse_args()
     if a.count_asm:
-        print(json.dumps({"k_bus": count_asm()}))
+        print(json.dumps({"k_bus": count_asm(), "k_busramp": count_asm_ramp()}))
         return
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -135,14 +183,10 @@ def main():
         line = {"shape": name, "streams": S, "buses": B, "channels_in": ci, "channels_out": co, "frames": FRAMES,
                 "sends_per_bus": k_of_bus, "groups_per_bus": round(float(flags.sum()) / B, 2), "steps": a.steps}
         rd, wr = B * k_of_bus * FRAMES * ci * 2, B * FRAMES * co * 2
-        for policy in (("plain", "nt") if p.fast else ("plain",)):
-            cm.lib.cmhip_test_bus_nt_loads(m.h, 1 if policy == "nt" else 0)
-            t0 = time.perf_counter()
-            while time.perf_counter() - t0 < 0.15:             # the bus's own launches bring the clocks up
-                m.run(src.dev_in, src.stride, FRAMES, dst, out_stride)
-                m.sync()
+
+        def timed(steps):
             ms = []
-            for _ in range(a.steps):
+            for _ in range(steps):
                 assert hip.hipEventRecord(e0, st) == 0
                 m.run(src.dev_in, src.stride, FRAMES, dst, out_stride)
                 assert hip.hipEventRecord(e1, st) == 0
@@ -150,10 +194,45 @@ def main():
                 t = C.c_float()
                 assert hip.hipEventElapsedTime(C.byref(t), e0, e1) == 0
                 ms.append(t.value)
+            return ms
+
+        for policy in (("plain", "nt") if p.fast else ("plain",)):
+            cm.lib.cmhip_test_bus_nt_loads(m.h, 1 if policy == "nt" else 0)
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < 0.15:             # the bus's own launches bring the clocks up
+                m.run(src.dev_in, src.stride, FRAMES, dst, out_stride)
+                m.sync()
+            ms = timed(a.steps)
             med = statistics.median(ms)
             line[policy + "_loads"] = {"kernel_ms_median": round(med, 4), "kernel_ms_min": round(min(ms), 4),
                                        "kernel_ms_max": round(max(ms), 4),
                                        "GBs_read_plus_written": round((rd + wr) / med / 1e6, 1)}
+        if a.ramp:
+            cm.lib.cmhip_test_bus_nt_loads(m.h, 0)
+            Wt = np.ascontiguousarray(W[::-1], dtype=np.int16)   # targets: the same matrices, handed round
+            W0 = np.ascontiguousarray(W, dtype=np.int16)
+            steps = min(a.steps, 10)
+            assert (3 + steps) * FRAMES < 1 << 20
+            modes = {}
+            for mode in ("every_send_mid_ramp", "one_send_in_64_mid_ramp", "no_send_ramping"):
+                m.ramp_sends(0, W0, 0)                           # everything steps back; ramp state exists from now on
+                if mode == "every_send_mid_ramp":
+                    m.ramp_sends(0, Wt, 1 << 20)
+                elif mode == "one_send_in_64_mid_ramp":
+                    for j in range(0, len(bus), 64):
+                        m.ramp_sends(j, Wt[j:j + 1], 1 << 20)
+                ramping = sum(1 for j in range(0, len(bus), 64) if m.ramp_state(j)[1]) if mode != "no_send_ramping" else 0
+                for _ in range(3):
+                    m.run(src.dev_in, src.stride, FRAMES, dst, out_stride)
+                m.sync()
+                ms = timed(steps)
+                med = statistics.median(ms)
+                modes[mode] = {"kernel_ms_median": round(med, 4), "kernel_ms_min": round(min(ms), 4),
+                               "kernel_ms_max": round(max(ms), 4), "steps": steps, "sampled_sends_ramping": ramping,
+                               "of_plain_loads": round(med / line["plain_loads"]["kernel_ms_median"], 3)}
+            pr = cm.plan_busramp(B, ci, co, FRAMES)
+            modes["plan"] = {"tile_frames": pr.tile_frames, "grid": pr.grid, "lds_bytes": pr.lds_bytes}
+            line["ramp"] = modes
         read, copy = yard.ceiling(0), yard.ceiling(1)
         best = line["plain_loads"]["GBs_read_plus_written"]
         line.update({"read_MB": round(rd / 1e6, 1), "written_MB": round(wr / 1e6, 1),
