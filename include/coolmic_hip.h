@@ -720,6 +720,111 @@ void    *cmhip_lim_hip_stream(cmhip_lim_t *m);
 /* host only, no device needed */
 int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigned int threshold, unsigned int drive);
 
+/* ---- dynamics: compressor and gate, an object of its own beside the batch ----------- */
+/* A dynamics stage takes S streams of `channels` interleaved int16 channels in and gives the same out, delayed by a
+ * fixed number of frames and multiplied by a gain that never exceeds unity and follows the level through a per-stream
+ * static curve: a compressor (the curve falls above a threshold) and a downward expander / gate (it falls below one) in
+ * exact integers.  It stands between a bus and the limiter.  Make-up gain is not here: it is the drive of the limiter
+ * that follows, so |y| <= |x| holds by construction, nothing saturates and nothing can hide an error.
+ *
+ * Geometry, per object: detector_log2 = a in 3..10, A = 2^a, the level window; smooth_log2 = b in 3..9, B = 2^b, the
+ *   gain's ramp length; the delay is D = B - 1 frames; hold = H >= 0 frames with W = B + H <= 2048;
+ *   HIST = (A - 1) + (W - 1) + (B - 1) <= 3581 is the number of earlier frames an output depends on.
+ * Arithmetic.  For frame n of a stream, counted over everything it was ever given; frames before the first (or before
+ *   a reset) are zero:
+ *       e[n]  = max_c |x[n][c]|                         0..32768
+ *       L[n]  = (sum(e[n-A+1 .. n])) >> a               mean magnitude over A frames, 0..32768; the sum is below 2^26
+ *       l[n]  = max(L[n-W+1 .. n])                      level with look-ahead and hold
+ *       g[n]  = curve(l[n])                             0..32768, Q15, unity = 32768
+ *       s[n]  = (sum(g[n-B+1 .. n])) >> b               linear ramps over B frames; the sum is at most 2^24
+ *       y[n][ch] = (x[n-D][ch] * s[n] + 2^14) >> 15     arithmetic shift; |y| <= |x|, fits int16 for x = -32768 too
+ *   All channels of a frame share one gain (linked).  Taking the maximum of the level, not the minimum of the gain,
+ *   lets one stage serve both ends of the curve: a rising level is seen B - 1 frames before it comes out, so the
+ *   compressor's reduction and the gate's opening are both in place at the onset; a falling level is held for W
+ *   frames, so the compressor releases late and the gate closes late.
+ * The curve, per stream, settable between runs: CMHIP_DYN_CURVE = 128 uint16 entries T[]; entries 0..122 are used and
+ *   each must be at most 32768, entries 123..127 are ignored.  The knots lie on a pseudo-logarithmic level grid, 8 per
+ *   octave, and a lookup interpolates linearly between two knots:
+ *       l == 0:            idx = 0, frac = 0, sh = 0
+ *       l >= 1, E = floor(log2 l):
+ *          E >= 3:         idx = 1 + 8E + ((l >> (E-3)) & 7),  frac = l & ((1 << (E-3)) - 1),  sh = E - 3
+ *          E <  3:         idx = 1 + 8E + ((l << (3-E)) & 7),  frac = 0,                       sh = 0
+ *       curve(l) = T[idx] + (((int)T[idx+1] - (int)T[idx]) * frac >> sh)      arithmetic shift; |product| < 2^27
+ *   Knot k >= 1 stands for level (8 + (k-1) % 8) * 2^((k-1) / 8 - 3); knot 121 is level 32768, the largest index ever
+ *   reached, with frac = 0; knot 122 is read but multiplied by 0.  The device takes the table as the specification (as
+ *   the resampler its table and the mixer its matrix).  At creation every stream's curve is all 32768: the stage is a
+ *   pure delay of D frames, bit for bit.
+ * Cuts.  A run evaluates every frame it looks at with the curve in force for that run, the HIST history frames
+ *   included: the history holds raw input frames, not levels or gains.  Between curve changes the concatenated output
+ *   does not depend on how a stream was cut into runs.  A stream given 0 frames keeps everything.
+ * Gain meter.  Per stream the minimum s[n] over the frames output since the last reset of the meter, Q15; 32768 when
+ *   nothing was reduced.
+ *
+ * cmhip_dyn_run has cmhip_lim_run's contract: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in
+ *   samples, both device-accessible; asynchronous on the stage's stream.  `frames` frames per stream, or
+ *   frames_per_stream[s] <= frames (host array of S entries, may be NULL; free on return, with cmhip_mix_run's possible
+ *   wait on the host for the fifth run queued back to back).  COOLMIC_ERROR_INVAL, with nothing launched and nothing
+ *   changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or smaller than frames *
+ *   channels, frames > max_frames, a per-stream count is above frames, the run's grid would reach 2^31 workgroups, or
+ *   the byte ranges [in, in + S * in_stride samples) and [out, out + S * out_stride samples) overlap at all.
+ *   COOLMIC_ERROR_FAULT for NULL arrays.  Samples past a stream's count are neither read nor written.  A stream
+ *   produces as many output frames as it is given input frames; the first D after creation or a reset are zeros from
+ *   the history, and a caller flushes with D frames of silence.
+ * cmhip_dyn_set_curve (stream -1: all) is ordered with the runs by the stream alone: runs queued before it use the old
+ *   curve, runs queued after it the new one, without a host wait; the caller's table is free on return.  A table with a
+ *   used entry above 32768 is refused and the old curve stays.  cmhip_dyn_get_curve answers from the host's mirror:
+ *   the 128 entries the last accepted set (or creation) left.
+ * cmhip_dyn_reset (stream -1: all) zeroes the history and re-arms the meter, on the stage's stream.
+ * cmhip_dyn_min_gain waits for the stream and writes the S meters to out[]; reset != 0 re-arms them all afterwards.
+ * cmhip_dyn_delay: D.  cmhip_dyn_check (host only): 0 for a valid geometry, else COOLMIC_ERROR_INVAL.
+ * cmhip_dyn_design (host only, no device needed) fills the 128 entries from a compressor (threshold ct in dBFS, ratio
+ *   R >= 1, knee width K >= 0 dB) and a gate (threshold gt in dBFS, expander ratio Re >= 1, range rng >= 0 dB; rng == 0:
+ *   no gate).  For a knot of level v > 0: x = 20 log10(v / 32768), d = x - ct;
+ *       comp = 0                                   if 2d < -K
+ *              (1/R - 1) (d + K/2)^2 / (2K)        if 2|d| <= K and K > 0        (the usual soft knee)
+ *              (1/R - 1) d                         otherwise
+ *       gate = max(-rng, (x - gt)(Re - 1))         where x < gt and rng > 0, else 0
+ *       entry = min(32768, floor(32768 * 10^((comp + gate) / 20) + 0.5))
+ *   Knot 0 (silence) gets -rng dB; entries 123..127 are zero.  Non-finite values, R < 1, Re < 1 and negative K or rng
+ *   are refused with COOLMIC_ERROR_INVAL, NULL pointers with COOLMIC_ERROR_FAULT.
+ * Composition: as the limiter -- with hip_stream shared the order is the stream's.  The chain is source -> rate
+ *   (cmhip_src_t) -> width (cmhip_mix_t) -> sum (cmhip_bus_t) -> dynamics (cmhip_dyn_t) -> limit (cmhip_lim_t) -> batch.
+ * cmhip_dyn_new returns NULL on failure; max_frames * channels may not pass 2^31 samples. */
+#define CMHIP_DYN_CURVE 128
+typedef struct cmhip_dyn cmhip_dyn_t;
+typedef struct cmhip_dyn_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int detector_log2;   /* a in 3..10: the level is the mean magnitude over 2^a frames */
+    unsigned int smooth_log2;     /* b in 3..9: B = 2^b, delay B - 1 frames */
+    unsigned int hold;            /* H frames, B + hold <= 2048 */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_dyn_desc_t;
+typedef struct cmhip_dyn_curve_desc {
+    double comp_threshold_db;     /* ct, dBFS */
+    double comp_ratio;            /* R >= 1 */
+    double comp_knee_db;          /* K >= 0 */
+    double gate_threshold_db;     /* gt, dBFS */
+    double gate_ratio;            /* Re >= 1 */
+    double gate_range_db;         /* rng >= 0; 0: no gate */
+} cmhip_dyn_curve_desc_t;
+cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d);
+void     cmhip_dyn_free(cmhip_dyn_t *m);
+unsigned int cmhip_dyn_delay(const cmhip_dyn_t *m);
+int      cmhip_dyn_set_curve(cmhip_dyn_t *m, long stream, const uint16_t *curve /* [CMHIP_DYN_CURVE] */);
+int      cmhip_dyn_get_curve(const cmhip_dyn_t *m, unsigned int stream, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
+int      cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_dyn_reset(cmhip_dyn_t *m, long stream);
+int      cmhip_dyn_min_gain(cmhip_dyn_t *m, uint32_t *out /* [S] */, int reset);
+int      cmhip_dyn_sync(cmhip_dyn_t *m);
+void    *cmhip_dyn_hip_stream(cmhip_dyn_t *m);
+/* host only, no device needed */
+int      cmhip_dyn_check(unsigned int detector_log2, unsigned int smooth_log2, unsigned int hold);
+int      cmhip_dyn_design(const cmhip_dyn_curve_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

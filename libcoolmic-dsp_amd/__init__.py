@@ -110,6 +110,18 @@ class LimDesc(C.Structure):
                 ("hold", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class DynDesc(C.Structure):
+    """cmhip_dyn_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("detector_log2", C.c_uint),
+                ("smooth_log2", C.c_uint), ("hold", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
+class DynCurveDesc(C.Structure):
+    """cmhip_dyn_curve_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("comp_threshold_db", "comp_ratio", "comp_knee_db", "gate_threshold_db",
+                                          "gate_ratio", "gate_range_db")]
+
+
 class Placement(C.Structure):
     """cmhip_placement_t (include/coolmic_hip.h)"""
     _fields_ = [("searched", C.c_int), ("candidates", C.c_int), ("chosen_in", C.c_int),
@@ -246,6 +258,18 @@ SIGNATURES = {
     "cmhip_lim_sync": (C.c_int, [_vp]),
     "cmhip_lim_hip_stream": (_vp, [_vp]),
     "cmhip_lim_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
+    "cmhip_dyn_new": (_vp, [_P(DynDesc)]),
+    "cmhip_dyn_free": (None, [_vp]),
+    "cmhip_dyn_delay": (C.c_uint, [_vp]),
+    "cmhip_dyn_set_curve": (C.c_int, [_vp, C.c_long, _vp]),
+    "cmhip_dyn_get_curve": (C.c_int, [_vp, C.c_uint, _vp]),
+    "cmhip_dyn_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_dyn_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_dyn_min_gain": (C.c_int, [_vp, _vp, C.c_int]),
+    "cmhip_dyn_sync": (C.c_int, [_vp]),
+    "cmhip_dyn_hip_stream": (_vp, [_vp]),
+    "cmhip_dyn_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint]),
+    "cmhip_dyn_design": (C.c_int, [_P(DynCurveDesc), _vp]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -390,6 +414,11 @@ if hasattr(lib, "cmhip_test_plan_busramp"):     # (not in builds older than the 
 if hasattr(lib, "cmhip_test_plan_lim"):         # (not in builds older than the peak limiter)
     lib.cmhip_test_plan_lim.restype = None
     lib.cmhip_test_plan_lim.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
+if hasattr(lib, "cmhip_test_plan_dyn"):         # (not in builds older than the dynamics stage)
+    lib.cmhip_test_plan_dyn.restype = None
+    lib.cmhip_test_plan_dyn.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
+    lib.cmhip_test_dyn_curve_ok.restype = C.c_int
+    lib.cmhip_test_dyn_curve_ok.argtypes = [_vp]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -656,6 +685,55 @@ def plan_lim(streams, channels, lookahead_log2, hold, frames):
 def lim_check(lookahead_log2, hold, threshold, drive):
     """cmhip_lim_check as it is -> error number (0: valid)"""
     return lib.cmhip_lim_check(lookahead_log2, hold, threshold, drive)
+
+
+DYN_CURVE = 128     # CMHIP_DYN_CURVE
+
+
+class DynPlan(C.Structure):
+    """cmhip::DynPlan (csrc/dyn_plan.h): what the dynamics stage's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_frames",
+                                                               "lds_bytes", "halo", "passes")]
+
+
+def plan_dyn(streams, channels, detector_log2, smooth_log2, hold, frames):
+    """Test hook: the dynamics launcher's plan for a run whose longest stream has `frames` frames (host logic, needs no
+    GPU)"""
+    p = DynPlan()
+    lib.cmhip_test_plan_dyn(streams, channels, detector_log2, smooth_log2, hold, frames, C.addressof(p))
+    return p
+
+
+def dyn_check(detector_log2, smooth_log2, hold):
+    """cmhip_dyn_check as it is -> error number (0: valid)"""
+    return lib.cmhip_dyn_check(detector_log2, smooth_log2, hold)
+
+
+def _dyn_table(curve):
+    t = np.ascontiguousarray(curve, dtype=np.uint16)
+    assert t.size == DYN_CURVE
+    return t
+
+
+def dyn_curve_ok(curve):
+    """Test hook: what cmhip_dyn_set_curve asks of a table of 128 entries (host logic, needs no GPU)"""
+    return bool(lib.cmhip_test_dyn_curve_ok(_dyn_table(curve).ctypes.data))
+
+
+def dyn_design_rc(comp_threshold_db=0.0, comp_ratio=1.0, comp_knee_db=0.0, gate_threshold_db=-96.0, gate_ratio=1.0,
+                  gate_range_db=0.0):
+    """cmhip_dyn_design as it is -> (error number, uint16 [128])"""
+    d = DynCurveDesc(comp_threshold_db, comp_ratio, comp_knee_db, gate_threshold_db, gate_ratio, gate_range_db)
+    t = np.zeros(DYN_CURVE, dtype=np.uint16)
+    return lib.cmhip_dyn_design(C.byref(d), t.ctypes.data), t
+
+
+def dyn_design(**kw):
+    """a curve of 128 entries from a compressor (threshold dBFS, ratio, knee dB) and a gate (threshold dBFS, expander
+    ratio, range dB; range 0: no gate); host only"""
+    rc, t = dyn_design_rc(**kw)
+    _check("dyn_design", rc)
+    return t
 
 
 RUN_FAMILIES = ("none", "fast", "fast_ro", "wide", "rows")     # RunPlan::family
@@ -976,7 +1054,7 @@ class Batch:
 
 
 class _Stage:
-    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Limiter): the end of the handle `h`, its
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter): the end of the handle `h`, its
     stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
 
     _stem = None
@@ -1217,6 +1295,57 @@ class Limiter(_Stage):
         """waits for the stream -> the streams' gain-reduction meters, uint32 [S] in Q15"""
         out = np.zeros(self.streams, dtype=np.uint32)
         _check("lim_min_gain", lib.cmhip_lim_min_gain(self.h, out.ctypes.data, 1 if reset else 0))
+        return out
+
+
+class Dynamics(_Stage):
+    """cmhip_dyn_t: a compressor / gate of S streams beside a batch; per stream a curve of 128 uint16 gains (Q15, at most
+    32768) over a level grid of 8 knots per octave (dyn_design makes one).  The output is the input delayed by delay()
+    frames and never louder than it; make-up gain is the drive of the Limiter that follows."""
+
+    _stem = "dyn"
+
+    def __init__(self, streams, channels, detector_log2, smooth_log2, hold, max_frames, curve=None, device=0,
+                 hip_stream=None):
+        d = DynDesc(device, streams, channels, detector_log2, smooth_log2, hold, max_frames, hip_stream)
+        self.h = lib.cmhip_dyn_new(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_dyn_new", ERROR_INVAL)
+        self.streams, self.channels, self.max_frames = streams, channels, max_frames
+        if curve is not None:
+            self.set_curve(-1, curve)
+
+    def delay(self):
+        return lib.cmhip_dyn_delay(self.h)
+
+    def set_curve_rc(self, stream, curve):
+        """cmhip_dyn_set_curve as it is -> error number"""
+        return lib.cmhip_dyn_set_curve(self.h, stream, _dyn_table(curve).ctypes.data)
+
+    def set_curve(self, stream, curve):
+        """stream -1: every stream.  Ordered with the runs on the stage's stream."""
+        _check("dyn_set_curve", self.set_curve_rc(stream, curve))
+
+    def get_curve(self, stream):
+        t = np.zeros(DYN_CURVE, dtype=np.uint16)
+        _check("dyn_get_curve", lib.cmhip_dyn_get_curve(self.h, stream, t.ctypes.data))
+        return t
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_dyn_run as it is -> error number"""
+        return lib.cmhip_dyn_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers)"""
+        _check("dyn_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        _check("dyn_reset", lib.cmhip_dyn_reset(self.h, stream))
+
+    def min_gain(self, reset=False):
+        """waits for the stream -> the streams' gain meters, uint32 [S] in Q15"""
+        out = np.zeros(self.streams, dtype=np.uint32)
+        _check("dyn_min_gain", lib.cmhip_dyn_min_gain(self.h, out.ctypes.data, 1 if reset else 0))
         return out
 
 

@@ -1,0 +1,254 @@
+// cmhip_dyn.hip -- the dynamics stage on the host side (include/coolmic_hip.h, "dynamics"): the object beside the
+// batch, its validation, the launch of k_dyn.hip's kernels, the curves, reset, the gain meter and the curve designer.
+//
+// Device state of a dynamics stage: one curve of DYN_CURVE uint16 entries per stream, the streams' history, int16
+// [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
+// cmhip_lim.hip's d_hist), and the meter, uint32 [S].  The host keeps a mirror of the curves; cmhip_dyn_get_curve answers
+// from it.  A new curve reaches the device inside a kernel's arguments (k_dyn_set), so it is ordered with the runs by
+// the stream alone and no staging memory outlives the call.
+#include "cmhip_engine.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <new>
+
+constexpr uint64_t DYN_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
+
+struct cmhip_dyn : StageBase {
+    cmhip_dyn_desc_t d;
+    DynGeom g;
+    uint16_t *d_curve;
+    uint32_t *d_gmin;
+    int16_t *d_hist;
+    unsigned parity;
+    std::vector<uint16_t> curve;       // the mirror: [S][DYN_CURVE]
+};
+
+static_assert(CMHIP_DYN_CURVE == DYN_CURVE, "the header's curve length is the kernels'");
+
+static size_t dyn_slot(const cmhip_dyn_t *m) { return (size_t)m->g.halo * m->d.channels; }     // samples per stream
+
+extern "C" int cmhip_dyn_check(unsigned detector_log2, unsigned smooth_log2, unsigned hold)
+{
+    if (!dyn_geom(detector_log2, smooth_log2, hold, nullptr))
+        return fail(COOLMIC_ERROR_INVAL, "dyn: detector_log2 %u, smooth_log2 %u, hold %u: 3..10, 3..9, and "
+                    "2^smooth_log2 + hold <= 2048", detector_log2, smooth_log2, hold);
+    return COOLMIC_ERROR_NONE;
+}
+
+// test hook: what cmhip_dyn_set_curve asks of a table (host logic, needs no GPU)
+extern "C" int cmhip_test_dyn_curve_ok(const uint16_t *curve) { return curve && dyn_curve_ok(curve) ? 1 : 0; }
+
+// ---------------------------------------------------------------------------
+// the curve designer (host only)
+
+extern "C" int cmhip_dyn_design(const cmhip_dyn_curve_desc_t *c, uint16_t *curve)
+{
+    if (!c || !curve)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_design: NULL argument");
+    const double ct = c->comp_threshold_db, R = c->comp_ratio, K = c->comp_knee_db;
+    const double gt = c->gate_threshold_db, Re = c->gate_ratio, rng = c->gate_range_db;
+    if (!isfinite(ct) || !isfinite(R) || !isfinite(K) || !isfinite(gt) || !isfinite(Re) || !isfinite(rng))
+        return fail(COOLMIC_ERROR_INVAL, "dyn_design: every parameter must be finite");
+    if (R < 1.0 || Re < 1.0 || K < 0.0 || rng < 0.0)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_design: ratios must be at least 1, knee and range at least 0 dB");
+    auto entry = [](double db) {
+        const double q = floor(32768.0 * pow(10.0, db / 20.0) + 0.5);
+        return (uint16_t)(q < 32768.0 ? q : 32768.0);
+    };
+    curve[0] = entry(-rng);                          // silence: the gate's full range
+    for (unsigned k = 1; k < DYN_CURVE_USED; k++) {
+        const double v = ldexp((double)(8u + (k - 1u) % 8u), (int)((k - 1u) / 8u) - 3);      // the knot's level
+        const double x = 20.0 * log10(v / 32768.0), d = x - ct;
+        double comp;
+        if (2.0 * d < -K)
+            comp = 0.0;
+        else if (K > 0.0 && 2.0 * fabs(d) <= K)
+            comp = (1.0 / R - 1.0) * (d + K / 2.0) * (d + K / 2.0) / (2.0 * K);
+        else
+            comp = (1.0 / R - 1.0) * d;
+        double gate = 0.0;
+        if (rng > 0.0 && x < gt)
+            gate = fmax(-rng, (x - gt) * (Re - 1.0));
+        curve[k] = entry(comp + gate);
+    }
+    for (unsigned k = DYN_CURVE_USED; k < DYN_CURVE; k++)
+        curve[k] = 0;
+    return COOLMIC_ERROR_NONE;
+}
+
+// ---------------------------------------------------------------------------
+// the object
+
+static int dyn_init(cmhip_dyn_t *m)
+{
+    const cmhip_dyn_desc_t &d = m->d;
+    const size_t S = d.streams;
+    if (m->open(d.device, d.hip_stream, S))
+        return COOLMIC_ERROR_GENERIC;
+    HIP_TRY(hipMalloc((void **)&m->d_curve, S * DYN_CURVE * sizeof(uint16_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * dyn_slot(m) * sizeof(int16_t)));
+    HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * dyn_slot(m) * sizeof(int16_t), m->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)DYN_UNITY, S, m->stream));
+    m->curve.assign(S * DYN_CURVE, (uint16_t)DYN_UNITY);         // at creation: unity everywhere, a pure delay
+    const hipError_t e = launch_dyn_set(m->d_curve, 0, d.streams, m->curve.data(), m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "dyn_new: %s", hipGetErrorString(e));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void cmhip_dyn_free(cmhip_dyn_t *m)
+{
+    if (!m)
+        return;
+    m->close();
+    (void)hipFree(m->d_curve);
+    (void)hipFree(m->d_gmin);
+    (void)hipFree(m->d_hist);
+    delete m;
+}
+
+extern "C" cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d)
+{
+    if (!d) {
+        fail(COOLMIC_ERROR_FAULT, "dyn_new: NULL argument");
+        return nullptr;
+    }
+    DynGeom g;
+    if (d->streams == 0 || d->channels == 0 || d->channels > MAX_CH || d->max_frames == 0 ||
+        !dyn_geom(d->detector_log2, d->smooth_log2, d->hold, &g)) {
+        fail(COOLMIC_ERROR_INVAL, "dyn_new: streams, channels (1..16) and max_frames must be positive, detector_log2 in "
+             "3..10, smooth_log2 in 3..9 and 2^smooth_log2 + hold <= 2048");
+        return nullptr;
+    }
+    if (d->max_frames > DYN_MAX_SAMPLES / d->channels) {
+        fail(COOLMIC_ERROR_INVAL, "dyn_new: max_frames %zu: a slot of a run would pass 2^31 samples", d->max_frames);
+        return nullptr;
+    }
+    if ((uint64_t)d->streams * g.halo * d->channels >= (1ull << 31)) {
+        fail(COOLMIC_ERROR_INVAL, "dyn_new: %u streams: the history would pass 2^31 samples", d->streams);
+        return nullptr;
+    }
+    cmhip_dyn_t *m = new (std::nothrow) cmhip_dyn();
+    if (!m) {
+        fail(COOLMIC_ERROR_NOMEM, "dyn_new: out of memory");
+        return nullptr;
+    }
+    m->d = *d;
+    m->g = g;
+    if (dyn_init(m)) {
+        cmhip_dyn_free(m);
+        return nullptr;
+    }
+    return m;
+}
+
+extern "C" unsigned cmhip_dyn_delay(const cmhip_dyn_t *m) { return m ? m->g.D : 0u; }
+
+extern "C" int cmhip_dyn_set_curve(cmhip_dyn_t *m, long stream, const uint16_t *curve)
+{
+    if (!m || !curve)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_set_curve: NULL argument");
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_set_curve: stream %ld out of range", stream);
+    if (!dyn_curve_ok(curve))
+        return fail(COOLMIC_ERROR_INVAL, "dyn_set_curve: an entry of 0..%u is above 32768", DYN_CURVE_USED - 1u);
+    HIP_TRY(hipSetDevice(m->d.device));
+    const hipError_t e = launch_dyn_set(m->d_curve, sr.lo, sr.n, curve, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "dyn_set_curve: %s", hipGetErrorString(e));
+    for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
+        memcpy(&m->curve[s * DYN_CURVE], curve, DYN_CURVE * sizeof(uint16_t));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_dyn_get_curve(const cmhip_dyn_t *m, unsigned stream, uint16_t *curve)
+{
+    if (!m || !curve)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_get_curve: NULL argument");
+    if (stream >= m->d.streams)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_get_curve: stream %u out of range", stream);
+    memcpy(curve, &m->curve[(size_t)stream * DYN_CURVE], DYN_CURVE * sizeof(uint16_t));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" void *cmhip_dyn_hip_stream(cmhip_dyn_t *m) { return m ? (void *)m->stream : nullptr; }
+
+extern "C" int cmhip_dyn_sync(cmhip_dyn_t *m) { return stage_sync(m, "dyn_sync"); }
+
+extern "C" int cmhip_dyn_reset(cmhip_dyn_t *m, long stream)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_reset: stage is NULL");
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_reset: stream %ld out of range", stream);
+    HIP_TRY(hipSetDevice(m->d.device));
+    const size_t lo = sr.lo, n = sr.n, per = dyn_slot(m);
+    // (the slot the next run reads; the other one is rewritten by that run)
+    HIP_TRY(hipMemsetAsync(m->d_hist + ((size_t)m->parity * m->d.streams + lo) * per, 0, n * per * sizeof(int16_t),
+                           m->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->d_gmin + lo), (int)DYN_UNITY, n, m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_dyn_min_gain(cmhip_dyn_t *m, uint32_t *out, int reset)
+{
+    if (!m || !out)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_min_gain: NULL argument");
+    HIP_TRY(hipSetDevice(m->d.device));
+    HIP_TRY(hipMemcpyAsync(out, m->d_gmin, m->d.streams * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (reset)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)DYN_UNITY, m->d.streams, m->stream));
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, size_t frames,
+                             const uint32_t *frames_per_stream, void *out, size_t out_stride)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_run: NULL argument");
+    const unsigned S = m->d.streams, C = m->d.channels;
+    // (the two arrays may not share a byte: a tile reads the frames in front of it again after its neighbour may have
+    // written them)
+    const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
+                        STAGE_APART};
+    const int refused = stage_run_refusal("dyn_run", r);
+    if (refused)
+        return refused;
+    if (plan_dyn(S, C, m->g.a, m->g.b, m->g.H, (uint32_t)frames).err)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
+                    frames);
+    // nothing was touched so far; from here on the run happens
+    if (frames == 0)
+        return COOLMIC_ERROR_NONE;
+    HIP_TRY(hipSetDevice(m->d.device));
+    DynArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = (const int16_t *)in;
+    a.out = (int16_t *)out;
+    a.nframes = frames_per_stream ? m->d_counts : nullptr;
+    a.curve = m->d_curve;
+    a.hist = m->d_hist;
+    a.gmin = m->d_gmin;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.frames = (uint32_t)frames;
+    a.streams = S;
+    a.channels = C;
+    a.parity = m->parity;
+    a.a = m->g.a;
+    a.b = m->g.b;
+    a.W = m->g.W;
+    if (frames_per_stream)
+        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
+    const hipError_t e = launch_dyn(a, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "dyn_run: %s", hipGetErrorString(e));
+    m->parity ^= 1u;                         // the kernel wrote the other slots
+    return COOLMIC_ERROR_NONE;
+}

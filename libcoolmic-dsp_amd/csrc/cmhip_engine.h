@@ -11,6 +11,7 @@
 //   cmhip_mix.hip      channel mixing and matrix ramps
 //   cmhip_bus.hip      the mix bus
 //   cmhip_lim.hip      the peak limiter
+//   cmhip_dyn.hip      the dynamics stage: compressor and gate
 #pragma once
 
 #include "cmhip_internal.h"

@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_dyn.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "lim_plan.h"
+#include "dyn_plan.h"
 
 namespace cmhip {
 
@@ -282,6 +283,31 @@ struct LimArgs {
     uint32_t       tile_frames;    // frames per tile
 };
 
+// Dynamics (k_dyn.hip; the arithmetic: include/coolmic_hip.h): a run of a dynamics stage over S stream slots.
+struct DynArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    const uint16_t *curve;         // [S][DYN_CURVE] the streams' curves
+    // [2][S][halo * C] the last halo input frames per stream, interleaved, oldest first; the two slots of LimArgs::hist
+    int16_t       *hist;
+    uint32_t      *gmin;           // [S] the gain meter: minimum s[n], Q15
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       parity;
+    uint32_t       a, b, W;        // detector_log2, smooth_log2, B + hold
+    // (the launcher fills these in)
+    uint32_t       halo;           // DynGeom::halo
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_frames;    // frames per tile
+};
+// a curve as it travels: a kernel argument of 256 bytes, entries k and k + 1 in dword k / 2
+struct DynCurveArg {
+    uint32_t w[DYN_CURVE / 2];
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -405,6 +431,10 @@ hipError_t launch_lim(const LimArgs &a, hipStream_t st);
 // (threshold and drive into the parameter words of streams first .. first + count - 1; they travel as kernel arguments)
 hipError_t launch_lim_set(uint32_t *par, uint32_t first, uint32_t count, uint32_t threshold, uint32_t drive,
                           hipStream_t st);
+// Dynamics (k_dyn.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/dyn_plan.h's.
+hipError_t launch_dyn(const DynArgs &a, hipStream_t st);
+// (one curve into the tables of streams first .. first + count - 1; it travels as a kernel argument)
+hipError_t launch_dyn_set(uint16_t *curve, uint32_t first, uint32_t count, const uint16_t *table, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,
