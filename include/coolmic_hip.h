@@ -759,6 +759,22 @@ int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigne
  *   does not depend on how a stream was cut into runs.  A stream given 0 frames keeps everything.
  * Gain meter.  Per stream the minimum s[n] over the frames output since the last reset of the meter, Q15; 32768 when
  *   nothing was reduced.
+ * Side-chain keys.  Per stream s a key k = key[s], another stream of the same object whose level steers the gain of s
+ *   (ducking: the music falls when the voice speaks; many streams on one key: linked stems).  Only the first line of
+ *   the arithmetic changes:
+ *       e[n]  = max_c |x_k[n][c]|                       the key's raw input, never its gain
+ *   L, l, g = curve_s(l), s[n] and y[n][ch] = (x_s[n-D][ch] * s[n] + 2^14) >> 15 stay as they are: the curve, the delay,
+ *   the history of the delayed samples and the meter are stream s's own, and |y| <= |x| still holds by construction.
+ *   Frame n of a run of s is aligned with frame n of the same run of k; the frames before the run come from the history
+ *   of each stream, so history frame -j of s is aligned with history frame -j of k.  The detector reads the key's raw
+ *   input, so a key may be keyed itself, two streams may key each other, and many streams may share one key.  Every
+ *   stream still produces its own output: a key is an ordinary stream.  A run with frames_per_stream is refused with
+ *   COOLMIC_ERROR_INVAL -- nothing launched, nothing changed, the message names both streams and both counts -- when a
+ *   keyed stream and its key get different counts; equal counts of 0 are fine, both keep everything.  Between changes
+ *   of curve or key the concatenated output does not depend on how the streams were cut into runs.  cmhip_dyn_reset(s)
+ *   zeroes the history and the meter of s only: resetting a key changes what its followers detect, resetting a
+ *   follower leaves its key's history alone.  At creation every stream is its own key, and an object on which no key
+ *   is set behaves, and runs, exactly as one without this paragraph.
  *
  * cmhip_dyn_run has cmhip_lim_run's contract: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in
  *   samples, both device-accessible; asynchronous on the stage's stream.  `frames` frames per stream, or
@@ -774,6 +790,11 @@ int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigne
  *   curve, runs queued after it the new one, without a host wait; the caller's table is free on return.  A table with a
  *   used entry above 32768 is refused and the old curve stays.  cmhip_dyn_get_curve answers from the host's mirror:
  *   the 128 entries the last accepted set (or creation) left.
+ * cmhip_dyn_set_key (stream -1: all; key -1, or key == stream: the stream's own detector) is ordered with the runs by the
+ *   stream alone, as cmhip_dyn_set_curve is: runs queued before it use the old key, runs queued after it the new one,
+ *   without a host wait and without staging memory.  A NULL stage is COOLMIC_ERROR_FAULT; a stream or a key out of
+ *   range is COOLMIC_ERROR_INVAL and the old map stays.  cmhip_dyn_get_key answers from the host's mirror, -1 for a
+ *   stream on its own detector (COOLMIC_ERROR_FAULT for NULL, COOLMIC_ERROR_INVAL for a stream out of range).
  * cmhip_dyn_reset (stream -1: all) zeroes the history and re-arms the meter, on the stage's stream.
  * cmhip_dyn_min_gain waits for the stream and writes the S meters to out[]; reset != 0 re-arms them all afterwards.
  * cmhip_dyn_delay: D.  cmhip_dyn_check (host only): 0 for a valid geometry, else COOLMIC_ERROR_INVAL.
@@ -787,6 +808,14 @@ int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigne
  *       entry = min(32768, floor(32768 * 10^((comp + gate) / 20) + 0.5))
  *   Knot 0 (silence) gets -rng dB; entries 123..127 are zero.  Non-finite values, R < 1, Re < 1 and negative K or rng
  *   are refused with COOLMIC_ERROR_INVAL, NULL pointers with COOLMIC_ERROR_FAULT.
+ * cmhip_dyn_design_duck (host only, in doubles) fills the 128 entries with a curve for a keyed stream: unity below a
+ *   threshold of the KEY's level, depth dB down above it.  For a knot of level v > 0: x = 20 log10(v / 32768),
+ *   d = x - threshold;
+ *       g = -depth * clamp((d + K/2) / K, 0, 1)    with K = knee > 0
+ *       g = -depth where d >= 0, else 0            with K = 0
+ *       entry = min(32768, floor(32768 * 10^(g / 20) + 0.5))
+ *   Knot 0 (silence) is 32768; entries 123..127 are zero.  Non-finite values, depth < 0 or knee < 0 are refused with
+ *   COOLMIC_ERROR_INVAL, NULL pointers with COOLMIC_ERROR_FAULT.
  * Composition: as the limiter -- with hip_stream shared the order is the stream's.  The chain is source -> rate
  *   (cmhip_src_t) -> width (cmhip_mix_t) -> sum (cmhip_bus_t) -> dynamics (cmhip_dyn_t) -> limit (cmhip_lim_t) -> batch.
  * cmhip_dyn_new returns NULL on failure; max_frames * channels may not pass 2^31 samples. */
@@ -810,11 +839,14 @@ typedef struct cmhip_dyn_curve_desc {
     double gate_ratio;            /* Re >= 1 */
     double gate_range_db;         /* rng >= 0; 0: no gate */
 } cmhip_dyn_curve_desc_t;
+typedef struct cmhip_dyn_duck_desc { double threshold_db, depth_db, knee_db; } cmhip_dyn_duck_desc_t;
 cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d);
 void     cmhip_dyn_free(cmhip_dyn_t *m);
 unsigned int cmhip_dyn_delay(const cmhip_dyn_t *m);
 int      cmhip_dyn_set_curve(cmhip_dyn_t *m, long stream, const uint16_t *curve /* [CMHIP_DYN_CURVE] */);
 int      cmhip_dyn_get_curve(const cmhip_dyn_t *m, unsigned int stream, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
+int      cmhip_dyn_set_key(cmhip_dyn_t *m, long stream, long key);   /* stream -1: all; key -1 (or == stream): own detector */
+int      cmhip_dyn_get_key(const cmhip_dyn_t *m, unsigned int stream, long *key);   /* -1 for own */
 int      cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, size_t frames,
                        const uint32_t *frames_per_stream, void *out, size_t out_stride);
 int      cmhip_dyn_reset(cmhip_dyn_t *m, long stream);
@@ -824,6 +856,7 @@ void    *cmhip_dyn_hip_stream(cmhip_dyn_t *m);
 /* host only, no device needed */
 int      cmhip_dyn_check(unsigned int detector_log2, unsigned int smooth_log2, unsigned int hold);
 int      cmhip_dyn_design(const cmhip_dyn_curve_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
+int      cmhip_dyn_design_duck(const cmhip_dyn_duck_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
 
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of

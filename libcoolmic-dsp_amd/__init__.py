@@ -122,6 +122,11 @@ class DynCurveDesc(C.Structure):
                                           "gate_ratio", "gate_range_db")]
 
 
+class DynDuckDesc(C.Structure):
+    """cmhip_dyn_duck_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("threshold_db", "depth_db", "knee_db")]
+
+
 class Placement(C.Structure):
     """cmhip_placement_t (include/coolmic_hip.h)"""
     _fields_ = [("searched", C.c_int), ("candidates", C.c_int), ("chosen_in", C.c_int),
@@ -270,6 +275,9 @@ SIGNATURES = {
     "cmhip_dyn_hip_stream": (_vp, [_vp]),
     "cmhip_dyn_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint]),
     "cmhip_dyn_design": (C.c_int, [_P(DynCurveDesc), _vp]),
+    "cmhip_dyn_set_key": (C.c_int, [_vp, C.c_long, C.c_long]),
+    "cmhip_dyn_get_key": (C.c_int, [_vp, C.c_uint, _P(C.c_long)]),
+    "cmhip_dyn_design_duck": (C.c_int, [_P(DynDuckDesc), _vp]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -733,6 +741,21 @@ def dyn_design(**kw):
     ratio, range dB; range 0: no gate); host only"""
     rc, t = dyn_design_rc(**kw)
     _check("dyn_design", rc)
+    return t
+
+
+def dyn_design_duck_rc(threshold_db=0.0, depth_db=0.0, knee_db=0.0):
+    """cmhip_dyn_design_duck as it is -> (error number, uint16 [128])"""
+    d = DynDuckDesc(threshold_db, depth_db, knee_db)
+    t = np.zeros(DYN_CURVE, dtype=np.uint16)
+    return lib.cmhip_dyn_design_duck(C.byref(d), t.ctypes.data), t
+
+
+def dyn_design_duck(**kw):
+    """a curve of 128 entries for a keyed stream: unity below the key's threshold (dBFS), depth dB down above it, a
+    knee of knee dB between; host only"""
+    rc, t = dyn_design_duck_rc(**kw)
+    _check("dyn_design_duck", rc)
     return t
 
 
@@ -1301,7 +1324,8 @@ class Limiter(_Stage):
 class Dynamics(_Stage):
     """cmhip_dyn_t: a compressor / gate of S streams beside a batch; per stream a curve of 128 uint16 gains (Q15, at most
     32768) over a level grid of 8 knots per octave (dyn_design makes one).  The output is the input delayed by delay()
-    frames and never louder than it; make-up gain is the drive of the Limiter that follows."""
+    frames and never louder than it; make-up gain is the drive of the Limiter that follows.  set_key lets the level of
+    another stream steer a stream's gain (a side-chain: ducking, linked stems)."""
 
     _stem = "dyn"
 
@@ -1330,6 +1354,21 @@ class Dynamics(_Stage):
         t = np.zeros(DYN_CURVE, dtype=np.uint16)
         _check("dyn_get_curve", lib.cmhip_dyn_get_curve(self.h, stream, t.ctypes.data))
         return t
+
+    def set_key_rc(self, stream, key):
+        """cmhip_dyn_set_key as it is -> error number"""
+        return lib.cmhip_dyn_set_key(self.h, stream, key)
+
+    def set_key(self, stream, key):
+        """the detector of `stream` (-1: every stream) reads stream `key` (-1, or the stream itself: its own frames).
+        Ordered with the runs on the stage's stream."""
+        _check("dyn_set_key", self.set_key_rc(stream, key))
+
+    def get_key(self, stream):
+        """-> the stream's key, -1 for its own detector (from the host's mirror)"""
+        k = C.c_long()
+        _check("dyn_get_key", lib.cmhip_dyn_get_key(self.h, stream, C.byref(k)))
+        return k.value
 
     def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
         """cmhip_dyn_run as it is -> error number"""

@@ -1,11 +1,14 @@
 // cmhip_dyn.hip -- the dynamics stage on the host side (include/coolmic_hip.h, "dynamics"): the object beside the
-// batch, its validation, the launch of k_dyn.hip's kernels, the curves, reset, the gain meter and the curve designer.
+// batch, its validation, the launch of k_dyn.hip's kernels (k_dynkey.hip's while a side-chain key is set), the curves,
+// the keys, reset, the gain meter and the curve designers.
 //
 // Device state of a dynamics stage: one curve of DYN_CURVE uint16 entries per stream, the streams' history, int16
 // [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
-// cmhip_lim.hip's d_hist), and the meter, uint32 [S].  The host keeps a mirror of the curves; cmhip_dyn_get_curve answers
-// from it.  A new curve reaches the device inside a kernel's arguments (k_dyn_set), so it is ordered with the runs by
-// the stream alone and no staging memory outlives the call.
+// cmhip_lim.hip's d_hist), the meter, uint32 [S], and the key map, uint32 [S]: the stream whose level steers stream s,
+// s itself where no key is set.  The host keeps a mirror of the curves and of the map; cmhip_dyn_get_curve and
+// cmhip_dyn_get_key answer from them, and the mirror's count of keyed streams chooses a run's kernels.  A new curve or
+// key reaches the device inside a kernel's arguments (k_dyn_set, k_dynk_set), so it is ordered with the runs by the
+// stream alone and no staging memory outlives the call.
 #include "cmhip_engine.h"
 
 #include <math.h>
@@ -22,7 +25,10 @@ struct cmhip_dyn : StageBase {
     uint32_t *d_gmin;
     int16_t *d_hist;
     unsigned parity;
+    uint32_t *d_key;
     std::vector<uint16_t> curve;       // the mirror: [S][DYN_CURVE]
+    std::vector<uint32_t> key;         // the mirror: [S], s where stream s follows its own level
+    size_t keyed;                      // streams of the mirror with key[s] != s
 };
 
 static_assert(CMHIP_DYN_CURVE == DYN_CURVE, "the header's curve length is the kernels'");
@@ -78,6 +84,33 @@ extern "C" int cmhip_dyn_design(const cmhip_dyn_curve_desc_t *c, uint16_t *curve
     return COOLMIC_ERROR_NONE;
 }
 
+// a duck curve: unity below the threshold, depth_db down above it, a linear knee (in dB) between
+extern "C" int cmhip_dyn_design_duck(const cmhip_dyn_duck_desc_t *c, uint16_t *curve)
+{
+    if (!c || !curve)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_design_duck: NULL argument");
+    const double th = c->threshold_db, depth = c->depth_db, K = c->knee_db;
+    if (!isfinite(th) || !isfinite(depth) || !isfinite(K))
+        return fail(COOLMIC_ERROR_INVAL, "dyn_design_duck: every parameter must be finite");
+    if (depth < 0.0 || K < 0.0)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_design_duck: depth and knee must be at least 0 dB");
+    curve[0] = (uint16_t)DYN_UNITY;                  // silence: nothing to duck under
+    for (unsigned k = 1; k < DYN_CURVE_USED; k++) {
+        const double v = ldexp((double)(8u + (k - 1u) % 8u), (int)((k - 1u) / 8u) - 3);      // the knot's level
+        const double x = 20.0 * log10(v / 32768.0), d = x - th;
+        double g;
+        if (K > 0.0)
+            g = -depth * fmin(fmax((d + K / 2.0) / K, 0.0), 1.0);
+        else
+            g = d >= 0.0 ? -depth : 0.0;
+        const double q = floor(32768.0 * pow(10.0, g / 20.0) + 0.5);
+        curve[k] = (uint16_t)(q < 32768.0 ? q : 32768.0);
+    }
+    for (unsigned k = DYN_CURVE_USED; k < DYN_CURVE; k++)
+        curve[k] = 0;
+    return COOLMIC_ERROR_NONE;
+}
+
 // ---------------------------------------------------------------------------
 // the object
 
@@ -90,12 +123,20 @@ static int dyn_init(cmhip_dyn_t *m)
     HIP_TRY(hipMalloc((void **)&m->d_curve, S * DYN_CURVE * sizeof(uint16_t)));
     HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * dyn_slot(m) * sizeof(int16_t)));
+    HIP_TRY(hipMalloc((void **)&m->d_key, S * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * dyn_slot(m) * sizeof(int16_t), m->stream));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)DYN_UNITY, S, m->stream));
     m->curve.assign(S * DYN_CURVE, (uint16_t)DYN_UNITY);         // at creation: unity everywhere, a pure delay
     const hipError_t e = launch_dyn_set(m->d_curve, 0, d.streams, m->curve.data(), m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "dyn_new: %s", hipGetErrorString(e));
+    m->key.resize(S);                                            // at creation: every stream is its own key
+    for (size_t s = 0; s < S; s++)
+        m->key[s] = (uint32_t)s;
+    m->keyed = 0;
+    const hipError_t k = launch_dyn_set_key(m->d_key, 0, d.streams, 0, true, m->stream);
+    if (k != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "dyn_new: %s", hipGetErrorString(k));
     return COOLMIC_ERROR_NONE;
 }
 
@@ -107,6 +148,7 @@ extern "C" void cmhip_dyn_free(cmhip_dyn_t *m)
     (void)hipFree(m->d_curve);
     (void)hipFree(m->d_gmin);
     (void)hipFree(m->d_hist);
+    (void)hipFree(m->d_key);
     delete m;
 }
 
@@ -175,6 +217,41 @@ extern "C" int cmhip_dyn_get_curve(const cmhip_dyn_t *m, unsigned stream, uint16
     return COOLMIC_ERROR_NONE;
 }
 
+extern "C" int cmhip_dyn_set_key(cmhip_dyn_t *m, long stream, long key)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_set_key: stage is NULL");
+    const StreamRange sr = stream_range(stream, m->d.streams);
+    if (!sr.ok)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_set_key: stream %ld out of range", stream);
+    if (key < -1 || (key >= 0 && (unsigned long)key >= m->d.streams))
+        return fail(COOLMIC_ERROR_INVAL, "dyn_set_key: key %ld out of range", key);
+    HIP_TRY(hipSetDevice(m->d.device));
+    const bool own = key < 0;
+    const hipError_t e = launch_dyn_set_key(m->d_key, sr.lo, sr.n, own ? 0u : (uint32_t)key, own, m->stream);
+    if (e != hipSuccess)
+        return fail(COOLMIC_ERROR_GENERIC, "dyn_set_key: %s", hipGetErrorString(e));
+    for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++) {
+        const uint32_t k = own ? (uint32_t)s : (uint32_t)key;
+        if (m->key[s] != s)
+            m->keyed--;
+        if (k != s)
+            m->keyed++;
+        m->key[s] = k;
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_dyn_get_key(const cmhip_dyn_t *m, unsigned stream, long *key)
+{
+    if (!m || !key)
+        return fail(COOLMIC_ERROR_FAULT, "dyn_get_key: NULL argument");
+    if (stream >= m->d.streams)
+        return fail(COOLMIC_ERROR_INVAL, "dyn_get_key: stream %u out of range", stream);
+    *key = m->key[stream] == stream ? -1L : (long)m->key[stream];
+    return COOLMIC_ERROR_NONE;
+}
+
 extern "C" void *cmhip_dyn_hip_stream(cmhip_dyn_t *m) { return m ? (void *)m->stream : nullptr; }
 
 extern "C" int cmhip_dyn_sync(cmhip_dyn_t *m) { return stage_sync(m, "dyn_sync"); }
@@ -223,6 +300,14 @@ extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, s
     if (plan_dyn(S, C, m->g.a, m->g.b, m->g.H, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "dyn_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
+    // a keyed stream and its key advance together: frame n of the one is frame n of the other
+    if (frames_per_stream && m->keyed)
+        for (unsigned s = 0; s < S; s++) {
+            const uint32_t k = m->key[s];
+            if (frames_per_stream[s] != frames_per_stream[k])
+                return fail(COOLMIC_ERROR_INVAL, "dyn_run: stream %u has %u frames, its key, stream %u, has %u", s,
+                            frames_per_stream[s], k, frames_per_stream[k]);
+        }
     // nothing was touched so far; from here on the run happens
     if (frames == 0)
         return COOLMIC_ERROR_NONE;
@@ -246,7 +331,7 @@ extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, s
     a.W = m->g.W;
     if (frames_per_stream)
         HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    const hipError_t e = launch_dyn(a, m->stream);
+    const hipError_t e = m->keyed ? launch_dynk(a, m->d_key, m->stream) : launch_dyn(a, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "dyn_run: %s", hipGetErrorString(e));
     m->parity ^= 1u;                         // the kernel wrote the other slots

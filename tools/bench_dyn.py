@@ -11,8 +11,15 @@ cmhip_batch_ceiling's plain copy (read + write), the yardstick, and the peak lim
 nearest pass counts (a = 8, H = 1024: 19 passes; a = 9, H = 1536: 20 passes).
 
     python tools/bench_dyn.py [--steps N] [--shapes a,b]      one JSON line per shape
-    python tools/bench_dyn.py --count-asm                     per kernel the instructions of build/k_dyn.s (`make asm`;
-                                                              no GPU needed), and the passes per geometry
+    python tools/bench_dyn.py --count-asm                     per kernel the instructions of build/k_dyn.s and
+                                                              build/k_dynkey.s (`make asm`; no GPU needed), and the
+                                                              passes per geometry
+    python tools/bench_dyn.py --key [--steps N] [--shapes a,b]
+        side-chain keys (cmhip_dyn_set_key, csrc/k_dynkey.hip): per shape, on one object, the same slots and in one
+        process, the plain run (no key set: k_dyn.hip's kernels), the plain run again (its repeat shows the spread of
+        the unkeyed kernels inside one session), a run with every odd stream keyed on its even neighbour, a run with
+        every stream keyed (on its neighbour, 2i <-> 2i + 1), and the plain run a third time after the keys were
+        cleared; one JSON line per shape with the medians and their min-max
 """
 import argparse
 import ctypes as C
@@ -47,18 +54,18 @@ def passes(a, b, hold):
             "all": a + p + (1 if W > (1 << p) else 0) + b}
 
 
-def count_asm():
-    """per kernel of build/k_dyn.s: all its instructions by class, and, cut at the barriers, the two phases of a doubling
-    pass over a thread's 30 elements and the curve lookup between the passes"""
-    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", "k_dyn.s")
+def count_asm(stem="k_dyn"):
+    """per kernel of build/k_dyn.s (or, stem "k_dynk", build/k_dynkey.s): all its instructions by class, and, cut at the
+    barriers, the two phases of a doubling pass over a thread's 30 elements and the curve lookup between the passes"""
+    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", "k_dynkey.s" if stem == "k_dynk" else "k_dyn.s")
     if not os.path.exists(path):
         return None
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"^(_ZN5cmhip\w*k_dyn_(?:fast|any)\w*):.*?^\s*s_endpgm", text, flags=re.S | re.M):
+    for m in re.finditer(r"^(_ZN5cmhip\w*%s_(?:fast|any)\w*):.*?^\s*s_endpgm" % stem, text, flags=re.S | re.M):
         sym, body = m.group(1), m.group(0)
-        f = re.search(r"k_dyn_fastILi(\d)E", sym)
-        name = "k_dyn_fast<%s>" % f.group(1) if f else "k_dyn_any"
+        f = re.search(r"%s_fastILi(\d)E" % stem, sym)
+        name = "%s_fast<%s>" % (stem, f.group(1)) if f else stem + "_any"
         # the kernel cut at its barriers.  Inside a loop of doubling passes the stretch from one pass's middle barrier
         # to the next one's holds the first one's 30 writes and the next one's 30 partner reads: one pass's worth of
         # work, the leanest stretch with both.  The curve lookup (30 table reads, 30 writes) is the heaviest such stretch.
@@ -121,14 +128,66 @@ def timed(hip, stage, steps, run):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def keyed(a):
+    """--key: the plain run, its repeat, odd streams keyed, every stream keyed, the plain run again: one object per shape"""
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    cm = ge.load_package()
+    hip = None
+    for name in a.shapes.split(","):
+        S, ch, F, la, lb, hold = SHAPES[name]
+        S -= S % 2                                              # pairs
+        src = cm.Batch(S, ch, F, flags=cm.OUT_PCM | cm.VU, rate=48000)
+        src.generate(cm.GEN_NOISE, 12345, F)
+        src.sync()
+        m = cm.Dynamics(S, ch, la, lb, hold, F, curve=cm.dyn_design(**CURVE))
+        out_stride = (F * ch + 7) // 8 * 8
+        dst = cm.lib.cmhip_device_alloc(0, S * out_stride * 2)
+        assert dst
+        if hip is None:
+            hip = hip_runtime()
+            hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+            hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+            hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+            hip.hipEventSynchronize.argtypes = [C.c_void_p]
+        run = lambda: m.run(src.dev_in, src.stride, F, dst, out_stride)
+        rec = lambda t: {"kernel_ms_median": round(t[0], 4), "kernel_ms_min": round(t[1], 4), "kernel_ms_max": round(t[2], 4)}
+        line = {"shape": name, "key": True, "streams": S, "channels": ch, "frames": F, "detector_log2": la,
+                "smooth_log2": lb, "hold": hold, "steps": a.steps, "passes": passes(la, lb, hold)["all"]}
+        line["plain"] = rec(timed(hip, m, a.steps, run))
+        line["plain_repeated"] = rec(timed(hip, m, a.steps, run))
+        for s in range(1, S, 2):
+            m.set_key(s, s - 1)
+        line["odd_streams_keyed"] = rec(timed(hip, m, a.steps, run))
+        for s in range(0, S, 2):
+            m.set_key(s, s + 1)
+        line["every_stream_keyed"] = rec(timed(hip, m, a.steps, run))
+        m.set_key(-1, -1)
+        line["plain_after_clearing"] = rec(timed(hip, m, a.steps, run))
+        base = line["plain"]["kernel_ms_median"]
+        for k in ("plain_repeated", "odd_streams_keyed", "every_stream_keyed", "plain_after_clearing"):
+            line[k]["over_plain"] = round(line[k]["kernel_ms_median"] / base, 4)
+        line["MB_read_by_the_detector_from_another_slot"] = {"odd_streams_keyed": round(S // 2 * F * ch * 2 / 1e6, 1),
+                                                             "every_stream_keyed": round(S * F * ch * 2 / 1e6, 1)}
+        print(json.dumps(line), flush=True)
+        m.close()
+        cm.lib.cmhip_device_free(0, dst)
+        src.close()
+    print(json.dumps({"k_dynk": count_asm("k_dynk")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--count-asm", action="store_true")
+    ap.add_argument("--key", action="store_true")
     a = ap.parse_args()
     if a.count_asm:
-        print(json.dumps({"k_dyn": count_asm()}))
+        print(json.dumps({"k_dyn": count_asm(), "k_dynk": count_asm("k_dynk")}))
+        return
+    if a.key:
+        keyed(a)
         return
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
