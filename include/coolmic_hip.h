@@ -695,7 +695,45 @@ int      cmhip_bus_ramp_state(const cmhip_bus_t *m, size_t send, uint32_t *done,
  * Composition: as the mixer -- out = cmhip_batch_dev_in(b), out_stride = cmhip_batch_stride(b) of a batch with the same
  *   channels; with hip_stream = cmhip_batch_hip_stream(b) the order is the stream's.  The chain is source -> rate
  *   (cmhip_src_t) -> width (cmhip_mix_t) -> sum (cmhip_bus_t) -> limit (cmhip_lim_t) -> batch.
- * cmhip_lim_new returns NULL on failure; max_frames * channels may not pass 2^31 samples. */
+ * cmhip_lim_new returns NULL on failure; max_frames * channels may not pass 2^31 samples.
+ *
+ * True-peak detector.  A limiter has a detector, fixed at creation: CMHIP_LIM_DETECT_SAMPLE (0) is everything above,
+ *   CMHIP_LIM_DETECT_TRUE_PEAK (1) derives the gain from the 4x oversampled signal of BS.1770 Annex 2 (the filter of the
+ *   batch's true-peak meter, H = cmhip_tp_coefficients(), 4 phases of 12 taps in units of 2^-13), so that the ceiling
+ *   also holds between the samples: what EBU R128's -1 dBTP asks for at the end of a programme chain.
+ *   Arithmetic.  For frame n of a stream, counted over everything it was ever given, zeros before the first frame or a
+ *   reset:
+ *       y_p[n][c] = sum_{k<12} H[p][k] * x[n-k][c]         p = 0..3, exact in int32
+ *       t[n]   = max_c max(|x[n-8][c]| << 13, max_p |y_p[n-2][c]|)          <= 16571 * 32768 < 2^30
+ *       pr[n]  = (drive * t[n] + 2^25 - 1) >> 25           64-bit product; <= 1 060 528 < 2^21
+ *       g[n]   = 32768 if pr[n] <= T, else floor(T * 32768 / pr[n])
+ *       m[n], S[n], s[n], c[n] exactly as above
+ *       y[n][ch] = (x[n-Dtp][ch] * c[n] + 2^26) >> 27,     Dtp = A + 7
+ *   Alignment.  Phase 0 peaks at tap 6 and phase 3 at tap 5, so the four values y_p[n-2] lie between x[n-8] and x[n-7]:
+ *     t[n] covers sample n - 8 and the interval behind it, in the filter's units of 2^13 per sample unit.
+ *   Geometry.  An output depends on HISTtp = A + W - 2 + 13 earlier frames.  The detector requires hold >= 1 and
+ *     A + W <= 2549 (HISTtp <= 2560; only a = 9 is affected: hold <= 1525).  Why hold >= 1: the interval between x[m]
+ *     and x[m+1] is detector index m + 8, and output frame n carries x[n - Dtp].  For the gain on x[m+1] to be bounded
+ *     by that interval's g as well, every window m[n-j], j < A, must contain g-index n - D - 1, which needs
+ *     j + W - 1 >= D + 1 at j = 0: W >= A + 1.
+ *   Sample ceiling, by construction as above: |x[n-8]| * 2^13 <= t[n] gives |x| * drive <= 4096 * pr, and s[n] <= g of
+ *     that frame, so |y| <= T always and nothing is saturated.
+ *   True-peak ceiling where the gain is constant: if s is the same over the 12 frames a filter output spans, then
+ *     |sum_k H[p][k] * y[n-k]| <= T * 2^13 + 8286: the signal's part is at most T * 2^13 by the definition of g, the
+ *     output rounding's at most sum |H[p][k]| / 2.  Where the gain MOVES inside those 12 frames this is NOT a guarantee:
+ *     the filtered product is not the product of the filtered signal.  DESIGN 4.10 records the overshoot a model shows
+ *     (a longer attack makes it smaller); a caller who needs a proof meters the result (cmhip_batch_set_true_peak).
+ *   Unchanged: transparency (below the threshold at unity drive the output is the input delayed by Dtp, bit for bit),
+ *     cuts (the history is raw input, HISTtp frames rounded up to 8), a stream given 0 frames keeps everything, the meter
+ *     is the minimum of s, the parameter word and the order of cmhip_lim_set with the runs.  A caller flushes with Dtp
+ *     frames of silence.
+ * cmhip_lim_new_detector: cmhip_lim_new with a detector (0: cmhip_lim_new itself); NULL for a detector above 1 and, for
+ *   detector 1, for hold == 0 or A + W > 2549.  cmhip_lim_detector: the object's.  cmhip_lim_delay: D or Dtp.
+ *   run, set, get, reset, min_gain, sync and hip_stream serve both.
+ * cmhip_lim_check_detector (host only): cmhip_lim_check for a detector.  cmhip_lim_threshold_dbtp (host only): the
+ *   threshold for a ceiling in dBTP, floor(32768 * 10^(dbtp / 20)) clamped to 1..32767 (-1.0 gives 29204); 0 for NaN. */
+#define CMHIP_LIM_DETECT_SAMPLE    0u
+#define CMHIP_LIM_DETECT_TRUE_PEAK 1u
 typedef struct cmhip_lim cmhip_lim_t;
 typedef struct cmhip_lim_desc {
     int          device;          /* HIP device ordinal */
@@ -707,6 +745,8 @@ typedef struct cmhip_lim_desc {
     void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
 } cmhip_lim_desc_t;
 cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d);
+cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsigned int detector);
+unsigned int cmhip_lim_detector(const cmhip_lim_t *m);
 void     cmhip_lim_free(cmhip_lim_t *m);
 unsigned int cmhip_lim_delay(const cmhip_lim_t *m);
 int      cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned int threshold, unsigned int drive);
@@ -719,6 +759,9 @@ int      cmhip_lim_sync(cmhip_lim_t *m);
 void    *cmhip_lim_hip_stream(cmhip_lim_t *m);
 /* host only, no device needed */
 int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigned int threshold, unsigned int drive);
+int      cmhip_lim_check_detector(unsigned int detector, unsigned int lookahead_log2, unsigned int hold,
+                                  unsigned int threshold, unsigned int drive);
+unsigned int cmhip_lim_threshold_dbtp(double dbtp);
 
 /* ---- dynamics: compressor and gate, an object of its own beside the batch ----------- */
 /* A dynamics stage takes S streams of `channels` interleaved int16 channels in and gives the same out, delayed by a

@@ -263,6 +263,10 @@ SIGNATURES = {
     "cmhip_lim_sync": (C.c_int, [_vp]),
     "cmhip_lim_hip_stream": (_vp, [_vp]),
     "cmhip_lim_check": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
+    "cmhip_lim_new_detector": (_vp, [_P(LimDesc), C.c_uint]),
+    "cmhip_lim_detector": (C.c_uint, [_vp]),
+    "cmhip_lim_check_detector": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
+    "cmhip_lim_threshold_dbtp": (C.c_uint, [C.c_double]),
     "cmhip_dyn_new": (_vp, [_P(DynDesc)]),
     "cmhip_dyn_free": (None, [_vp]),
     "cmhip_dyn_delay": (C.c_uint, [_vp]),
@@ -422,6 +426,9 @@ if hasattr(lib, "cmhip_test_plan_busramp"):     # (not in builds older than the 
 if hasattr(lib, "cmhip_test_plan_lim"):         # (not in builds older than the peak limiter)
     lib.cmhip_test_plan_lim.restype = None
     lib.cmhip_test_plan_lim.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
+if hasattr(lib, "cmhip_test_plan_limtp"):       # (not in builds older than the limiter's true-peak detector)
+    lib.cmhip_test_plan_limtp.restype = None
+    lib.cmhip_test_plan_limtp.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
 if hasattr(lib, "cmhip_test_plan_dyn"):         # (not in builds older than the dynamics stage)
     lib.cmhip_test_plan_dyn.restype = None
     lib.cmhip_test_plan_dyn.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
@@ -693,6 +700,26 @@ def plan_lim(streams, channels, lookahead_log2, hold, frames):
 def lim_check(lookahead_log2, hold, threshold, drive):
     """cmhip_lim_check as it is -> error number (0: valid)"""
     return lib.cmhip_lim_check(lookahead_log2, hold, threshold, drive)
+
+
+LIM_DETECT_SAMPLE, LIM_DETECT_TRUE_PEAK = 0, 1     # CMHIP_LIM_DETECT_*
+
+
+def plan_limtp(streams, channels, lookahead_log2, hold, frames):
+    """Test hook: plan_lim for a limiter with the true-peak detector (host logic, needs no GPU)"""
+    p = LimPlan()
+    lib.cmhip_test_plan_limtp(streams, channels, lookahead_log2, hold, frames, C.addressof(p))
+    return p
+
+
+def lim_check_detector(detector, lookahead_log2, hold, threshold, drive):
+    """cmhip_lim_check_detector as it is -> error number (0: valid)"""
+    return lib.cmhip_lim_check_detector(detector, lookahead_log2, hold, threshold, drive)
+
+
+def lim_threshold_dbtp(dbtp):
+    """cmhip_lim_threshold_dbtp: the threshold for a ceiling in dBTP (0 for NaN)"""
+    return lib.cmhip_lim_threshold_dbtp(dbtp)
 
 
 DYN_CURVE = 128     # CMHIP_DYN_CURVE
@@ -1273,22 +1300,30 @@ class Bus(_Stage):
 
 class Limiter(_Stage):
     """cmhip_lim_t: a look-ahead peak limiter of S streams beside a batch; per stream a threshold (sample units) and a
-    drive (units of 2^-12).  The output is the input delayed by delay() frames and never above the threshold."""
+    drive (units of 2^-12).  The output is the input delayed by delay() frames and never above the threshold.
+    detector=None creates it with cmhip_lim_new, a detector (LIM_DETECT_SAMPLE: the same limiter; LIM_DETECT_TRUE_PEAK: the
+    gain follows the 4x oversampled signal) with cmhip_lim_new_detector."""
 
     _stem = "lim"
 
     def __init__(self, streams, channels, lookahead_log2, hold, max_frames, threshold=None, drive=None, device=0,
-                 hip_stream=None):
+                 hip_stream=None, detector=None):
         d = LimDesc(device, streams, channels, lookahead_log2, hold, max_frames, hip_stream)
-        self.h = lib.cmhip_lim_new(C.byref(d))
+        if detector is None:                        # the constructor without a detector: the sample detector
+            what, self.h = "cmhip_lim_new", lib.cmhip_lim_new(C.byref(d))
+        else:
+            what, self.h = "cmhip_lim_new_detector", lib.cmhip_lim_new_detector(C.byref(d), detector)
         if not self.h:
-            raise CoolmicError("cmhip_lim_new", ERROR_INVAL)
+            raise CoolmicError(what, ERROR_INVAL)
         self.streams, self.channels, self.max_frames = streams, channels, max_frames
         if threshold is not None or drive is not None:
             self.set(-1, 32767 if threshold is None else threshold, 4096 if drive is None else drive)
 
     def delay(self):
         return lib.cmhip_lim_delay(self.h)
+
+    def detector(self):
+        return lib.cmhip_lim_detector(self.h)
 
     def set_rc(self, stream, threshold, drive):
         """cmhip_lim_set as it is -> error number"""

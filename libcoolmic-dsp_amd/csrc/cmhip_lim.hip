@@ -1,5 +1,6 @@
 // cmhip_lim.hip -- the peak limiter on the host side (include/coolmic_hip.h, "peak limiter"): the limiter object beside
-// the batch, its validation, the launch of k_lim.hip's kernels, parameters, reset and the gain-reduction meter.
+// the batch, its validation, the launch of k_lim.hip's kernels (the sample detector) or k_limtp.hip's (the true-peak
+// detector, fixed at creation), parameters, reset and the gain-reduction meter.
 //
 // Device state of a limiter: one parameter word per stream (threshold | drive << 16), the streams' history, int16
 // [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
@@ -8,6 +9,7 @@
 // by the stream alone and no staging memory outlives the call.
 #include "cmhip_engine.h"
 
+#include <math.h>
 #include <string.h>
 
 #include <new>
@@ -16,7 +18,8 @@ constexpr uint64_t LIM_MAX_SAMPLES = 1ull << 31;     // per slot and run: the ke
 
 struct cmhip_lim : StageBase {
     cmhip_lim_desc_t d;
-    LimGeom g;
+    LimGeom g;                         // of the detector: D, HIST and halo differ between the two
+    unsigned detector;
     uint32_t *d_par;
     uint32_t *d_gmin;
     int16_t *d_hist;
@@ -34,6 +37,29 @@ extern "C" int cmhip_lim_check(unsigned lookahead_log2, unsigned hold, unsigned 
     if (!lim_params_ok(threshold, drive))
         return fail(COOLMIC_ERROR_INVAL, "lim: threshold %u, drive %u: 1..32767 and 1..65535", threshold, drive);
     return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_lim_check_detector(unsigned detector, unsigned lookahead_log2, unsigned hold, unsigned threshold,
+                                        unsigned drive)
+{
+    if (detector == CMHIP_LIM_DETECT_SAMPLE)
+        return cmhip_lim_check(lookahead_log2, hold, threshold, drive);
+    if (detector != CMHIP_LIM_DETECT_TRUE_PEAK)
+        return fail(COOLMIC_ERROR_INVAL, "lim: detector %u: 0 (sample) or 1 (true peak)", detector);
+    if (!lim_geom_tp(lookahead_log2, hold, nullptr))
+        return fail(COOLMIC_ERROR_INVAL, "lim: true-peak detector: lookahead_log2 %u, hold %u: 3..9, hold >= 1, and "
+                    "2 * 2^lookahead_log2 + hold <= 2549", lookahead_log2, hold);
+    if (!lim_params_ok(threshold, drive))
+        return fail(COOLMIC_ERROR_INVAL, "lim: threshold %u, drive %u: 1..32767 and 1..65535", threshold, drive);
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" unsigned cmhip_lim_threshold_dbtp(double dbtp)
+{
+    if (isnan(dbtp))
+        return 0u;
+    const double t = floor(32768.0 * pow(10.0, dbtp / 20.0));
+    return t < 1.0 ? 1u : t > (double)LIM_T_MAX ? LIM_T_MAX : (unsigned)t;
 }
 
 static int lim_init(cmhip_lim_t *m)
@@ -67,13 +93,28 @@ extern "C" void cmhip_lim_free(cmhip_lim_t *m)
 
 extern "C" cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d)
 {
+    return cmhip_lim_new_detector(d, CMHIP_LIM_DETECT_SAMPLE);
+}
+
+extern "C" cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsigned detector)
+{
     if (!d) {
         fail(COOLMIC_ERROR_FAULT, "lim_new: NULL argument");
         return nullptr;
     }
+    if (detector > CMHIP_LIM_DETECT_TRUE_PEAK) {
+        fail(COOLMIC_ERROR_INVAL, "lim_new: detector %u: 0 (sample) or 1 (true peak)", detector);
+        return nullptr;
+    }
     LimGeom g;
+    if (detector == CMHIP_LIM_DETECT_TRUE_PEAK && lim_geom(d->lookahead_log2, d->hold, &g) &&
+        !lim_geom_tp(g.a, g.H, nullptr)) {           // (a geometry the sample detector would take)
+        fail(COOLMIC_ERROR_INVAL, "lim_new: the true-peak detector needs hold >= 1 and 2 * 2^lookahead_log2 + hold <= "
+             "2549 (lookahead_log2 %u, hold %u)", d->lookahead_log2, d->hold);
+        return nullptr;
+    }
     if (d->streams == 0 || d->channels == 0 || d->channels > MAX_CH || d->max_frames == 0 ||
-        !lim_geom(d->lookahead_log2, d->hold, &g)) {
+        !lim_geom_of(detector, d->lookahead_log2, d->hold, &g)) {
         fail(COOLMIC_ERROR_INVAL, "lim_new: streams, channels (1..16) and max_frames must be positive, lookahead_log2 "
              "in 3..9 and 2^lookahead_log2 + hold <= 2048");
         return nullptr;
@@ -93,6 +134,7 @@ extern "C" cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d)
     }
     m->d = *d;
     m->g = g;
+    m->detector = detector;
     if (lim_init(m)) {
         cmhip_lim_free(m);
         return nullptr;
@@ -102,6 +144,8 @@ extern "C" cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d)
 
 extern "C" unsigned cmhip_lim_delay(const cmhip_lim_t *m) { return m ? m->g.D : 0u; }
 
+extern "C" unsigned cmhip_lim_detector(const cmhip_lim_t *m) { return m ? m->detector : 0u; }
+
 extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, unsigned drive)
 {
     if (!m)
@@ -109,7 +153,7 @@ extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, un
     const StreamRange sr = stream_range(stream, m->d.streams);
     if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "lim_set: stream %ld out of range", stream);
-    const int rc = cmhip_lim_check(m->g.a, m->g.H, threshold, drive);
+    const int rc = cmhip_lim_check_detector(m->detector, m->g.a, m->g.H, threshold, drive);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(m->d.device));
@@ -179,7 +223,7 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     const int refused = stage_run_refusal("lim_run", r);
     if (refused)
         return refused;
-    if (plan_lim(S, C, m->g.a, m->g.H, (uint32_t)frames).err)
+    if (plan_lim_of(m->detector, S, C, m->g.a, m->g.H, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "lim_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
     // nothing was touched so far; from here on the run happens
@@ -204,7 +248,8 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     a.W = m->g.W;
     if (frames_per_stream)
         HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    const hipError_t e = launch_lim(a, m->stream);
+    const hipError_t e =
+        m->detector == CMHIP_LIM_DETECT_TRUE_PEAK ? launch_limtp(a, m->stream) : launch_lim(a, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "lim_run: %s", hipGetErrorString(e));
     m->parity ^= 1u;                         // the kernel wrote the other slots

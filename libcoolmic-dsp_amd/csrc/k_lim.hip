@@ -26,27 +26,9 @@
 //      non-temporal vectors, the stream's ragged end through store_tail.  The minimum of s over the tile is reduced
 //      over the workgroup and merged with ONE atomicMin.
 //   4. The stream's last tile writes the other history slot: the last halo frames of (old slot, run's input).
-#include "cmhip_device.h"
+#include "k_lim.h"
 
 namespace cmhip {
-
-constexpr u32 LIM_R = (LIM_TILE_MAX + LIM_HALO_MAX) / LIM_BLOCK;     // 26 elements per thread at most
-
-// floor(num / pr) for num = T << 15 (15 significant bits: exact as a float), T < pr <= 2^19 (exact as a float): the
-// quotient is below 2^15, the reciprocal instruction (v_rcp_f32 / v_rcp_iflag_f32) is within one ulp and the product
-// rounds once, so the estimate is less than 2^-6 away from the quotient and its floor at most one off, either way; one
-// correction step each way makes it exact
-// (tests/test_lim_host.py runs this form over every pr for nine thresholds, the reciprocal one ulp low, exact, high)
-__device__ __forceinline__ u32 lim_div(u32 num, u32 pr)
-{
-    u32 q = (u32)((float)num * __builtin_amdgcn_rcpf((float)pr));
-    const int r = (int)(num - q * pr);               // in (-pr, 2 pr)
-    if (r < 0)
-        q -= 1u;
-    else if ((u32)r >= pr)
-        q += 1u;
-    return q;
-}
 
 __device__ __forceinline__ u32 lim_gain(u32 peak, u32 drive, u32 T)
 {
@@ -54,44 +36,8 @@ __device__ __forceinline__ u32 lim_gain(u32 peak, u32 drive, u32 T)
     return pr <= T ? LIM_UNITY : lim_div(T << 15, pr);
 }
 
-__device__ __forceinline__ u32 lim_abs(int x) { return (u32)(x < 0 ? -x : x); }
-__device__ __forceinline__ int lim_lo(u32 w) { return (int)(short)(w & 0xffffu); }
-__device__ __forceinline__ int lim_hi(u32 w) { return (int)w >> 16; }
-
-// one sample: the 64-bit product (v_mad_i64_i32), exact; |y| <= T, so nothing is clamped
-__device__ __forceinline__ u32 lim_apply(int x, u32 c)
-{
-    const long long y = ((long long)x * (long long)(int)c + (1ll << 26)) >> 27;
-    return (u32)(int)y & 0xffffu;
-}
-
-// vector vv of the stream as a tile sees it: the history slot below 0, the run's slot from 0 on, zeros past the count
-__device__ __forceinline__ void lim_load(u32 (&x)[4], const int16_t *ins, const int16_t *hs, u32 hv, int vv, u32 nfull,
-                                         u32 ntail)
-{
-    if (vv < 0) {
-        const u32x4 w = reinterpret_cast<const u32x4 *>(hs)[hv + vv];
-        x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
-    } else {
-        const u32 v = (u32)vv;
-        load_vec(x, ins, v, v < nfull, v == nfull && ntail != 0, ntail);
-    }
-}
-// sample q of the same sequence (q >= -halo * C, below the count)
-__device__ __forceinline__ int lim_sample(const int16_t *ins, const int16_t *hs, u32 hsamp, int q)
-{
-    return q < 0 ? hs[hsamp + q] : ins[q];
-}
-
-// the other history slot: the last halo frames of (old slot, the run's F frames)
-__device__ __forceinline__ void lim_write_hist(const int16_t *ins, const int16_t *hs, int16_t *hn, u32 hsamp, u32 F, u32 C)
-{
-    const int first = (int)(F * C) - (int)hsamp;     // sample of the sequence that becomes sample 0 of the slot
-    for (u32 i = threadIdx.x; i < hsamp; i += LIM_BLOCK)
-        hn[i] = (int16_t)lim_sample(ins, hs, hsamp, first + (int)i);
-}
-
 // C: 1 or 2, or 0 for a run-time channel count
+// (k_limtp.hip's limtp_tile carries a second copy of steps 2 to 4 and the meter: a change to them goes into both)
 template <int CT>
 __device__ __forceinline__ void lim_tile(const LimArgs &a, u32 *L, u32 *red)
 {

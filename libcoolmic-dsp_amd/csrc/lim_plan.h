@@ -9,6 +9,11 @@
 //   A workgroup of 256 threads takes one stream and a tile of tile_frames frames: the largest power of two <= 4096 that
 //   is >= halo (so the frames in front of a tile never reach past the previous tile) and whose per-frame dwords,
 //   (tile_frames + halo) * 4 bytes of dynamic LDS, fit 64 KiB (no per-device limit is raised).
+//
+// The true-peak detector (LIM_DETECT_TRUE_PEAK; k_limtp.hip) looks at the 4x oversampled signal: its g of frame n covers
+// sample n - 8 and the interval behind it and needs the 13 frames x[n-13 .. n-1].  D = A + 7 (so that D + 1 stays a
+// multiple of 8 frames), HIST = A + W - 2 + 13; hold >= 1, so that an interval's gain also covers the interval's second
+// end sample, and A + W <= 2549, so that HIST <= 2560 = LIM_HALO_MAX: lim_geom_tp / plan_limtp.  The rest is the same.
 #ifndef CMHIP_LIM_PLAN_H
 #define CMHIP_LIM_PLAN_H
 
@@ -26,6 +31,10 @@ constexpr uint32_t LIM_HALO_MAX = 2560;              // a = 9, W = 2048: HIST = 
 constexpr uint32_t LIM_T_MAX = 32767;
 constexpr uint32_t LIM_DRIVE_MAX = 65535;
 constexpr uint32_t LIM_UNITY = 32768;                // Q15
+constexpr uint32_t LIM_DETECT_SAMPLE = 0, LIM_DETECT_TRUE_PEAK = 1;
+constexpr uint32_t LIM_TP_FRONT = 13;                // frames in front of frame n that the true-peak g[n] reads
+constexpr uint32_t LIM_TP_LAG = 8;                   // what the true-peak detector adds to the delay
+constexpr uint32_t LIM_TP_AW_MAX = LIM_HALO_MAX + 2u - LIM_TP_FRONT;     // 2549: A + W at most
 
 struct LimGeom {
     uint32_t a, A, D, H, W, hist, halo;
@@ -51,6 +60,28 @@ inline bool lim_geom(uint32_t lookahead_log2, uint32_t hold, LimGeom *g)
     return true;
 }
 
+// the same for the true-peak detector: also false for hold 0 and for A + W > 2549
+inline bool lim_geom_tp(uint32_t lookahead_log2, uint32_t hold, LimGeom *g)
+{
+    LimGeom t;
+    if (hold == 0 || !lim_geom(lookahead_log2, hold, &t) || t.A + t.W > LIM_TP_AW_MAX)
+        return false;
+    if (g) {
+        t.D += LIM_TP_LAG;
+        t.hist += LIM_TP_FRONT;
+        t.halo = (t.hist + 7u) & ~7u;
+        *g = t;
+    }
+    return true;
+}
+
+inline bool lim_geom_of(uint32_t detector, uint32_t lookahead_log2, uint32_t hold, LimGeom *g)
+{
+    return detector == LIM_DETECT_SAMPLE      ? lim_geom(lookahead_log2, hold, g)
+           : detector == LIM_DETECT_TRUE_PEAK ? lim_geom_tp(lookahead_log2, hold, g)
+                                              : false;
+}
+
 inline bool lim_params_ok(uint32_t threshold, uint32_t drive)
 {
     return threshold >= 1u && threshold <= LIM_T_MAX && drive >= 1u && drive <= LIM_DRIVE_MAX;
@@ -66,12 +97,14 @@ struct LimPlan {
     uint32_t halo;
 };
 
-// the plan of a run whose longest stream has `frames` frames
-inline LimPlan plan_lim(uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold, uint32_t frames)
+// the plan of a run whose longest stream has `frames` frames, for either detector
+inline LimPlan plan_lim_of(uint32_t detector, uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold,
+                           uint32_t frames)
 {
     LimPlan p{};
     LimGeom g;
-    if (streams == 0 || frames == 0 || channels == 0 || channels > LIM_MAX_CH || !lim_geom(lookahead_log2, hold, &g))
+    if (streams == 0 || frames == 0 || channels == 0 || channels > LIM_MAX_CH ||
+        !lim_geom_of(detector, lookahead_log2, hold, &g))
         return p;
     uint32_t tile = LIM_TILE_MAX;
     while (tile / 2u >= g.halo && tile / 2u >= 8u && (tile + g.halo) * 4u > LIM_LDS_LIMIT)
@@ -89,6 +122,16 @@ inline LimPlan plan_lim(uint32_t streams, uint32_t channels, uint32_t lookahead_
     p.chunks = (uint32_t)tiles;
     p.grid = streams * p.chunks;
     return p;
+}
+
+inline LimPlan plan_lim(uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold, uint32_t frames)
+{
+    return plan_lim_of(LIM_DETECT_SAMPLE, streams, channels, lookahead_log2, hold, frames);
+}
+
+inline LimPlan plan_limtp(uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold, uint32_t frames)
+{
+    return plan_lim_of(LIM_DETECT_TRUE_PEAK, streams, channels, lookahead_log2, hold, frames);
 }
 
 }  // namespace cmhip
