@@ -818,6 +818,26 @@ unsigned int cmhip_lim_threshold_dbtp(double dbtp);
  *   zeroes the history and the meter of s only: resetting a key changes what its followers detect, resetting a
  *   follower leaves its key's history alone.  At creation every stream is its own key, and an object on which no key
  *   is set behaves, and runs, exactly as one without this paragraph.
+ * RMS detector.  A dynamics stage has a detector, fixed at creation: CMHIP_DYN_DETECT_MEAN (0) is everything above,
+ *   CMHIP_DYN_DETECT_RMS (1) follows the power of the loudest channel, as a broadcast compressor and the loudness meter
+ *   beside it do, so that a threshold in dBFS means the same for speech, music and tones.  One line of the arithmetic
+ *   changes:
+ *       e[n]  = max_c |x[n][c]|                          as above (with a key: the key's raw input), 0..32768
+ *       M[n]  = (sum(e[k]^2, k = n-A+1 .. n)) >> a       mean square; the sum is at most 2^40, M <= 2^30
+ *       L[n]  = isqrt(M[n])                              the largest r with r*r <= M[n]; 0..32768
+ *       l, g, s, y                                       as above
+ *   The root is exact: no result depends on how a floating-point operation rounds.  Everything else stays the stream's
+ *   own and stays as it is: the geometry (a, b, H, W, HIST, D = B - 1), the curve and its index, the history of raw
+ *   frames, cuts, the meter, resets, side-chain keys and every refusal; |y| <= |x| still holds by construction.  The
+ *   curve keeps its meaning, gain against level on the amplitude grid, so cmhip_dyn_design and cmhip_dyn_design_duck
+ *   serve both detectors unchanged.
+ *   For a signal of constant magnitude both detectors give the same level (the mean of A equal squares is the square,
+ *   and its root the magnitude).  A full-scale sine reads 23170 (32768 / sqrt 2, -3.01 dBFS) under RMS; under the mean
+ *   it reads about 20861 (32768 * 2 / pi, -3.92 dBFS), 0.91 dB lower, while a square wave reads its amplitude under both.
+ * cmhip_dyn_new_detector: cmhip_dyn_new with a detector (cmhip_dyn_new(d) is cmhip_dyn_new_detector(d, 0) and runs the
+ *   kernels it always ran); NULL for a detector above 1.  cmhip_dyn_detector: the object's (0 for NULL).  Every other
+ *   call serves both.  cmhip_dyn_check_detector (host only): cmhip_dyn_check for a detector, COOLMIC_ERROR_INVAL for a
+ *   detector above 1.
  *
  * cmhip_dyn_run has cmhip_lim_run's contract: `in` is int16 [S][in_stride], `out` int16 [S][out_stride], strides in
  *   samples, both device-accessible; asynchronous on the stage's stream.  `frames` frames per stream, or
@@ -863,12 +883,14 @@ unsigned int cmhip_lim_threshold_dbtp(double dbtp);
  *   (cmhip_src_t) -> width (cmhip_mix_t) -> sum (cmhip_bus_t) -> dynamics (cmhip_dyn_t) -> limit (cmhip_lim_t) -> batch.
  * cmhip_dyn_new returns NULL on failure; max_frames * channels may not pass 2^31 samples. */
 #define CMHIP_DYN_CURVE 128
+#define CMHIP_DYN_DETECT_MEAN 0u
+#define CMHIP_DYN_DETECT_RMS  1u
 typedef struct cmhip_dyn cmhip_dyn_t;
 typedef struct cmhip_dyn_desc {
     int          device;          /* HIP device ordinal */
     unsigned int streams;         /* S >= 1 */
     unsigned int channels;        /* 1..16 */
-    unsigned int detector_log2;   /* a in 3..10: the level is the mean magnitude over 2^a frames */
+    unsigned int detector_log2;   /* a in 3..10: the level is the mean magnitude (or the RMS) over 2^a frames */
     unsigned int smooth_log2;     /* b in 3..9: B = 2^b, delay B - 1 frames */
     unsigned int hold;            /* H frames, B + hold <= 2048 */
     size_t       max_frames;      /* per run and stream */
@@ -884,6 +906,8 @@ typedef struct cmhip_dyn_curve_desc {
 } cmhip_dyn_curve_desc_t;
 typedef struct cmhip_dyn_duck_desc { double threshold_db, depth_db, knee_db; } cmhip_dyn_duck_desc_t;
 cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d);
+cmhip_dyn_t *cmhip_dyn_new_detector(const cmhip_dyn_desc_t *d, unsigned int detector);
+unsigned int cmhip_dyn_detector(const cmhip_dyn_t *m);
 void     cmhip_dyn_free(cmhip_dyn_t *m);
 unsigned int cmhip_dyn_delay(const cmhip_dyn_t *m);
 int      cmhip_dyn_set_curve(cmhip_dyn_t *m, long stream, const uint16_t *curve /* [CMHIP_DYN_CURVE] */);
@@ -898,6 +922,8 @@ int      cmhip_dyn_sync(cmhip_dyn_t *m);
 void    *cmhip_dyn_hip_stream(cmhip_dyn_t *m);
 /* host only, no device needed */
 int      cmhip_dyn_check(unsigned int detector_log2, unsigned int smooth_log2, unsigned int hold);
+int      cmhip_dyn_check_detector(unsigned int detector, unsigned int detector_log2, unsigned int smooth_log2,
+                                  unsigned int hold);
 int      cmhip_dyn_design(const cmhip_dyn_curve_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
 int      cmhip_dyn_design_duck(const cmhip_dyn_duck_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
 

@@ -282,6 +282,9 @@ SIGNATURES = {
     "cmhip_dyn_set_key": (C.c_int, [_vp, C.c_long, C.c_long]),
     "cmhip_dyn_get_key": (C.c_int, [_vp, C.c_uint, _P(C.c_long)]),
     "cmhip_dyn_design_duck": (C.c_int, [_P(DynDuckDesc), _vp]),
+    "cmhip_dyn_new_detector": (_vp, [_P(DynDesc), C.c_uint]),
+    "cmhip_dyn_detector": (C.c_uint, [_vp]),
+    "cmhip_dyn_check_detector": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "cmhip_batch_vu_node_partial": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_batch_vu_node_record": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
     "cmhip_node_finish": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(VuResult)]),
@@ -434,6 +437,11 @@ if hasattr(lib, "cmhip_test_plan_dyn"):         # (not in builds older than the 
     lib.cmhip_test_plan_dyn.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
     lib.cmhip_test_dyn_curve_ok.restype = C.c_int
     lib.cmhip_test_dyn_curve_ok.argtypes = [_vp]
+if hasattr(lib, "cmhip_test_plan_dynrms"):      # (not in builds older than the dynamics stage's RMS detector)
+    lib.cmhip_test_plan_dynrms.restype = None
+    lib.cmhip_test_plan_dynrms.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
+    lib.cmhip_test_dyn_isqrt.restype = C.c_uint32
+    lib.cmhip_test_dyn_isqrt.argtypes = [C.c_uint32]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -742,6 +750,26 @@ def plan_dyn(streams, channels, detector_log2, smooth_log2, hold, frames):
 def dyn_check(detector_log2, smooth_log2, hold):
     """cmhip_dyn_check as it is -> error number (0: valid)"""
     return lib.cmhip_dyn_check(detector_log2, smooth_log2, hold)
+
+
+DYN_DETECT_MEAN, DYN_DETECT_RMS = 0, 1     # CMHIP_DYN_DETECT_*
+
+
+def plan_dynrms(streams, channels, detector_log2, smooth_log2, hold, frames):
+    """Test hook: plan_dyn for a stage with the RMS detector (host logic, needs no GPU)"""
+    p = DynPlan()
+    lib.cmhip_test_plan_dynrms(streams, channels, detector_log2, smooth_log2, hold, frames, C.addressof(p))
+    return p
+
+
+def dyn_check_detector(detector, detector_log2, smooth_log2, hold):
+    """cmhip_dyn_check_detector as it is -> error number (0: valid)"""
+    return lib.cmhip_dyn_check_detector(detector, detector_log2, smooth_log2, hold)
+
+
+def dyn_isqrt(v):
+    """Test hook: the RMS detector's root of a 32-bit value, as the kernels take it (csrc/dyn_plan.h)"""
+    return lib.cmhip_test_dyn_isqrt(v)
 
 
 def _dyn_table(curve):
@@ -1360,22 +1388,30 @@ class Dynamics(_Stage):
     """cmhip_dyn_t: a compressor / gate of S streams beside a batch; per stream a curve of 128 uint16 gains (Q15, at most
     32768) over a level grid of 8 knots per octave (dyn_design makes one).  The output is the input delayed by delay()
     frames and never louder than it; make-up gain is the drive of the Limiter that follows.  set_key lets the level of
-    another stream steer a stream's gain (a side-chain: ducking, linked stems)."""
+    another stream steer a stream's gain (a side-chain: ducking, linked stems).  detector=None creates it with
+    cmhip_dyn_new, a detector (DYN_DETECT_MEAN: the same stage; DYN_DETECT_RMS: the level is the root of the mean square)
+    with cmhip_dyn_new_detector."""
 
     _stem = "dyn"
 
     def __init__(self, streams, channels, detector_log2, smooth_log2, hold, max_frames, curve=None, device=0,
-                 hip_stream=None):
+                 hip_stream=None, detector=None):
         d = DynDesc(device, streams, channels, detector_log2, smooth_log2, hold, max_frames, hip_stream)
-        self.h = lib.cmhip_dyn_new(C.byref(d))
+        if detector is None:                        # the constructor without a detector: the mean detector
+            what, self.h = "cmhip_dyn_new", lib.cmhip_dyn_new(C.byref(d))
+        else:
+            what, self.h = "cmhip_dyn_new_detector", lib.cmhip_dyn_new_detector(C.byref(d), detector)
         if not self.h:
-            raise CoolmicError("cmhip_dyn_new", ERROR_INVAL)
+            raise CoolmicError(what, ERROR_INVAL)
         self.streams, self.channels, self.max_frames = streams, channels, max_frames
         if curve is not None:
             self.set_curve(-1, curve)
 
     def delay(self):
         return lib.cmhip_dyn_delay(self.h)
+
+    def detector(self):
+        return lib.cmhip_dyn_detector(self.h)
 
     def set_curve_rc(self, stream, curve):
         """cmhip_dyn_set_curve as it is -> error number"""

@@ -1,6 +1,6 @@
 // cmhip_dyn.hip -- the dynamics stage on the host side (include/coolmic_hip.h, "dynamics"): the object beside the
-// batch, its validation, the launch of k_dyn.hip's kernels (k_dynkey.hip's while a side-chain key is set), the curves,
-// the keys, reset, the gain meter and the curve designers.
+// batch, its validation, the launch of k_dyn.hip's kernels (k_dynkey.hip's while a side-chain key is set; k_dynrms.hip's
+// for an object with the RMS detector), the curves, the keys, reset, the gain meter and the curve designers.
 //
 // Device state of a dynamics stage: one curve of DYN_CURVE uint16 entries per stream, the streams' history, int16
 // [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
@@ -21,6 +21,7 @@ constexpr uint64_t DYN_MAX_SAMPLES = 1ull << 31;     // per slot and run: the ke
 struct cmhip_dyn : StageBase {
     cmhip_dyn_desc_t d;
     DynGeom g;
+    uint32_t detector;                 // DYN_DETECT_*, fixed at creation
     uint16_t *d_curve;
     uint32_t *d_gmin;
     int16_t *d_hist;
@@ -32,6 +33,8 @@ struct cmhip_dyn : StageBase {
 };
 
 static_assert(CMHIP_DYN_CURVE == DYN_CURVE, "the header's curve length is the kernels'");
+static_assert(CMHIP_DYN_DETECT_MEAN == DYN_DETECT_MEAN && CMHIP_DYN_DETECT_RMS == DYN_DETECT_RMS,
+              "the header's detectors are the kernels'");
 
 static size_t dyn_slot(const cmhip_dyn_t *m) { return (size_t)m->g.halo * m->d.channels; }     // samples per stream
 
@@ -41,6 +44,13 @@ extern "C" int cmhip_dyn_check(unsigned detector_log2, unsigned smooth_log2, uns
         return fail(COOLMIC_ERROR_INVAL, "dyn: detector_log2 %u, smooth_log2 %u, hold %u: 3..10, 3..9, and "
                     "2^smooth_log2 + hold <= 2048", detector_log2, smooth_log2, hold);
     return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_dyn_check_detector(unsigned detector, unsigned detector_log2, unsigned smooth_log2, unsigned hold)
+{
+    if (detector > DYN_DETECT_RMS)
+        return fail(COOLMIC_ERROR_INVAL, "dyn: detector %u: 0 (mean magnitude) or 1 (RMS)", detector);
+    return cmhip_dyn_check(detector_log2, smooth_log2, hold);
 }
 
 // test hook: what cmhip_dyn_set_curve asks of a table (host logic, needs no GPU)
@@ -152,10 +162,14 @@ extern "C" void cmhip_dyn_free(cmhip_dyn_t *m)
     delete m;
 }
 
-extern "C" cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d)
+extern "C" cmhip_dyn_t *cmhip_dyn_new_detector(const cmhip_dyn_desc_t *d, unsigned detector)
 {
     if (!d) {
         fail(COOLMIC_ERROR_FAULT, "dyn_new: NULL argument");
+        return nullptr;
+    }
+    if (detector > DYN_DETECT_RMS) {
+        fail(COOLMIC_ERROR_INVAL, "dyn_new: detector %u: 0 (mean magnitude) or 1 (RMS)", detector);
         return nullptr;
     }
     DynGeom g;
@@ -180,12 +194,17 @@ extern "C" cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d)
     }
     m->d = *d;
     m->g = g;
+    m->detector = detector;
     if (dyn_init(m)) {
         cmhip_dyn_free(m);
         return nullptr;
     }
     return m;
 }
+
+extern "C" cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d) { return cmhip_dyn_new_detector(d, DYN_DETECT_MEAN); }
+
+extern "C" unsigned cmhip_dyn_detector(const cmhip_dyn_t *m) { return m ? m->detector : 0u; }
 
 extern "C" unsigned cmhip_dyn_delay(const cmhip_dyn_t *m) { return m ? m->g.D : 0u; }
 
@@ -331,7 +350,12 @@ extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, s
     a.W = m->g.W;
     if (frames_per_stream)
         HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    const hipError_t e = m->keyed ? launch_dynk(a, m->d_key, m->stream) : launch_dyn(a, m->stream);
+    // (the keyed kernels only while a key is set; the mean detector's launches are the ones it always had)
+    hipError_t e;
+    if (m->detector == DYN_DETECT_RMS)
+        e = launch_dynrms(a, m->keyed ? m->d_key : nullptr, m->stream);
+    else
+        e = m->keyed ? launch_dynk(a, m->d_key, m->stream) : launch_dyn(a, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "dyn_run: %s", hipGetErrorString(e));
     m->parity ^= 1u;                         // the kernel wrote the other slots

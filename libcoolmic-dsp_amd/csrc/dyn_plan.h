@@ -1,6 +1,6 @@
 // dyn_plan.h -- the geometry, the curve's index function and the launch plan of the dynamics stage
-// (include/coolmic_hip.h, "dynamics").  Plain C++17, no HIP: tests/cpp/dyn_plan_test.cpp compiles it with g++ alone; the
-// kernels (k_dyn.hip) use the same index function.
+// (include/coolmic_hip.h, "dynamics").  Plain C++17, no HIP: tests/cpp/dyn_plan_test.cpp and tests/cpp/dyn_rms_test.cpp
+// compile it with g++ alone; the kernels (k_dyn.hip, k_dynrms.hip) use the same index function and the same root.
 //
 //   a = detector_log2 in 3..10, A = 2^a: the level window.  b = smooth_log2 in 3..9, B = 2^b: the gain's ramp; D = B - 1
 //   (the delay).  H = hold, W = B + H <= 2048.  HIST = (A - 1) + (W - 1) + (B - 1): the earlier frames an output depends on.
@@ -35,6 +35,9 @@ constexpr uint32_t DYN_UNITY = 32768;                // Q15
 constexpr uint32_t DYN_CURVE = 128;                  // entries of a curve (CMHIP_DYN_CURVE)
 constexpr uint32_t DYN_CURVE_USED = 123;             // entries 0..122 are read
 constexpr uint32_t DYN_KNOT_MAX = 121;               // level 32768: the largest index a lookup reaches
+constexpr uint32_t DYN_DETECT_MEAN = 0;              // CMHIP_DYN_DETECT_*: L is the mean magnitude over A frames ...
+constexpr uint32_t DYN_DETECT_RMS = 1;               // ... or the root of the mean square
+constexpr uint32_t DYN_SQ_SPLIT = 15;                // e^2 = hi * 2^15 + lo: the halves the RMS detector sums apart
 
 struct DynGeom {
     uint32_t a, A, b, B, D, H, W, hist, halo;
@@ -97,6 +100,30 @@ inline uint32_t dyn_curve_at(const uint16_t *T, uint32_t l)
     return (uint32_t)(t0 + (((t1 - t0) * (int)i.frac) >> i.sh));
 }
 
+// The RMS detector's root: the largest r with r * r <= v, for every v below 2^32.  The seed is a float root and the result
+// does not rest on how it rounds: (float)v is off by at most v * 2^-24, a root of a few units in the last place keeps the
+// relative error of the seed below 2^-21, and the root is at most 65536, so the seed lies within 2^-5 of sqrt(v) and its
+// integer part within 1 of the answer.  One step down and one step up, compared in integers, repair that.  The seed is
+// clamped to 65535 first, so r * r and v - r * r stay inside 32 bits.
+CMHIP_DYN_HD inline uint32_t dyn_isqrt(uint32_t v)
+{
+    uint32_t r = (uint32_t)__builtin_sqrtf((float)v);
+    r = r > 65535u ? 65535u : r;
+    if (r * r > v)
+        r--;
+    if (v - r * r > 2u * r)                           // (r + 1)^2 <= v
+        r++;
+    return r;
+}
+
+// The RMS detector's sum of squares from its two halves: with e^2 = hi * 2^15 + lo, lo < 2^15, and the sums of hi and of
+// lo over A = 2^a frames (each at most 2^25), (sum_hi * 2^15 + sum_lo) >> a without 64 bits: a <= 10 < 15, so the first
+// term is a multiple of 2^a and the shift splits.  At most 2^30.
+CMHIP_DYN_HD inline uint32_t dyn_mean_square(uint32_t sum_hi, uint32_t sum_lo, uint32_t a)
+{
+    return (sum_hi << (DYN_SQ_SPLIT - a)) + (sum_lo >> a);
+}
+
 struct DynPlan {
     int      err;                  // 1: refused, the grid would reach 2^31 workgroups
     uint32_t fast;                 // the mono / stereo kernel; otherwise the any-channel-count kernel
@@ -105,17 +132,18 @@ struct DynPlan {
     uint32_t tile_frames;
     uint32_t lds_bytes;            // dynamic LDS of the launch
     uint32_t halo;
-    uint32_t passes;               // a + floor(log2 W) + (W not a power of two) + b
+    uint32_t passes;               // a + floor(log2 W) + (W not a power of two) + b; the RMS detector: a more
 };
 
-// the plan of a run whose longest stream has `frames` frames
+// the plan of a run whose longest stream has `frames` frames.  The RMS detector has the mean detector's tile, grid and
+// LDS: the two halves of a square go through the same dword per frame one after the other (a more add passes).
 inline DynPlan plan_dyn(uint32_t streams, uint32_t channels, uint32_t detector_log2, uint32_t smooth_log2, uint32_t hold,
-                        uint32_t frames)
+                        uint32_t frames, uint32_t detector = DYN_DETECT_MEAN)
 {
     DynPlan p{};
     DynGeom g;
     if (streams == 0 || frames == 0 || channels == 0 || channels > DYN_MAX_CH ||
-        !dyn_geom(detector_log2, smooth_log2, hold, &g))
+        detector > DYN_DETECT_RMS || !dyn_geom(detector_log2, smooth_log2, hold, &g))
         return p;
     uint32_t tile = DYN_TILE_MAX;
     while (tile / 2u >= g.halo && tile / 2u >= 8u && (tile + g.halo) * 4u > DYN_LDS_LIMIT)
@@ -135,7 +163,7 @@ inline DynPlan plan_dyn(uint32_t streams, uint32_t channels, uint32_t detector_l
     uint32_t P = 1, lw = 0;
     for (; 2u * P <= g.W; P *= 2u)
         lw++;
-    p.passes = g.a + lw + (g.W > P ? 1u : 0u) + g.b;
+    p.passes = g.a + lw + (g.W > P ? 1u : 0u) + g.b + (detector == DYN_DETECT_RMS ? g.a : 0u);
     return p;
 }
 

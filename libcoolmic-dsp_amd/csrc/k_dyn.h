@@ -1,5 +1,6 @@
-// k_dyn.h -- what the dynamics stage's kernel files share (k_dyn.hip, k_dynkey.hip): the helpers and the tile body of the
-// decomposition k_dyn.hip describes, with the detector's source as a compile-time parameter.  KEYED = false: the level
+// k_dyn.h -- what the dynamics stage's kernel files share (k_dyn.hip, k_dynkey.hip, k_dynrms.hip): the helpers and the
+// tile body of the decomposition k_dyn.hip describes, with the detector's source and the detector as compile-time
+// parameters (DET = DYN_DETECT_RMS: k_dynrms.hip, which says how step 2 sums the squares).  KEYED = false: the level
 // follows the stream's own frames (k_dyn_fast<C>, k_dyn_any).  KEYED = true: step 1 takes its run slot, history slot
 // and history vector base from stream key[s] (k_dynk_fast<C>, k_dynk_any); step 3, step 4, the copy of a stream
 // without frames, the curve and the meter stay stream s's own.  A keyed stream and its key have equal counts (the host
@@ -67,8 +68,9 @@ __device__ __forceinline__ void dyn_stage_curve(const uint16_t *c, u32 *cv)
         cv[tid] = (u32)c[tid] | (u32)c[tid + 1u] << 16;
 }
 
-// C: 1 or 2, or 0 for a run-time channel count; KEYED: the detector reads stream key[s] (key: uint32 [S], else unused)
-template <int CT, bool KEYED>
+// C: 1 or 2, or 0 for a run-time channel count; KEYED: the detector reads stream key[s] (key: uint32 [S], else unused);
+// DET: DYN_DETECT_MEAN or DYN_DETECT_RMS
+template <int CT, bool KEYED, u32 DET = DYN_DETECT_MEAN>
 __device__ __forceinline__ void dyn_tile(const DynArgs &a, const u32 *key, u32 *L, u32 *cv, u32 *red)
 {
     const u32 C = CT ? (u32)CT : a.channels;
@@ -183,8 +185,47 @@ __device__ __forceinline__ void dyn_tile(const DynArgs &a, const u32 *key, u32 *
         __syncthreads();
     };
     const u32 W = a.W, la = a.a, lb = a.b;
-    for (u32 d = 1; d < (1u << la); d *= 2u)
-        pass(d, std::false_type{}, 2u * d == (1u << la) ? la : 0u);     // sums below 2^26; leaves L
+    if constexpr (DET == DYN_DETECT_RMS) {
+        // the mean square from two 32-bit sums: e^2 = hi * 2^15 + lo; the low halves go through the a passes first while e
+        // waits in registers, then the high halves while sum_lo waits there; the two meet in dyn_mean_square, and the
+        // root leaves L.  An element without a partner or a slot past N takes the same entries in both rounds, so it too
+        // is a mean of A squares, at most 2^30.
+        u32 w[DYN_R];
+#pragma unroll
+        for (u32 i = 0; i < DYN_R; i++) {
+            const u32 j = tid + DYN_BLOCK * i;
+            w[i] = v[i];
+            v[i] = (w[i] * w[i]) & ((1u << DYN_SQ_SPLIT) - 1u);
+            if (j < N)
+                L[j] = v[i];
+        }
+        __syncthreads();
+        for (u32 d = 1; d < (1u << la); d *= 2u)
+            pass(d, std::false_type{}, 0);                   // sums below 2^25
+#pragma unroll
+        for (u32 i = 0; i < DYN_R; i++) {
+            const u32 j = tid + DYN_BLOCK * i;
+            const u32 hi = (w[i] * w[i]) >> DYN_SQ_SPLIT;
+            w[i] = v[i];
+            v[i] = hi;
+            if (j < N)
+                L[j] = v[i];
+        }
+        __syncthreads();
+        for (u32 d = 1; d < (1u << la); d *= 2u)
+            pass(d, std::false_type{}, 0);                   // sums at most 2^25
+#pragma unroll
+        for (u32 i = 0; i < DYN_R; i++) {
+            const u32 j = tid + DYN_BLOCK * i;
+            v[i] = dyn_isqrt(dyn_mean_square(v[i], w[i], la));
+            if (j < N)
+                L[j] = v[i];
+        }
+        __syncthreads();
+    } else {
+        for (u32 d = 1; d < (1u << la); d *= 2u)
+            pass(d, std::false_type{}, 2u * d == (1u << la) ? la : 0u);     // sums below 2^26; leaves L
+    }
     u32 P = 1;
     for (; 2u * P <= W; P *= 2u)
         pass(P, std::true_type{}, 0);

@@ -20,6 +20,11 @@ nearest pass counts (a = 8, H = 1024: 19 passes; a = 9, H = 1536: 20 passes).
         the unkeyed kernels inside one session), a run with every odd stream keyed on its even neighbour, a run with
         every stream keyed (on its neighbour, 2i <-> 2i + 1), and the plain run a third time after the keys were
         cleared; one JSON line per shape with the medians and their min-max
+    python tools/bench_dyn.py --rms [--steps N] [--shapes a,b]
+        the RMS detector (cmhip_dyn_new_detector, csrc/k_dynrms.hip) beside the mean detector: per shape two objects of
+        one geometry on the same arrays in one process, in the order mean, RMS, mean again, then both with every stream
+        keyed (2i <-> 2i + 1); one JSON line per shape with the medians, their min-max, the pass counts of both plans
+        and RMS over mean beside (P + a) / P; then the instruction counts of build/k_dynrms.s
 """
 import argparse
 import ctypes as C
@@ -57,7 +62,8 @@ def passes(a, b, hold):
 def count_asm(stem="k_dyn"):
     """per kernel of build/k_dyn.s (or, stem "k_dynk", build/k_dynkey.s): all its instructions by class, and, cut at the
     barriers, the two phases of a doubling pass over a thread's 30 elements and the curve lookup between the passes"""
-    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", "k_dynkey.s" if stem == "k_dynk" else "k_dyn.s")
+    files = {"k_dyn": "k_dyn.s", "k_dynk": "k_dynkey.s", "k_dynrms": "k_dynrms.s", "k_dynrmsk": "k_dynrms.s"}
+    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", files[stem])
     if not os.path.exists(path):
         return None
     text = open(path).read()
@@ -95,6 +101,29 @@ def count_asm(stem="k_dyn"):
             lean, heavy = min(both, key=lambda c: c["valu"]), max(both, key=lambda c: c["valu"])
             rec["per_element_and_pass"] = {k: round(lean[k] / ELEMENTS, 2) for k in ("valu", "salu", "lds_reads", "lds_writes")}
             rec["per_element_of_the_lookup"] = {k: round(heavy[k] / ELEMENTS, 2) for k in ("valu", "lds_reads", "lds_writes")}
+        # the loops of doubling passes as the assembler laid them out: from a backward branch's target to the branch, two
+        # barriers inside.  (In the RMS kernels the stretch with 30 reads and 30 writes above is not a pass but the first
+        # split -- own elements read, squared, the low halves written -- so there the loops are the per-pass figures.)
+        ins, labels = [], {}
+        for ln in body.splitlines():
+            ln = ln.split(";")[0].strip()
+            lab = re.match(r"(\.LBB\w+):", ln)
+            if lab:
+                labels[lab.group(1)] = len(ins)
+            elif ln and not ln.startswith(".") and not ln.endswith(":"):
+                ins.append(ln)
+        found = []
+        for k, ln in enumerate(ins):
+            br = re.match(r"s_c?branch\w*\s+(\.LBB\w+)", ln)
+            if br and labels.get(br.group(1), k + 1) <= k:
+                b = [x.split()[0] for x in ins[labels[br.group(1)]:k + 1]]
+                n = lambda pre: sum(op.startswith(pre) for op in b)
+                if n("s_barrier") == 2 and n("ds_read") >= ELEMENTS - 1 and n("ds_write") >= ELEMENTS - 1:
+                    found.append({"valu": n("v_"), "salu": n("s_") - n("s_barrier") - n("s_waitcnt") - n("s_nop"),
+                                  "lds_reads": n("ds_read"), "lds_writes": n("ds_write"), "instructions": len(b)})
+        rec["pass_loops"] = found
+        if stem.startswith("k_dynrms"):
+            rec.pop("per_element_and_pass", None)
         out[name] = rec
     return {"kernels": out, "passes": {k: passes(v[3], v[4], v[5]) for k, v in SHAPES.items()}}
 
@@ -176,15 +205,72 @@ def keyed(a):
     print(json.dumps({"k_dynk": count_asm("k_dynk")}))
 
 
+def rms(a):
+    """--rms: per shape the mean detector, the RMS detector, the mean detector again, then both with every stream keyed"""
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    cm = ge.load_package()
+    hip = None
+    for name in a.shapes.split(","):
+        S, ch, F, la, lb, hold = SHAPES[name]
+        S -= S % 2                                              # pairs
+        src = cm.Batch(S, ch, F, flags=cm.OUT_PCM | cm.VU, rate=48000)
+        src.generate(cm.GEN_NOISE, 12345, F)
+        src.sync()
+        curve = cm.dyn_design(**CURVE)
+        mean = cm.Dynamics(S, ch, la, lb, hold, F, curve=curve)
+        root = cm.Dynamics(S, ch, la, lb, hold, F, curve=curve, detector=cm.DYN_DETECT_RMS)
+        assert (mean.detector(), root.detector()) == (cm.DYN_DETECT_MEAN, cm.DYN_DETECT_RMS)
+        out_stride = (F * ch + 7) // 8 * 8
+        dst = cm.lib.cmhip_device_alloc(0, S * out_stride * 2)
+        assert dst
+        if hip is None:
+            hip = hip_runtime()
+            hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+            hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+            hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+            hip.hipEventSynchronize.argtypes = [C.c_void_p]
+        rec = lambda t: {"kernel_ms_median": round(t[0], 4), "kernel_ms_min": round(t[1], 4), "kernel_ms_max": round(t[2], 4)}
+        go = lambda m: rec(timed(hip, m, a.steps, lambda: m.run(src.dev_in, src.stride, F, dst, out_stride)))
+        pm, pr = cm.plan_dyn(S, ch, la, lb, hold, F), cm.plan_dynrms(S, ch, la, lb, hold, F)
+        line = {"shape": name, "rms": True, "streams": S, "channels": ch, "frames": F, "detector_log2": la,
+                "smooth_log2": lb, "hold": hold, "steps": a.steps, "passes_mean": pm.passes, "passes_rms": pr.passes,
+                "lds_bytes": [pm.lds_bytes, pr.lds_bytes], "expected_rms_over_mean": round(pr.passes / pm.passes, 4)}
+        line["mean"] = go(mean)
+        line["rms_detector"] = go(root)
+        line["mean_repeated"] = go(mean)
+        for m in (mean, root):
+            for s in range(S):
+                m.set_key(s, s ^ 1)
+        line["mean_every_stream_keyed"] = go(mean)
+        line["rms_every_stream_keyed"] = go(root)
+        line["min_gain_stream0"] = {"mean": int(mean.min_gain()[0]), "rms": int(root.min_gain()[0])}
+        line["rms_over_mean"] = round(line["rms_detector"]["kernel_ms_median"] / line["mean"]["kernel_ms_median"], 4)
+        line["rms_over_mean_keyed"] = round(line["rms_every_stream_keyed"]["kernel_ms_median"] /
+                                            line["mean_every_stream_keyed"]["kernel_ms_median"], 4)
+        line["mean_repeated_over_mean"] = round(line["mean_repeated"]["kernel_ms_median"] / line["mean"]["kernel_ms_median"], 4)
+        print(json.dumps(line), flush=True)
+        mean.close()
+        root.close()
+        cm.lib.cmhip_device_free(0, dst)
+        src.close()
+    print(json.dumps({"k_dynrms": count_asm("k_dynrms"), "k_dynrmsk": count_asm("k_dynrmsk")}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--count-asm", action="store_true")
     ap.add_argument("--key", action="store_true")
+    ap.add_argument("--rms", action="store_true")
     a = ap.parse_args()
     if a.count_asm:
-        print(json.dumps({"k_dyn": count_asm(), "k_dynk": count_asm("k_dynk")}))
+        print(json.dumps({"k_dyn": count_asm(), "k_dynk": count_asm("k_dynk"), "k_dynrms": count_asm("k_dynrms"),
+                          "k_dynrmsk": count_asm("k_dynrmsk")}))
+        return
+    if a.rms:
+        rms(a)
         return
     if a.key:
         keyed(a)
