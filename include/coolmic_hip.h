@@ -731,7 +731,29 @@ int      cmhip_bus_ramp_state(const cmhip_bus_t *m, size_t send, uint32_t *done,
  *   detector 1, for hold == 0 or A + W > 2549.  cmhip_lim_detector: the object's.  cmhip_lim_delay: D or Dtp.
  *   run, set, get, reset, min_gain, sync and hip_stream serve both.
  * cmhip_lim_check_detector (host only): cmhip_lim_check for a detector.  cmhip_lim_threshold_dbtp (host only): the
- *   threshold for a ceiling in dBTP, floor(32768 * 10^(dbtp / 20)) clamped to 1..32767 (-1.0 gives 29204); 0 for NaN. */
+ *   threshold for a ceiling in dBTP, floor(32768 * 10^(dbtp / 20)) clamped to 1..32767 (-1.0 gives 29204); 0 for NaN.
+ *
+ * Release stage.  Without it the gain returns to unity over the A frames of the attack, after the hold: on a bass note
+ *   or a dense mix it follows the waveform.  A limiter may have a release of its own, fixed at creation, for either
+ *   detector: release_log2 = rho in 0..11, R = 2^rho frames, slope q = 32768 >> rho (Q15 gain units per frame).  Between
+ *   m and S of the arithmetic above:
+ *       m[n]   = min(g[n-W+1 .. n])                        as above
+ *       r[n]   = min over 0 <= k < R of (m[n-k] + k*q)     the release: r <= m, r[n] <= r[n-1] + q
+ *       S[n]   = sum(r[n-A+1 .. n]),  s[n] = S[n] >> a     as above, on r instead of m
+ *   k*q reaches 32768 at k = R, so the window of R frames is exact: no earlier frame can matter.  rho = 0 gives r = m,
+ *   the limiter above.  The gain falls as fast as before and rises by at most q per frame: a full-scale recovery takes R
+ *   frames on top of the boxcar's A (2048 frames, 42.7 ms at 48 kHz, at rho = 11).
+ *   Ceiling: every r[n-j] <= m[n-j] <= g[n-D], so |y| <= T holds by construction as above and nothing saturates.
+ *   Unchanged: the delay (D or Dtp: the stage adds none), transparency (below the threshold the output is the pure
+ *     delay), cuts (r is a function of a bounded window of raw input: the history stays raw frames), the meter, the
+ *     parameter word and the order of cmhip_lim_set with the runs.
+ *   Geometry.  HIST grows by R - 1: HIST = A + W - 2 + (R - 1), plus 13 with the true-peak detector, rounded up to 8
+ *     frames for the history slot, and may not pass 4096 (a = 9, rho = 11: hold <= 1027, with the true-peak detector
+ *     hold <= 1014).  The bounds above stay as they are.
+ * cmhip_lim_new_release: cmhip_lim_new_detector with a release stage (release_log2 0: cmhip_lim_new_detector itself);
+ *   NULL also for release_log2 > 11 and for HIST > 4096.  cmhip_lim_release: the object's release_log2.
+ *   run, set, get, reset, min_gain, sync, delay and hip_stream serve every form.
+ * cmhip_lim_check_release (host only): cmhip_lim_check_detector for a release stage. */
 #define CMHIP_LIM_DETECT_SAMPLE    0u
 #define CMHIP_LIM_DETECT_TRUE_PEAK 1u
 typedef struct cmhip_lim cmhip_lim_t;
@@ -746,7 +768,9 @@ typedef struct cmhip_lim_desc {
 } cmhip_lim_desc_t;
 cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d);
 cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsigned int detector);
+cmhip_lim_t *cmhip_lim_new_release(const cmhip_lim_desc_t *d, unsigned int detector, unsigned int release_log2);
 unsigned int cmhip_lim_detector(const cmhip_lim_t *m);
+unsigned int cmhip_lim_release(const cmhip_lim_t *m);
 void     cmhip_lim_free(cmhip_lim_t *m);
 unsigned int cmhip_lim_delay(const cmhip_lim_t *m);
 int      cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned int threshold, unsigned int drive);
@@ -761,6 +785,8 @@ void    *cmhip_lim_hip_stream(cmhip_lim_t *m);
 int      cmhip_lim_check(unsigned int lookahead_log2, unsigned int hold, unsigned int threshold, unsigned int drive);
 int      cmhip_lim_check_detector(unsigned int detector, unsigned int lookahead_log2, unsigned int hold,
                                   unsigned int threshold, unsigned int drive);
+int      cmhip_lim_check_release(unsigned int detector, unsigned int lookahead_log2, unsigned int hold,
+                                 unsigned int release_log2, unsigned int threshold, unsigned int drive);
 unsigned int cmhip_lim_threshold_dbtp(double dbtp);
 
 /* ---- dynamics: compressor and gate, an object of its own beside the batch ----------- */

@@ -267,6 +267,9 @@ SIGNATURES = {
     "cmhip_lim_detector": (C.c_uint, [_vp]),
     "cmhip_lim_check_detector": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
     "cmhip_lim_threshold_dbtp": (C.c_uint, [C.c_double]),
+    "cmhip_lim_new_release": (_vp, [_P(LimDesc), C.c_uint, C.c_uint]),
+    "cmhip_lim_release": (C.c_uint, [_vp]),
+    "cmhip_lim_check_release": (C.c_int, [C.c_uint] * 6),
     "cmhip_dyn_new": (_vp, [_P(DynDesc)]),
     "cmhip_dyn_free": (None, [_vp]),
     "cmhip_dyn_delay": (C.c_uint, [_vp]),
@@ -432,6 +435,9 @@ if hasattr(lib, "cmhip_test_plan_lim"):         # (not in builds older than the 
 if hasattr(lib, "cmhip_test_plan_limtp"):       # (not in builds older than the limiter's true-peak detector)
     lib.cmhip_test_plan_limtp.restype = None
     lib.cmhip_test_plan_limtp.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
+if hasattr(lib, "cmhip_test_plan_limrel"):      # (not in builds older than the limiter's release stage)
+    lib.cmhip_test_plan_limrel.restype = None
+    lib.cmhip_test_plan_limrel.argtypes = [C.c_uint32] * 7 + [C.c_void_p]
 if hasattr(lib, "cmhip_test_plan_dyn"):         # (not in builds older than the dynamics stage)
     lib.cmhip_test_plan_dyn.restype = None
     lib.cmhip_test_plan_dyn.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
@@ -723,6 +729,19 @@ def plan_limtp(streams, channels, lookahead_log2, hold, frames):
 def lim_check_detector(detector, lookahead_log2, hold, threshold, drive):
     """cmhip_lim_check_detector as it is -> error number (0: valid)"""
     return lib.cmhip_lim_check_detector(detector, lookahead_log2, hold, threshold, drive)
+
+
+def plan_limrel(detector, streams, channels, lookahead_log2, hold, release_log2, frames):
+    """Test hook: the plan of a run of a limiter with a release stage, for either detector (host logic, needs no GPU);
+    release_log2 0 gives plan_lim's or plan_limtp's plan"""
+    p = LimPlan()
+    lib.cmhip_test_plan_limrel(detector, streams, channels, lookahead_log2, hold, release_log2, frames, C.addressof(p))
+    return p
+
+
+def lim_check_release(detector, lookahead_log2, hold, release_log2, threshold, drive):
+    """cmhip_lim_check_release as it is -> error number (0: valid)"""
+    return lib.cmhip_lim_check_release(detector, lookahead_log2, hold, release_log2, threshold, drive)
 
 
 def lim_threshold_dbtp(dbtp):
@@ -1330,14 +1349,19 @@ class Limiter(_Stage):
     """cmhip_lim_t: a look-ahead peak limiter of S streams beside a batch; per stream a threshold (sample units) and a
     drive (units of 2^-12).  The output is the input delayed by delay() frames and never above the threshold.
     detector=None creates it with cmhip_lim_new, a detector (LIM_DETECT_SAMPLE: the same limiter; LIM_DETECT_TRUE_PEAK: the
-    gain follows the 4x oversampled signal) with cmhip_lim_new_detector."""
+    gain follows the 4x oversampled signal) with cmhip_lim_new_detector.  release_log2=None leaves the constructor as
+    that; a number (0..11: the gain rises by at most 32768 >> release_log2 per frame; 0: no release stage) creates the
+    limiter with cmhip_lim_new_release, detector None then meaning the sample detector."""
 
     _stem = "lim"
 
     def __init__(self, streams, channels, lookahead_log2, hold, max_frames, threshold=None, drive=None, device=0,
-                 hip_stream=None, detector=None):
+                 hip_stream=None, detector=None, release_log2=None):
         d = LimDesc(device, streams, channels, lookahead_log2, hold, max_frames, hip_stream)
-        if detector is None:                        # the constructor without a detector: the sample detector
+        if release_log2 is not None:
+            what, self.h = "cmhip_lim_new_release", lib.cmhip_lim_new_release(
+                C.byref(d), LIM_DETECT_SAMPLE if detector is None else detector, release_log2)
+        elif detector is None:                      # the constructor without a detector: the sample detector
             what, self.h = "cmhip_lim_new", lib.cmhip_lim_new(C.byref(d))
         else:
             what, self.h = "cmhip_lim_new_detector", lib.cmhip_lim_new_detector(C.byref(d), detector)
@@ -1352,6 +1376,10 @@ class Limiter(_Stage):
 
     def detector(self):
         return lib.cmhip_lim_detector(self.h)
+
+    def release(self):
+        """release_log2 (0: no release stage)"""
+        return lib.cmhip_lim_release(self.h)
 
     def set_rc(self, stream, threshold, drive):
         """cmhip_lim_set as it is -> error number"""

@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_dyn.hip, k_dynkey.hip, k_dynrms.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_dynkey.hip, k_dynrms.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -260,7 +260,7 @@ struct BusRampArgs {
     const uint32_t *ramp;          // [n sends][BUSR_HDR + 2 n]
 };
 
-// Peak limiter (k_lim.hip, k_limtp.hip; the arithmetic: include/coolmic_hip.h): a limiter's run over S stream slots.
+// Peak limiter (k_lim.hip, k_limtp.hip, k_limrel.hip; the arithmetic: include/coolmic_hip.h): a limiter's run over S stream slots.
 struct LimArgs {
     const int16_t *in;             // int16 [S][in_stride]
     int16_t       *out;            // int16 [S][out_stride]
@@ -430,6 +430,9 @@ hipError_t launch_busramp_advance(uint32_t *ramp, const uint32_t *bus_frames, ui
 hipError_t launch_lim(const LimArgs &a, hipStream_t st);
 // The same with the true-peak detector (k_limtp.hip): LimArgs as they are, halo and delay are lim_geom_tp's.
 hipError_t launch_limtp(const LimArgs &a, hipStream_t st);
+// Either of them with a release stage of 2^release_log2 frames (k_limrel.hip): halo is lim_geom_rel's, the plan
+// plan_limrel's; release_log2 0 is launch_lim or launch_limtp itself.
+hipError_t launch_limrel(const LimArgs &a, uint32_t detector, uint32_t release_log2, hipStream_t st);
 // (threshold and drive into the parameter words of streams first .. first + count - 1; they travel as kernel arguments)
 hipError_t launch_lim_set(uint32_t *par, uint32_t first, uint32_t count, uint32_t threshold, uint32_t drive,
                           hipStream_t st);

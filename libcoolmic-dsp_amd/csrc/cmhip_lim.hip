@@ -1,6 +1,7 @@
 // cmhip_lim.hip -- the peak limiter on the host side (include/coolmic_hip.h, "peak limiter"): the limiter object beside
 // the batch, its validation, the launch of k_lim.hip's kernels (the sample detector) or k_limtp.hip's (the true-peak
-// detector, fixed at creation), parameters, reset and the gain-reduction meter.
+// detector, fixed at creation), or k_limrel.hip's for either detector where the object has a release stage
+// (release_log2 >= 1, fixed at creation), parameters, reset and the gain-reduction meter.
 //
 // Device state of a limiter: one parameter word per stream (threshold | drive << 16), the streams' history, int16
 // [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
@@ -18,8 +19,9 @@ constexpr uint64_t LIM_MAX_SAMPLES = 1ull << 31;     // per slot and run: the ke
 
 struct cmhip_lim : StageBase {
     cmhip_lim_desc_t d;
-    LimGeom g;                         // of the detector: D, HIST and halo differ between the two
+    LimGeom g;                         // of the detector and the release: D, HIST and halo differ
     unsigned detector;
+    unsigned rho;                      // release_log2; 0: no release stage
     uint32_t *d_par;
     uint32_t *d_gmin;
     int16_t *d_hist;
@@ -51,6 +53,19 @@ extern "C" int cmhip_lim_check_detector(unsigned detector, unsigned lookahead_lo
                     "2 * 2^lookahead_log2 + hold <= 2549", lookahead_log2, hold);
     if (!lim_params_ok(threshold, drive))
         return fail(COOLMIC_ERROR_INVAL, "lim: threshold %u, drive %u: 1..32767 and 1..65535", threshold, drive);
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_lim_check_release(unsigned detector, unsigned lookahead_log2, unsigned hold, unsigned release_log2,
+                                       unsigned threshold, unsigned drive)
+{
+    const int rc = cmhip_lim_check_detector(detector, lookahead_log2, hold, threshold, drive);
+    if (rc)
+        return rc;
+    if (!lim_geom_rel(detector, lookahead_log2, hold, release_log2, nullptr))
+        return fail(COOLMIC_ERROR_INVAL, "lim: release_log2 %u (lookahead_log2 %u, hold %u): 0..11, and HIST = 2 * "
+                    "2^lookahead_log2 + hold - 2 + 2^release_log2 - 1 (+ 13 with the true-peak detector) <= 4096",
+                    release_log2, lookahead_log2, hold);
     return COOLMIC_ERROR_NONE;
 }
 
@@ -98,6 +113,11 @@ extern "C" cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d)
 
 extern "C" cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsigned detector)
 {
+    return cmhip_lim_new_release(d, detector, 0);
+}
+
+extern "C" cmhip_lim_t *cmhip_lim_new_release(const cmhip_lim_desc_t *d, unsigned detector, unsigned release_log2)
+{
     if (!d) {
         fail(COOLMIC_ERROR_FAULT, "lim_new: NULL argument");
         return nullptr;
@@ -119,6 +139,12 @@ extern "C" cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsign
              "in 3..9 and 2^lookahead_log2 + hold <= 2048");
         return nullptr;
     }
+    if (!lim_geom_rel(detector, g.a, g.H, release_log2, &g)) {       // (release_log2 0 leaves g as it is)
+        fail(COOLMIC_ERROR_INVAL, "lim_new: release_log2 %u (lookahead_log2 %u, hold %u): 0..11, and the history, 2 * "
+             "2^lookahead_log2 + hold - 2 + 2^release_log2 - 1 frames (+ 13 with the true-peak detector), may not pass "
+             "4096", release_log2, d->lookahead_log2, d->hold);
+        return nullptr;
+    }
     if (d->max_frames > LIM_MAX_SAMPLES / d->channels) {
         fail(COOLMIC_ERROR_INVAL, "lim_new: max_frames %zu: a slot of a run would pass 2^31 samples", d->max_frames);
         return nullptr;
@@ -135,6 +161,7 @@ extern "C" cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsign
     m->d = *d;
     m->g = g;
     m->detector = detector;
+    m->rho = release_log2;
     if (lim_init(m)) {
         cmhip_lim_free(m);
         return nullptr;
@@ -145,6 +172,8 @@ extern "C" cmhip_lim_t *cmhip_lim_new_detector(const cmhip_lim_desc_t *d, unsign
 extern "C" unsigned cmhip_lim_delay(const cmhip_lim_t *m) { return m ? m->g.D : 0u; }
 
 extern "C" unsigned cmhip_lim_detector(const cmhip_lim_t *m) { return m ? m->detector : 0u; }
+
+extern "C" unsigned cmhip_lim_release(const cmhip_lim_t *m) { return m ? m->rho : 0u; }
 
 extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, unsigned drive)
 {
@@ -223,7 +252,7 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     const int refused = stage_run_refusal("lim_run", r);
     if (refused)
         return refused;
-    if (plan_lim_of(m->detector, S, C, m->g.a, m->g.H, (uint32_t)frames).err)
+    if (plan_limrel(m->detector, S, C, m->g.a, m->g.H, m->rho, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "lim_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
     // nothing was touched so far; from here on the run happens
@@ -248,8 +277,7 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     a.W = m->g.W;
     if (frames_per_stream)
         HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    const hipError_t e =
-        m->detector == CMHIP_LIM_DETECT_TRUE_PEAK ? launch_limtp(a, m->stream) : launch_lim(a, m->stream);
+    const hipError_t e = launch_limrel(a, m->detector, m->rho, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "lim_run: %s", hipGetErrorString(e));
     m->parity ^= 1u;                         // the kernel wrote the other slots

@@ -1,6 +1,7 @@
-// k_lim.h -- the device helpers the limiter's kernel files share (k_lim.hip, k_limtp.hip): the exact division, the
-// 64-bit product of one sample, and a stream seen as one sequence across the seam between its history slot and the
-// run's slot (k_lim.hip describes the decomposition).
+// k_lim.h -- the device helpers the limiter's kernel files share (k_lim.hip, k_limtp.hip, k_limrel.hip): the exact
+// division, the two detectors' gain of one frame (the sample detector's lim_gain, the true-peak detector's FIR in pair
+// form and limtp_gain), the 64-bit product of one sample, and a stream seen as one sequence across the seam between its
+// history slot and the run's slot (k_lim.hip describes the decomposition).
 #ifndef CMHIP_K_LIM_H
 #define CMHIP_K_LIM_H
 
@@ -27,9 +28,50 @@ __device__ __forceinline__ u32 lim_div(u32 num, u32 pr)
     return q;
 }
 
+// the sample detector: g of a frame whose largest magnitude is `peak`
+__device__ __forceinline__ u32 lim_gain(u32 peak, u32 drive, u32 T)
+{
+    const u32 pr = (peak * drive + 4095u) >> 12;     // <= 65535 * 32768 + 4095 < 2^31
+    return pr <= T ? LIM_UNITY : lim_div(T << 15, pr);
+}
+
 __device__ __forceinline__ u32 lim_abs(int x) { return (u32)(x < 0 ? -x : x); }
 __device__ __forceinline__ int lim_lo(u32 w) { return (int)(short)(w & 0xffffu); }
 __device__ __forceinline__ int lim_hi(u32 w) { return (int)w >> 16; }
+
+// the true-peak detector (k_limtp.hip describes the pair form)
+constexpr u32 limtp_pair(unsigned p, unsigned i)
+{
+    return (u32)(uint16_t)tp_h(p, 2 * i + 1) | ((u32)(uint16_t)tp_h(p, 2 * i) << 16);
+}
+
+__device__ __forceinline__ int limtp_dot2(u32 x, u32 k, int acc)
+{
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, x), __builtin_bit_cast(v2s, k), acc, false);
+}
+
+// t <= 16571 * 32768 < 2^30; drive * t < 2^46 (v_mad_u64_u32); pr <= 1 060 528 < 2^21
+__device__ __forceinline__ u32 limtp_gain(u32 t, u32 drive, u32 T)
+{
+    const u32 pr = (u32)(((u64)drive * (u64)t + ((1ull << 25) - 1ull)) >> 25);
+    return pr <= T ? LIM_UNITY : lim_div(T << 15, pr);
+}
+
+// max(|y_0|, .., |y_3|) at local frame t of the dwords d, channel c (pair(t, c): x_c[t-1] | x_c[t] << 16)
+template <class Pair>
+__device__ __forceinline__ u32 limtp_fir(Pair pair, u32 t, u32 c)
+{
+    int y[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (u32 i = 0; i < TP_TAPS / 2; i++) {
+        const u32 pr = pair(t - 2u * i, c);
+        y[0] = limtp_dot2(pr, limtp_pair(0, i), y[0]);
+        y[1] = limtp_dot2(pr, limtp_pair(1, i), y[1]);
+        y[2] = limtp_dot2(pr, limtp_pair(2, i), y[2]);
+        y[3] = limtp_dot2(pr, limtp_pair(3, i), y[3]);
+    }
+    return max(max(lim_abs(y[0]), lim_abs(y[1])), max(lim_abs(y[2]), lim_abs(y[3])));
+}
 
 // one sample: the 64-bit product (v_mad_i64_i32), exact; |y| <= T, so nothing is clamped
 __device__ __forceinline__ u32 lim_apply(int x, u32 c)

@@ -30,14 +30,9 @@
 
 namespace cmhip {
 
-__device__ __forceinline__ u32 lim_gain(u32 peak, u32 drive, u32 T)
-{
-    const u32 pr = (peak * drive + 4095u) >> 12;     // <= 65535 * 32768 + 4095 < 2^31
-    return pr <= T ? LIM_UNITY : lim_div(T << 15, pr);
-}
-
 // C: 1 or 2, or 0 for a run-time channel count
-// (k_limtp.hip's limtp_tile carries a second copy of steps 2 to 4 and the meter: a change to them goes into both)
+// (k_limtp.hip's limtp_tile and k_limrel.hip's limrel_tile carry copies of steps 2 to 4 and the meter: a change to them
+// goes into all three)
 template <int CT>
 __device__ __forceinline__ void lim_tile(const LimArgs &a, u32 *L, u32 *red)
 {

@@ -14,6 +14,12 @@
 // sample n - 8 and the interval behind it and needs the 13 frames x[n-13 .. n-1].  D = A + 7 (so that D + 1 stays a
 // multiple of 8 frames), HIST = A + W - 2 + 13; hold >= 1, so that an interval's gain also covers the interval's second
 // end sample, and A + W <= 2549, so that HIST <= 2560 = LIM_HALO_MAX: lim_geom_tp / plan_limtp.  The rest is the same.
+//
+// The release stage (release_log2 = rho in 1..11, R = 2^rho; k_limrel.hip) puts a min-plus convolution with a ramp of
+// slope q = 32768 >> rho between the minimum and the sum: HIST grows by R - 1 and may reach 4096 = LIMREL_HIST_MAX, the
+// tile, so the tile is always 4096 frames and a workgroup evaluates up to 8192 elements, LIMREL_SLOTS = 32 per thread,
+// 32 KiB of dynamic LDS: lim_geom_rel / plan_limrel.  rho = 0 is the limiter without the stage: lim_geom_rel and
+// plan_limrel then give what lim_geom_of and plan_lim_of give, and the launchers take k_lim.hip's and k_limtp.hip's kernels.
 #ifndef CMHIP_LIM_PLAN_H
 #define CMHIP_LIM_PLAN_H
 
@@ -35,6 +41,9 @@ constexpr uint32_t LIM_DETECT_SAMPLE = 0, LIM_DETECT_TRUE_PEAK = 1;
 constexpr uint32_t LIM_TP_FRONT = 13;                // frames in front of frame n that the true-peak g[n] reads
 constexpr uint32_t LIM_TP_LAG = 8;                   // what the true-peak detector adds to the delay
 constexpr uint32_t LIM_TP_AW_MAX = LIM_HALO_MAX + 2u - LIM_TP_FRONT;     // 2549: A + W at most
+constexpr uint32_t LIMREL_RHO_MAX = 11;              // release_log2 at most: R = 2048 frames
+constexpr uint32_t LIMREL_HIST_MAX = LIM_TILE_MAX;   // HIST with a release: a history halo never exceeds the tile
+constexpr uint32_t LIMREL_SLOTS = (LIM_TILE_MAX + LIMREL_HIST_MAX) / LIM_BLOCK;      // 32 elements per thread at most
 
 struct LimGeom {
     uint32_t a, A, D, H, W, hist, halo;
@@ -80,6 +89,22 @@ inline bool lim_geom_of(uint32_t detector, uint32_t lookahead_log2, uint32_t hol
     return detector == LIM_DETECT_SAMPLE      ? lim_geom(lookahead_log2, hold, g)
            : detector == LIM_DETECT_TRUE_PEAK ? lim_geom_tp(lookahead_log2, hold, g)
                                               : false;
+}
+
+// the same with a release stage of 2^release_log2 frames: also false for release_log2 > 11 and for HIST > 4096
+// (release_log2 0: lim_geom_of)
+inline bool lim_geom_rel(uint32_t detector, uint32_t lookahead_log2, uint32_t hold, uint32_t release_log2, LimGeom *g)
+{
+    LimGeom t;
+    if (release_log2 > LIMREL_RHO_MAX || !lim_geom_of(detector, lookahead_log2, hold, &t))
+        return false;
+    t.hist += (1u << release_log2) - 1u;
+    if (t.hist > LIMREL_HIST_MAX)
+        return false;
+    t.halo = (t.hist + 7u) & ~7u;
+    if (g)
+        *g = t;
+    return true;
 }
 
 inline bool lim_params_ok(uint32_t threshold, uint32_t drive)
@@ -132,6 +157,34 @@ inline LimPlan plan_lim(uint32_t streams, uint32_t channels, uint32_t lookahead_
 inline LimPlan plan_limtp(uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold, uint32_t frames)
 {
     return plan_lim_of(LIM_DETECT_TRUE_PEAK, streams, channels, lookahead_log2, hold, frames);
+}
+
+// the plan of a run of a limiter with a release stage, for either detector: the tile is 4096 frames for every geometry
+// (halo <= 4096 <= tile, (4096 + 4096) * 4 bytes are 32 KiB); release_log2 0 gives plan_lim_of's plan
+inline LimPlan plan_limrel(uint32_t detector, uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold,
+                           uint32_t release_log2, uint32_t frames)
+{
+    LimPlan p{};
+    LimGeom g;
+    if (release_log2 == 0)
+        return plan_lim_of(detector, streams, channels, lookahead_log2, hold, frames);
+    if (streams == 0 || frames == 0 || channels == 0 || channels > LIM_MAX_CH ||
+        !lim_geom_rel(detector, lookahead_log2, hold, release_log2, &g))
+        return p;
+    const uint32_t tile = LIM_TILE_MAX;
+    const uint64_t tiles = ((uint64_t)frames + tile - 1u) / tile;
+    if (tiles * streams >= (1ull << 31)) {
+        p.err = 1;
+        return p;
+    }
+    p.fast = channels <= 2u ? 1u : 0u;
+    p.block = LIM_BLOCK;
+    p.tile_frames = tile;
+    p.lds_bytes = (tile + g.halo) * 4u;
+    p.halo = g.halo;
+    p.chunks = (uint32_t)tiles;
+    p.grid = streams * p.chunks;
+    return p;
 }
 
 }  // namespace cmhip

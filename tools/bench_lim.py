@@ -12,6 +12,11 @@ batch's own slots (read + write), the yardstick.
     python tools/bench_lim.py [--steps N] [--shapes a,b]      one JSON line per shape
     python tools/bench_lim.py --count-asm                     per kernel the instructions of build/k_lim.s (`make asm`;
                                                               no GPU needed), and the passes per geometry
+    python tools/bench_lim.py --release [--steps N] [--shapes a,b]
+        the release stage (cmhip_lim_new_release, csrc/k_limrel.hip): per shape three limiters in one process on the same
+        arrays, release_log2 0 (k_lim.hip's kernel as it always ran), 6 and 11, timed the same way; beside each time its
+        ratio to the release_log2 0 time and what the structure predicts, (P + rho) / P * (t + halo_rho) / (t + halo_0),
+        P the passes without the stage
 """
 import argparse
 import ctypes as C
@@ -89,14 +94,82 @@ def hip_runtime():
     raise RuntimeError("no HIP runtime mapped")
 
 
+RELEASES = (0, 6, 11)
+
+
+def timed_runs(cm, hip, m, src, F, dst, out_stride, steps):
+    """150 ms of the limiter's own launches, then `steps` runs bracketed by HIP events -> the times in ms"""
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    st = C.c_void_p(m.hip_stream())
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.15:
+        m.run(src.dev_in, src.stride, F, dst, out_stride)
+        m.sync()
+    ms = []
+    for _ in range(steps):
+        assert hip.hipEventRecord(e0, st) == 0
+        m.run(src.dev_in, src.stride, F, dst, out_stride)
+        assert hip.hipEventRecord(e1, st) == 0
+        assert hip.hipEventSynchronize(e1) == 0
+        t = C.c_float()
+        assert hip.hipEventElapsedTime(C.byref(t), e0, e1) == 0
+        ms.append(t.value)
+    return ms
+
+
+def release_main(cm, shapes, names, steps, detector):
+    """--release: per shape one JSON line with the release_log2 0, 6 and 11 limiters of one detector"""
+    hip = hip_runtime()
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+    hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipEventSynchronize.argtypes = [C.c_void_p]
+    for name in names:
+        S, ch, F, la, hold = shapes[name]
+        src = cm.Batch(S, ch, F, flags=cm.OUT_PCM | cm.VU, rate=48000)
+        src.generate(cm.GEN_NOISE, 12345, F)
+        src.sync()
+        out_stride = (F * ch + 7) // 8 * 8
+        dst = cm.lib.cmhip_device_alloc(0, S * out_stride * 2)
+        assert dst
+        rd = wr = S * F * ch * 2
+        P = sum(passes(la, hold).values())
+        line = {"shape": name, "detector": detector, "streams": S, "channels": ch, "frames": F, "lookahead_log2": la,
+                "hold": hold, "threshold": THRESHOLD, "drive": DRIVE, "steps": steps, "passes_without_release": P}
+        base = None
+        for rho in RELEASES:
+            m = cm.Limiter(S, ch, la, hold, F, threshold=THRESHOLD, drive=DRIVE, detector=detector, release_log2=rho)
+            ms = timed_runs(cm, hip, m, src, F, dst, out_stride, steps)
+            p = cm.plan_limrel(detector, S, ch, la, hold, rho, F)
+            med = statistics.median(ms)
+            if rho == 0:
+                base = (med, p.tile_frames + p.halo)
+            line["release_log2_%d" % rho] = {
+                "kernel_ms_median": round(med, 4), "kernel_ms_min": round(min(ms), 4), "kernel_ms_max": round(max(ms), 4),
+                "GBs_read_plus_written": round((rd + wr) / med / 1e6, 1), "over_release_0": round(med / base[0], 3),
+                "predicted_over_release_0": round((P + rho) / P * (p.tile_frames + p.halo) / base[1], 3),
+                "min_gain_stream0": int(m.min_gain()[0]), "halo": p.halo, "lds_bytes": p.lds_bytes}
+            m.close()
+        print(json.dumps(line), flush=True)
+        cm.lib.cmhip_device_free(0, dst)
+        src.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--count-asm", action="store_true")
+    ap.add_argument("--release", action="store_true")
     a = ap.parse_args()
     if a.count_asm:
         print(json.dumps({"k_lim": count_asm()}))
+        return
+    if a.release:
+        sys.path.insert(0, ROOT)
+        import __graft_entry__ as ge
+        release_main(ge.load_package(), SHAPES, a.shapes.split(","), a.steps, 0)
         return
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge

@@ -14,6 +14,8 @@ cmhip_batch_ceiling's plain copy on the input batch's own slots (read + write), 
     python tools/bench_limtp.py --count-asm                   per kernel the instructions of build/k_limtp.s (`make asm`;
                                                               no GPU needed): the whole kernel, and the FIR's share per
                                                               sample of the fast forms
+    python tools/bench_limtp.py --release [--steps N] [--shapes a,b]
+        tools/bench_lim.py --release with the true-peak detector: release_log2 0 (k_limtp.hip's kernel), 6 and 11
 """
 import argparse
 import ctypes as C
@@ -83,9 +85,17 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--count-asm", action="store_true")
+    ap.add_argument("--release", action="store_true")
     a = ap.parse_args()
     if a.count_asm:
         print(json.dumps({"k_limtp": count_asm()}))
+        return
+    if a.release:
+        sys.path.insert(0, ROOT)
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import __graft_entry__ as ge
+        import bench_lim
+        bench_lim.release_main(ge.load_package(), SHAPES, a.shapes.split(","), a.steps, 1)
         return
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
