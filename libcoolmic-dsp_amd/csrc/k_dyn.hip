@@ -10,7 +10,8 @@
 //   k_dyn_any       3..16 channels: sample by sample; no speed goal
 //   k_dyn_set       writes one curve, handed over as a kernel argument, into a range of streams
 //
-// The decomposition is k_lim.hip's.  A workgroup of 256 threads takes one stream and a tile of tile_frames frames, and
+// The decomposition is the limiter's (k_lim_tile.h).
+// A workgroup of 256 threads takes one stream and a tile of tile_frames frames, and
 // evaluates N = halo + tile_frames frames: the tile's own and the halo in front of them, which are the stream's history
 // slot where the tile is the run's first and the run's own input otherwise (tile_frames >= halo).  Seen from a tile a
 // stream is ONE sequence of 16-byte vectors: vector v >= 0 is vector v of the run's slot, vector v < 0 is vector

@@ -1,7 +1,7 @@
-// k_lim.h -- the device helpers the limiter's kernel files share (k_lim.hip, k_limtp.hip, k_limrel.hip): the exact
-// division, the two detectors' gain of one frame (the sample detector's lim_gain, the true-peak detector's FIR in pair
-// form and limtp_gain), the 64-bit product of one sample, and a stream seen as one sequence across the seam between its
-// history slot and the run's slot (k_lim.hip describes the decomposition).
+// k_lim.h -- the device helpers of the limiter's tile (k_lim_tile.h, which k_lim.hip, k_limtp.hip and k_limrel.hip
+// instantiate): the exact division, the two detectors' gain of one frame (the sample detector's lim_gain, the true-peak
+// detector's FIR in pair form and limtp_gain), the 64-bit product of one sample, and a stream seen as one sequence across
+// the seam between its history slot and the run's slot (k_lim_tile.h describes the decomposition).
 #ifndef CMHIP_K_LIM_H
 #define CMHIP_K_LIM_H
 
@@ -9,7 +9,7 @@
 
 namespace cmhip {
 
-constexpr u32 LIM_R = (LIM_TILE_MAX + LIM_HALO_MAX) / LIM_BLOCK;     // 26 elements per thread at most
+constexpr u32 LIM_R = (LIM_TILE_MAX + LIM_HALO_MAX) / LIM_BLOCK;     // without a release: 26 elements per thread at most
 
 // floor(num / pr) for num = T << 15 (15 significant bits: exact as a float), T < pr <= 2^21 (exact as a float; the
 // sample detector stays at or below 2^19, the true-peak detector below 2^21): the quotient is below 2^15, the reciprocal
@@ -39,7 +39,7 @@ __device__ __forceinline__ u32 lim_abs(int x) { return (u32)(x < 0 ? -x : x); }
 __device__ __forceinline__ int lim_lo(u32 w) { return (int)(short)(w & 0xffffu); }
 __device__ __forceinline__ int lim_hi(u32 w) { return (int)w >> 16; }
 
-// the true-peak detector (k_limtp.hip describes the pair form)
+// the true-peak detector (k_lim_tile.h describes the pair form)
 constexpr u32 limtp_pair(unsigned p, unsigned i)
 {
     return (u32)(uint16_t)tp_h(p, 2 * i + 1) | ((u32)(uint16_t)tp_h(p, 2 * i) << 16);
@@ -96,6 +96,32 @@ __device__ __forceinline__ void lim_load(u32 (&x)[4], const int16_t *ins, const 
 __device__ __forceinline__ int lim_sample(const int16_t *ins, const int16_t *hs, u32 hsamp, int q)
 {
     return q < 0 ? hs[hsamp + q] : ins[q];
+}
+
+// the g of vector w's frames (8 mono, 4 stereo) into LDS, 16 bytes at a time
+template <int CT>
+__device__ __forceinline__ void lim_put_g(u32 *L, u32 w, const u32 *g)
+{
+    u32x4 *Lv = reinterpret_cast<u32x4 *>(L);
+    const u32x4 g0 = {g[0], g[1], g[2], g[3]};
+    if constexpr (CT == 1) {
+        const u32x4 g1 = {g[4], g[5], g[6], g[7]};
+        Lv[2 * w] = g0;
+        Lv[2 * w + 1] = g1;
+    } else {
+        Lv[w] = g0;
+    }
+}
+
+// output vector v8 of the stream: whole where the count covers it, the ragged end through store_tail, nothing past it
+__device__ __forceinline__ void lim_store(int16_t *outs, u32 v8, const u32 (&o)[4], u32 nfull, u32 ntail)
+{
+    if (v8 < nfull) {
+        const u32x4 ov = {o[0], o[1], o[2], o[3]};
+        __builtin_nontemporal_store(ov, reinterpret_cast<u32x4 *>(outs) + v8);
+    } else if (v8 == nfull) {
+        store_tail(outs, v8, o, ntail);
+    }
 }
 
 // the other history slot: the last halo frames of (old slot, the run's F frames)

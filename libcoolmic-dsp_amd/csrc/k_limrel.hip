@@ -1,6 +1,7 @@
-// k_limrel.hip -- gfx950 (MI355X, wave64) look-ahead limiter with the RELEASE STAGE, for both detectors: k_lim.hip's
+// k_limrel.hip -- gfx950 (MI355X, wave64) look-ahead limiter with the RELEASE STAGE, for both detectors: the limiter's
 // tile with 32 element slots per thread and rho release passes between the minimum passes and the sum passes
-// (include/coolmic_hip.h, "peak limiter", "release stage", has the arithmetic to the bit; csrc/lim_plan.h the geometry):
+// (include/coolmic_hip.h, "peak limiter", "release stage", has the arithmetic to the bit; csrc/lim_plan.h the geometry;
+// csrc/k_lim_tile.h the tile, its steps and why the ramp doubles as a window does):
 //     g, m as in k_lim.hip (the sample detector) or k_limtp.hip (the true-peak detector)
 //     r[n] = min over 0 <= k < R of (m[n-k] + k*q)         R = 2^rho frames, q = 32768 >> rho per frame
 //     s    = (sum of r over the last A frames) >> a         y[n][ch] = (x[n-D][ch] * (drive * s[n]) + 2^26) >> 27
@@ -12,344 +13,25 @@
 // A limiter with rho = 0 never comes here: it launches k_lim.hip's or k_limtp.hip's kernels (launch_limrel).
 //
 // The tile is 4096 frames for every geometry and a workgroup evaluates N = halo + 4096 <= 8192 elements, one dword of
-// dynamic LDS each (32 KiB at most); thread t keeps elements j = t + 256 i, i < 32.  Step 1 (g per frame, per
-// detector), the seam between the history slot and the run's slot, the delayed re-read, the meter and the history write
-// are k_lim.hip's and k_limtp.hip's, restated here with the wider tile (the helpers come from k_lim.h; the tile body is
-// a copy because those files' generated code is kept as it is).
-//
-// The release is a min-plus convolution with a ramp, and a ramp doubles as a window does: after k passes
-//     v[j] = min over i < 2^k of (m[j-i] + i*q),    pass k:  v[j] = min(v[j], v[j - 2^k] + (q << k)),
-// k = 0 .. rho - 1.  A partner in front of element 0 counts as 32768: with the added q << k > 0 it never wins, which is
-// what "no earlier frame" means.  (R - 1) * q < 32768 = R * q, so a window of R frames is the whole ramp: an m further
-// back would have to be below zero to matter.  Element j is right after all passes when j >= HIST.
-#include "k_lim.h"
+// dynamic LDS each (32 KiB at most); thread t keeps elements j = t + 256 i, i < LIMREL_SLOTS = 32, and a fast form takes
+// at most 4 (mono), 8 (stereo) vectors per thread in step 1.
+#include "k_lim_tile.h"
 
 namespace cmhip {
-
-constexpr u32 LIMREL_R = LIMREL_SLOTS;               // 32 elements per thread at most
-
-struct LimRelArgs : LimArgs {
-    uint32_t rho;                                    // release_log2, 1..11
-};
-
-// TP: the true-peak detector.  CT: 1 or 2, or 0 for a run-time channel count
-template <bool TP, int CT>
-__device__ __forceinline__ void limrel_tile(const LimRelArgs &a, u32 *L, u32 *red)
-{
-    const u32 C = CT ? (u32)CT : a.channels;
-    const u32 tid = threadIdx.x, tile = a.tile_frames, halo = a.halo;
-    const u32 s = blockIdx.x / a.chunks;             // stream
-    const u32 k = blockIdx.x - s * a.chunks;         // tile inside the stream
-    const u32 F = a.nframes ? a.nframes[s] : a.frames;
-    const u32 f0 = k * tile;
-    const u32 hsamp = halo * C, hv = hsamp >> 3;
-    const int16_t *ins = a.in + (u64)s * a.in_stride;
-    int16_t *outs = a.out + (u64)s * a.out_stride;
-    const int16_t *hs = a.hist + ((u64)a.parity * a.streams + s) * hsamp;
-    int16_t *hn = a.hist + ((u64)(a.parity ^ 1u) * a.streams + s) * hsamp;
-    if (f0 >= F) {                                   // (uniform)
-        if (F == 0 && k == 0)                        // a stream without frames keeps its history across the flip
-            lim_write_hist(ins, hs, hn, hsamp, 0, C);
-        return;
-    }
-    const u32 nt = min(tile, F - f0);                // the tile's frames
-    const u32 N = halo + tile;                       // <= 8192 = 256 * LIMREL_R
-    const u32 ns = F * C, nfull = ns >> 3, ntail = ns & 7u;
-    u32 T, drive;
-
-    // ---- 1. g of frames f0 - halo .. f0 + tile - 1
-    if constexpr (CT != 0 && !TP) {                  // (k_lim.hip)
-        constexpr u32 FPV = 8u / (u32)CT;            // frames per vector
-        constexpr u32 VPT = (LIMREL_R * (u32)CT + 7u) / 8u;  // vectors per thread at most: 4 (mono), 8 (stereo)
-        const u32 NV = N / FPV;
-        const int vbase = (int)((f0 * C) >> 3) - (int)hv;
-        u32 x[VPT][4];
-#pragma unroll
-        for (u32 i = 0; i < VPT; i++) {
-            const u32 w = tid + LIM_BLOCK * i;
-            x[i][0] = x[i][1] = x[i][2] = x[i][3] = 0;
-            if (w < NV)
-                lim_load(x[i], ins, hs, hv, vbase + (int)w, nfull, ntail);
-        }
-        // the stream's parameters, read only now: the tile's loads depend on kernel arguments alone and are on their way
-        __builtin_amdgcn_sched_barrier(0);
-        const u32 pw = uniform(*(a.par + s));
-        T = pw & 0xffffu;
-        drive = pw >> 16;
-        u32x4 *Lv = reinterpret_cast<u32x4 *>(L);
-#pragma unroll
-        for (u32 i = 0; i < VPT; i++) {
-            const u32 w = tid + LIM_BLOCK * i;
-            if (w < NV) {
-                u32 g[8];
-#pragma unroll
-                for (u32 d = 0; d < 4; d++) {
-                    const u32 lo = lim_abs(lim_lo(x[i][d])), hi = lim_abs(lim_hi(x[i][d]));
-                    if constexpr (CT == 1) {
-                        g[2 * d] = lim_gain(lo, drive, T);
-                        g[2 * d + 1] = lim_gain(hi, drive, T);
-                    } else {
-                        g[d] = lim_gain(max(lo, hi), drive, T);
-                    }
-                }
-                const u32x4 g0 = {g[0], g[1], g[2], g[3]};
-                if constexpr (CT == 1) {
-                    const u32x4 g1 = {g[4], g[5], g[6], g[7]};
-                    Lv[2 * w] = g0;
-                    Lv[2 * w + 1] = g1;
-                } else {
-                    Lv[w] = g0;
-                }
-            }
-        }
-    } else if constexpr (CT != 0) {                  // (k_limtp.hip)
-        constexpr u32 FPV = 8u / (u32)CT;            // frames per vector
-        constexpr u32 VPT = (LIMREL_R * (u32)CT + 7u) / 8u;  // own vectors per thread at most: 4 (mono), 8 (stereo)
-        constexpr u32 HV = 16u / FPV;                // vectors in front of them: 16 frames, 13 needed
-        constexpr u32 H0 = HV * FPV;                 // local index of the thread's first own frame
-        const u32 NV = N / FPV;
-        const u32 cnt = (NV + LIM_BLOCK - 1u) / LIM_BLOCK;   // (uniform) own vectors per thread, <= VPT
-        const u32 w0 = tid * cnt;                    // the first of them, counted in the evaluated range
-        const int vbase = (int)((f0 * C) >> 3) - (int)hv;
-        u32 d[(HV + VPT) * 4];
-#pragma unroll
-        for (u32 i = 0; i < HV + VPT; i++) {
-            u32 x[4] = {0, 0, 0, 0};
-            const int w = (int)(w0 + i) - (int)HV;   // vector of the evaluated range; below 0: in front of it
-            const int vv = vbase + w;                // ... of the stream's sequence; below -hv: in front of the slot
-            if (i < HV + cnt && w < (int)NV && vv >= -(int)hv)
-                lim_load(x, ins, hs, hv, vv, nfull, ntail);
-            d[4 * i] = x[0]; d[4 * i + 1] = x[1]; d[4 * i + 2] = x[2]; d[4 * i + 3] = x[3];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const u32 pw = uniform(*(a.par + s));
-        T = pw & 0xffffu;
-        drive = pw >> 16;
-        auto pair = [&](u32 t, u32 c) -> u32 {       // x_c[t-1] | x_c[t] << 16 (k_tpeak.hip)
-            if constexpr (CT == 1) {
-                (void)c;
-                return (t & 1u) ? d[t >> 1] : __builtin_amdgcn_alignbit(d[t >> 1], d[(t >> 1) - 1u], 16);
-            } else {
-                return __builtin_amdgcn_perm(d[t], d[t - 1u], c == 0 ? 0x05040100u : 0x07060302u);
-            }
-        };
-        auto sample = [&](u32 t, u32 c) -> int {     // x_c[t]
-            if constexpr (CT == 1) {
-                (void)c;
-                return (t & 1u) ? lim_hi(d[t >> 1]) : lim_lo(d[t >> 1]);
-            } else {
-                return c == 0 ? lim_lo(d[t]) : lim_hi(d[t]);
-            }
-        };
-        u32x4 *Lv = reinterpret_cast<u32x4 *>(L);
-#pragma unroll
-        for (u32 i = 0; i < VPT; i++) {
-            const u32 w = w0 + i;
-            if (i < cnt && w < NV) {
-                u32 g[FPV];
-#pragma unroll
-                for (u32 f = 0; f < FPV; f++) {
-                    const u32 t = H0 + i * FPV + f;  // local frame of element n: y at n - 2, the sample at n - 8
-                    u32 pk = 0;
-#pragma unroll
-                    for (u32 c = 0; c < (u32)CT; c++) {
-                        pk = max(pk, lim_abs(sample(t - 8u, c)) << 13);
-                        pk = max(pk, limtp_fir(pair, t - 2u, c));
-                        // (one FIR at a time: left to itself the scheduler interleaves the tile's dot chains)
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    g[f] = limtp_gain(pk, drive, T);
-                }
-                const u32x4 g0 = {g[0], g[1], g[2], g[3]};
-                if constexpr (CT == 1) {
-                    const u32x4 g1 = {g[4], g[5], g[6], g[7]};
-                    Lv[2 * w] = g0;
-                    Lv[2 * w + 1] = g1;
-                } else {
-                    Lv[w] = g0;
-                }
-            }
-        }
-    } else {
-        const u32 pw = uniform(*(a.par + s));
-        T = pw & 0xffffu;
-        drive = pw >> 16;
-        for (u32 j = tid; j < N; j += LIM_BLOCK) {
-            const int n = (int)(f0 + j) - (int)halo;             // frame
-            u32 pk = 0;
-            if constexpr (!TP) {
-                if (n < (int)F)
-                    for (u32 c = 0; c < C; c++)
-                        pk = max(pk, lim_abs(lim_sample(ins, hs, hsamp, n * (int)C + (int)c)));
-                L[j] = lim_gain(pk, drive, T);
-            } else {
-                for (u32 c = 0; c < C; c++) {
-                    int x[LIM_TP_FRONT];             // x[i] is frame n - 13 + i: zeros in front of the slot and past the count
-#pragma unroll
-                    for (u32 i = 0; i < LIM_TP_FRONT; i++) {
-                        const int p = n - (int)LIM_TP_FRONT + (int)i;
-                        x[i] = p >= -(int)halo && p < (int)F ? lim_sample(ins, hs, hsamp, p * (int)C + (int)c) : 0;
-                    }
-                    pk = max(pk, lim_abs(x[LIM_TP_FRONT - 8u]) << 13);
-#pragma unroll
-                    for (u32 ph = 0; ph < 4; ph++) {
-                        int y = 0;
-#pragma unroll
-                        for (u32 t = 0; t < TP_TAPS; t++)
-                            y += (int)tp_h(ph, t) * x[LIM_TP_FRONT - 2u - t];
-                        pk = max(pk, lim_abs(y));
-                    }
-                }
-                L[j] = limtp_gain(pk, drive, T);
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- 2. sliding minimum over W, release ramp over R, boxcar sum over A: doubling, own elements in registers
-    u32 v[LIMREL_R];
-#pragma unroll
-    for (u32 i = 0; i < LIMREL_R; i++) {
-        const u32 j = tid + LIM_BLOCK * i;
-        v[i] = j < N ? L[j] : LIM_UNITY;
-    }
-    // (at entry LDS holds v and every thread is past its reads)
-    // kind 0: v = min(v, partner); 1: v = min(v, partner + add); 2: v += partner, v >> shift goes to LDS
-    auto pass = [&](u32 dist, auto kind, u32 add, u32 shift) {
-        constexpr int K = decltype(kind)::value;
-        u32 o[LIMREL_R];
-#pragma unroll
-        for (u32 i = 0; i < LIMREL_R; i++) {
-            const u32 j = tid + LIM_BLOCK * i;
-            o[i] = j < N && j >= dist ? L[j - dist] : (K == 2 ? 0u : LIM_UNITY);
-        }
-        __syncthreads();
-#pragma unroll
-        for (u32 i = 0; i < LIMREL_R; i++) {
-            const u32 j = tid + LIM_BLOCK * i;
-            if constexpr (K == 0)
-                v[i] = min(v[i], o[i]);
-            else if constexpr (K == 1)
-                v[i] = min(v[i], o[i] + add);
-            else
-                v[i] = v[i] + o[i];
-            if (j < N)
-                L[j] = v[i] >> shift;
-        }
-        __syncthreads();
-    };
-    using k_min = std::integral_constant<int, 0>;
-    using k_rel = std::integral_constant<int, 1>;
-    using k_sum = std::integral_constant<int, 2>;
-    const u32 W = a.W, la = a.a, rho = a.rho;
-    u32 P = 1;
-    for (; 2u * P <= W; P *= 2u)
-        pass(P, k_min{}, 0, 0);
-    if (W > P)
-        pass(W - P, k_min{}, 0, 0);
-    const u32 q = LIM_UNITY >> rho;
-    for (u32 e = 0; e < rho; e++)
-        pass(1u << e, k_rel{}, q << e, 0);
-    for (u32 d = 1; d < (1u << la); d *= 2u)
-        pass(d, k_sum{}, 0, 2u * d == (1u << la) ? la : 0u);         // the last pass leaves s = S >> a in LDS
-
-    // ---- the gain-reduction meter: minimum of s over the tile's frames, one atomic per workgroup
-    {
-        u32 red_max = 0;                             // of 32768 - s
-#pragma unroll
-        for (u32 i = 0; i < LIMREL_R; i++) {
-            const u32 j = tid + LIM_BLOCK * i;
-            if (j >= halo && j < halo + nt)
-                red_max = max(red_max, LIM_UNITY - (v[i] >> la));
-        }
-        red_max = wave_max_u32(red_max);
-        if ((tid & 63u) == 0)
-            red[tid >> 6] = red_max;
-        __syncthreads();
-        if (tid == 0) {
-            const u32 m = max(max(red[0], red[1]), max(red[2], red[3]));
-            if (m)
-                atomicMin(a.gmin + s, LIM_UNITY - m);
-        }
-    }
-
-    // ---- 3. y[n] = x[n - D] * (drive * s[n]): output vectors f0*C/8 .. of the tile
-    const u32 D = (1u << la) - 1u + (TP ? LIM_TP_LAG : 0u);          // D + 1 is a multiple of 8 frames for both
-    const u32 vb = (f0 * C) >> 3, nv = (nt * C + 7u) >> 3;
-    u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
-    const u32 *Ls = L + halo;                        // s of the tile's frames
-    if constexpr (CT != 0) {
-        constexpr u32 FPV = 8u / (u32)CT;
-        const u32 back = ((D + 1u) * C) >> 3;        // the delayed samples of vector v: CT of vector v - back ...
-        for (u32 w = tid; w < nv; w += LIM_BLOCK) {
-            const u32 v8 = vb + w;
-            u32 x0[4], x1[4];
-            lim_load(x0, ins, hs, hv, (int)v8 - (int)back, nfull, ntail);
-            lim_load(x1, ins, hs, hv, (int)v8 - (int)back + 1, nfull, ntail);     // ... and the first 8 - CT of the next
-            const u32x4 *sv = reinterpret_cast<const u32x4 *>(Ls + w * FPV);
-            u32 o[4];
-            if constexpr (CT == 1) {
-                const u32x4 s0 = sv[0], s1 = sv[1];
-                const u32 sf[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-                const u32 xs[5] = {x0[0], x0[1], x0[2], x0[3], x1[0]};
-#pragma unroll
-                for (u32 d = 0; d < 4; d++)          // output samples 2d, 2d + 1 are input samples 2d + 1, 2d + 2
-                    o[d] = lim_apply(lim_hi(xs[d]), drive * sf[2 * d]) | lim_apply(lim_lo(xs[d + 1]), drive * sf[2 * d + 1]) << 16;
-            } else {
-                const u32x4 s0 = sv[0];
-                const u32 sf[4] = {s0.x, s0.y, s0.z, s0.w};
-                const u32 xs[4] = {x0[1], x0[2], x0[3], x1[0]};
-#pragma unroll
-                for (u32 d = 0; d < 4; d++)
-                    o[d] = lim_apply(lim_lo(xs[d]), drive * sf[d]) | lim_apply(lim_hi(xs[d]), drive * sf[d]) << 16;
-            }
-            if (v8 < nfull) {
-                const u32x4 ov = {o[0], o[1], o[2], o[3]};
-                __builtin_nontemporal_store(ov, dst + v8);
-            } else if (v8 == nfull) {
-                store_tail(outs, v8, o, ntail);
-            }
-        }
-    } else {
-        for (u32 w = tid; w < nv; w += LIM_BLOCK) {
-            const u32 v8 = vb + w;
-            u32 o[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (u32 e = 0; e < 8; e++) {
-                const u32 qs = v8 * 8u + e;          // output sample of the stream
-                if (qs < ns) {
-                    const u32 n = qs / C;
-                    const int x = lim_sample(ins, hs, hsamp, (int)qs - (int)(D * C));
-                    o[e >> 1] |= lim_apply(x, drive * Ls[n - f0]) << (16u * (e & 1u));
-                }
-            }
-            if (v8 < nfull) {
-                const u32x4 ov = {o[0], o[1], o[2], o[3]};
-                __builtin_nontemporal_store(ov, dst + v8);
-            } else if (v8 == nfull) {
-                store_tail(outs, v8, o, ntail);
-            }
-        }
-    }
-
-    // ---- 4. the stream's last tile leaves the history of the next run
-    if (F <= f0 + tile)
-        lim_write_hist(ins, hs, hn, hsamp, F, C);
-}
 
 template <int C>
 __global__ __launch_bounds__(LIM_BLOCK) void k_limrel_fast(LimRelArgs a)
 {
     extern __shared__ u32x4 limrel_lds[];
     __shared__ u32 red[4];
-    limrel_tile<false, C>(a, reinterpret_cast<u32 *>(limrel_lds), red);
+    lim_tile<false, true, LIMREL_SLOTS, C>(a, reinterpret_cast<u32 *>(limrel_lds), red);
 }
 
 __global__ __launch_bounds__(LIM_BLOCK) void k_limrel_any(LimRelArgs a)
 {
     extern __shared__ u32x4 limrel_lds[];
     __shared__ u32 red[4];
-    limrel_tile<false, 0>(a, reinterpret_cast<u32 *>(limrel_lds), red);
+    lim_tile<false, true, LIMREL_SLOTS, 0>(a, reinterpret_cast<u32 *>(limrel_lds), red);
 }
 
 template <int C>
@@ -357,14 +39,14 @@ __global__ __launch_bounds__(LIM_BLOCK) void k_limtprel_fast(LimRelArgs a)
 {
     extern __shared__ u32x4 limrel_lds[];
     __shared__ u32 red[4];
-    limrel_tile<true, C>(a, reinterpret_cast<u32 *>(limrel_lds), red);
+    lim_tile<true, true, LIMREL_SLOTS, C>(a, reinterpret_cast<u32 *>(limrel_lds), red);
 }
 
 __global__ __launch_bounds__(LIM_BLOCK) void k_limtprel_any(LimRelArgs a)
 {
     extern __shared__ u32x4 limrel_lds[];
     __shared__ u32 red[4];
-    limrel_tile<true, 0>(a, reinterpret_cast<u32 *>(limrel_lds), red);
+    lim_tile<true, true, LIMREL_SLOTS, 0>(a, reinterpret_cast<u32 *>(limrel_lds), red);
 }
 
 // ---------------------------------------------------------------------------
@@ -375,29 +57,12 @@ hipError_t launch_limrel(const LimArgs &a, uint32_t detector, uint32_t release_l
     if (release_log2 == 0)                           // the limiter without the stage: the kernels it always had
         return detector == LIM_DETECT_TRUE_PEAK ? launch_limtp(a, st) : launch_lim(a, st);
     const LimPlan p = plan_limrel(detector, a.streams, a.channels, a.a, a.W - (1u << a.a), release_log2, a.frames);
-    if (p.grid == 0)
-        return p.err ? hipErrorInvalidValue : hipSuccess;
     LimRelArgs b;
     static_cast<LimArgs &>(b) = a;
-    b.halo = p.halo;
-    b.chunks = p.chunks;
-    b.tile_frames = p.tile_frames;
     b.rho = release_log2;
-    const dim3 grid(p.grid), block(p.block);
-    if (detector == LIM_DETECT_TRUE_PEAK) {
-        switch (a.channels) {
-        case 1: hipLaunchKernelGGL((k_limtprel_fast<1>), grid, block, p.lds_bytes, st, b); break;
-        case 2: hipLaunchKernelGGL((k_limtprel_fast<2>), grid, block, p.lds_bytes, st, b); break;
-        default: hipLaunchKernelGGL(k_limtprel_any, grid, block, p.lds_bytes, st, b); break;
-        }
-    } else {
-        switch (a.channels) {
-        case 1: hipLaunchKernelGGL((k_limrel_fast<1>), grid, block, p.lds_bytes, st, b); break;
-        case 2: hipLaunchKernelGGL((k_limrel_fast<2>), grid, block, p.lds_bytes, st, b); break;
-        default: hipLaunchKernelGGL(k_limrel_any, grid, block, p.lds_bytes, st, b); break;
-        }
-    }
-    return hipGetLastError();
+    if (detector == LIM_DETECT_TRUE_PEAK)
+        return lim_launch<LimRelArgs>(p, b, st, k_limtprel_fast<1>, k_limtprel_fast<2>, k_limtprel_any);
+    return lim_launch<LimRelArgs>(p, b, st, k_limrel_fast<1>, k_limrel_fast<2>, k_limrel_any);
 }
 
 // test hook: the plan of a run of a limiter with a release stage (host logic, needs no GPU)

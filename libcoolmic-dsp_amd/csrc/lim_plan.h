@@ -19,7 +19,9 @@
 // slope q = 32768 >> rho between the minimum and the sum: HIST grows by R - 1 and may reach 4096 = LIMREL_HIST_MAX, the
 // tile, so the tile is always 4096 frames and a workgroup evaluates up to 8192 elements, LIMREL_SLOTS = 32 per thread,
 // 32 KiB of dynamic LDS: lim_geom_rel / plan_limrel.  rho = 0 is the limiter without the stage: lim_geom_rel and
-// plan_limrel then give what lim_geom_of and plan_lim_of give, and the launchers take k_lim.hip's and k_limtp.hip's kernels.
+// plan_limrel then give what lim_geom_of and plan_lim_of give, and the launchers take k_lim.hip's and k_limtp.hip's
+// kernels (LIM_R = 26 slots per thread, csrc/k_lim.h).  The slot counts are arguments of the one tile template
+// (csrc/k_lim_tile.h).
 #ifndef CMHIP_LIM_PLAN_H
 #define CMHIP_LIM_PLAN_H
 
@@ -122,18 +124,10 @@ struct LimPlan {
     uint32_t halo;
 };
 
-// the plan of a run whose longest stream has `frames` frames, for either detector
-inline LimPlan plan_lim_of(uint32_t detector, uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold,
-                           uint32_t frames)
+// what every plan ends in, the geometry known: the tiles of a run whose longest stream has `frames` frames
+inline LimPlan lim_plan_tiles(uint32_t streams, uint32_t channels, uint32_t frames, uint32_t halo, uint32_t tile)
 {
     LimPlan p{};
-    LimGeom g;
-    if (streams == 0 || frames == 0 || channels == 0 || channels > LIM_MAX_CH ||
-        !lim_geom_of(detector, lookahead_log2, hold, &g))
-        return p;
-    uint32_t tile = LIM_TILE_MAX;
-    while (tile / 2u >= g.halo && tile / 2u >= 8u && (tile + g.halo) * 4u > LIM_LDS_LIMIT)
-        tile >>= 1;                                   // (never taken today: 4096 + 2560 frames are 26 KiB)
     const uint64_t tiles = ((uint64_t)frames + tile - 1u) / tile;
     if (tiles * streams >= (1ull << 31)) {
         p.err = 1;
@@ -142,11 +136,29 @@ inline LimPlan plan_lim_of(uint32_t detector, uint32_t streams, uint32_t channel
     p.fast = channels <= 2u ? 1u : 0u;
     p.block = LIM_BLOCK;
     p.tile_frames = tile;
-    p.lds_bytes = (tile + g.halo) * 4u;
-    p.halo = g.halo;
+    p.lds_bytes = (tile + halo) * 4u;
+    p.halo = halo;
     p.chunks = (uint32_t)tiles;
     p.grid = streams * p.chunks;
     return p;
+}
+
+inline bool lim_run_ok(uint32_t streams, uint32_t channels, uint32_t frames)
+{
+    return streams != 0 && frames != 0 && channels != 0 && channels <= LIM_MAX_CH;
+}
+
+// the plan of a run whose longest stream has `frames` frames, for either detector
+inline LimPlan plan_lim_of(uint32_t detector, uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold,
+                           uint32_t frames)
+{
+    LimGeom g;
+    if (!lim_run_ok(streams, channels, frames) || !lim_geom_of(detector, lookahead_log2, hold, &g))
+        return LimPlan{};
+    uint32_t tile = LIM_TILE_MAX;
+    while (tile / 2u >= g.halo && tile / 2u >= 8u && (tile + g.halo) * 4u > LIM_LDS_LIMIT)
+        tile >>= 1;                                   // (never taken today: 4096 + 2560 frames are 26 KiB)
+    return lim_plan_tiles(streams, channels, frames, g.halo, tile);
 }
 
 inline LimPlan plan_lim(uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold, uint32_t frames)
@@ -164,27 +176,12 @@ inline LimPlan plan_limtp(uint32_t streams, uint32_t channels, uint32_t lookahea
 inline LimPlan plan_limrel(uint32_t detector, uint32_t streams, uint32_t channels, uint32_t lookahead_log2, uint32_t hold,
                            uint32_t release_log2, uint32_t frames)
 {
-    LimPlan p{};
     LimGeom g;
     if (release_log2 == 0)
         return plan_lim_of(detector, streams, channels, lookahead_log2, hold, frames);
-    if (streams == 0 || frames == 0 || channels == 0 || channels > LIM_MAX_CH ||
-        !lim_geom_rel(detector, lookahead_log2, hold, release_log2, &g))
-        return p;
-    const uint32_t tile = LIM_TILE_MAX;
-    const uint64_t tiles = ((uint64_t)frames + tile - 1u) / tile;
-    if (tiles * streams >= (1ull << 31)) {
-        p.err = 1;
-        return p;
-    }
-    p.fast = channels <= 2u ? 1u : 0u;
-    p.block = LIM_BLOCK;
-    p.tile_frames = tile;
-    p.lds_bytes = (tile + g.halo) * 4u;
-    p.halo = g.halo;
-    p.chunks = (uint32_t)tiles;
-    p.grid = streams * p.chunks;
-    return p;
+    if (!lim_run_ok(streams, channels, frames) || !lim_geom_rel(detector, lookahead_log2, hold, release_log2, &g))
+        return LimPlan{};
+    return lim_plan_tiles(streams, channels, frames, g.halo, LIM_TILE_MAX);
 }
 
 }  // namespace cmhip

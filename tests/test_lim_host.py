@@ -19,14 +19,15 @@ PKG = os.path.join(ROOT, "libcoolmic-dsp_amd")
 PLAN_SRC = os.path.join(ROOT, "tests", "cpp", "lim_plan_test.cpp")
 
 
-def _gpu_test_module():
-    spec = importlib.util.spec_from_file_location("test_gpu_lim_model", os.path.join(ROOT, "tests", "test_gpu_lim.py"))
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name + "_for_lim", os.path.join(ROOT, "tests", name + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
 
 
-TG = _gpu_test_module()            # the model, the signal and the dense cases of the GPU tests
+MH = _load("test_limtp_host")      # the emulation of the tile that all three limiter kernel files instantiate
+TG = MH.TG                         # tests/test_gpu_lim.py: the model, the signal and the dense cases of the GPU tests
 UNITY = 32768
 
 
@@ -99,7 +100,7 @@ def test_plan(cm):
                 assert t >= hist and t >= p.halo == halo and t <= 4096 and t & (t - 1) == 0
                 assert p.lds_bytes == (t + halo) * 4 <= 65536    # what a workgroup may use without a raised limit
                 assert t == 4096 or (2 * t + halo) * 4 > 65536   # the largest power of two that fits
-                assert t + halo <= 256 * 26                      # the elements a thread keeps (k_lim.hip: LIM_R)
+                assert t + halo <= 256 * 26                      # the elements a thread keeps (k_lim.h: LIM_R)
                 for frames in (1, t - 1, t, t + 1, 100000):
                     q = cm.plan_lim(3, ch, a, H, frames)
                     assert (q.err, q.chunks, q.grid, q.tile_frames) == (0, -(-frames // t), 3 * -(-frames // t), t)
@@ -165,113 +166,11 @@ def test_division_is_exact(T):
 
 
 # ---------------------------------------------------------------------------
-# The decomposition of k_lim_fast<C> / k_lim_any (csrc/k_lim.hip), step by step in numpy, one workgroup per tile.
+# The decomposition of k_lim_fast<C> / k_lim_any (csrc/k_lim.hip): the one emulation of the tile
+# (tests/test_limtp_host.py) with the sample detector, no release and these kernels' 26 slots per thread.
 
-BLOCK, R = 256, 26
-
-
-def _gain(peak, drive, T):
-    pr = (peak * drive + 4095) >> 12
-    return np.where(pr <= T, UNITY, (T * 32768) // np.maximum(pr, 1))
-
-
-def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
-    """one stream of one run: x int16 [F][C], slot int64 [halo * C] (the history slot the run reads)
-    -> out int64 [F * C + 8] (UNWRITTEN where nothing was stored), the slot the run writes, min s or None"""
-    A, D, W, hist = TG.geometry(a, H)
-    F = x.shape[0]
-    ns, hsamp = F * ch, halo * ch
-    hv, nfull, ntail = hsamp // 8, ns // 8, ns % 8
-    assert hsamp % 8 == 0 and tile >= halo >= hist
-    # the stream as a tile sees it: the slot's vectors below 0, the run's from 0 on, zeros past the count
-    seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)])
-
-    def vec(vv):                                                  # [n] vector indices -> [n][8] samples
-        vv = np.asarray(vv)
-        assert (vv >= -hv).all()
-        return seq[(hsamp + vv * 8)[:, None] + np.arange(8)]
-
-    def sample(q):
-        q = np.asarray(q)
-        assert (q >= -hsamp).all() and (q < ns).all()
-        return seq[hsamp + q]
-
-    out = np.full(ns + 8, UNWRITTEN, dtype=np.int64)
-    new_slot = sample(ns - hsamp + np.arange(hsamp))              # 4. (the last tile, or tile 0 of a stream with 0 frames)
-    if F == 0:
-        assert np.array_equal(new_slot, slot)
-        return out, new_slot, None
-    gmin = UNITY
-    N = halo + tile
-    tid, i = np.meshgrid(np.arange(BLOCK), np.arange(R), indexing="ij")
-    own = (tid + BLOCK * i).reshape(-1)
-    own = own[own < N]
-    assert np.array_equal(np.sort(own), np.arange(N))            # every element has exactly one thread
-    for f0 in range(0, F, tile):
-        nt = min(tile, F - f0)
-        L = np.full(N, UNWRITTEN, dtype=np.int64)
-        # ---- 1. g of frames f0 - halo .. f0 + tile - 1
-        if ch <= 2:
-            fpv = 8 // ch
-            NV = N // fpv
-            assert NV <= BLOCK * ((R * ch + 7) // 8)
-            vbase = f0 * ch // 8 - hv
-            assert f0 == 0 or vbase >= 0                          # only the run's first tile reads the slot
-            v = np.abs(vec(vbase + np.arange(NV)))
-            peak = v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])
-            L[:] = _gain(peak, drive, T).reshape(-1)
-        else:
-            p = f0 - halo + np.arange(N)
-            peak = np.zeros(N, dtype=np.int64)
-            inside = p < F
-            peak[inside] = np.abs(sample(p[inside, None] * ch + np.arange(ch))).max(axis=1)
-            L[:] = _gain(peak, drive, T)
-        assert (L != UNWRITTEN).all()
-        # ---- 2. the passes: partner from LDS, own element back
-        j = np.arange(N)
-
-        def one_pass(L, dist, is_min, shift, vreg):
-            o = np.where(j >= dist, L[np.maximum(j - dist, 0)], UNITY if is_min else 0)
-            vreg = np.minimum(vreg, o) if is_min else vreg + o
-            assert vreg.max() < 2 ** 32
-            return vreg >> shift, vreg
-
-        vreg = L.copy()
-        P = 1
-        while 2 * P <= W:
-            L, vreg = one_pass(L, P, True, 0, vreg)
-            P *= 2
-        if W > P:
-            L, vreg = one_pass(L, W - P, True, 0, vreg)
-        d = 1
-        while d < A:
-            L, vreg = one_pass(L, d, False, a if 2 * d == A else 0, vreg)
-            d *= 2
-        Ls = L[halo:]
-        gmin = min(gmin, int(Ls[:nt].min()))
-        # ---- 3. the tile's output vectors
-        vb, nv = f0 * ch // 8, (nt * ch + 7) // 8
-        v8 = vb + np.arange(nv)
-        if ch <= 2:
-            back = (D + 1) * ch // 8
-            x0, x1 = vec(v8 - back), vec(v8 - back + 1)
-            xs = np.concatenate([x0[:, ch:], x1[:, :ch]], axis=1)                 # mono: samples 1..8, stereo: 2..9
-            sf = Ls[(np.arange(nv) * (8 // ch))[:, None] + np.arange(8) // ch]
-            y = (xs * (drive * sf) + (1 << 26)) >> 27
-        else:
-            q = v8[:, None] * 8 + np.arange(8)
-            ok = q < ns
-            qq = np.where(ok, q, 0)
-            y = np.where(ok, (sample(qq - D * ch) * (drive * Ls[np.where(ok, qq // ch - f0, 0)]) + (1 << 26)) >> 27, 0)
-        for w in range(nv):
-            if v8[w] < nfull:
-                out[v8[w] * 8:v8[w] * 8 + 8] = y[w]
-            elif v8[w] == nfull:
-                out[v8[w] * 8:v8[w] * 8 + ntail] = y[w, :ntail]
-    return out, new_slot, gmin
-
-
-UNWRITTEN = 1 << 40
+SLOTS = 26
+UNWRITTEN = MH.UNWRITTEN
 
 
 @pytest.mark.parametrize("channels", [1, 2, 3, 16])
@@ -285,7 +184,7 @@ def test_emulated_decomposition_equals_the_model(cm, a, H, T, drive, channels):
         slot = np.zeros(halo * channels, dtype=np.int64)
         got_min = UNITY
         for x, want in ((xs[s][:counts[s]], ragged[s]), (xs[s], full[s])):
-            out, slot, m = _emulate_run(x, slot, T, drive, a, H, channels, t, halo)
+            out, slot, m = MH._emulate_run(0, x, slot, T, drive, a, H, 0, channels, t, halo, SLOTS)
             w = want.astype(np.int64).reshape(-1)
             assert np.array_equal(out[:w.size], w), (channels, s)
             assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
@@ -339,7 +238,8 @@ def test_kernel_assembly_house_rules():
     assert any("k_lim_fastILi1E" in k for k in names) and any("k_lim_fastILi2E" in k for k in names), names
     assert any("k_lim_any" in k for k in names) and any("k_lim_set" in k for k in names), names
     assert all(v == 0 for v in scratch.values()), scratch
-    src = open(os.path.join(PKG, "csrc", "k_lim.hip")).read()
-    assert "getenv" not in src
-    for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-        assert not re.findall(r"\bCMHIP_\w+", m.group(1)), m.group(0)
+    for name in ("k_lim.hip", "k_lim.h", "k_lim_tile.h"):
+        src = open(os.path.join(PKG, "csrc", name)).read()
+        assert "getenv" not in src
+        for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
+            assert not re.findall(r"\bCMHIP_(?!K_LIM(?:_TILE)?_H\b)\w+", m.group(1)), m.group(0)

@@ -411,145 +411,11 @@ def test_model_properties(det, i):
 
 
 # ---------------------------------------------------------------------------
-# The decomposition of k_limrel_fast<C> / k_limrel_any / k_limtprel_fast<C> / k_limtprel_any (csrc/k_limrel.hip), step by
-# step in numpy, one workgroup per tile.
+# The decomposition of k_limrel_fast<C> / k_limrel_any / k_limtprel_fast<C> / k_limtprel_any (csrc/k_limrel.hip): the one
+# emulation of the tile (tests/test_limtp_host.py) with these kernels' 32 slots per thread and their release.
 
-BLOCK, SLOTS = 256, 32
-UNWRITTEN = 1 << 40
-
-
-def _emulate_run(det, x, slot, T, drive, a, H, rho, ch, tile, halo):
-    """one stream of one run: x int16 [F][C], slot int64 [halo * C] (the history slot the run reads)
-    -> out int64 [F * C + 8] (UNWRITTEN where nothing was stored), the slot the run writes, min s or None"""
-    A, D, W, hist, R, q = geometry_rel(det, a, H, rho)
-    F = x.shape[0]
-    ns, hsamp = F * ch, halo * ch
-    hv, nfull, ntail = hsamp // 8, ns // 8, ns % 8
-    assert hsamp % 8 == 0 and tile >= halo >= hist >= D and (D + 1) % 8 == 0 and rho >= 1
-    # the stream as a tile sees it: the slot's vectors below 0, the run's from 0 on, zeros past the count
-    seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)])
-
-    def vec(vv):                                                  # [...] vector indices -> [...][8] samples
-        vv = np.asarray(vv)
-        assert (vv >= -hv).all()
-        return seq[(hsamp + vv * 8)[..., None] + np.arange(8)]
-
-    def sample(qq):
-        qq = np.asarray(qq)
-        assert (qq >= -hsamp).all() and (qq < ns).all()
-        return seq[hsamp + qq]
-
-    out = np.full(ns + 8, UNWRITTEN, dtype=np.int64)
-    new_slot = sample(ns - hsamp + np.arange(hsamp))              # 4. (the last tile, or tile 0 of a stream with 0 frames)
-    if F == 0:
-        assert np.array_equal(new_slot, slot)
-        return out, new_slot, None
-    gmin = UNITY
-    N = halo + tile
-    tid, i = np.meshgrid(np.arange(BLOCK), np.arange(SLOTS), indexing="ij")
-    own = (tid + BLOCK * i).reshape(-1)                           # thread t keeps elements t + 256 i, i < 32
-    own = own[own < N]
-    assert N <= BLOCK * SLOTS and np.array_equal(np.sort(own), np.arange(N))  # every element has exactly one thread
-    for f0 in range(0, F, tile):
-        nt = min(tile, F - f0)
-        L = np.full(N, UNWRITTEN, dtype=np.int64)
-        vbase = f0 * ch // 8 - hv
-        assert f0 == 0 or vbase >= 0                              # only the run's first tile reads the slot: halo <= tile
-        # ---- 1. g of frames f0 - halo .. f0 + tile - 1
-        if ch <= 2 and not det:
-            fpv = 8 // ch
-            NV = N // fpv
-            assert N % fpv == 0 and NV <= BLOCK * ((SLOTS * ch + 7) // 8)
-            v = np.abs(vec(vbase + np.arange(NV)))
-            peak = v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])
-            L[:] = gains_of_peak(peak, drive, T).reshape(-1)
-        elif ch <= 2:
-            fpv = 8 // ch
-            HV = 16 // fpv                                        # vectors in front of a thread's own: 16 frames
-            NV = N // fpv
-            cnt = -(-NV // BLOCK)                                 # own vectors per thread, consecutive
-            assert N % fpv == 0 and cnt <= (SLOTS * ch + 7) // 8
-            w = (np.arange(BLOCK) * cnt)[:, None] + np.arange(-HV, cnt)[None, :]         # [thread][local vector]
-            vv = vbase + w
-            loaded = (w < NV) & (vv >= -hv)                       # the rest are zeros: in front of the slot, past the range
-            d = np.where(loaded[..., None], vec(np.where(loaded, vv, 0)), 0)             # [thread][local vector][8]
-            loc = d.reshape(BLOCK, (HV + cnt) * fpv, ch)          # [thread][local frame][channel]
-            t = 16 + np.arange(cnt * fpv)                         # the own frames' local indices
-            pk = np.zeros((BLOCK, cnt * fpv), dtype=np.int64)
-            for c in range(ch):
-                fir = MH._pair_dot(loc[:, :, c])                  # of local frames 11 ..
-                pk = np.maximum(pk, np.maximum(np.abs(loc[:, t - 8, c]) << 13, fir[:, t - 2 - 11]))
-            j = (w[:, HV:, None] * fpv + np.arange(fpv)).reshape(BLOCK, -1)              # the elements they are
-            keep = np.repeat(w[:, HV:] < NV, fpv, axis=1)
-            assert np.array_equal(np.sort(j[keep]), np.arange(N))                        # each written once
-            L[j[keep]] = MH._gain(pk[keep], drive, T)
-        elif not det:
-            p = f0 - halo + np.arange(N)
-            peak = np.zeros(N, dtype=np.int64)
-            inside = p < F
-            peak[inside] = np.abs(sample(p[inside, None] * ch + np.arange(ch))).max(axis=1)
-            L[:] = gains_of_peak(peak, drive, T)
-        else:
-            n = f0 - halo + np.arange(N)
-            p = n[:, None] - MH.FRONT + np.arange(MH.FRONT)       # frames n - 13 .. n - 1
-            inside = (p >= -halo) & (p < F)
-            xs = np.where(inside[..., None], sample(np.where(inside, p, 0)[..., None] * ch + np.arange(ch)), 0)
-            pk = np.abs(xs[:, MH.FRONT - 8]).max(axis=1) << 13
-            for ph in range(4):
-                y = sum(MH.TP_H[ph, k] * xs[:, MH.FRONT - 2 - k] for k in range(12))
-                pk = np.maximum(pk, np.abs(y).max(axis=1))
-            L[:] = MH._gain(pk, drive, T)
-        assert (L != UNWRITTEN).all()
-        # ---- 2. the passes: partner from LDS (32768, or 0 for a sum, in front of element 0), own element back
-        j = np.arange(N)
-
-        def one_pass(L, dist, kind, add, shift, vreg):
-            o = np.where(j >= dist, L[np.maximum(j - dist, 0)], 0 if kind == 2 else UNITY)
-            vreg = np.minimum(vreg, o) if kind == 0 else np.minimum(vreg, o + add) if kind == 1 else vreg + o
-            assert vreg.max() < 2 ** 32 and (o + add).max() < 2 ** 32
-            return vreg >> shift, vreg
-
-        vreg = L.copy()
-        P = 1
-        while 2 * P <= W:
-            L, vreg = one_pass(L, P, 0, 0, 0, vreg)
-            P *= 2
-        if W > P:
-            L, vreg = one_pass(L, W - P, 0, 0, 0, vreg)
-        for e in range(rho):
-            L, vreg = one_pass(L, 1 << e, 1, q << e, 0, vreg)
-        dd = 1
-        while dd < A:
-            L, vreg = one_pass(L, dd, 2, 0, a if 2 * dd == A else 0, vreg)
-            dd *= 2
-        Ls = L[halo:]
-        gmin = min(gmin, int(Ls[:nt].min()))
-        # ---- 3. the tile's output vectors: the delayed samples of vector v lie in vectors v - back and v - back + 1
-        vb, nv = f0 * ch // 8, (nt * ch + 7) // 8
-        v8 = vb + np.arange(nv)
-        if ch <= 2:
-            back = (D + 1) * ch // 8
-            assert (D + 1) * ch % 8 == 0 and (v8 - back >= -hv).all()
-            x0, x1 = vec(v8 - back), vec(v8 - back + 1)
-            xs = np.concatenate([x0[:, ch:], x1[:, :ch]], axis=1)                 # mono: samples 1..8, stereo: 2..9
-            sf = Ls[(np.arange(nv) * (8 // ch))[:, None] + np.arange(8) // ch]
-            y = (xs * (drive * sf) + (1 << 26)) >> 27
-        else:
-            qq = v8[:, None] * 8 + np.arange(8)
-            ok = qq < ns
-            qq = np.where(ok, qq, 0)
-            y = np.where(ok, (sample(qq - D * ch) * (drive * Ls[np.where(ok, qq // ch - f0, 0)]) + (1 << 26)) >> 27, 0)
-        for k in range(nv):
-            if v8[k] < nfull:
-                out[v8[k] * 8:v8[k] * 8 + 8] = y[k]
-            elif v8[k] == nfull:
-                out[v8[k] * 8:v8[k] * 8 + ntail] = y[k, :ntail]
-    return out, new_slot, gmin
-
-
-def gains_of_peak(peak, drive, T):
-    pr = (peak * drive + 4095) >> 12
-    return np.where(pr <= T, UNITY, (T * 32768) // np.maximum(pr, 1))
+SLOTS = 32
+UNWRITTEN = MH.UNWRITTEN
 
 
 @pytest.mark.parametrize("channels", [1, 2, 3, 16])
@@ -565,7 +431,8 @@ def test_emulated_decomposition_equals_the_model(cm, det, i, channels):
         slot = np.zeros(halo * channels, dtype=np.int64)
         got_min = UNITY
         for x, want in ((xs[s][:counts[s]], ragged[s]), (xs[s], full[s])):
-            out, slot, m = _emulate_run(det, x, slot, T, drive, a, H, rho, channels, t, halo)
+            assert rho >= 1
+            out, slot, m = MH._emulate_run(det, x, slot, T, drive, a, H, rho, channels, t, halo, SLOTS)
             w = want.astype(np.int64).reshape(-1)
             assert np.array_equal(out[:w.size], w), (channels, s)
             assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
@@ -598,7 +465,8 @@ def test_kernel_assembly_house_rules():
                  "k_limtprel_any"):
         assert any(stem in k for k in names), (stem, names)
     assert len(names) == 6 and all(v == 0 for v in scratch.values()), scratch
-    src = open(os.path.join(PKG, "csrc", "k_limrel.hip")).read()
-    assert "getenv" not in src
-    for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-        assert not re.findall(r"\bCMHIP_\w+", m.group(1)), m.group(0)
+    for name in ("k_limrel.hip", "k_lim.h", "k_lim_tile.h"):
+        src = open(os.path.join(PKG, "csrc", name)).read()
+        assert "getenv" not in src
+        for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
+            assert not re.findall(r"\bCMHIP_(?!K_LIM(?:_TILE)?_H\b)\w+", m.group(1)), m.group(0)

@@ -413,10 +413,17 @@ def test_sample_detector_lets_an_inter_sample_peak_through():
 
 
 # ---------------------------------------------------------------------------
-# The decomposition of k_limtp_fast<C> / k_limtp_any (csrc/k_limtp.hip), step by step in numpy, one workgroup per tile.
+# The decomposition of the limiter's one tile (csrc/k_lim_tile.h: lim_tile<TP, REL, SLOTS, CT>), step by step in numpy,
+# one workgroup per tile.  tests/test_lim_host.py and tests/test_limrel_host.py run it too, each with the slot count and
+# the release of its own kernels.
 
-BLOCK, R = 256, 26
+BLOCK = 256
 UNWRITTEN = 1 << 40
+
+
+def _gain_sample(peak, drive, T):
+    pr = (peak * drive + 4095) >> 12
+    return np.where(pr <= T, UNITY, (T * 32768) // np.maximum(pr, 1))
 
 
 def _gain(t, drive, T):
@@ -438,14 +445,16 @@ def _pair_dot(loc):
     return np.abs(y).max(axis=0)
 
 
-def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
-    """one stream of one run: x int16 [F][C], slot int64 [halo * C] (the history slot the run reads)
+def _emulate_run(det, x, slot, T, drive, a, H, rho, ch, tile, halo, slots):
+    """one stream of one run of detector det (0 sample, 1 true peak) with a release of 2^rho frames (rho 0: none) and
+    `slots` elements per thread: x int16 [F][C], slot int64 [halo * C] (the history slot the run reads)
     -> out int64 [F * C + 8] (UNWRITTEN where nothing was stored), the slot the run writes, min s or None"""
-    A, D, W, hist = geometry_tp(a, H)
+    A, D, W, hist = geometry_tp(a, H) if det else TG.geometry(a, H)
+    hist, q = hist + (1 << rho) - 1, UNITY >> rho
     F = x.shape[0]
     ns, hsamp = F * ch, halo * ch
     hv, nfull, ntail = hsamp // 8, ns // 8, ns % 8
-    assert hsamp % 8 == 0 and tile >= halo >= hist >= D and (D + 1) % 8 == 0
+    assert hsamp % 8 == 0 and tile >= halo >= hist >= D and (D + 1) % 8 == 0 and rho >= 0
     # the stream as a tile sees it: the slot's vectors below 0, the run's from 0 on, zeros past the count
     seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)])
 
@@ -454,10 +463,10 @@ def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
         assert (vv >= -hv).all()
         return seq[(hsamp + vv * 8)[..., None] + np.arange(8)]
 
-    def sample(q):
-        q = np.asarray(q)
-        assert (q >= -hsamp).all() and (q < ns).all()
-        return seq[hsamp + q]
+    def sample(qq):
+        qq = np.asarray(qq)
+        assert (qq >= -hsamp).all() and (qq < ns).all()
+        return seq[hsamp + qq]
 
     out = np.full(ns + 8, UNWRITTEN, dtype=np.int64)
     new_slot = sample(ns - hsamp + np.arange(hsamp))              # 4. (the last tile, or tile 0 of a stream with 0 frames)
@@ -466,25 +475,33 @@ def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
         return out, new_slot, None
     gmin = UNITY
     N = halo + tile
-    tid, i = np.meshgrid(np.arange(BLOCK), np.arange(R), indexing="ij")
-    own = (tid + BLOCK * i).reshape(-1)
+    tid, i = np.meshgrid(np.arange(BLOCK), np.arange(slots), indexing="ij")
+    own = (tid + BLOCK * i).reshape(-1)                           # thread t keeps elements t + 256 i, i < slots
     own = own[own < N]
-    assert np.array_equal(np.sort(own), np.arange(N))            # every element has exactly one thread
+    assert N <= BLOCK * slots and np.array_equal(np.sort(own), np.arange(N))  # every element has exactly one thread
     for f0 in range(0, F, tile):
         nt = min(tile, F - f0)
         L = np.full(N, UNWRITTEN, dtype=np.int64)
+        vbase = f0 * ch // 8 - hv
+        assert f0 == 0 or vbase >= 0                              # only the run's first tile reads the slot: halo <= tile
         # ---- 1. g of frames f0 - halo .. f0 + tile - 1
-        if ch <= 2:
+        if ch <= 2 and not det:
+            fpv = 8 // ch
+            NV = N // fpv
+            assert N % fpv == 0 and NV <= BLOCK * ((slots * ch + 7) // 8)
+            v = np.abs(vec(vbase + np.arange(NV)))
+            peak = v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])
+            L[:] = _gain_sample(peak, drive, T).reshape(-1)
+        elif ch <= 2:
             fpv = 8 // ch
             HV = 16 // fpv                                        # vectors in front of a thread's own: 16 frames
             NV = N // fpv
             cnt = -(-NV // BLOCK)                                 # own vectors per thread, consecutive
-            assert N % fpv == 0 and cnt <= (R * ch + 7) // 8
-            vbase = f0 * ch // 8 - hv
+            assert N % fpv == 0 and cnt <= (slots * ch + 7) // 8
             w = (np.arange(BLOCK) * cnt)[:, None] + np.arange(-HV, cnt)[None, :]         # [thread][local vector]
             vv = vbase + w
             loaded = (w < NV) & (vv >= -hv)                       # the rest are zeros: in front of the slot, past the range
-            assert f0 == 0 or (vv >= -hv).all() or f0 * ch // 8 < HV
+            assert f0 == 0 or (vv >= -hv).all()                   # ... and past the first tile nothing lies in front of it
             d = np.where(loaded[..., None], vec(np.where(loaded, vv, 0)), 0)             # [thread][local vector][8]
             loc = d.reshape(BLOCK, (HV + cnt) * fpv, ch)          # [thread][local frame][channel]
             t = 16 + np.arange(cnt * fpv)                         # the own frames' local indices
@@ -496,6 +513,12 @@ def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
             keep = np.repeat(w[:, HV:] < NV, fpv, axis=1)
             assert np.array_equal(np.sort(j[keep]), np.arange(N))                        # each written once
             L[j[keep]] = _gain(pk[keep], drive, T)
+        elif not det:
+            p = f0 - halo + np.arange(N)
+            peak = np.zeros(N, dtype=np.int64)
+            inside = p < F
+            peak[inside] = np.abs(sample(p[inside, None] * ch + np.arange(ch))).max(axis=1)
+            L[:] = _gain_sample(peak, drive, T)
         else:
             n = f0 - halo + np.arange(N)
             p = n[:, None] - FRONT + np.arange(FRONT)             # frames n - 13 .. n - 1
@@ -507,25 +530,27 @@ def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
                 pk = np.maximum(pk, np.abs(y).max(axis=1))
             L[:] = _gain(pk, drive, T)
         assert (L != UNWRITTEN).all()
-        # ---- 2. the passes: partner from LDS, own element back
+        # ---- 2. the passes: partner from LDS (32768, or 0 for a sum, in front of element 0), own element back
         j = np.arange(N)
 
-        def one_pass(L, dist, is_min, shift, vreg):
-            o = np.where(j >= dist, L[np.maximum(j - dist, 0)], UNITY if is_min else 0)
-            vreg = np.minimum(vreg, o) if is_min else vreg + o
-            assert vreg.max() < 2 ** 32
+        def one_pass(L, dist, kind, add, shift, vreg):
+            o = np.where(j >= dist, L[np.maximum(j - dist, 0)], 0 if kind == 2 else UNITY)
+            vreg = np.minimum(vreg, o) if kind == 0 else np.minimum(vreg, o + add) if kind == 1 else vreg + o
+            assert vreg.max() < 2 ** 32 and (o + add).max() < 2 ** 32
             return vreg >> shift, vreg
 
         vreg = L.copy()
         P = 1
         while 2 * P <= W:
-            L, vreg = one_pass(L, P, True, 0, vreg)
+            L, vreg = one_pass(L, P, 0, 0, 0, vreg)
             P *= 2
         if W > P:
-            L, vreg = one_pass(L, W - P, True, 0, vreg)
+            L, vreg = one_pass(L, W - P, 0, 0, 0, vreg)
+        for e in range(rho):
+            L, vreg = one_pass(L, 1 << e, 1, q << e, 0, vreg)
         dd = 1
         while dd < A:
-            L, vreg = one_pass(L, dd, False, a if 2 * dd == A else 0, vreg)
+            L, vreg = one_pass(L, dd, 2, 0, a if 2 * dd == A else 0, vreg)
             dd *= 2
         Ls = L[halo:]
         gmin = min(gmin, int(Ls[:nt].min()))
@@ -533,16 +558,16 @@ def _emulate_run(x, slot, T, drive, a, H, ch, tile, halo):
         vb, nv = f0 * ch // 8, (nt * ch + 7) // 8
         v8 = vb + np.arange(nv)
         if ch <= 2:
-            back = (D + 1) * ch // 8                              # (A + 8) C / 8
+            back = (D + 1) * ch // 8                              # A C / 8, or (A + 8) C / 8 for the true-peak detector
             assert (D + 1) * ch % 8 == 0 and (v8 - back >= -hv).all()
             x0, x1 = vec(v8 - back), vec(v8 - back + 1)
             xs = np.concatenate([x0[:, ch:], x1[:, :ch]], axis=1)                 # mono: samples 1..8, stereo: 2..9
             sf = Ls[(np.arange(nv) * (8 // ch))[:, None] + np.arange(8) // ch]
             y = (xs * (drive * sf) + (1 << 26)) >> 27
         else:
-            q = v8[:, None] * 8 + np.arange(8)
-            ok = q < ns
-            qq = np.where(ok, q, 0)
+            qq = v8[:, None] * 8 + np.arange(8)
+            ok = qq < ns
+            qq = np.where(ok, qq, 0)
             y = np.where(ok, (sample(qq - D * ch) * (drive * Ls[np.where(ok, qq // ch - f0, 0)]) + (1 << 26)) >> 27, 0)
         for k in range(nv):
             if v8[k] < nfull:
@@ -563,7 +588,7 @@ def test_emulated_decomposition_equals_the_model(cm, a, H, T, drive, channels):
         slot = np.zeros(halo * channels, dtype=np.int64)
         got_min = UNITY
         for x, want in ((xs[s][:counts[s]], ragged[s]), (xs[s], full[s])):
-            out, slot, m = _emulate_run(x, slot, T, drive, a, H, channels, t, halo)
+            out, slot, m = _emulate_run(1, x, slot, T, drive, a, H, 0, channels, t, halo, 26)
             w = want.astype(np.int64).reshape(-1)
             assert np.array_equal(out[:w.size], w), (channels, s)
             assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
@@ -595,8 +620,8 @@ def test_kernel_assembly_house_rules():
     assert any("k_limtp_fastILi1E" in k for k in names) and any("k_limtp_fastILi2E" in k for k in names), names
     assert any("k_limtp_any" in k for k in names) and len(names) == 3, names
     assert all(v == 0 for v in scratch.values()), scratch
-    for name in ("k_limtp.hip", "k_lim.h"):
+    for name in ("k_limtp.hip", "k_lim.h", "k_lim_tile.h"):
         src = open(os.path.join(PKG, "csrc", name)).read()
         assert "getenv" not in src
         for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-            assert not re.findall(r"\bCMHIP_(?!K_LIM_H\b)\w+", m.group(1)), m.group(0)
+            assert not re.findall(r"\bCMHIP_(?!K_LIM(?:_TILE)?_H\b)\w+", m.group(1)), m.group(0)

@@ -36,7 +36,7 @@ SHAPES = {          # streams, channels, frames, lookahead_log2, hold
     "x6_a6": (1365, 6, 65536, 6, 0),
 }
 THRESHOLD, DRIVE = 29204, 8192
-ELEMENTS = 26       # per thread and pass (k_lim.hip: LIM_R)
+ELEMENTS = 26       # per thread and pass (csrc/k_lim.h: LIM_R, the slots of the kernels without a release)
 
 
 def passes(a, hold):
