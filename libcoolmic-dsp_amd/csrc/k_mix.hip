@@ -16,93 +16,7 @@
 namespace cmhip {
 
 // ---------------------------------------------------------------------------
-// Form 1: mono / stereo on both sides.  A lane works in UNITS of UF frames, the fewest that are whole 16-byte vectors
-// on both sides: VI input vectors and VO output vectors.  NU units per lane make four vectors on the wider side:
-//     1 -> 1   UF 8, 1 in, 1 out, NU 4: a tile of 2048 frames      2 -> 1   UF 8, 2 in, 1 out, NU 2: 1024 frames
-//     2 -> 2   UF 4, 1 in, 1 out, NU 4: 1024 frames                1 -> 2   UF 8, 1 in, 2 out, NU 2: 1024 frames
-// Unit j of a lane is unit n0 + 64 j + lane of the stream, so a wave's instruction covers 64 consecutive units.
-
-// Every output sample is ONE dot instruction on an input dword.  Stereo in: the dword is a frame, the weight dword
-// the row.  Mono in: the dword holds two frames, and the row's weight sits in the half of the frame it belongs to
-// (the other half is zero), so no sample is extracted from its dword.
-template <int CI, int CO, bool FULL>
-__device__ __forceinline__ void mix_fast_tile(const MixArgs &a, u32 s, u32 k, u32 F, const int16_t *a_in,
-                                              int16_t *a_out, u64 in_stride, u64 out_stride)
-{
-    using G = MixFast<CI, CO>;
-    constexpr u32 VI = G::VI, VO = G::VO, NU = G::NU;
-    const u32 lane = threadIdx.x & 63u;
-    const int16_t *ins = a_in + (u64)s * in_stride;
-    int16_t *outs = a_out + (u64)s * out_stride;
-    const u32 ns_in = F * (u32)CI, ns_out = F * (u32)CO;
-    const u32 nfull_in = ns_in >> 3, ntail_in = ns_in & 7u;
-    const u32 nfull_out = ns_out >> 3, ntail_out = ns_out & 7u;
-    const u32 n0 = k * 64u * NU;
-
-    // ---- load: every vector of the tile, before the matrix is read
-    u32 x[NU][VI][4];
-#pragma unroll
-    for (u32 j = 0; j < NU; j++) {
-#pragma unroll
-        for (u32 i = 0; i < VI; i++) {
-            const u32 v = (n0 + 64u * j + lane) * VI + i;
-            load_vec(x[j][i], ins, v, FULL || v < nfull_in, !FULL && ntail_in && v == nfull_in, ntail_in);
-        }
-    }
-
-    // ---- the stream's matrix, read only now (the tile's loads depend on kernel arguments alone and are on their
-    // way; the barrier keeps the scheduler from moving these reads back up).  One or two dwords at FIXED offsets
-    // from the row's address, which is computed in full: no scalar load with a register and an immediate offset.
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr u32 NW = (u32)CO;                      // CP == 1: one dword per output channel
-    const u32 *wrow = a.wk + (u64)s * NW;
-    u32 wk[2];
-    wk[0] = uniform(wrow[0]);
-    wk[1] = NW > 1 ? uniform(wrow[NW - 1u]) : 0u;
-    u32 wlo[2], whi[2];                              // mono in: the weight in the low / the high half
-#pragma unroll
-    for (u32 o = 0; o < 2; o++) {
-        wlo[o] = wk[o] & 0xffffu;
-        whi[o] = wk[o] << 16;
-    }
-
-    // ---- arithmetic and stores
-    u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
-    // (output vector i of unit j.  Called once or twice per unit, not from a loop over i: around a loop of one
-    // iteration the optimiser promotes the store out of it and the copy it makes is an ordinary store, not "nt")
-    auto out_vec = [&](u32 j, auto ic) {
-        constexpr u32 i = decltype(ic)::value;
-        u32x4 ov;
-#pragma unroll
-        for (u32 d = 0; d < 4; d++) {
-            int acc[2];
-#pragma unroll
-            for (u32 h = 0; h < 2; h++) {
-                const u32 e = (i * 4u + d) * 2u + h;                 // output sample of the unit
-                const u32 f = e / (u32)CO, oc = e % (u32)CO;
-                const u32 dw = (f * (u32)CI) >> 1;                   // the input dword that holds frame f
-                const u32 xin = x[j][dw >> 2][dw & 3u];
-                const u32 w = CI == 2 ? wk[oc] : ((f & 1u) ? whi[oc] : wlo[oc]);
-                acc[h] = mix_dot2(xin, w, 8192);
-            }
-            ov[d] = mix_pack(acc[0], acc[1]);
-        }
-        const u32 v = (n0 + 64u * j + lane) * VO + i;
-        if (FULL || v < nfull_out) {
-            __builtin_nontemporal_store(ov, dst + v);
-        } else if (ntail_out && v == nfull_out) {
-            const u32 o[4] = {ov.x, ov.y, ov.z, ov.w};
-            store_tail(outs, v, o, ntail_out);
-        }
-    };
-#pragma unroll
-    for (u32 j = 0; j < NU; j++) {
-        out_vec(j, std::integral_constant<u32, 0>{});
-        if constexpr (VO == 2)
-            out_vec(j, std::integral_constant<u32, 1>{});
-    }
-}
-
+// Form 1: mono / stereo on both sides (k_mix.h has the units and the tile)
 template <int CI, int CO>
 __global__ __launch_bounds__(64) void k_mix_fast(MixArgs a)
 {
@@ -119,9 +33,9 @@ __global__ __launch_bounds__(64) void k_mix_fast(MixArgs a)
     if (f0 >= F)                                     // (uniform)
         return;
     if (f0 + G::TILE_FRAMES <= F)
-        mix_fast_tile<CI, CO, true>(a, s, k, F, a_in, a_out, in_stride, out_stride);
+        mixr_fast_tile<CI, CO, true, false>(a, nullptr, 0, 0, s, k, F, a_in, a_out, in_stride, out_stride);
     else
-        mix_fast_tile<CI, CO, false>(a, s, k, F, a_in, a_out, in_stride, out_stride);
+        mixr_fast_tile<CI, CO, false, false>(a, nullptr, 0, 0, s, k, F, a_in, a_out, in_stride, out_stride);
 }
 
 // ---------------------------------------------------------------------------
@@ -153,7 +67,6 @@ __global__ __launch_bounds__(MIX_BLOCK) void k_mix_any(MixArgs a)
 
     u32 *wl = reinterpret_cast<u32 *>(mix_lds);
     u32 *plane = wl + mix_wk_lds(CI, CO);
-    int16_t *plane16 = reinterpret_cast<int16_t *>(plane);
     int16_t *ot = reinterpret_cast<int16_t *>(plane + CP * tile);
 
     for (u32 i = tid; i < CO * CP; i += MIX_BLOCK)
@@ -167,23 +80,7 @@ __global__ __launch_bounds__(MIX_BLOCK) void k_mix_any(MixArgs a)
             const u32 v = vb + w;
             u32 x[4];
             load_vec(x, ins, v, v < nfull, v == nfull && ntail != 0, ntail);
-            if ((CI & 1u) == 0) {
-#pragma unroll
-                for (u32 i = 0; i < 4; i++) {
-                    const u32 e = w * 4u + i;                        // dword of the tile
-                    const u32 f = e / CP, kk = e - f * CP;
-                    if (f < nt)
-                        plane[kk * tile + f] = x[i];
-                }
-            } else {
-#pragma unroll
-                for (u32 i = 0; i < 8; i++) {
-                    const u32 e = w * 8u + i;                        // sample of the tile
-                    const u32 f = e / CI, c = e - f * CI;
-                    if (f < nt)
-                        plane16[((c >> 1) * tile + f) * 2u + (c & 1u)] = (int16_t)(x[i >> 1] >> (16u * (i & 1u)));
-                }
-            }
+            mix_scatter_vec(plane, x, w, nt, CI, CP, tile);
         }
     }
     __syncthreads();
@@ -242,33 +139,8 @@ __global__ __launch_bounds__(MIX_BLOCK) void k_mix_set(MixSetArgs a)
 
 MixPlan plan_mix(const MixArgs &a)
 {
-    MixPlan p{};
-    p.err = hipSuccess;
     const u32 CI = a.channels_in, CO = a.channels_out;
-    if (a.streams == 0 || a.frames == 0 || CI == 0 || CI > MAX_CH || CO == 0 || CO > MAX_CH)
-        return p;
-    MixPlan refused{};
-    refused.err = hipErrorInvalidValue;
-    u32 tile, lds = 0;
-    const bool fast = CI <= 2 && CO <= 2;
-    if (fast) {
-        tile = CI == 1 && CO == 1 ? MixFast<1, 1>::TILE_FRAMES : MixFast<2, 2>::TILE_FRAMES;     // (2048 : 1024)
-    } else {
-        // the largest power-of-two tile whose planes and output fit beside the matrix
-        for (tile = MIX_TILE_MAX; mix_lds_bytes(CI, CO, tile) > MIX_LDS_LIMIT; tile >>= 1)
-            ;
-        lds = mix_lds_bytes(CI, CO, tile);
-    }
-    const u64 tiles = ((u64)a.frames + tile - 1u) / tile;
-    if (tiles * a.streams >= (1ull << 31))                   // (as plan_run: no grid of 2^31 workgroups)
-        return refused;
-    p.fast = fast ? 1u : 0u;
-    p.block = fast ? 64u : MIX_BLOCK;
-    p.tile_frames = tile;
-    p.lds_bytes = lds;
-    p.chunks = (u32)tiles;
-    p.grid = a.streams * p.chunks;
-    return p;
+    return mix_plan_tiles<MixPlan>(a.streams, CI, CO, a.frames, [=](u32 tile) { return mix_lds_bytes(CI, CO, tile); });
 }
 
 hipError_t launch_mix(const MixArgs &a, hipStream_t st)

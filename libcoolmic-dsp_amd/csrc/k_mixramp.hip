@@ -20,111 +20,7 @@
 namespace cmhip {
 
 // ---------------------------------------------------------------------------
-// Form 1: k_mix_fast's tile (k_mix.hip explains units and vectors).  RAMP: per frame of a unit one position (a 32 x 32
-// -> 64 multiply, a funnel shift, two mins), per matrix entry two multiply-adds and the shift, and the row's dword is
-// packed as the dot instruction wants it.  Mono in: the weight goes into the half of the dword its frame sits in; the
-// two halves of an input dword now belong to different frames and meet different weights.
-template <int CI, int CO, bool FULL, bool RAMP>
-__device__ __forceinline__ void mixr_fast_tile(const MixArgs &a, const u32 *rec, u32 R, u32 done, u32 s, u32 k, u32 F,
-                                               const int16_t *a_in, int16_t *a_out, u64 in_stride, u64 out_stride)
-{
-    using G = MixFast<CI, CO>;
-    constexpr u32 VI = G::VI, VO = G::VO, NU = G::NU, UF = G::UF;
-    const u32 lane = threadIdx.x & 63u;
-    const int16_t *ins = a_in + (u64)s * in_stride;
-    int16_t *outs = a_out + (u64)s * out_stride;
-    const u32 ns_in = F * (u32)CI, ns_out = F * (u32)CO;
-    const u32 nfull_in = ns_in >> 3, ntail_in = ns_in & 7u;
-    const u32 nfull_out = ns_out >> 3, ntail_out = ns_out & 7u;
-    const u32 n0 = k * 64u * NU;
-
-    // ---- load: every vector of the tile, before the matrices are read
-    u32 x[NU][VI][4];
-#pragma unroll
-    for (u32 j = 0; j < NU; j++) {
-#pragma unroll
-        for (u32 i = 0; i < VI; i++) {
-            const u32 v = (n0 + 64u * j + lane) * VI + i;
-            load_vec(x[j][i], ins, v, FULL || v < nfull_in, !FULL && ntail_in && v == nfull_in, ntail_in);
-        }
-    }
-
-    // ---- the stream's matrices, at FIXED offsets from an address computed in full (k_mix_fast tells why)
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr u32 NW = (u32)CO;                      // CP == 1: one dword per output channel
-    u32 wk[2] = {0, 0}, w0k[2] = {0, 0}, w1k[2] = {0, 0}, inc = 0;
-    if constexpr (RAMP) {
-        inc = uniform(rec[MIXR_INC]);
-        w0k[0] = uniform(rec[MIXR_HDR]);
-        w1k[0] = uniform(rec[MIXR_HDR + NW]);
-        if constexpr (NW > 1) {
-            w0k[1] = uniform(rec[MIXR_HDR + NW - 1u]);
-            w1k[1] = uniform(rec[MIXR_HDR + 2u * NW - 1u]);
-        }
-    } else {
-        const u32 *wrow = a.wk + (u64)s * NW;
-        wk[0] = uniform(wrow[0]);
-        wk[1] = NW > 1 ? uniform(wrow[NW - 1u]) : 0u;
-    }
-    u32 wlo[2], whi[2];                              // the plain path, mono in: the weight in the low / the high half
-#pragma unroll
-    for (u32 o = 0; o < 2; o++) {
-        wlo[o] = wk[o] & 0xffffu;
-        whi[o] = wk[o] << 16;
-    }
-
-    // ---- arithmetic and stores
-    u32x4 *dst = reinterpret_cast<u32x4 *>(outs);
-    u32 wf[UF][2];                                   // RAMP: per frame of the unit, the dword its dot meets, per row
-    auto out_vec = [&](u32 j, auto ic) {             // (called once or twice per unit, not from a loop: k_mix_fast)
-        constexpr u32 i = decltype(ic)::value;
-        u32x4 ov;
-#pragma unroll
-        for (u32 d = 0; d < 4; d++) {
-            int acc[2];
-#pragma unroll
-            for (u32 h = 0; h < 2; h++) {
-                const u32 e = (i * 4u + d) * 2u + h;                 // output sample of the unit
-                const u32 f = e / (u32)CO, oc = e % (u32)CO;
-                const u32 dw = (f * (u32)CI) >> 1;                   // the input dword that holds frame f
-                const u32 xin = x[j][dw >> 2][dw & 3u];
-                const u32 w = RAMP ? wf[f][oc] : CI == 2 ? wk[oc] : ((f & 1u) ? whi[oc] : wlo[oc]);
-                acc[h] = mix_dot2(xin, w, 8192);
-            }
-            ov[d] = mix_pack(acc[0], acc[1]);
-        }
-        const u32 v = (n0 + 64u * j + lane) * VO + i;
-        if (FULL || v < nfull_out) {
-            __builtin_nontemporal_store(ov, dst + v);
-        } else if (ntail_out && v == nfull_out) {
-            const u32 o[4] = {ov.x, ov.y, ov.z, ov.w};
-            store_tail(outs, v, o, ntail_out);
-        }
-    };
-#pragma unroll
-    for (u32 j = 0; j < NU; j++) {
-        if constexpr (RAMP) {
-            const u32 nb = done + (n0 + 64u * j + lane) * UF + 1u;   // the ramp's frame number of the unit's frame 0
-#pragma unroll
-            for (u32 f = 0; f < UF; f++) {
-                const u32 p = mixr_pos(nb + f, R, inc);
-#pragma unroll
-                for (u32 oc = 0; oc < (u32)CO; oc++) {
-                    if constexpr (CI == 2) {
-                        wf[f][oc] = mixr_wk(w0k[oc], w1k[oc], p);
-                    } else {
-                        const u32 w = (u32)mixr_w((int)(short)w0k[oc], (int)(short)w1k[oc], p);
-                        wf[f][oc] = (f & 1u) ? w << 16 : w & 0xffffu;
-                    }
-                }
-            }
-        }
-        out_vec(j, std::integral_constant<u32, 0>{});
-        if constexpr (VO == 2)
-            out_vec(j, std::integral_constant<u32, 1>{});
-    }
-}
-
+// Form 1: k_mix_fast's tile (k_mix.h), with the ramp's path where the tile begins inside the ramp
 template <int CI, int CO>
 __global__ __launch_bounds__(64) void k_mixr_fast(MixRampArgs ra)
 {
@@ -158,13 +54,9 @@ __global__ __launch_bounds__(64) void k_mixr_fast(MixRampArgs ra)
 
 // ---------------------------------------------------------------------------
 // Form 2: k_mix_any's tile and staging (k_mix.hip explains the planes).  Beside the target's matrix the workgroup
-// copies W0 and W1 into LDS; the thread that owns a frame computes the frame's position once and every weight dword
-// right before its dot.  An odd C_in's padding half is zero in W0 and in W1, so it is zero at every position.
-__host__ __device__ constexpr u32 mixr_lds_bytes(u32 ci, u32 co, u32 tile)
-{
-    return mix_lds_bytes(ci, co, tile) + 8u * mix_wk_lds(ci, co);
-}
-
+// copies W0 and W1 into LDS (mixr_lds_bytes, k_mix.h); the thread that owns a frame computes the frame's position once
+// and every weight dword right before its dot.  An odd C_in's padding half is zero in W0 and in W1, so it is zero at
+// every position.
 __global__ __launch_bounds__(MIX_BLOCK) void k_mixr_any(MixRampArgs ra)
 {
     extern __shared__ u32x4 mixr_lds[];
@@ -188,7 +80,6 @@ __global__ __launch_bounds__(MIX_BLOCK) void k_mixr_any(MixRampArgs ra)
     u32 *wl = reinterpret_cast<u32 *>(mixr_lds);     // the target, W0, W1: nl dwords each
     u32 *w0l = wl + nl, *w1l = w0l + nl;
     u32 *plane = w1l + nl;
-    int16_t *plane16 = reinterpret_cast<int16_t *>(plane);
     int16_t *ot = reinterpret_cast<int16_t *>(plane + CP * tile);
 
     for (u32 i = tid; i < n; i += MIX_BLOCK) {
@@ -207,23 +98,7 @@ __global__ __launch_bounds__(MIX_BLOCK) void k_mixr_any(MixRampArgs ra)
             const u32 v = vb + w;
             u32 x[4];
             load_vec(x, ins, v, v < nfull, v == nfull && ntail != 0, ntail);
-            if ((CI & 1u) == 0) {
-#pragma unroll
-                for (u32 i = 0; i < 4; i++) {
-                    const u32 e = w * 4u + i;                        // dword of the tile
-                    const u32 f = e / CP, kk = e - f * CP;
-                    if (f < nt)
-                        plane[kk * tile + f] = x[i];
-                }
-            } else {
-#pragma unroll
-                for (u32 i = 0; i < 8; i++) {
-                    const u32 e = w * 8u + i;                        // sample of the tile
-                    const u32 f = e / CI, c = e - f * CI;
-                    if (f < nt)
-                        plane16[((c >> 1) * tile + f) * 2u + (c & 1u)] = (int16_t)(x[i >> 1] >> (16u * (i & 1u)));
-                }
-            }
+            mix_scatter_vec(plane, x, w, nt, CI, CP, tile);
         }
     }
     __syncthreads();

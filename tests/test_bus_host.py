@@ -20,14 +20,16 @@ PKG = os.path.join(ROOT, "libcoolmic-dsp_amd")
 ROUTE_SRC = os.path.join(ROOT, "tests", "cpp", "bus_route_test.cpp")
 
 
-def _gpu_test_module():
-    spec = importlib.util.spec_from_file_location("test_gpu_bus_model", os.path.join(ROOT, "tests", "test_gpu_bus.py"))
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name + "_for_bus", os.path.join(ROOT, "tests", name + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
 
 
-TG = _gpu_test_module()            # the model and the tables of the GPU tests
+RH = _load("test_bus_ramp_host")   # the emulations of both kernels' decomposition: every send at rest, they are k_bus.hip's
+TG = RH.TG.TB                      # tests/test_gpu_bus.py: the model and the tables of the GPU tests
+UNWRITTEN = RH.UNWRITTEN
 
 
 def test_header_compiles_as_c_and_cxx(tmp_path):
@@ -259,82 +261,23 @@ def test_plan(cm):
 # interleaved output tile and its whole vectors / ragged end by the BUS's count.  It holds the index arithmetic (every
 # plane element read was written, nothing past a count is read or written) where no GPU is.
 
-UNWRITTEN = 1 << 40
+# The steps are tests/test_bus_ramp_host.py's emulation of k_busr_any with every send at rest: the kernels share them.
+
+def _at_rest(table, buses, ci, co):
+    """the table as a model whose sends all rest on their matrices; what the emulation compiles of it is the routing
+    compiler's table"""
+    bus, stream, W = table
+    model = RH.TG.BusRampModel(buses, ci, co)
+    model.set(bus, stream, W)
+    first, order, flags = RH._compile_two_ended(model)
+    assert (first, [stream[j] for j in order], flags) == _compile_py(buses, ci, co, bus, stream, W)[:3]
+    return model
 
 
 def _emulate_any(xs, table, buses, ci, co, tile, max_frames):
     """-> per bus the output slot as the kernel leaves it (UNWRITTEN where it stored nothing)"""
-    bus, stream, W = table
-    first, so, _, wk = _compile_py(buses, ci, co, bus, stream, W)
-    cp = (ci + 1) // 2
-    klo = ((wk & 0xffff) ^ 0x8000) - 0x8000                                   # the halves of the packed dwords, signed
-    khi = (((wk >> 16) & 0xffff) ^ 0x8000) - 0x8000
-    counts = [np.asarray(x).reshape(-1, ci).shape[0] for x in xs]
-    slots = []
-    for x, c in zip(xs, counts):                                             # the input slots: poison past the count
-        slot = np.full(max_frames * ci + 8, UNWRITTEN, dtype=np.int64)
-        slot[:c * ci] = np.asarray(x, dtype=np.int64).reshape(-1)
-        slots.append(slot)
-    outs = []
-    for b in range(buses):
-        out = np.full(max_frames * co + 8, UNWRITTEN, dtype=np.int64)
-        outs.append(out)
-        j0, j1 = first[b], first[b + 1]
-        if j0 == j1:
-            continue
-        F = max(counts[so[j]] for j in range(j0, j1))
-        ns_out = F * co
-        for f0 in range(0, F, tile):                                         # one workgroup each
-            nt = min(tile, F - f0)
-            acc = np.zeros((tile, co), dtype=np.int64)
-            assert (f0 * ci) % 8 == 0 and (f0 * co) % 8 == 0
-            for j in range(j0, j1):
-                c, ins = counts[so[j]], slots[so[j]]
-                if c <= f0:
-                    continue
-                ntj = min(tile, c - f0)
-                assert ntj <= nt
-                plo = np.full((cp, tile), UNWRITTEN, dtype=np.int64)
-                phi = np.full((cp, tile), UNWRITTEN, dtype=np.int64)
-                ns_in = c * ci
-                vb, nv = f0 * ci // 8, (ntj * ci + 7) // 8
-                for w in range(nv):
-                    v = vb + w
-                    vec = np.zeros(8, dtype=np.int64)                        # load_vec: whole, or the ragged end
-                    if v < ns_in // 8:
-                        vec[:] = ins[v * 8:v * 8 + 8]
-                    else:
-                        assert v == ns_in // 8 and ns_in % 8
-                        vec[:ns_in % 8] = ins[v * 8:v * 8 + ns_in % 8]
-                    assert (vec != UNWRITTEN).all()                          # nothing past the send's count was read
-                    if ci % 2 == 0:
-                        for i in range(4):
-                            f, k = divmod(w * 4 + i, cp)
-                            if f < ntj:
-                                plo[k, f], phi[k, f] = vec[2 * i], vec[2 * i + 1]
-                    else:
-                        for i in range(8):
-                            f, ch = divmod(w * 8 + i, ci)
-                            if f < ntj:
-                                (phi if ch & 1 else plo)[ch >> 1, f] = vec[i]
-                lo, hi = plo[:, :ntj], phi[:, :ntj].copy()
-                assert (lo != UNWRITTEN).all()
-                if ci % 2:
-                    assert (hi[cp - 1] == UNWRITTEN).all() and not khi[j, :, cp - 1].any()
-                    hi[cp - 1] = 12345                                       # whatever LDS held: it meets a zero weight
-                assert (hi != UNWRITTEN).all()
-                p = klo[j] @ lo + khi[j] @ hi                                # [co][ntj]
-                assert np.abs(p).max() < 2 ** 31
-                acc[:ntj] += p.T
-            ot = np.full(tile * co, UNWRITTEN, dtype=np.int64)
-            ot[:nt * co] = np.clip((acc[:nt] + 8192) >> 14, -32768, 32767).reshape(-1)
-            vb, nv = f0 * co // 8, (nt * co + 7) // 8
-            for w in range(nv):
-                v = vb + w
-                if v < ns_out // 8:
-                    out[v * 8:v * 8 + 8] = ot[w * 8:w * 8 + 8]
-                elif v == ns_out // 8:
-                    out[v * 8:v * 8 + ns_out % 8] = ot[w * 8:w * 8 + ns_out % 8]
+    outs, paths = RH._emulate_any(xs, _at_rest(table, buses, ci, co), tile, max_frames)
+    assert paths <= {False}                                      # the plain path alone
     return outs
 
 
@@ -357,84 +300,13 @@ def test_emulated_decomposition_equals_the_model(cm, ci, co):
 
 
 def _emulate_fast(xs, table, buses, ci, co, max_frames):
-    """k_bus_fast<CI, CO> (csrc/k_bus.hip): one wave per (bus, tile) walks the bus's sends -- a send whose stream ends
-    at or before the tile is skipped, its flag still closes the group; a lane's units and vectors zero-filled past the
-    SEND's count; one dot per output sample and send on the input dword that holds the frame, chained in int32 inside
-    a group (held below 2^31 here) and added into the int64 at a flag; one rounding; whole vectors and the ragged end
-    by the BUS's count -> per bus the slot, and the tile"""
-    bus, stream, W = table
-    first, so, flags, wk = _compile_py(buses, ci, co, bus, stream, W)
-    klo = ((wk & 0xffff) ^ 0x8000) - 0x8000
-    khi = (((wk >> 16) & 0xffff) ^ 0x8000) - 0x8000
-    uf = 8 // min(ci, co)
-    vi, vo = uf * ci // 8, uf * co // 8
-    nu = 4 // max(vi, vo)
-    tile = 64 * nu * uf
-    counts = [np.asarray(x).reshape(-1, ci).shape[0] for x in xs]
-    slots = []
-    for x, c in zip(xs, counts):
-        slot = np.full(max_frames * ci + 8, UNWRITTEN, dtype=np.int64)
-        slot[:c * ci] = np.asarray(x, dtype=np.int64).reshape(-1)
-        slots.append(slot)
-    lane = np.arange(64)
-    outs = []
-    for b in range(buses):
-        out = np.full(max_frames * co + 16, UNWRITTEN, dtype=np.int64)
-        outs.append(out)
-        j0, j1 = first[b], first[b + 1]
-        if j0 == j1:
-            continue
-        F = max(counts[so[j]] for j in range(j0, j1))
-        wide = sum(flags[j0:j1]) > 1
-        ns_out = F * co
-        for k in range(-(-F // tile)):                               # one wave each
-            f0 = k * tile
-            acc = np.full((64, nu, vo * 8), 0 if wide else 8192, dtype=np.int64)
-            tot = np.zeros((64, nu, vo * 8), dtype=np.int64)
-            for j in range(j0, j1):
-                if wide and flags[j]:
-                    tot += acc
-                    acc[:] = 0
-                c, ins = counts[so[j]], slots[so[j]]
-                if c <= f0:
-                    continue
-                ns_in = c * ci
-                # the unit's input dwords as (low, high) halves: [lane][unit][vi * 4]
-                lo = np.zeros((64, nu, vi * 4), dtype=np.int64)
-                hi = np.zeros((64, nu, vi * 4), dtype=np.int64)
-                for u in range(nu):
-                    for i in range(vi):
-                        for ln in lane:
-                            v = ((k * 64 * nu) + 64 * u + ln) * vi + i
-                            vec = np.zeros(8, dtype=np.int64)
-                            if v < ns_in // 8:
-                                vec[:] = ins[v * 8:v * 8 + 8]
-                            elif v == ns_in // 8 and ns_in % 8:
-                                assert f0 + tile > c
-                                vec[:ns_in % 8] = ins[v * 8:v * 8 + ns_in % 8]
-                            else:
-                                assert f0 + tile > c                  # zeros: nothing past the send's count is read
-                            assert (vec != UNWRITTEN).all()
-                            lo[ln, u, i * 4:i * 4 + 4], hi[ln, u, i * 4:i * 4 + 4] = vec[0::2], vec[1::2]
-                for e in range(vo * 8):                              # output sample of the unit
-                    f, oc = divmod(e, co)
-                    dw = (f * ci) >> 1
-                    if ci == 2:
-                        wl, wh = klo[j, oc, 0], khi[j, oc, 0]
-                    else:
-                        wl, wh = (0, klo[j, oc, 0]) if f & 1 else (klo[j, oc, 0], 0)
-                    acc[:, :, e] += lo[:, :, dw] * wl + hi[:, :, dw] * wh
-                assert np.abs(acc).max() < 2 ** 31                   # the int32 chain of a group never wraps
-            y = np.clip((tot + acc + (8192 if wide else 0)) >> 14, -32768, 32767)
-            for u in range(nu):
-                for i in range(vo):
-                    for ln in lane:
-                        v = ((k * 64 * nu) + 64 * u + ln) * vo + i
-                        o8 = y[ln, u, i * 8:i * 8 + 8]
-                        if v < ns_out // 8:
-                            out[v * 8:v * 8 + 8] = o8
-                        elif v == ns_out // 8 and ns_out % 8:
-                            out[v * 8:v * 8 + ns_out % 8] = o8[:ns_out % 8]
+    """k_bus_fast<CI, CO> (csrc/k_bus.h, bus_fast_tile without the ramp): one wave per (bus, tile) walks the bus's sends
+    -- a send whose stream ends at or before the tile is skipped, its flag still closes the group; a lane's units and
+    vectors zero-filled past the SEND's count; one dot per output sample and send on the input dword that holds the
+    frame, chained in int32 inside a group (held below 2^31 here) and added into the int64 at a flag; one rounding;
+    whole vectors and the ragged end by the BUS's count -> per bus the slot, and the tile"""
+    outs, tile, paths = RH._emulate_fast(xs, _at_rest(table, buses, ci, co), max_frames)
+    assert not [p for p in paths if p[0]]                        # (ramp, wide): the plain path alone
     return outs, tile
 
 
@@ -476,7 +348,7 @@ def test_kernel_assembly_house_rules():
     forms = {re.search(r"k_bus_fastILi(\d)ELi(\d)E", k).groups() for k in fast}
     assert forms == {("1", "1"), ("1", "2"), ("2", "1"), ("2", "2")} and any("k_bus_any" in k for k in scratch), sorted(scratch)
     assert all(v == 0 for v in fast.values()), fast
-    src = open(os.path.join(PKG, "csrc", "k_bus.hip")).read()
+    src = "".join(open(os.path.join(PKG, "csrc", f)).read() for f in ("k_bus.hip", "k_bus.h", "k_mix.h"))
     assert "getenv" not in src
     for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-        assert not re.findall(r"\bCMHIP_\w+", m.group(1)), m.group(0)
+        assert not re.findall(r"\bCMHIP_(?!K_(?:BUS|MIX)_H\b)\w+", m.group(1)), m.group(0)   # (but the include guards)

@@ -233,7 +233,8 @@ def test_plan_busramp(cm):
 # BOTH ends of every running ramp, per (tile, send) the uniform choice between the ramp path and the plain one with the
 # target.  k_busr_fast: a lane's units, int32 inside a group (held below 2^31 here), int64 across groups.  k_busr_any:
 # vectors staged into pair planes as far as the SEND's stream reaches, one thread per frame.  Positions are read, not
-# advanced.  The rehearsal before GPU time.
+# advanced.  The rehearsal before GPU time.  With every send at rest these are the decompositions of k_bus.hip's two
+# kernels: tests/test_bus_host.py calls them so.
 
 UNWRITTEN = 1 << 40
 
@@ -283,14 +284,15 @@ def _slots(xs, ci, max_frames):
     return counts, slots
 
 
-def _vector(ins, ns_in, v, may_be_past):
-    vec = np.zeros(8, dtype=np.int64)
+def _vector(ins, ns_in, v, ragged_ok, past_ok):
+    vec = np.zeros(8, dtype=np.int64)                            # load_vec: whole, the ragged end zero padded, or zeros
     if v < ns_in // 8:
         vec[:] = ins[v * 8:v * 8 + 8]
     elif v == ns_in // 8 and ns_in % 8:
+        assert ragged_ok
         vec[:ns_in % 8] = ins[v * 8:v * 8 + ns_in % 8]
     else:
-        assert may_be_past                                       # zeros: nothing past the send's count is read
+        assert past_ok                                           # zeros: nothing past the send's count is read
     assert (vec != UNWRITTEN).all()
     return vec
 
@@ -334,7 +336,7 @@ def _emulate_fast(xs, model, max_frames):
                 for u in range(nu):
                     for i in range(vi):
                         for ln in lane:
-                            vec = _vector(ins, ns_in, ((k * 64 * nu) + 64 * u + ln) * vi + i, f0 + tile > c)
+                            vec = _vector(ins, ns_in, ((k * 64 * nu) + 64 * u + ln) * vi + i, f0 + tile > c, f0 + tile > c)
                             lo[ln, u, i * 4:i * 4 + 4], hi[ln, u, i * 4:i * 4 + 4] = vec[0::2], vec[1::2]
                 if ramp:                                         # [lane][unit][frame of the unit] -> per entry
                     inc = -(-(1 << 32) // send.R)
@@ -406,7 +408,7 @@ def _emulate_any(xs, model, tile, max_frames):
                 ns_in = c * ci
                 vb, nv = f0 * ci // 8, (ntj * ci + 7) // 8
                 for w in range(nv):
-                    vec = _vector(ins, ns_in, vb + w, False)
+                    vec = _vector(ins, ns_in, vb + w, True, False)       # whole, or the ragged end: none past it
                     if ci % 2 == 0:
                         for i in range(4):
                             f, k = divmod(w * 4 + i, cp)
@@ -538,9 +540,9 @@ def test_kernel_assembly_house_rules():
     assert any("k_busr_any" in k for k in scratch) and any("k_busr_advance" in k for k in scratch)
     assert all(v == 0 for v in fast.values()), fast
     assert not [k for k in scratch if "k_bus_fast" in k or "k_bus_any" in k]     # (tests/test_bus_host.py counts those)
-    src = open(os.path.join(PKG, "csrc", "k_busramp.hip")).read()
+    src = "".join(open(os.path.join(PKG, "csrc", f)).read() for f in ("k_busramp.hip", "k_bus.h", "k_mix.h"))
     assert "getenv" not in src and not re.search(r"\basm\b|__asm__", src)
     for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-        assert not re.findall(r"\bCMHIP_\w+", m.group(1)), m.group(0)
+        assert not re.findall(r"\bCMHIP_(?!K_(?:BUS|MIX)_H\b)\w+", m.group(1)), m.group(0)   # (but the include guards)
     mk = open(os.path.join(PKG, "Makefile")).read()
     assert re.search(r"^HIP_SRC\s*=.*\bk_busramp\.hip\b", mk, flags=re.M) and "build/k_busramp.s" in mk

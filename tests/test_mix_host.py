@@ -16,14 +16,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "libcoolmic-dsp_amd")
 
 
-def _gpu_test_module():
-    spec = importlib.util.spec_from_file_location("test_gpu_mix_model", os.path.join(ROOT, "tests", "test_gpu_mix.py"))
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name + "_for_mix", os.path.join(ROOT, "tests", name + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
 
 
-TG = _gpu_test_module()            # the model and the dense matrices of the GPU tests
+RH = _load("test_mix_ramp_host")   # the emulations of both kernels' decomposition: no ramp running, they are k_mix.hip's
+TG = RH.TR.TG                      # tests/test_gpu_mix.py: the model and the dense matrices of the GPU tests
+UNWRITTEN = RH.UNWRITTEN
 
 PRESETS = {
     "MIX_MONO_TO_STEREO": (0, 1, 2, [[16384], [16384]]),
@@ -155,71 +157,14 @@ def test_plan(cm):
 # one of the stream zero padded, none past it), the scatter into CP planes of dwords (even C_in: by dwords, odd: by
 # halves, the unused half never written), one thread per frame with the kernel-form matrix, the interleaved output tile
 # and its whole vectors / ragged end.  It holds the index arithmetic (every plane element read was written, nothing past
-# a stream's count is read or written) where no GPU is.
+# a stream's count is read or written) where no GPU is.  The steps are tests/test_mix_ramp_host.py's emulation of
+# k_mixr_any with no ramp running: the kernels share them.
 
-UNWRITTEN = 1 << 40
-
-
-def _kernel_form(W):
-    co, ci = W.shape
-    cp = (ci + 1) // 2
-    lo, hi = np.zeros((co, cp), dtype=np.int64), np.zeros((co, cp), dtype=np.int64)
-    lo[:, :(ci + 1) // 2] = W[:, 0::2]
-    hi[:, :ci // 2] = W[:, 1::2]
-    return lo, hi
-
-
-def _emulate_any(x, W, tile, slot_pad=5):
+def _emulate_any(x, W, tile):
     """x int16 [F][C_in], W [C_out][C_in] -> the output slot as the kernel leaves it (UNWRITTEN where it stored nothing)"""
     W = np.asarray(W, dtype=np.int64)
-    co, ci = W.shape
-    cp = (ci + 1) // 2
-    F = x.shape[0]
-    ins = x.reshape(-1).astype(np.int64)
-    klo, khi = _kernel_form(W)
-    outs = np.full(F * co + slot_pad + 8, UNWRITTEN, dtype=np.int64)
-    ns_in, ns_out = F * ci, F * co
-    for f0 in range(0, F, tile):                                 # one workgroup each
-        nt = min(tile, F - f0)
-        plo = np.full((cp, tile), UNWRITTEN, dtype=np.int64)     # the halves of the planes' dwords
-        phi = np.full((cp, tile), UNWRITTEN, dtype=np.int64)
-        assert (f0 * ci) % 8 == 0 and (f0 * co) % 8 == 0
-        vb, nv = f0 * ci // 8, (nt * ci + 7) // 8
-        for w in range(nv):
-            v = vb + w
-            vec = np.zeros(8, dtype=np.int64)                    # load_vec: whole, or the ragged end zero padded
-            if v < ns_in // 8:
-                vec[:] = ins[v * 8:v * 8 + 8]
-            else:
-                assert v == ns_in // 8 and ns_in % 8
-                vec[:ns_in % 8] = ins[v * 8:]
-            if ci % 2 == 0:
-                for i in range(4):
-                    f, k = divmod(w * 4 + i, cp)
-                    if f < nt:
-                        plo[k, f], phi[k, f] = vec[2 * i], vec[2 * i + 1]
-            else:
-                for i in range(8):
-                    f, c = divmod(w * 8 + i, ci)
-                    if f < nt:
-                        (phi if c & 1 else plo)[c >> 1, f] = vec[i]
-        ot = np.full(tile * co, UNWRITTEN, dtype=np.int64)
-        for f in range(nt):                                      # the threads
-            lo, hi = plo[:, f], phi[:, f].copy()
-            assert (lo != UNWRITTEN).all()
-            if ci % 2:
-                assert hi[cp - 1] == UNWRITTEN and khi[:, cp - 1].max() == 0 == khi[:, cp - 1].min()
-                hi[cp - 1] = 12345                               # whatever LDS held: it meets a zero weight
-            assert (hi != UNWRITTEN).all()
-            acc = 8192 + klo @ lo + khi @ hi
-            ot[f * co:(f + 1) * co] = np.clip(acc >> 14, -32768, 32767)
-        vb, nv = f0 * co // 8, (nt * co + 7) // 8
-        for w in range(nv):
-            v = vb + w
-            if v < ns_out // 8:
-                outs[v * 8:v * 8 + 8] = ot[w * 8:w * 8 + 8]
-            elif v == ns_out // 8:
-                outs[v * 8:v * 8 + ns_out % 8] = ot[w * 8:w * 8 + ns_out % 8]
+    outs, paths = RH._emulate_any(x, W, W, 0, 0, tile)
+    assert paths <= {False}                                      # the plain path alone
     return outs
 
 
@@ -237,57 +182,17 @@ def test_emulated_decomposition_equals_the_model(cm, ci, co):
         assert (got[want.size:] == UNWRITTEN).all(), (ci, co, F)  # nothing past the stream's count
     # the kernel form: dword k of row o is W[o][2k] | W[o][2k+1] << 16, an odd C_in padded with zero
     W = TG.dense_matrix(ci, co, 1)
-    lo, hi = _kernel_form(W.astype(np.int64))
+    lo, hi = RH._kernel_form(W.astype(np.int64))
     assert np.array_equal(lo, W[:, 0::2]) and np.array_equal(hi[:, :ci // 2], W[:, 1::2])
 
 
 def _emulate_fast(x, W):
-    """k_mix_fast<CI, CO> (csrc/k_mix.hip): a lane's units, their vectors on both sides, one dot per output sample on
-    the input dword that holds the frame -- with mono input the weight in the half the frame sits in -> the slot"""
+    """k_mix_fast<CI, CO> (csrc/k_mix.h, mixr_fast_tile without the ramp): a lane's units, their vectors on both sides,
+    one dot per output sample on the input dword that holds the frame -- with mono input the weight in the half the
+    frame sits in -> the slot"""
     W = np.asarray(W, dtype=np.int64)
-    co, ci = W.shape
-    uf = 8 // min(ci, co)
-    vi, vo = uf * ci // 8, uf * co // 8
-    nu = 4 // max(vi, vo)
-    tile = 64 * nu * uf
-    F = x.shape[0]
-    ins = x.reshape(-1).astype(np.int64)
-    ns_in, ns_out = F * ci, F * co
-    outs = np.full(F * co + 13, UNWRITTEN, dtype=np.int64)
-    wk = [(int(W[o, 0]), int(W[o, 1]) if ci == 2 else 0) for o in range(co)]        # (low half, high half)
-    for k in range(-(-F // tile)):                               # one wave each
-        full = (k + 1) * tile <= F
-        for lane in range(64):
-            for j in range(nu):
-                n = k * 64 * nu + 64 * j + lane
-                dwords = []                                      # the unit's input, as (low, high) halves
-                for i in range(vi):
-                    v = n * vi + i
-                    vec = np.zeros(8, dtype=np.int64)
-                    if v < ns_in // 8:
-                        vec[:] = ins[v * 8:v * 8 + 8]
-                    elif v == ns_in // 8 and ns_in % 8:
-                        assert not full
-                        vec[:ns_in % 8] = ins[v * 8:]
-                    else:
-                        assert not full                          # zeros: nothing past the count is read
-                    dwords += [(vec[2 * d], vec[2 * d + 1]) for d in range(4)]
-                for i in range(vo):
-                    o8 = np.zeros(8, dtype=np.int64)
-                    for e in range(i * 8, i * 8 + 8):            # output sample of the unit
-                        f, oc = divmod(e, co)
-                        lo, hi = dwords[(f * ci) >> 1]
-                        if ci == 2:
-                            wlo, whi = wk[oc]
-                        else:
-                            wlo, whi = (0, wk[oc][0]) if f & 1 else (wk[oc][0], 0)
-                        o8[e - i * 8] = min(max((8192 + lo * wlo + hi * whi) >> 14, -32768), 32767)
-                    v = n * vo + i
-                    if v < ns_out // 8:
-                        outs[v * 8:v * 8 + 8] = o8
-                    elif v == ns_out // 8 and ns_out % 8:
-                        assert not full
-                        outs[v * 8:v * 8 + ns_out % 8] = o8[:ns_out % 8]
+    outs, tile, paths = RH._emulate_fast(x, W, W, 0, 0)
+    assert paths <= {False}
     return outs, tile
 
 
@@ -321,7 +226,7 @@ def test_kernel_assembly_house_rules():
     fast = {k: v for k, v in scratch.items() if "k_mix_fast" in k}
     assert len(fast) == 4 and any("k_mix_any" in k for k in scratch), sorted(scratch)
     assert all(v == 0 for v in fast.values()), fast
-    src = open(os.path.join(PKG, "csrc", "k_mix.hip")).read()
+    src = "".join(open(os.path.join(PKG, "csrc", f)).read() for f in ("k_mix.hip", "k_mix.h"))
     assert "getenv" not in src
     for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-        assert not re.findall(r"\bCMHIP_\w+", m.group(1)), m.group(0)
+        assert not re.findall(r"\bCMHIP_(?!K_MIX_H\b)\w+", m.group(1)), m.group(0)   # (but the header's include guard)

@@ -177,6 +177,8 @@ def test_mirror_under_address_and_ub_sanitizers(tmp_path):
 # target.  k_mixr_fast: a lane's units and vectors, one dot per output sample on the dword that holds the frame, with
 # mono input the frame's weight in the half its frame sits in.  k_mixr_any: 16-byte vectors staged into pair planes, one
 # thread per frame computing every weight dword of its frame, the staged output tile.  The rehearsal before GPU time.
+# With no ramp running (done = R = 0, both matrices the stream's own) these are the decompositions of k_mix.hip's two
+# kernels: tests/test_mix_host.py calls them so.
 
 UNWRITTEN = 1 << 40
 
@@ -193,15 +195,27 @@ def _dev_w(w0, w1, p):
     return (N + ((N >> 31) & 32767)) >> 15
 
 
-def _load_vectors(ins, ns, v, full):
+def _load_vectors(ins, ns, v, ragged_ok, past_ok):
     vec = np.zeros(8, dtype=np.int64)                            # load_vec: whole, the ragged end zero padded, or zeros
     if v < ns // 8:
         vec[:] = ins[v * 8:v * 8 + 8]
+    elif v == ns // 8 and ns % 8:
+        assert ragged_ok
+        vec[:ns % 8] = ins[v * 8:]
     else:
-        assert not full
-        if v == ns // 8 and ns % 8:
-            vec[:ns % 8] = ins[v * 8:]
+        assert past_ok                                           # zeros: nothing past the count is read
     return vec
+
+
+def _kernel_form(W):
+    """(low, high) halves of the kernel form's dwords: dword k of row o is W[o][2k] | W[o][2k+1] << 16, an odd C_in
+    padded with zero"""
+    co, ci = W.shape
+    cp = (ci + 1) // 2
+    lo, hi = np.zeros((co, cp), dtype=np.int64), np.zeros((co, cp), dtype=np.int64)
+    lo[:, :] = W[:, 0::2]
+    hi[:, :ci // 2] = W[:, 1::2]
+    return lo, hi
 
 
 def _emulate_fast(x, w0, w1, done, R):
@@ -225,7 +239,7 @@ def _emulate_fast(x, w0, w1, done, R):
                 u = k * 64 * nu + 64 * j + lane
                 dwords = []
                 for i in range(vi):
-                    vec = _load_vectors(ins, ns_in, u * vi + i, full)
+                    vec = _load_vectors(ins, ns_in, u * vi + i, not full, not full)
                     dwords += [(vec[2 * d], vec[2 * d + 1]) for d in range(4)]
                 wf = []                                          # per frame and row: (weight of the low, the high half)
                 for f in range(uf):
@@ -258,14 +272,7 @@ def _emulate_any(x, w0, w1, done, R, tile):
     F = x.shape[0]
     ins = x.reshape(-1).astype(np.int64)
     ns_in, ns_out = F * ci, F * co
-
-    def kernel_form(W):                                          # (low, high) halves, an odd C_in padded with zero
-        lo, hi = np.zeros((co, cp), dtype=np.int64), np.zeros((co, cp), dtype=np.int64)
-        lo[:, :] = W[:, 0::2]
-        hi[:, :ci // 2] = W[:, 1::2]
-        return lo, hi
-
-    k0, k1 = kernel_form(w0), kernel_form(w1)
+    k0, k1 = _kernel_form(w0), _kernel_form(w1)
     outs = np.full(F * co + 13, UNWRITTEN, dtype=np.int64)
     paths = set()
     for f0 in range(0, F, tile):                                 # one workgroup each
@@ -277,7 +284,7 @@ def _emulate_any(x, w0, w1, done, R, tile):
         assert (f0 * ci) % 8 == 0 and (f0 * co) % 8 == 0
         vb, nv = f0 * ci // 8, (nt * ci + 7) // 8
         for w in range(nv):
-            vec = _load_vectors(ins, ns_in, vb + w, False)
+            vec = _load_vectors(ins, ns_in, vb + w, True, False)     # whole, or the ragged end: none past it
             if ci % 2 == 0:
                 for i in range(4):
                     f, k = divmod(w * 4 + i, cp)
@@ -291,10 +298,11 @@ def _emulate_any(x, w0, w1, done, R, tile):
         ot = np.full(tile * co, UNWRITTEN, dtype=np.int64)
         for f in range(nt):                                      # the threads
             lo, hi = plo[:, f], phi[:, f].copy()
+            assert (lo != UNWRITTEN).all()
             if ci % 2:
-                assert hi[cp - 1] == UNWRITTEN
+                assert hi[cp - 1] == UNWRITTEN and not k0[1][:, cp - 1].any() and not k1[1][:, cp - 1].any()
                 hi[cp - 1] = 12345                               # whatever LDS held: it meets a zero weight
-            assert (lo != UNWRITTEN).all() and (hi != UNWRITTEN).all()
+            assert (hi != UNWRITTEN).all()
             p = _dev_pos(done + f0 + f + 1, R, inc) if ramp else 32768
             for o in range(co):
                 acc = 8192
@@ -392,7 +400,7 @@ def test_kernel_assembly_house_rules():
     assert len(fast) == 4 and any("k_mixr_any" in k for k in scratch), sorted(scratch)
     assert all(v == 0 for v in fast.values()), fast
     assert not [k for k in scratch if "k_mix_fast" in k or "k_mix_any" in k]     # (tests/test_mix_host.py counts those)
-    src = open(os.path.join(PKG, "csrc", "k_mixramp.hip")).read()
+    src = "".join(open(os.path.join(PKG, "csrc", f)).read() for f in ("k_mixramp.hip", "k_mix.h"))
     assert "getenv" not in src
     for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
-        assert not re.findall(r"\bCMHIP_\w+", m.group(1)), m.group(0)
+        assert not re.findall(r"\bCMHIP_(?!K_MIX_H\b)\w+", m.group(1)), m.group(0)   # (but the header's include guard)

@@ -41,7 +41,7 @@ SHAPES = {          # buses, C_in, C_out, sends per bus (None: mix-minus of `bus
     "x6_to_s2_k4": (1024, 6, 2, 4),
     "mix_minus_64": (64, 1, 1, None),
 }
-# output samples a lane makes per send of the mono / stereo kernels (BusFast::NOUT, csrc/k_bus.hip)
+# output samples a lane makes per send of the mono / stereo kernels (MixFast::NOUT, csrc/k_mix.h)
 FAST_OUTPUTS = {(1, 1): 32, (1, 2): 32, (2, 1): 16, (2, 2): 32}
 
 

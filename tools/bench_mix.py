@@ -35,7 +35,7 @@ SHAPES = {          # streams, C_in, C_out, frames, preset (None: dense)
     "x6_to_s2_norm": (1365, 6, 2, 65536, "MIX_51_TO_STEREO_NORM"),
     "x16_to_x16": (512, 16, 16, 65536, None),
 }
-# output samples a lane makes per pass of the mono / stereo kernels' whole-tile path (MixFast, csrc/k_mix.hip)
+# output samples a lane makes per pass of the mono / stereo kernels' whole-tile path (MixFast, csrc/k_mix.h)
 FAST_OUTPUTS = {(1, 1): 32, (1, 2): 32, (2, 1): 16, (2, 2): 32}
 
 
