@@ -1,6 +1,6 @@
 // cmhip_dyn.hip -- the dynamics stage on the host side (include/coolmic_hip.h, "dynamics"): the object beside the
-// batch, its validation, the launch of k_dyn.hip's kernels (k_dynkey.hip's while a side-chain key is set; k_dynrms.hip's
-// for an object with the RMS detector), the curves, the keys, reset, the gain meter and the curve designers.
+// batch, its validation, the launch of k_dyn.hip's kernels (the keyed ones while a side-chain key is set, the RMS
+// ones for an object with the RMS detector), the curves, the keys, reset, the gain meter and the curve designers.
 //
 // Device state of a dynamics stage: one curve of DYN_CURVE uint16 entries per stream, the streams' history, int16
 // [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
@@ -350,12 +350,8 @@ extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, s
     a.W = m->g.W;
     if (frames_per_stream)
         HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    // (the keyed kernels only while a key is set; the mean detector's launches are the ones it always had)
-    hipError_t e;
-    if (m->detector == DYN_DETECT_RMS)
-        e = launch_dynrms(a, m->keyed ? m->d_key : nullptr, m->stream);
-    else
-        e = m->keyed ? launch_dynk(a, m->d_key, m->stream) : launch_dyn(a, m->stream);
+    // (the keyed kernels only while a key is set)
+    const hipError_t e = launch_dyn(a, m->detector, m->keyed ? m->d_key : nullptr, m->stream);
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "dyn_run: %s", hipGetErrorString(e));
     m->parity ^= 1u;                         // the kernel wrote the other slots

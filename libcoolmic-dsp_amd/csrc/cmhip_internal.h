@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_dynkey.hip, k_dynrms.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -436,18 +436,15 @@ hipError_t launch_limrel(const LimArgs &a, uint32_t detector, uint32_t release_l
 // (threshold and drive into the parameter words of streams first .. first + count - 1; they travel as kernel arguments)
 hipError_t launch_lim_set(uint32_t *par, uint32_t first, uint32_t count, uint32_t threshold, uint32_t drive,
                           hipStream_t st);
-// Dynamics (k_dyn.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/dyn_plan.h's.
-hipError_t launch_dyn(const DynArgs &a, hipStream_t st);
+// Dynamics (k_dyn.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/dyn_plan.h's.  detector is
+// DYN_DETECT_*.  key == nullptr: every stream's detector reads the stream itself; otherwise the detector of stream s
+// reads stream key[s] (uint32 [S] on the device; a keyed stream and its key have equal counts).
+hipError_t launch_dyn(const DynArgs &a, uint32_t detector, const uint32_t *key, hipStream_t st);
 // (one curve into the tables of streams first .. first + count - 1; it travels as a kernel argument)
 hipError_t launch_dyn_set(uint16_t *curve, uint32_t first, uint32_t count, const uint16_t *table, hipStream_t st);
-// Side-chain keys (k_dynkey.hip): launch_dyn's run with the detector of stream s reading stream key[s] (uint32 [S] on
-// the device; a keyed stream and its key have equal counts), and the map's writer: streams first .. first + count - 1
-// get `key`, or each itself where own is set; both values travel as kernel arguments.
-hipError_t launch_dynk(const DynArgs &a, const uint32_t *key, hipStream_t st);
+// (the key map's writer: streams first .. first + count - 1 get `key`, or each itself where own is set; both values
+// travel as kernel arguments)
 hipError_t launch_dyn_set_key(uint32_t *map, uint32_t first, uint32_t count, uint32_t key, bool own, hipStream_t st);
-// The RMS detector (k_dynrms.hip): launch_dyn's run, or launch_dynk's where key is not nullptr, with the level taken as
-// the root of the mean square.
-hipError_t launch_dynrms(const DynArgs &a, const uint32_t *key, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

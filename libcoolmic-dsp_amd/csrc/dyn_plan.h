@@ -1,6 +1,6 @@
 // dyn_plan.h -- the geometry, the curve's index function and the launch plan of the dynamics stage
 // (include/coolmic_hip.h, "dynamics").  Plain C++17, no HIP: tests/cpp/dyn_plan_test.cpp and tests/cpp/dyn_rms_test.cpp
-// compile it with g++ alone; the kernels (k_dyn.hip, k_dynrms.hip) use the same index function and the same root.
+// compile it with g++ alone; the kernels (k_dyn.hip) use the same index function and the same root.
 //
 //   a = detector_log2 in 3..10, A = 2^a: the level window.  b = smooth_log2 in 3..9, B = 2^b: the gain's ramp; D = B - 1
 //   (the delay).  H = hold, W = B + H <= 2048.  HIST = (A - 1) + (W - 1) + (B - 1): the earlier frames an output depends on.

@@ -1,10 +1,9 @@
-// k_dyn.h -- what the dynamics stage's kernel files share (k_dyn.hip, k_dynkey.hip, k_dynrms.hip): the helpers and the
-// tile body of the decomposition k_dyn.hip describes, with the detector's source and the detector as compile-time
-// parameters (DET = DYN_DETECT_RMS: k_dynrms.hip, which says how step 2 sums the squares).  KEYED = false: the level
-// follows the stream's own frames (k_dyn_fast<C>, k_dyn_any).  KEYED = true: step 1 takes its run slot, history slot
-// and history vector base from stream key[s] (k_dynk_fast<C>, k_dynk_any); step 3, step 4, the copy of a stream
-// without frames, the curve and the meter stay stream s's own.  A keyed stream and its key have equal counts (the host
-// refuses a run otherwise), so one count bounds both.
+// k_dyn.h -- the device side of the dynamics stage's kernels (k_dyn.hip): the helpers and the tile body of the
+// decomposition k_dyn.hip describes, with the detector's source and the detector as compile-time parameters (k_dyn.hip,
+// "RMS", says why step 2 sums the squares in two halves).  KEYED = false: the level follows the stream's own frames
+// (k_dyn<CT, DET>).  KEYED = true: step 1 takes its run slot, history slot and history vector base from stream key[s]
+// (k_dynk<CT, DET>); step 3, step 4, the copy of a stream without frames, the curve and the meter stay stream s's own.
+// A keyed stream and its key have equal counts (the host refuses a run otherwise), so one count bounds both.
 #ifndef CMHIP_K_DYN_H
 #define CMHIP_K_DYN_H
 

@@ -270,10 +270,13 @@ def test_model_properties(a, b, H):
 
 
 # ---------------------------------------------------------------------------
-# The decomposition of k_dyn_fast<C> / k_dyn_any (csrc/k_dyn.hip), step by step in numpy, one workgroup per tile.
+# The decomposition of k_dyn<CT, DET> / k_dynk<CT, DET> (csrc/k_dyn.hip, the body csrc/k_dyn.h's dyn_tile), step by step
+# in numpy, one workgroup per tile.  tests/test_dyn_key_host.py and tests/test_dyn_rms_host.py hold their models to it too.
 
 BLOCK, R = 256, 30
 UNWRITTEN = 1 << 40
+SPLIT = 15                                        # DYN_SQ_SPLIT
+MEAN, RMS = 0, 1                                  # DYN_DETECT_*
 
 
 def _pack(T):
@@ -300,97 +303,117 @@ def _lookup(cv, l):
     return t0 + (prod >> sh)
 
 
-def _emulate_run(x, slot, T, a, b, H, ch, tile, halo):
-    """one stream of one run: x int16 [F][C], slot int64 [halo * C] (the history slot the run reads)
+def _dyn_isqrt(v):
+    """csrc/dyn_plan.h: dyn_isqrt, operation by operation, in 32-bit ranges"""
+    assert v.min() >= 0 and v.max() < 2 ** 32
+    r = np.sqrt(v.astype(np.float32)).astype(np.int64)           # (float)v rounds to 24 bits; the root is single precision
+    r = np.minimum(r, 65535)
+    assert (r * r < 2 ** 32).all()
+    r = np.where(r * r > v, r - 1, r)
+    assert (r >= 0).all() and (v - r * r >= 0).all()             # nothing wraps
+    return np.where(v - r * r > 2 * r, r + 1, r)
+
+
+def _emulate_run(x, slot, xk, slotk, T, a, b, H, ch, tile, halo, det):
+    """one stream of one run: x int16 [F][C] and slot int64 [halo * C] (the history slot the run reads) the stream's own,
+    xk and slotk the key's (the stream's own where it has no key), det MEAN or RMS
     -> out int64 [F * C + 8] (UNWRITTEN where nothing was stored), the slot the run writes, min s or None"""
     A, B, D, W, hist = TG.geometry(a, b, H)
     F = x.shape[0]
+    assert xk.shape[0] == F                                      # (the host refuses a run otherwise)
     ns, hsamp = F * ch, halo * ch
     hv, nfull, ntail = hsamp // 8, ns // 8, ns % 8
     assert hsamp % 8 == 0 and tile >= halo >= hist
     cv = _pack(T)
-    # the stream as a tile sees it: the slot's vectors below 0, the run's from 0 on, zeros past the count
-    seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)])
+    # a stream as a tile sees it: the slot's vectors below 0, the run's from 0 on, zeros past the count
+    pad = np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)
+    seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), pad])         # the stream itself
+    seqk = np.concatenate([slotk, xk.astype(np.int64).reshape(-1), pad])      # ... and the detector's source
 
-    def vec(vv):                                                  # [n] vector indices -> [n][8] samples
+    def vec(q, vv):                                               # [n] vector indices -> [n][8] samples
         vv = np.asarray(vv)
         assert (vv >= -hv).all()
-        return seq[(hsamp + vv * 8)[:, None] + np.arange(8)]
+        return q[(hsamp + vv * 8)[:, None] + np.arange(8)]
 
-    def sample(q):
-        q = np.asarray(q)
-        assert (q >= -hsamp).all() and (q < ns).all()
-        return seq[hsamp + q]
+    def sample(q, i):
+        i = np.asarray(i)
+        assert (i >= -hsamp).all() and (i < ns).all()
+        return q[hsamp + i]
 
     out = np.full(ns + 8, UNWRITTEN, dtype=np.int64)
-    new_slot = sample(ns - hsamp + np.arange(hsamp))              # 4. (the last tile, or tile 0 of a stream with 0 frames)
-    if F == 0:
+    new_slot = sample(seq, ns - hsamp + np.arange(hsamp))         # 4. (the last tile, or tile 0 of a stream with 0 frames),
+    if F == 0:                                                    # from the stream's OWN slots
         assert np.array_equal(new_slot, slot)
         return out, new_slot, None
     gmin = UNITY
     N = halo + tile
     tid, i = np.meshgrid(np.arange(BLOCK), np.arange(R), indexing="ij")
-    own = (tid + BLOCK * i).reshape(-1)
-    own = own[own < N]
-    assert np.array_equal(np.sort(own), np.arange(N))            # every element has exactly one thread
+    own = (tid + BLOCK * i).reshape(-1)                           # the thread-to-element map: j = tid + 256 i
+    assert np.array_equal(np.sort(own[own < N]), np.arange(N))    # every element has exactly one thread
     for f0 in range(0, F, tile):
         nt = min(tile, F - f0)
-        L = np.full(N, UNWRITTEN, dtype=np.int64)
-        # ---- 1. e of frames f0 - halo .. f0 + tile - 1
+        # ---- 1. e of frames f0 - halo .. f0 + tile - 1, from the KEY's slots, across the seam between history and run
         if ch <= 2:
             fpv = 8 // ch
             NV = N // fpv
             assert NV <= BLOCK * ((R * ch + 7) // 8)
             vbase = f0 * ch // 8 - hv
-            assert f0 == 0 or vbase >= 0                          # only the run's first tile reads the slot
-            v = np.abs(vec(vbase + np.arange(NV)))
-            L[:] = (v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])).reshape(-1)
+            assert f0 == 0 or vbase >= 0                          # only the run's first tile reads the (key's) history slot
+            v = np.abs(vec(seqk, vbase + np.arange(NV)))
+            e = (v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])).reshape(-1)
         else:
             p = f0 - halo + np.arange(N)
-            peak = np.zeros(N, dtype=np.int64)
+            e = np.zeros(N, dtype=np.int64)
             inside = p < F
-            peak[inside] = np.abs(sample(p[inside, None] * ch + np.arange(ch))).max(axis=1)
-            L[:] = peak
-        assert (L != UNWRITTEN).all()
+            e[inside] = np.abs(sample(seqk, p[inside, None] * ch + np.arange(ch))).max(axis=1)
+        assert e.size == N and e.max() <= 32768
         # ---- 2. the passes: partner from LDS, own element back, shifted by the last pass of a sum
         j = np.arange(N)
         passes = 0
 
         def one_pass(L, dist, is_max, shift):
+            nonlocal passes
             o = L[np.maximum(j, dist) - dist]                      # (unguarded: an element without a partner takes element 0)
             v = (np.maximum(L, o) if is_max else L + o)
             assert v.max() < 2 ** 32
+            passes += 1
             return v >> shift
 
-        d = 1
-        while d < A:
-            L = one_pass(L, d, False, a if 2 * d == A else 0)
-            d *= 2
-            passes += 1
+        def boxcar(L, n, shift):                                  # log2 n add passes, the last one shifts
+            d = 1
+            while d < n:
+                L = one_pass(L, d, False, shift if 2 * d == n else 0)
+                d *= 2
+            return L
+
+        if det == RMS:
+            sq = e * e
+            assert sq.max() < 2 ** 32                             # the square itself fits a dword
+            lo = boxcar(sq & ((1 << SPLIT) - 1), A, 0)            # the low halves first, e waiting in registers
+            hi = boxcar(sq >> SPLIT, A, 0)
+            assert lo.max() <= 2 ** 25 and hi.max() <= 2 ** 25
+            M = (hi << (SPLIT - a)) + (lo >> a)                   # dyn_mean_square
+            assert M.max() <= 2 ** 30                             # also where an element had no partner
+            L = _dyn_isqrt(M)
+        else:
+            L = boxcar(e, A, a)
         P = 1
         while 2 * P <= W:
             L = one_pass(L, P, True, 0)
             P *= 2
-            passes += 1
         if W > P:
             L = one_pass(L, W - P, True, 0)
-            passes += 1
-        L = _lookup(cv, np.minimum(L, UNITY))
-        d = 1
-        while d < B:
-            L = one_pass(L, d, False, b if 2 * d == B else 0)
-            d *= 2
-            passes += 1
-        assert passes == a + int(np.log2(W)) + (1 if W & (W - 1) else 0) + b
+        L = boxcar(_lookup(cv, np.minimum(L, UNITY)), B, b)
+        assert passes == (2 * a if det == RMS else a) + int(np.log2(W)) + (1 if W & (W - 1) else 0) + b
         Ls = L[halo:]
         gmin = min(gmin, int(Ls[:nt].min()))
-        # ---- 3. the tile's output vectors
+        # ---- 3. the tile's output vectors, the delayed samples from the stream's OWN slots
         vb, nv = f0 * ch // 8, (nt * ch + 7) // 8
         v8 = vb + np.arange(nv)
         if ch <= 2:
             back = (D + 1) * ch // 8
             assert (D + 1) * ch % 8 == 0 and back <= hv
-            x0, x1 = vec(v8 - back), vec(v8 - back + 1)
+            x0, x1 = vec(seq, v8 - back), vec(seq, v8 - back + 1)
             xs = np.concatenate([x0[:, ch:], x1[:, :ch]], axis=1)                 # mono: samples 1..8, stereo: 2..9
             sf = Ls[(np.arange(nv) * (8 // ch))[:, None] + np.arange(8) // ch]
             prod = xs * sf
@@ -398,7 +421,7 @@ def _emulate_run(x, slot, T, a, b, H, ch, tile, halo):
             q = v8[:, None] * 8 + np.arange(8)
             ok = q < ns
             qq = np.where(ok, q, 0)
-            prod = np.where(ok, sample(qq - D * ch) * Ls[np.where(ok, qq // ch - f0, 0)], 0)
+            prod = np.where(ok, sample(seq, qq - D * ch) * Ls[np.where(ok, qq // ch - f0, 0)], 0)
         assert np.abs(prod + (1 << 14)).max() < 2 ** 31           # the kernel multiplies in 32 bits
         y = (prod + (1 << 14)) >> 15
         for w in range(nv):
@@ -409,6 +432,28 @@ def _emulate_run(x, slot, T, a, b, H, ch, tile, halo):
     return out, new_slot, gmin
 
 
+def _hold_emulation_to(keys, xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo, det):
+    """the ragged run, then the uniform run on the slots it left, stream s reading keys[s]: outputs, the untouched rest
+    and the meter against the model's"""
+    S = len(counts)
+    slots = [np.zeros(halo * channels, dtype=np.int64) for _ in range(S)]
+    got_min = [UNITY] * S
+    for cut, wants in ((counts, ragged), ([counts[0]] * S, full)):
+        new = []
+        for s in range(S):
+            k = keys[s]
+            assert cut[k] == cut[s]
+            out, slot, m = _emulate_run(xs[s][:cut[s]], slots[s], xs[k][:cut[k]], slots[k], T, a, b, H, channels, t, halo,
+                                        det)
+            w = wants[s].astype(np.int64).reshape(-1)
+            assert np.array_equal(out[:w.size], w), (channels, s)
+            assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
+            got_min[s] = min(got_min[s], UNITY if m is None else m)
+            new.append(slot)
+        slots = new                                               # the host flips the parity: every tile read the old slots
+    assert got_min == gmin
+
+
 @pytest.mark.parametrize("channels", [1, 2, 3, 16])
 @pytest.mark.parametrize("a,b,H", TG.SETS)
 def test_emulated_decomposition_equals_the_model(cm, a, b, H, channels):
@@ -416,16 +461,8 @@ def test_emulated_decomposition_equals_the_model(cm, a, b, H, channels):
     t, halo = p.tile_frames, p.halo
     xs, counts, T, ragged, full, unity, change, smallest, gmin = TG.dense_case(a, b, H, channels, t)
     TG.assert_dense(a, b, H, unity, change, smallest)
-    for s in range(len(counts)):
-        slot = np.zeros(halo * channels, dtype=np.int64)
-        got_min = UNITY
-        for x, want in ((xs[s][:counts[s]], ragged[s]), (xs[s], full[s])):
-            out, slot, m = _emulate_run(x, slot, T, a, b, H, channels, t, halo)
-            w = want.astype(np.int64).reshape(-1)
-            assert np.array_equal(out[:w.size], w), (channels, s)
-            assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
-            got_min = min(got_min, UNITY if m is None else m)
-        assert got_min == gmin[s]
+    assert all(x.shape[0] == counts[0] for x in xs)               # the uniform run takes every stream whole
+    _hold_emulation_to(list(range(len(counts))), xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo, MEAN)
 
 
 def test_emulated_lookup_of_every_level():

@@ -1,8 +1,8 @@
 """CPU: the host side of the dynamics stage's side-chain keys (cmhip_dyn_set_key, cmhip_dyn_get_key,
 cmhip_dyn_design_duck): the header, the duck designer against its formula in numpy, the NULL refusals, the keyed model's
-own properties, and an emulation of the keyed decomposition (csrc/k_dyn.h with KEYED = true: step 1's vectors from the
-KEY's slots across the history seam, step 3's two-vector read and the history write from the stream's own) at the
-plan's own tile against the keyed model of tests/test_gpu_dyn_key.py.  Nothing here needs a GPU."""
+own properties, and tests/test_dyn_host.py's emulation of the keyed decomposition (csrc/k_dyn.h with KEYED = true: step
+1's vectors from the KEY's slots across the history seam, step 3's two-vector read and the history write from the
+stream's own) at the plan's own tile against the keyed model of tests/test_gpu_dyn_key.py.  Nothing here needs a GPU."""
 import ctypes as C
 import importlib.util
 import os
@@ -23,7 +23,7 @@ def _load(name):
 
 TK = _load("test_gpu_dyn_key")     # the keyed model and the dense cases of the GPU tests
 TG = TK.TG                         # the unkeyed model (tests/test_gpu_dyn.py)
-TD = _load("test_dyn_host")        # the emulation's helpers
+TD = _load("test_dyn_host")        # the emulation of the kernels' decomposition
 UNITY = 32768
 
 
@@ -184,110 +184,7 @@ def test_slide_max_is_the_sliding_window_maximum():
 
 
 # ---------------------------------------------------------------------------
-# The keyed decomposition (csrc/k_dyn.h, KEYED = true) step by step in numpy, one workgroup per tile: tests/test_dyn_host.py's
-# emulation with step 1 on the key's sequence.
-
-BLOCK, R, UNWRITTEN = TD.BLOCK, TD.R, TD.UNWRITTEN
-
-
-def _emulate_keyed_run(x, slot, xk, slotk, T, a, b, H, ch, tile, halo):
-    """one stream of one run: x int16 [F][C] and slot int64 [halo * C] the stream's own, xk and slotk the key's
-    -> out int64 [F * C + 8] (UNWRITTEN where nothing was stored), the slot the run writes, min s or None"""
-    A, B, D, W, hist = TG.geometry(a, b, H)
-    F = x.shape[0]
-    assert xk.shape[0] == F                                      # (the host refuses a run otherwise)
-    ns, hsamp = F * ch, halo * ch
-    hv, nfull, ntail = hsamp // 8, ns // 8, ns % 8
-    assert hsamp % 8 == 0 and tile >= halo >= hist
-    cv = TD._pack(T)
-    pad = np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)
-    seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), pad])         # the stream as a tile sees it
-    seqk = np.concatenate([slotk, xk.astype(np.int64).reshape(-1), pad])      # ... and its key
-
-    def vec(q, vv):                                               # [n] vector indices -> [n][8] samples
-        vv = np.asarray(vv)
-        assert (vv >= -hv).all()
-        return q[(hsamp + vv * 8)[:, None] + np.arange(8)]
-
-    def sample(q, i):
-        i = np.asarray(i)
-        assert (i >= -hsamp).all() and (i < ns).all()
-        return q[hsamp + i]
-
-    out = np.full(ns + 8, UNWRITTEN, dtype=np.int64)
-    new_slot = sample(seq, ns - hsamp + np.arange(hsamp))         # 4. from the stream's OWN slots
-    if F == 0:
-        assert np.array_equal(new_slot, slot)
-        return out, new_slot, None
-    gmin = UNITY
-    N = halo + tile
-    for f0 in range(0, F, tile):
-        nt = min(tile, F - f0)
-        # ---- 1. e of frames f0 - halo .. f0 + tile - 1, from the KEY's slots
-        if ch <= 2:
-            fpv = 8 // ch
-            NV = N // fpv
-            assert NV <= BLOCK * ((R * ch + 7) // 8)
-            vbase = f0 * ch // 8 - hv
-            assert f0 == 0 or vbase >= 0                          # only the run's first tile reads the (key's) history slot
-            v = np.abs(vec(seqk, vbase + np.arange(NV)))
-            L = (v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])).reshape(-1)
-        else:
-            p = f0 - halo + np.arange(N)
-            L = np.zeros(N, dtype=np.int64)
-            inside = p < F
-            L[inside] = np.abs(sample(seqk, p[inside, None] * ch + np.arange(ch))).max(axis=1)
-        assert L.size == N
-        # ---- 2. the passes
-        j = np.arange(N)
-
-        def one_pass(L, dist, is_max, shift):
-            o = L[np.maximum(j, dist) - dist]
-            v = (np.maximum(L, o) if is_max else L + o)
-            assert v.max() < 2 ** 32
-            return v >> shift
-
-        d = 1
-        while d < A:
-            L = one_pass(L, d, False, a if 2 * d == A else 0)
-            d *= 2
-        P = 1
-        while 2 * P <= W:
-            L = one_pass(L, P, True, 0)
-            P *= 2
-        if W > P:
-            L = one_pass(L, W - P, True, 0)
-        L = TD._lookup(cv, np.minimum(L, UNITY))
-        d = 1
-        while d < B:
-            L = one_pass(L, d, False, b if 2 * d == B else 0)
-            d *= 2
-        Ls = L[halo:]
-        gmin = min(gmin, int(Ls[:nt].min()))
-        # ---- 3. the tile's output vectors, the delayed samples from the stream's OWN slots
-        vb, nv = f0 * ch // 8, (nt * ch + 7) // 8
-        v8 = vb + np.arange(nv)
-        if ch <= 2:
-            back = (D + 1) * ch // 8
-            assert (D + 1) * ch % 8 == 0 and back <= hv
-            x0, x1 = vec(seq, v8 - back), vec(seq, v8 - back + 1)
-            xs = np.concatenate([x0[:, ch:], x1[:, :ch]], axis=1)
-            sf = Ls[(np.arange(nv) * (8 // ch))[:, None] + np.arange(8) // ch]
-            prod = xs * sf
-        else:
-            q = v8[:, None] * 8 + np.arange(8)
-            ok = q < ns
-            qq = np.where(ok, q, 0)
-            prod = np.where(ok, sample(seq, qq - D * ch) * Ls[np.where(ok, qq // ch - f0, 0)], 0)
-        assert np.abs(prod + (1 << 14)).max() < 2 ** 31
-        y = (prod + (1 << 14)) >> 15
-        for w in range(nv):
-            if v8[w] < nfull:
-                out[v8[w] * 8:v8[w] * 8 + 8] = y[w]
-            elif v8[w] == nfull:
-                out[v8[w] * 8:v8[w] * 8 + ntail] = y[w, :ntail]
-    return out, new_slot, gmin
-
+# The keyed decomposition (csrc/k_dyn.h, KEYED = true): tests/test_dyn_host.py's emulation with step 1 on the key's sequence.
 
 @pytest.mark.parametrize("channels", [1, 2, 3, 16])
 @pytest.mark.parametrize("a,b,H", TG.SETS)
@@ -296,22 +193,7 @@ def test_emulated_keyed_decomposition_equals_the_keyed_model(cm, a, b, H, channe
     t, halo = p.tile_frames, p.halo
     xs, counts, keys, T, ragged, full, gmin, differ, change, smallest = TK.dense_key_case(a, b, H, channels, t)
     TK.assert_dense_key(differ, change, smallest)
-    S = len(counts)
-    slots = [np.zeros(halo * channels, dtype=np.int64) for _ in range(S)]
-    got_min = [UNITY] * S
-    for cut, wants in ((counts, ragged), ([counts[0]] * S, full)):
-        new = []
-        for s in range(S):
-            k = keys[s]
-            assert cut[k] == cut[s]
-            out, slot, m = _emulate_keyed_run(xs[s][:cut[s]], slots[s], xs[k][:cut[k]], slots[k], T, a, b, H, channels, t, halo)
-            w = wants[s].astype(np.int64).reshape(-1)
-            assert np.array_equal(out[:w.size], w), (channels, s)
-            assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
-            got_min[s] = min(got_min[s], UNITY if m is None else m)
-            new.append(slot)
-        slots = new                                               # the host flips the parity: every tile read the old slots
-    assert got_min == gmin
+    TD._hold_emulation_to(keys, xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo, TD.MEAN)
 
 
 @pytest.mark.parametrize("a,b,H", TG.SETS)

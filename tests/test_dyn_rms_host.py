@@ -2,9 +2,10 @@
 cmhip_dyn_check_detector): the header, the refusals, the root and the plan through the library and as a stand-alone C++
 program (csrc/dyn_plan.h: the root for every mean square, the two 32-bit sums against a 64-bit one, the plan), plainly
 and under AddressSanitizer + UBSan; the RMS model's own properties and what the header says about constant magnitudes
-and sines; and an emulation of the kernels' decomposition (csrc/k_dyn.h with DET = DYN_DETECT_RMS: the squares split at
-bit 15, each half through the a unguarded add passes, the halves recombined, the root from a single-precision seed and
-its integer repair) at the plan's own tile against the RMS model of tests/test_gpu_dyn_rms.py.  Nothing here needs a GPU."""
+and sines; and tests/test_dyn_host.py's emulation of the kernels' decomposition (csrc/k_dyn.h with DET =
+DYN_DETECT_RMS: the squares split at bit 15, each half through the a unguarded add passes, the halves recombined, the
+root from a single-precision seed and its integer repair) at the plan's own tile against the RMS model of
+tests/test_gpu_dyn_rms.py.  Nothing here needs a GPU."""
 import ctypes as C
 import importlib.util
 import os
@@ -28,7 +29,7 @@ def _load(name):
 
 TR = _load("test_gpu_dyn_rms")     # the RMS model and the cases of the GPU tests
 TK, TG = TR.TK, TR.TG              # the keyed and the unkeyed model of the mean detector
-TD = _load("test_dyn_host")        # the emulation's helpers
+TD = _load("test_dyn_host")        # the emulation of the kernels' decomposition
 UNITY = 32768
 MEAN, RMS = 0, 1
 
@@ -141,13 +142,13 @@ def test_model_properties(a, b, H):
         h = TG.next_hist(h, part)
         pos += part.shape[0]
     assert pos == x.shape[0] and np.array_equal(np.concatenate(parts), y)
-    # a stream that is its own key is the unkeyed model; the RmsModel class agrees with the functions
-    model = TR.RmsModel(2, 2, a, b, H)
+    # a stream that is its own key is the unkeyed model; the KeyModel class agrees with the functions
+    model = TK.KeyModel(2, 2, a, b, H, detector=RMS)
     model.set(-1, T)
     model.set_key(1, 0)
     k = TG.signal(91 + a, 3 * t, 2)
     ys = model.run([x, k])
-    assert np.array_equal(ys[0], y) and np.array_equal(ys[1], TR.model_rms_keyed(k, zero, x, zero, T, a, b, H)[0])
+    assert np.array_equal(ys[0], y) and np.array_equal(ys[1], TK.model_dyn_keyed(k, zero, x, zero, T, a, b, H, RMS)[0])
 
 
 @pytest.mark.parametrize("a,b,H", TG.SETS)
@@ -208,161 +209,8 @@ def test_the_root_separates_a_single_precision_sqrt():
 
 
 # ---------------------------------------------------------------------------
-# The RMS decomposition (csrc/k_dyn.h, DET = DYN_DETECT_RMS) step by step in numpy, one workgroup per tile:
-# tests/test_dyn_key_host.py's emulation with step 2's first line replaced.
-
-BLOCK, R, UNWRITTEN = TD.BLOCK, TD.R, TD.UNWRITTEN
-SPLIT = 15                                        # DYN_SQ_SPLIT
-
-
-def _dyn_isqrt(v):
-    """csrc/dyn_plan.h: dyn_isqrt, operation by operation, in 32-bit ranges"""
-    assert v.min() >= 0 and v.max() < 2 ** 32
-    r = np.sqrt(v.astype(np.float32)).astype(np.int64)           # (float)v rounds to 24 bits; the root is single precision
-    r = np.minimum(r, 65535)
-    assert (r * r < 2 ** 32).all()
-    r = np.where(r * r > v, r - 1, r)
-    assert (r >= 0).all() and (v - r * r >= 0).all()             # nothing wraps
-    return np.where(v - r * r > 2 * r, r + 1, r)
-
-
-def _emulate_rms_run(x, slot, xk, slotk, T, a, b, H, ch, tile, halo):
-    """one stream of one run: x int16 [F][C] and slot int64 [halo * C] the stream's own, xk and slotk the key's (the
-    stream's own where it has no key) -> out int64 [F * C + 8] (UNWRITTEN where nothing was stored), the slot the run
-    writes, min s or None"""
-    A, B, D, W, hist = TG.geometry(a, b, H)
-    F = x.shape[0]
-    assert xk.shape[0] == F
-    ns, hsamp = F * ch, halo * ch
-    hv, nfull, ntail = hsamp // 8, ns // 8, ns % 8
-    assert hsamp % 8 == 0 and tile >= halo >= hist
-    cv = TD._pack(T)
-    pad = np.zeros(16 + 8 * (tile // 8 + 1) * ch, dtype=np.int64)
-    seq = np.concatenate([slot, x.astype(np.int64).reshape(-1), pad])         # the stream as a tile sees it
-    seqk = np.concatenate([slotk, xk.astype(np.int64).reshape(-1), pad])      # ... and the detector's source
-
-    def vec(q, vv):                                               # [n] vector indices -> [n][8] samples
-        vv = np.asarray(vv)
-        assert (vv >= -hv).all()
-        return q[(hsamp + vv * 8)[:, None] + np.arange(8)]
-
-    def sample(q, i):
-        i = np.asarray(i)
-        assert (i >= -hsamp).all() and (i < ns).all()
-        return q[hsamp + i]
-
-    out = np.full(ns + 8, UNWRITTEN, dtype=np.int64)
-    new_slot = sample(seq, ns - hsamp + np.arange(hsamp))         # 4. from the stream's OWN slots
-    if F == 0:
-        assert np.array_equal(new_slot, slot)
-        return out, new_slot, None
-    gmin = UNITY
-    N = halo + tile
-    tid, i = np.meshgrid(np.arange(BLOCK), np.arange(R), indexing="ij")
-    own = (tid + BLOCK * i).reshape(-1)                           # the thread-to-element map: j = tid + 256 i
-    assert np.array_equal(np.sort(own[own < N]), np.arange(N))    # every element has exactly one thread
-    for f0 in range(0, F, tile):
-        nt = min(tile, F - f0)
-        # ---- 1. e of frames f0 - halo .. f0 + tile - 1, across the seam between the history slot and the run
-        if ch <= 2:
-            fpv = 8 // ch
-            NV = N // fpv
-            assert NV <= BLOCK * ((R * ch + 7) // 8)
-            vbase = f0 * ch // 8 - hv
-            assert f0 == 0 or vbase >= 0                          # only the run's first tile reads the history slot
-            v = np.abs(vec(seqk, vbase + np.arange(NV)))
-            e = (v if ch == 1 else np.maximum(v[:, 0::2], v[:, 1::2])).reshape(-1)
-        else:
-            p = f0 - halo + np.arange(N)
-            e = np.zeros(N, dtype=np.int64)
-            inside = p < F
-            e[inside] = np.abs(sample(seqk, p[inside, None] * ch + np.arange(ch))).max(axis=1)
-        assert e.size == N and e.max() <= 32768
-        # ---- 2. the passes
-        j = np.arange(N)
-        passes = 0
-
-        def one_pass(L, dist, is_max, shift):
-            o = L[np.maximum(j, dist) - dist]                      # (unguarded: an element without a partner takes element 0)
-            v = (np.maximum(L, o) if is_max else L + o)
-            assert v.max() < 2 ** 32
-            return v >> shift
-
-        sq = e * e
-        assert sq.max() < 2 ** 32                                 # the square itself fits a dword
-        lo, hi = sq & ((1 << SPLIT) - 1), sq >> SPLIT
-        halves = []
-        for half in (lo, hi):                                     # the low halves first, e waiting in registers
-            d = 1
-            while d < A:
-                half = one_pass(half, d, False, 0)
-                d *= 2
-                passes += 1
-            assert half.max() <= 2 ** 25
-            halves.append(half)
-        M = (halves[1] << (SPLIT - a)) + (halves[0] >> a)         # dyn_mean_square
-        assert M.max() <= 2 ** 30                                 # also where an element had no partner
-        L = _dyn_isqrt(M)
-        P = 1
-        while 2 * P <= W:
-            L = one_pass(L, P, True, 0)
-            P *= 2
-            passes += 1
-        if W > P:
-            L = one_pass(L, W - P, True, 0)
-            passes += 1
-        L = TD._lookup(cv, np.minimum(L, UNITY))
-        d = 1
-        while d < B:
-            L = one_pass(L, d, False, b if 2 * d == B else 0)
-            d *= 2
-            passes += 1
-        assert passes == 2 * a + int(np.log2(W)) + (1 if W & (W - 1) else 0) + b
-        Ls = L[halo:]
-        gmin = min(gmin, int(Ls[:nt].min()))
-        # ---- 3. the tile's output vectors, the delayed samples from the stream's OWN slots
-        vb, nv = f0 * ch // 8, (nt * ch + 7) // 8
-        v8 = vb + np.arange(nv)
-        if ch <= 2:
-            back = (D + 1) * ch // 8
-            assert (D + 1) * ch % 8 == 0 and back <= hv
-            x0, x1 = vec(seq, v8 - back), vec(seq, v8 - back + 1)
-            xs = np.concatenate([x0[:, ch:], x1[:, :ch]], axis=1)
-            sf = Ls[(np.arange(nv) * (8 // ch))[:, None] + np.arange(8) // ch]
-            prod = xs * sf
-        else:
-            q = v8[:, None] * 8 + np.arange(8)
-            ok = q < ns
-            qq = np.where(ok, q, 0)
-            prod = np.where(ok, sample(seq, qq - D * ch) * Ls[np.where(ok, qq // ch - f0, 0)], 0)
-        assert np.abs(prod + (1 << 14)).max() < 2 ** 31
-        y = (prod + (1 << 14)) >> 15
-        for w in range(nv):
-            if v8[w] < nfull:
-                out[v8[w] * 8:v8[w] * 8 + 8] = y[w]
-            elif v8[w] == nfull:
-                out[v8[w] * 8:v8[w] * 8 + ntail] = y[w, :ntail]
-    return out, new_slot, gmin
-
-
-def _hold_emulation_to(case_keys, xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo):
-    S = len(counts)
-    slots = [np.zeros(halo * channels, dtype=np.int64) for _ in range(S)]
-    got_min = [UNITY] * S
-    for cut, wants in ((counts, ragged), ([counts[0]] * S, full)):
-        new = []
-        for s in range(S):
-            k = case_keys[s]
-            assert cut[k] == cut[s]
-            out, slot, m = _emulate_rms_run(xs[s][:cut[s]], slots[s], xs[k][:cut[k]], slots[k], T, a, b, H, channels, t, halo)
-            w = wants[s].astype(np.int64).reshape(-1)
-            assert np.array_equal(out[:w.size], w), (channels, s)
-            assert (out[w.size:] == UNWRITTEN).all(), (channels, s)               # nothing past the stream's count
-            got_min[s] = min(got_min[s], UNITY if m is None else m)
-            new.append(slot)
-        slots = new                                               # the host flips the parity: every tile read the old slots
-    assert got_min == gmin
-
+# The RMS decomposition (csrc/k_dyn.h, DET = DYN_DETECT_RMS): tests/test_dyn_host.py's emulation with det = RMS, plain
+# (every stream its own key) and keyed.
 
 @pytest.mark.parametrize("channels", [1, 2, 3, 16])
 @pytest.mark.parametrize("a,b,H", TG.SETS)
@@ -373,7 +221,7 @@ def test_emulated_rms_decomposition_equals_the_model(cm, a, b, H, channels):
     assert p.passes == 2 * a + int(np.log2(W)) + (1 if W & (W - 1) else 0) + b and p.lds_bytes == (t + halo) * 4
     xs, counts, T, ragged, full, unity, change, smallest, gmin, differ = TR.dense_rms_case(a, b, H, channels, t)
     TR.assert_dense_rms(a, b, H, unity, change, smallest, differ)
-    _hold_emulation_to(list(range(len(counts))), xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo)
+    TD._hold_emulation_to(list(range(len(counts))), xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo, RMS)
 
 
 @pytest.mark.parametrize("channels", [1, 3])
@@ -383,7 +231,7 @@ def test_emulated_keyed_rms_decomposition_equals_the_model(cm, a, b, H, channels
     t, halo = p.tile_frames, p.halo
     xs, counts, keys, T, ragged, full, gmin, own, mean, change, smallest = TR.dense_rms_key_case(a, b, H, channels, t)
     TR.assert_dense_rms_key(own, mean, change, smallest)
-    _hold_emulation_to(keys, xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo)
+    TD._hold_emulation_to(keys, xs, counts, ragged, full, gmin, T, a, b, H, channels, t, halo, RMS)
 
 
 def test_emulated_root_on_the_edges():
@@ -391,11 +239,11 @@ def test_emulated_root_on_the_edges():
     r = np.arange(0, 32769, dtype=np.int64)
     for v in (r * r, np.maximum(r * r - 1, 0), r * r + 2 * r, r * r + 1):
         v = np.minimum(v, 2 ** 32 - 1)
-        assert np.array_equal(_dyn_isqrt(v), TR.isqrt(v))
+        assert np.array_equal(TD._dyn_isqrt(v), TR.isqrt(v))
     r = np.arange(32769, 65536, dtype=np.int64)
     for v in (r * r, r * r - 1, r * r + 2 * r):
-        assert np.array_equal(_dyn_isqrt(v), TR.isqrt(v))
-    assert _dyn_isqrt(np.array([2 ** 32 - 1]))[0] == 65535
+        assert np.array_equal(TD._dyn_isqrt(v), TR.isqrt(v))
+    assert TD._dyn_isqrt(np.array([2 ** 32 - 1]))[0] == 65535
 
 
 @pytest.mark.parametrize("a,b,H", TG.SETS)

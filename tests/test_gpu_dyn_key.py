@@ -1,4 +1,4 @@
-"""GPU: side-chain keys of the dynamics stage (cmhip_dyn_set_key, csrc/k_dynkey.hip) against the keyed model -- the model
+"""GPU: side-chain keys of the dynamics stage (cmhip_dyn_set_key, csrc/k_dyn.hip) against the keyed model -- the model
 of tests/test_gpu_dyn.py with e taken from (the key's history, the key's input) and everything else from the stream's
 own -- bit for bit, the sentinel past every count and the meter included: dense cases over five geometries and both
 kernel forms with a key map of every kind, cuts queued without a synchronisation, keys in order with the runs, the
@@ -29,11 +29,12 @@ def _load(name):
 TG = _load("test_gpu_dyn")                        # the unkeyed model, the signal, the dense curve, the rig
 geometry, signal, design, DENSE_CURVE, dense_seed = TG.geometry, TG.signal, TG.design, TG.DENSE_CURVE, TG.dense_seed
 SETS, SENTINEL, UNITY = TG.SETS, TG.SENTINEL, TG.UNITY
+MEAN, RMS = 0, 1                                  # CMHIP_DYN_DETECT_*
 DIFFER_SHARE = 0.50                               # of a follower's frames whose output differs from the own detector's
 
 
 # ---------------------------------------------------------------------------
-# the keyed model: include/coolmic_hip.h, "dynamics", "Side-chain keys"
+# the keyed model: include/coolmic_hip.h, "dynamics", "Side-chain keys" and "RMS detector"
 
 def _slide_max(v, n):
     """sliding maxima of n: entry i is max(v[i .. i + n - 1]) (two overlapping power-of-two windows; exact)"""
@@ -44,9 +45,21 @@ def _slide_max(v, n):
     return np.maximum(m[:m.size - (n - p)], m[n - p:]) if n > p else m
 
 
-def model_dyn_keyed(x, hist, xk, histk, T, a, b, H):
+def isqrt(v):
+    """int64 [n] in 0..2^52 -> the largest r with r * r <= v (the double root is within 1; integers decide)"""
+    v = np.asarray(v, dtype=np.int64)
+    r = np.sqrt(v.astype(np.float64)).astype(np.int64)
+    r = np.where(r * r > v, r - 1, r)
+    r = np.where((r + 1) * (r + 1) <= v, r + 1, r)
+    assert (r * r <= v).all() and ((r + 1) * (r + 1) > v).all()
+    return r
+
+
+def model_dyn_keyed(x, hist, xk, histk, T, a, b, H, detector=MEAN, root=isqrt):
     """model_dyn with the detector on another stream: x, hist the stream's own input and history, xk, histk the key's
-    (int16 [F][C], [HIST][C], the same F) -> y int16 [F][C], s int64 [F]"""
+    (int16 [F][C], [HIST][C], the same F; the stream's own where it has no key) -> y int16 [F][C], s int64 [F].
+    detector: MEAN or RMS ("RMS detector"); root: what takes the root of the mean square, so that a test can show what
+    a wrong one would give"""
     A, B, D, W, HIST = geometry(a, b, H)
     F = x.shape[0]
     assert xk.shape[0] == F and histk.shape == hist.shape
@@ -54,11 +67,13 @@ def model_dyn_keyed(x, hist, xk, histk, T, a, b, H):
         return x.copy(), np.zeros(0, np.int64)
     z = np.concatenate([hist, x]).astype(np.int64)
     e = np.abs(np.concatenate([histk, xk]).astype(np.int64)).max(axis=1)     # the only line that knows the key
-    L = TG._sums(e, A) >> a
+    # ... and the only one that knows the detector
+    L = root(TG._sums(e * e, A) >> a) if detector == RMS else TG._sums(e, A) >> a
+    assert detector == RMS or L.max() <= UNITY
     l = _slide_max(L, W)
-    g = TG.curve_at(T, l)
+    g = TG.curve_at(T, np.minimum(l, UNITY))                      # (a root that is one too large may pass 32768)
     s = TG._sums(g, B) >> b
-    assert s.size == F and L.max() <= UNITY and s.max() <= UNITY and s.min() >= 0
+    assert s.size == F and s.max() <= UNITY and s.min() >= 0
     xd = z[HIST - D: HIST - D + F]
     y = (xd * s[:, None] + (1 << 14)) >> 15
     assert (np.abs(y) <= np.abs(xd)).all()
@@ -66,11 +81,12 @@ def model_dyn_keyed(x, hist, xk, histk, T, a, b, H):
 
 
 class KeyModel(TG.Model):
-    """TG.Model with a key per stream; a run evaluates every stream on the histories as they were before it"""
+    """TG.Model with a detector and a key per stream; a run evaluates every stream on the histories as they were before it"""
 
-    def __init__(self, streams, channels, a, b, H):
+    def __init__(self, streams, channels, a, b, H, detector=MEAN):
         super().__init__(streams, channels, a, b, H)
         self.key = list(range(streams))
+        self.detector = detector
 
     def set_key(self, stream, key):
         for s in (range(self.S) if stream < 0 else [stream]):
@@ -79,7 +95,7 @@ class KeyModel(TG.Model):
     def run(self, xs):
         xs = [np.asarray(x, dtype=np.int16).reshape(-1, self.C) for x in xs]
         outs = [model_dyn_keyed(x, self.hist[s], xs[self.key[s]], self.hist[self.key[s]], self.curve[s], self.a, self.b,
-                                self.H) for s, x in enumerate(xs)]
+                                self.H, self.detector) for s, x in enumerate(xs)]
         for s, (x, (y, sg)) in enumerate(zip(xs, outs)):
             self.hist[s] = TG.next_hist(self.hist[s], x)
             if sg.size:

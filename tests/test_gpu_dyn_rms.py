@@ -1,4 +1,4 @@
-"""GPU: the RMS detector of the dynamics stage (cmhip_dyn_new_detector, csrc/k_dynrms.hip) against the RMS model -- the
+"""GPU: the RMS detector of the dynamics stage (cmhip_dyn_new_detector, csrc/k_dyn.h) against the RMS model -- the
 keyed model of tests/test_gpu_dyn_key.py with the one line L = isqrt(sum(e^2 over A) >> a) in int64 -- bit for bit, the
 sentinel past every count and the meter included: dense cases over five geometries and both kernel forms, plain and
 with a key map of every kind, the edges of the root on a curve that turns every level's parity into a gain, cuts queued
@@ -18,7 +18,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "libcoolmic-dsp_amd", "lib")
-MEAN, RMS = 0, 1                                  # CMHIP_DYN_DETECT_*
 
 
 def _load(name):
@@ -32,6 +31,7 @@ TK = _load("test_gpu_dyn_key")                    # the keyed model, its rig and
 TG = TK.TG                                        # the unkeyed model, the signal, the dense curve, the rig
 geometry, signal, design, DENSE_CURVE, dense_seed = TG.geometry, TG.signal, TG.design, TG.DENSE_CURVE, TG.dense_seed
 SETS, SENTINEL, UNITY = TG.SETS, TG.SENTINEL, TG.UNITY
+MEAN, RMS, isqrt = TK.MEAN, TK.RMS, TK.isqrt      # CMHIP_DYN_DETECT_*; the model's root
 CHANNELS = [1, 2, 3, 6, 16]
 DIFFER_MEAN = 0.25                                # of the long streams' frames whose output differs from the mean detector's
 DIFFER_OWN_KEYED = 0.50                           # of a follower's frames whose output differs from its own RMS detector's
@@ -39,56 +39,10 @@ DIFFER_MEAN_KEYED = 0.20                          # ... and from the keyed mean 
 
 
 # ---------------------------------------------------------------------------
-# the model: include/coolmic_hip.h, "dynamics", "RMS detector"
-
-def isqrt(v):
-    """int64 [n] in 0..2^52 -> the largest r with r * r <= v (the double root is within 1; integers decide)"""
-    v = np.asarray(v, dtype=np.int64)
-    r = np.sqrt(v.astype(np.float64)).astype(np.int64)
-    r = np.where(r * r > v, r - 1, r)
-    r = np.where((r + 1) * (r + 1) <= v, r + 1, r)
-    assert (r * r <= v).all() and ((r + 1) * (r + 1) > v).all()
-    return r
-
-
-def model_rms_keyed(x, hist, xk, histk, T, a, b, H, root=isqrt):
-    """TK.model_dyn_keyed with the RMS detector (xk, histk the stream's own where it has no key); root: what takes the
-    root of the mean square, so that a test can show what a wrong one would give"""
-    A, B, D, W, HIST = geometry(a, b, H)
-    F = x.shape[0]
-    assert xk.shape[0] == F and histk.shape == hist.shape
-    if F == 0:
-        return x.copy(), np.zeros(0, np.int64)
-    z = np.concatenate([hist, x]).astype(np.int64)
-    e = np.abs(np.concatenate([histk, xk]).astype(np.int64)).max(axis=1)
-    L = root((TG._sums(e * e, A)) >> a)                           # the only line that knows the detector
-    l = TK._slide_max(L, W)
-    g = TG.curve_at(T, np.minimum(l, UNITY))                      # (a root that is one too large may pass 32768)
-    s = TG._sums(g, B) >> b
-    assert s.size == F and s.max() <= UNITY and s.min() >= 0
-    xd = z[HIST - D: HIST - D + F]
-    y = (xd * s[:, None] + (1 << 14)) >> 15
-    assert (np.abs(y) <= np.abs(xd)).all()
-    return y.astype(np.int16), s
-
+# the model: TK.model_dyn_keyed with detector = RMS (include/coolmic_hip.h, "dynamics", "RMS detector")
 
 def model_rms(x, hist, T, a, b, H, root=isqrt):
-    return model_rms_keyed(x, hist, x, hist, T, a, b, H, root)
-
-
-class RmsModel(TK.KeyModel):
-    """TK.KeyModel with the RMS detector"""
-
-    def run(self, xs):
-        xs = [np.asarray(x, dtype=np.int16).reshape(-1, self.C) for x in xs]
-        outs = [model_rms_keyed(x, self.hist[s], xs[self.key[s]], self.hist[self.key[s]], self.curve[s], self.a, self.b,
-                                self.H) for s, x in enumerate(xs)]
-        for s, (x, (y, sg)) in enumerate(zip(xs, outs)):
-            self.hist[s] = TG.next_hist(self.hist[s], x)
-            if sg.size:
-                self.gmin[s] = min(self.gmin[s], int(sg.min()))
-                self.s[s].append(sg)
-        return [y for y, _ in outs]
+    return TK.model_dyn_keyed(x, hist, x, hist, T, a, b, H, RMS, root)
 
 
 class RmsRig(TK.KeyRig):
@@ -97,7 +51,7 @@ class RmsRig(TK.KeyRig):
     def __init__(self, cm, streams, channels, a, b, H, max_frames, curve=None, detector=RMS):
         self.cm, self.S, self.C = cm, streams, channels
         self.m = cm.Dynamics(streams, channels, a, b, H, max_frames, detector=detector)
-        self.model = (RmsModel if detector == RMS else TK.KeyModel)(streams, channels, a, b, H)
+        self.model = TK.KeyModel(streams, channels, a, b, H, detector=detector)
         assert self.m.delay() == self.model.D and self.m.detector() == detector
         self.stride = (max_frames * channels + 7) // 8 * 8 + 8
         self.src = cm.MappedPcm(types.SimpleNamespace(streams=streams, stride=self.stride))
@@ -115,7 +69,7 @@ def dense_rms_case(a, b, H, channels, t):
     run that follows it on one stage, the meter, and the figures of the dense conditions -- computed once, never changed"""
     xs, counts, T = TG.dense_case(a, b, H, channels, t)[:3]
     hist = geometry(a, b, H)[4]
-    model = RmsModel(len(counts), channels, a, b, H)
+    model = TK.KeyModel(len(counts), channels, a, b, H, detector=RMS)
     model.set(-1, T)
     ragged = model.run([x[:n] for x, n in zip(xs, counts)])
     full = model.run(xs)
@@ -168,7 +122,7 @@ def dense_rms_key_case(a, b, H, channels, t):
     (the two long groups, from silence) that differ from their own RMS detector's and from the keyed mean detector's"""
     xs, counts, keys, T, mean_ragged = TK.dense_key_case(a, b, H, channels, t)[:5]
     hist = geometry(a, b, H)[4]
-    model = RmsModel(len(counts), channels, a, b, H)
+    model = TK.KeyModel(len(counts), channels, a, b, H, detector=RMS)
     model.set(-1, T)
     for s, k in enumerate(keys):
         model.set_key(s, k)
@@ -328,7 +282,7 @@ def test_cuts_keyed(gpu, channels, a, b, H):
     S = len(keys)
     x = [signal(9000 + 10 * channels + s, 3 * t, channels) for s in range(S)]
     zero = np.zeros((hist, channels), dtype=np.int16)
-    want = [model_rms_keyed(x[s], zero, x[k], zero, T, a, b, H) for s, k in enumerate(keys)]
+    want = [TK.model_dyn_keyed(x[s], zero, x[k], zero, T, a, b, H, RMS) for s, k in enumerate(keys)]
     for s, k in enumerate(keys):
         assert k == s or (want[s][0] != model_rms(x[s], zero, T, a, b, H)[0]).any(axis=1).mean() >= DIFFER_OWN_KEYED, s
         mean = TK.model_dyn_keyed(x[s], zero, x[k], zero, T, a, b, H)[0]
@@ -512,7 +466,7 @@ def test_chain_with_an_rms_stage_into_a_batch(gpu, oracle):
         if sum_of[s] % 2:                                        # the presenters pause: the bed comes back up
             xs[s][1000:2500] = 0
     table = (sum_of, list(range(S)), np.full((S, 1, 1), 8192, dtype=np.int16))
-    dyn_m, lim_m = RmsModel(B1, 1, a, b, H), TL.Model(B1, 1, la, lh)
+    dyn_m, lim_m = TK.KeyModel(B1, 1, a, b, H, detector=RMS), TL.Model(B1, 1, la, lh)
     for p in range(P):
         dyn_m.set(2 * p, duck)
         dyn_m.set(2 * p + 1, comp)

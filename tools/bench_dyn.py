@@ -11,20 +11,19 @@ cmhip_batch_ceiling's plain copy (read + write), the yardstick, and the peak lim
 nearest pass counts (a = 8, H = 1024: 19 passes; a = 9, H = 1536: 20 passes).
 
     python tools/bench_dyn.py [--steps N] [--shapes a,b]      one JSON line per shape
-    python tools/bench_dyn.py --count-asm                     per kernel the instructions of build/k_dyn.s and
-                                                              build/k_dynkey.s (`make asm`; no GPU needed), and the
-                                                              passes per geometry
+    python tools/bench_dyn.py --count-asm                     per kernel the instructions of build/k_dyn.s
+                                                              (`make asm`; no GPU needed), and the passes per geometry
     python tools/bench_dyn.py --key [--steps N] [--shapes a,b]
-        side-chain keys (cmhip_dyn_set_key, csrc/k_dynkey.hip): per shape, on one object, the same slots and in one
-        process, the plain run (no key set: k_dyn.hip's kernels), the plain run again (its repeat shows the spread of
+        side-chain keys (cmhip_dyn_set_key; k_dynk<CT, DET>): per shape, on one object, the same slots and in one
+        process, the plain run (no key set: k_dyn<CT, DET>), the plain run again (its repeat shows the spread of
         the unkeyed kernels inside one session), a run with every odd stream keyed on its even neighbour, a run with
         every stream keyed (on its neighbour, 2i <-> 2i + 1), and the plain run a third time after the keys were
         cleared; one JSON line per shape with the medians and their min-max
     python tools/bench_dyn.py --rms [--steps N] [--shapes a,b]
-        the RMS detector (cmhip_dyn_new_detector, csrc/k_dynrms.hip) beside the mean detector: per shape two objects of
+        the RMS detector (cmhip_dyn_new_detector; DET = DYN_DETECT_RMS) beside the mean detector: per shape two objects of
         one geometry on the same arrays in one process, in the order mean, RMS, mean again, then both with every stream
         keyed (2i <-> 2i + 1); one JSON line per shape with the medians, their min-max, the pass counts of both plans
-        and RMS over mean beside (P + a) / P; then the instruction counts of build/k_dynrms.s
+        and RMS over mean beside (P + a) / P; then the instruction counts of the RMS kernels
 """
 import argparse
 import ctypes as C
@@ -60,18 +59,20 @@ def passes(a, b, hold):
 
 
 def count_asm(stem="k_dyn"):
-    """per kernel of build/k_dyn.s (or, stem "k_dynk", build/k_dynkey.s): all its instructions by class, and, cut at the
-    barriers, the two phases of a doubling pass over a thread's 30 elements and the curve lookup between the passes"""
-    files = {"k_dyn": "k_dyn.s", "k_dynk": "k_dynkey.s", "k_dynrms": "k_dynrms.s", "k_dynrmsk": "k_dynrms.s"}
-    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", files[stem])
+    """per kernel of build/k_dyn.s that `stem` names -- "k_dyn": k_dyn<CT, MEAN>, "k_dynk": k_dynk<CT, MEAN>, "k_dynrms":
+    k_dyn<CT, RMS>, "k_dynrmsk": k_dynk<CT, RMS>; printed as <stem>_fast<CT> and, for CT = 0, <stem>_any, the names the
+    earlier records carry -- all its instructions by class, and, cut at the barriers, the two phases of a doubling
+    pass over a thread's 30 elements and the curve lookup between the passes"""
+    template, det = {"k_dyn": ("k_dyn", 0), "k_dynk": ("k_dynk", 0), "k_dynrms": ("k_dyn", 1),
+                     "k_dynrmsk": ("k_dynk", 1)}[stem]
+    path = os.path.join(ROOT, "libcoolmic-dsp_amd", "build", "k_dyn.s")
     if not os.path.exists(path):
         return None
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"^(_ZN5cmhip\w*%s_(?:fast|any)\w*):.*?^\s*s_endpgm" % stem, text, flags=re.S | re.M):
-        sym, body = m.group(1), m.group(0)
-        f = re.search(r"%s_fastILi(\d)E" % stem, sym)
-        name = "%s_fast<%s>" % (stem, f.group(1)) if f else stem + "_any"
+    for m in re.finditer(r"^_ZN5cmhip\d+%sILi(\d)ELj%dEE\w*:.*?^\s*s_endpgm" % (template, det), text, flags=re.S | re.M):
+        ct, body = m.group(1), m.group(0)
+        name = "%s_fast<%s>" % (stem, ct) if ct != "0" else stem + "_any"
         # the kernel cut at its barriers.  Inside a loop of doubling passes the stretch from one pass's middle barrier
         # to the next one's holds the first one's 30 writes and the next one's 30 partner reads: one pass's worth of
         # work, the leanest stretch with both.  The curve lookup (30 table reads, 30 writes) is the heaviest such stretch.
