@@ -142,6 +142,25 @@ int                 coolmic_group_loudnesses(coolmic_group_t *self, coolmic_loud
 int                 coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights);
 int                 coolmic_group_loudness_reset(coolmic_group_t *self, long slot);
 
+/* Phase correlation and balance of every stream's channel pairs, opt-in: cmhip_batch_set_correlation() of
+ * <coolmic_hip.h> on the group's engine, with its return values and its specification (a mono group cannot be
+ * metered).  While it is on every block runs the correlation kernel ahead of the block kernel (beside the true-peak
+ * and loudness kernels when those are on too); the group's blocks lie in host memory, so the input set is read once
+ * more over PCIe -- that read is the cost of the group form.  It measures the transformed stream, not the
+ * equaliser's result: the two exclude each other with COOLMIC_ERROR_INVAL both ways round. */
+int                 coolmic_group_set_correlation(coolmic_group_t *self, int on);
+/* cmhip_batch_corr_set_pairs for the group's engine: the pairs are the same for every slot, and change only while
+ * every window is empty (COOLMIC_ERROR_BUSY otherwise). */
+int                 coolmic_group_correlation_set_pairs(coolmic_group_t *self, unsigned int n, const unsigned char pairs[][2]);
+/* One slot's correlation window since its last result, and all of them at once (results[] and rc[], which may be
+ * NULL, have coolmic_group_streams() entries): the slot handling and the per-slot contract of
+ * coolmic_group_true_peak(s) -- COOLMIC_ERROR_INVAL with the result left alone for a window without a frame, the
+ * window closed after everything pumped so far, the block in flight included.  coolmic_group_correlation_reset
+ * clears a slot's window, or with -1 every window of the engine. */
+int                 coolmic_group_correlation(coolmic_group_t *self, unsigned int slot, coolmic_correlation_result_t *result);
+int                 coolmic_group_correlations(coolmic_group_t *self, coolmic_correlation_result_t *results, int *rc);
+int                 coolmic_group_correlation_reset(coolmic_group_t *self, long slot);
+
 unsigned int        coolmic_group_streams(coolmic_group_t *self);
 
 #ifdef __cplusplus

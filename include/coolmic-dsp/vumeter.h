@@ -72,6 +72,25 @@ typedef struct {
     double channel_dbtp[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
 } coolmic_truepeak_result_t;
 
+/* Result of one phase-correlation window, as the batch engine (cmhip_batch_corr_result, <coolmic_hip.h>) and the
+ * group (coolmic_group_correlation, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  For
+ * each of `pairs` channel pairs (a[i], b[i]) of the transformed stream: the exact integer sums energy_a = sum x_a^2,
+ * energy_b = sum x_b^2 and cross = sum x_a * x_b over the window's frames, the correlation cross / sqrt(energy_a *
+ * energy_b) in [-1, 1] (0.0 when a leg is silent) and the balance 10 * log10(energy_a / energy_b) in dB (0.0 when
+ * both legs are silent, -inf / +inf when one is); the arithmetic is specified to the bit in <coolmic_hip.h>.
+ * Entries at and beyond `pairs` are zero.  360 bytes on LP64. */
+typedef struct {
+    uint_least32_t rate;
+    unsigned int channels;
+    size_t frames;
+    unsigned int pairs;
+    unsigned char a[8], b[8];
+    uint64_t energy_a[8], energy_b[8];
+    int64_t cross[8];
+    double correlation[8];
+    double balance_db[8];
+} coolmic_correlation_result_t;
+
 /* Programme loudness of one stream (ITU-R BS.1770 / EBU R128: K-weighting, 100 ms sub-blocks, 400 ms momentary,
  * 3 s short-term, gated integrated loudness), as the batch engine (cmhip_batch_loud_result, <coolmic_hip.h>) and the
  * group (coolmic_group_loudness, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  The

@@ -246,6 +246,55 @@ double cmhip_tp_dbtp(uint32_t peak);
 /* the filter, no device needed: H[0..3] in order, 12 taps each */
 void   cmhip_tp_coefficients(int16_t h[48]);
 
+/* ---- phase correlation / balance, opt-in ------------------------------------- */
+/* The needle between -1 and +1 that tells whether a stereo programme survives a mono sum, and the level balance of
+ * the two legs, for up to CMHIP_CORR_MAX_PAIRS channel pairs per stream.  Specified, and held, to the bit:
+ *
+ * Signal.  The TRANSFORMED stream (after channel map, gain and saturation: the samples the VU window accounts and
+ *   CMHIP_OUT_PCM writes, exactly as for true peak).  The pass reads the run's input slots and transforms them itself,
+ *   so an in-place batch needs nothing special.
+ * Pairs.  A batch has 1 to CMHIP_CORR_MAX_PAIRS pairs (a, b) of transformed channels, a != b, both below `channels`,
+ *   the same for all streams; the default is the single pair (0, 1).  cmhip_batch_corr_set_pairs replaces them, with
+ *   correlation on or off, but only while every window is empty (COOLMIC_ERROR_BUSY otherwise: result or reset first).
+ *   COOLMIC_ERROR_INVAL for n == 0, n > 8, a == b or a channel out of range; nothing is changed then.  A mono batch
+ *   cannot be metered: cmhip_batch_set_correlation(b, 1) returns COOLMIC_ERROR_INVAL for it.
+ * Window sums per stream and pair, over the frames accounted since the window opened, in exact integers:
+ *       energy_a = sum x_a^2  (uint64)      energy_b = sum x_b^2  (uint64)      cross = sum x_a * x_b  (int64)
+ *   One frame contributes at most 2^30 to each (-32768 squared is exactly 2^30; the cross term lies in
+ *   [-2^30 + 2^15, 2^30]), so a window is exact up to 2^33 frames -- 49 hours at 48 kHz.  The bound is not enforced:
+ *   close windows more often than that.  Integer sums do not depend on the order they are merged in, nor on how the
+ *   stream was cut into runs.  A stream that gets 0 frames in a run keeps its window.
+ * Host finish, in double, in this order, no device needed:
+ *   cmhip_corr_value(ea, eb, x): 0.0 when ea == 0 || eb == 0; otherwise (double)x / sqrt((double)ea * (double)eb),
+ *     clamped to [-1.0, 1.0].  Conversion, product, square root and quotient are each correctly rounded in IEEE 754,
+ *     so the value is one fixed double.
+ *   cmhip_corr_balance_db(ea, eb): 0.0 when both are 0; otherwise 10.0 * log10((double)ea / (double)eb), which is
+ *     -inf for ea == 0 and +inf for eb == 0.  Positive: a is the louder leg.
+ *
+ * cmhip_batch_set_correlation(b, 1), between runs (it waits for the batch's stream), allocates the [S][8][3] 64-bit
+ * sums on first use and opens empty windows; from then on every cmhip_batch_run / _run_slots launches the correlation
+ * kernel on the batch's stream AHEAD of the block kernel, beside the true-peak and loudness passes when those are on
+ * too.  (b, 0) stops that and discards the windows; the pairs are kept.  Correlation of the equaliser's result is not
+ * measured: COOLMIC_ERROR_INVAL while the batch's equaliser has sections, and cmhip_batch_set_eq with nsec > 0
+ * returns COOLMIC_ERROR_INVAL while correlation is on (nsec == 0 stays allowed).
+ * The result calls follow their true-peak counterparts: COOLMIC_ERROR_INVAL with `out` left alone for a window
+ * without a frame (per stream in rc[] for _results, rc may be NULL) and for a batch without correlation; the window
+ * is closed on success, by these calls only -- the windows are independent of the VU, true-peak and loudness windows.
+ * One device round trip serves all streams, the sums are cleared on the stream behind it.  Entries of a result at
+ * and beyond `pairs` are zero.  cmhip_batch_corr_reset clears windows (stream -1: all).
+ * cmhip_batch_timing keeps bracketing the block kernel only.  The pass is queued, and its frames are counted, before
+ * the block kernel is launched: after a cmhip_batch_run that returns an error, correlation (like true peak) may or
+ * may not hold that run's frames -- reset the stream's meters before trying the run again. */
+#define CMHIP_CORR_MAX_PAIRS 8
+int    cmhip_batch_set_correlation(cmhip_batch_t *b, int on);
+int    cmhip_batch_get_correlation(const cmhip_batch_t *b);   /* 0 / 1, negative error */
+int    cmhip_batch_corr_set_pairs(cmhip_batch_t *b, unsigned int n, const unsigned char pairs[][2]);
+int    cmhip_batch_corr_result(cmhip_batch_t *b, unsigned int stream, coolmic_correlation_result_t *out);
+int    cmhip_batch_corr_results(cmhip_batch_t *b, coolmic_correlation_result_t *out, int *rc);
+int    cmhip_batch_corr_reset(cmhip_batch_t *b, long stream);
+double cmhip_corr_value(uint64_t energy_a, uint64_t energy_b, int64_t cross);
+double cmhip_corr_balance_db(uint64_t energy_a, uint64_t energy_b);
+
 /* ---- programme loudness (ITU-R BS.1770 / EBU R128), opt-in -------------------- */
 /* Momentary, short-term and gated integrated loudness of the TRANSFORMED stream (after channel map, gain and
  * saturation: the samples the VU window accounts, as for true peak).  The arithmetic is specified to the bit:

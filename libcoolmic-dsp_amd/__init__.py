@@ -69,6 +69,26 @@ class TruePeakResult(C.Structure):
                 "channel_dbtp": [self.channel_dbtp[i] for i in range(ch)]}
 
 
+CORR_MAX_PAIRS = 8
+
+
+class CorrResult(C.Structure):
+    """coolmic_correlation_result_t (include/coolmic-dsp/vumeter.h): exact integer sums per channel pair and their
+    finish in double"""
+    _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t), ("pairs", C.c_uint),
+                ("a", C.c_ubyte * CORR_MAX_PAIRS), ("b", C.c_ubyte * CORR_MAX_PAIRS),
+                ("energy_a", C.c_uint64 * CORR_MAX_PAIRS), ("energy_b", C.c_uint64 * CORR_MAX_PAIRS),
+                ("cross", C.c_int64 * CORR_MAX_PAIRS), ("correlation", C.c_double * CORR_MAX_PAIRS),
+                ("balance_db", C.c_double * CORR_MAX_PAIRS)]
+
+    def as_dict(self):
+        n = self.pairs
+        d = {"rate": self.rate, "channels": self.channels, "frames": self.frames, "pairs": n}
+        for name in ("a", "b", "energy_a", "energy_b", "cross", "correlation", "balance_db"):
+            d[name] = [getattr(self, name)[i] for i in range(n)]
+        return d
+
+
 class LoudnessResult(C.Structure):
     """coolmic_loudness_result_t (include/coolmic-dsp/vumeter.h): LUFS doubles, -inf while there is nothing to report"""
     _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t), ("blocks", C.c_size_t),
@@ -206,6 +226,14 @@ SIGNATURES = {
     "cmhip_batch_tp_reset": (C.c_int, [_vp, C.c_long]),
     "cmhip_tp_dbtp": (C.c_double, [C.c_uint32]),
     "cmhip_tp_coefficients": (None, [_vp]),
+    "cmhip_batch_set_correlation": (C.c_int, [_vp, C.c_int]),
+    "cmhip_batch_get_correlation": (C.c_int, [_vp]),
+    "cmhip_batch_corr_set_pairs": (C.c_int, [_vp, C.c_uint, _vp]),
+    "cmhip_batch_corr_result": (C.c_int, [_vp, C.c_uint, _P(CorrResult)]),
+    "cmhip_batch_corr_results": (C.c_int, [_vp, _vp, _vp]),
+    "cmhip_batch_corr_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_corr_value": (C.c_double, [C.c_uint64, C.c_uint64, C.c_int64]),
+    "cmhip_corr_balance_db": (C.c_double, [C.c_uint64, C.c_uint64]),
     "cmhip_batch_set_loudness": (C.c_int, [_vp, C.c_int]),
     "cmhip_batch_get_loudness": (C.c_int, [_vp]),
     "cmhip_batch_loud_set_weights": (C.c_int, [_vp, C.c_long, _vp]),
@@ -376,6 +404,11 @@ SIGNATURES = {
     "coolmic_group_loudnesses": (C.c_int, [_vp, _vp, _vp]),
     "coolmic_group_loudness_set_weights": (C.c_int, [_vp, C.c_long, _vp]),
     "coolmic_group_loudness_reset": (C.c_int, [_vp, C.c_long]),
+    "coolmic_group_set_correlation": (C.c_int, [_vp, C.c_int]),
+    "coolmic_group_correlation_set_pairs": (C.c_int, [_vp, C.c_uint, _vp]),
+    "coolmic_group_correlation": (C.c_int, [_vp, C.c_uint, _P(CorrResult)]),
+    "coolmic_group_correlations": (C.c_int, [_vp, _vp, _vp]),
+    "coolmic_group_correlation_reset": (C.c_int, [_vp, C.c_long]),
     "coolmic_group_streams": (C.c_uint, [_vp]),
 }
 MISSING = []        # entry points this build of the library lacks (an older build under tools/ab_two_libs.py)
@@ -408,6 +441,11 @@ if hasattr(lib, "cmhip_test_plan_tpeak"):       # (not in builds older than true
     lib.cmhip_test_plan_tpeak.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.cmhip_debug_tp_count.restype = C.c_ulonglong
     lib.cmhip_debug_tp_count.argtypes = []
+if hasattr(lib, "cmhip_test_plan_corr"):        # (not in builds older than phase correlation)
+    lib.cmhip_test_plan_corr.restype = None
+    lib.cmhip_test_plan_corr.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
+    lib.cmhip_debug_corr_count.restype = C.c_ulonglong
+    lib.cmhip_debug_corr_count.argtypes = []
 if hasattr(lib, "cmhip_test_plan_loud"):        # (not in builds older than loudness)
     lib.cmhip_test_plan_loud.restype = None
     lib.cmhip_test_plan_loud.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -525,6 +563,36 @@ def tp_coefficients():
     h = np.zeros(48, dtype=np.int16)
     lib.cmhip_tp_coefficients(h.ctypes.data)
     return h.reshape(4, 12)
+
+
+class CorrPlan(C.Structure):
+    """cmhip::CorrPlan (csrc/cmhip_internal.h): what the correlation launcher launches for a run"""
+    _fields_ = [("err", C.c_int), ("fast", C.c_uint32), ("grid", C.c_uint32), ("block", C.c_uint32),
+                ("chunks", C.c_uint32)]
+
+
+def plan_corr(streams, channels, frames, npairs=1):
+    """Test hook: the correlation launcher's plan for a run (host logic, needs no GPU)"""
+    p = CorrPlan()
+    lib.cmhip_test_plan_corr(streams, channels, frames, npairs, C.addressof(p))
+    return p
+
+
+def corr_value(energy_a, energy_b, cross):
+    """the host finish of a correlation window: cross / sqrt(energy_a * energy_b) in [-1, 1], 0.0 for a silent leg"""
+    return lib.cmhip_corr_value(energy_a, energy_b, cross)
+
+
+def corr_balance_db(energy_a, energy_b):
+    """the host finish of a window's balance: 10 * log10(energy_a / energy_b), 0.0 when both are 0"""
+    return lib.cmhip_corr_balance_db(energy_a, energy_b)
+
+
+def _corr_pairs(pairs):
+    flat = [int(c) for p in pairs for c in p]
+    if len(flat) != 2 * len(pairs):
+        raise ValueError("corr_set_pairs: every pair is two channels")
+    return (C.c_ubyte * max(len(flat), 2))(*flat)
 
 
 class LoudPlan(C.Structure):
@@ -1068,6 +1136,32 @@ class Batch:
 
     def tp_reset(self, stream=-1):
         _check("tp_reset", lib.cmhip_batch_tp_reset(self.h, stream))
+
+    # phase correlation (opt-in)
+    def set_correlation(self, on):
+        """the error number (INVAL for a mono batch and while the equaliser has sections)"""
+        return lib.cmhip_batch_set_correlation(self.h, int(bool(on)))
+
+    def get_correlation(self):
+        return lib.cmhip_batch_get_correlation(self.h)
+
+    def corr_set_pairs(self, pairs):
+        """pairs: [(a, b), ...] -> the error number (BUSY while a window holds frames)"""
+        return lib.cmhip_batch_corr_set_pairs(self.h, len(pairs), _corr_pairs(pairs))
+
+    def corr_result(self, stream, out=None):
+        r = out if out is not None else CorrResult()
+        rc = lib.cmhip_batch_corr_result(self.h, stream, C.byref(r))
+        return rc, r
+
+    def corr_results(self, out=None):
+        out = out if out is not None else (CorrResult * self.streams)()
+        rc = (C.c_int * self.streams)()
+        _check("corr_results", lib.cmhip_batch_corr_results(self.h, out, rc))
+        return out, list(rc)
+
+    def corr_reset(self, stream=-1):
+        _check("corr_reset", lib.cmhip_batch_corr_reset(self.h, stream))
 
     # loudness (opt-in)
     def set_loudness(self, on):
@@ -1892,6 +1986,28 @@ class Group:
         rc = (C.c_int * n)()
         _check("group_true_peaks", lib.coolmic_group_true_peaks(self.ptr, out, rc))
         return out, list(rc)
+
+    def set_correlation(self, on):
+        return lib.coolmic_group_set_correlation(self.ptr, int(bool(on)))
+
+    def correlation_set_pairs(self, pairs):
+        return lib.coolmic_group_correlation_set_pairs(self.ptr, len(pairs), _corr_pairs(pairs))
+
+    def correlation(self, slot, out=None):
+        r = out if out is not None else CorrResult()
+        rc = lib.coolmic_group_correlation(self.ptr, slot, C.byref(r))
+        return rc, r
+
+    def correlations(self, out=None):
+        """every slot's correlation window at once -> (CorrResult array, rc list); `out`: the array to fill"""
+        n = self.streams()
+        out = out if out is not None else (CorrResult * n)()
+        rc = (C.c_int * n)()
+        _check("group_correlations", lib.coolmic_group_correlations(self.ptr, out, rc))
+        return out, list(rc)
+
+    def correlation_reset(self, slot=-1):
+        return lib.coolmic_group_correlation_reset(self.ptr, slot)
 
     def set_loudness(self, on):
         return lib.coolmic_group_set_loudness(self.ptr, int(bool(on)))

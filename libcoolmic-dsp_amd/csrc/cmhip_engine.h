@@ -3,6 +3,7 @@
 //   cmhip_place.hip    the opt-in placement search for a batch's two PCM arrays
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
 //   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
+//   cmhip_corr.hip     phase correlation: the opt-in state and pairs, its launch ahead of a run, results
 //   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
@@ -136,6 +137,13 @@ struct cmhip_batch {
     unsigned int tp_parity = 0;
     std::vector<unsigned long long> tp_frames;   // frames accounted per stream since its window opened
     std::vector<uint32_t> tp_host;         // [S][16] staging of a result call
+    // phase correlation (cmhip_corr.hip), all of it but the pairs unused until cmhip_batch_set_correlation(b, 1)
+    bool corr_on = false;
+    unsigned long long *d_corr = nullptr;  // [S][8][3] window sums: energy_a, energy_b, cross
+    unsigned int corr_npairs = 1;          // the channel pairs, the same for all streams (kept across off / on)
+    unsigned char corr_a[CORR_MAX_PAIRS] = {0}, corr_b[CORR_MAX_PAIRS] = {1};
+    std::vector<unsigned long long> corr_frames; // frames accounted per stream since its window opened
+    std::vector<unsigned long long> corr_host;   // [S][8][3] staging of a result call
     // loudness (cmhip_loud.hip), all of it unused until cmhip_batch_set_loudness(b, 1)
     bool loud_on = false;
     LoudState *d_loud = nullptr;           // [S][C] the rows' filter history and open sub-block
@@ -170,6 +178,10 @@ CMHIP_INTERNAL RunArgs cmhip_engine_run_args(const cmhip_batch_t *b, const int16
 // (only called while b->tp_on; frames_per_stream: the run's host array or nullptr, already uploaded to d_nframes)
 CMHIP_INTERNAL int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                        const uint32_t *frames_per_stream);
+// cmhip_corr.hip: the correlation pass of a run over `in`, queued on the batch's stream ahead of the block kernel
+// (only called while b->corr_on; frames_per_stream as for cmhip_engine_tp_run)
+CMHIP_INTERNAL int cmhip_engine_corr_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
+                                         const uint32_t *frames_per_stream);
 // cmhip_loud.hip: the loudness pass of a run over `in`, queued on the batch's stream ahead of the block kernel (only
 // called while b->loud_on; drains the ring first when the run could overflow it).  Returns an error number.
 CMHIP_INTERNAL int cmhip_engine_loud_run(cmhip_batch_t *b, const int16_t *in, size_t frames,

@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -143,6 +143,25 @@ struct TpArgs {
     uint32_t       streams;
     uint32_t       channels;
     uint32_t       parity;
+    uint64_t       stride;         // samples between stream slots (multiple of 8)
+    uint32_t       chunks;         // tiles per stream (the launcher fills it in)
+};
+
+// Phase correlation (k_corr.hip; the specification: include/coolmic_hip.h): per stream and channel pair (a, b) the
+// window sums of x_a^2, x_b^2 and x_a * x_b over the TRANSFORMED stream, exact 64-bit integers merged by integer
+// atomics.  No filter, no history, no parity slot.
+constexpr unsigned CORR_MAX_PAIRS = 8;
+constexpr unsigned CORR_SUMS = 3;              // energy_a, energy_b, cross (two's complement) per pair
+struct CorrArgs {
+    const int16_t *in;             // the run's INPUT slots: the kernel applies map and gain itself
+    const StreamParam *param;
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    unsigned long long *sums;      // [S][CORR_MAX_PAIRS][CORR_SUMS] the windows
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       npairs;
+    uint8_t        a[CORR_MAX_PAIRS], b[CORR_MAX_PAIRS];     // transformed channels of pair i (for k_corr_any)
     uint64_t       stride;         // samples between stream slots (multiple of 8)
     uint32_t       chunks;         // tiles per stream (the launcher fills it in)
 };
@@ -353,6 +372,17 @@ struct TpPlan {
 };
 TpPlan plan_tpeak(const TpArgs &a);
 hipError_t launch_tpeak(const TpArgs &a, hipStream_t st);
+// Phase correlation (k_corr.hip): the kernel of a run and its grid.  fast: stereo with one pair (one wave per 8 KiB
+// tile, sums of channel 0 / channel 1 / their product into pair 0 whichever way round the pair names them); otherwise
+// the any-channel-count kernel (one workgroup per 1024 frames).  A mono run has no pair: nothing to launch.
+struct CorrPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   fast;
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+    uint32_t   chunks;             // CorrArgs::chunks: tiles per stream
+};
+CorrPlan plan_corr(const CorrArgs &a);
+hipError_t launch_corr(const CorrArgs &a, hipStream_t st);
 // Loudness (k_loud.hip): one lane per row, one wave per workgroup.
 struct LoudPlan {
     hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups

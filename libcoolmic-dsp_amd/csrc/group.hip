@@ -64,6 +64,8 @@ struct coolmic_group {
     std::vector<coolmic_truepeak_result_t> *tp_out;  // the same for coolmic_group_true_peaks
     std::vector<int> *tp_rc;
     std::vector<coolmic_loudness_result_t> *loud_out;    // and for coolmic_group_loudnesses
+    std::vector<coolmic_correlation_result_t> *corr_out; // and for coolmic_group_correlations
+    std::vector<int> *corr_rc;
 };
 
 struct GroupHandle {
@@ -80,6 +82,8 @@ static void group_destroy(void *self)
     delete g->tp_out;
     delete g->tp_rc;
     delete g->loud_out;
+    delete g->corr_out;
+    delete g->corr_rc;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -631,6 +635,67 @@ extern "C" int coolmic_group_loudnesses(coolmic_group_t *self, coolmic_loudness_
             rc[i] = COOLMIC_ERROR_NONE;
     }
     return COOLMIC_ERROR_NONE;
+}
+
+// Phase correlation: thin wrappers over the engine (cmhip_corr.hip), with the slot handling of the true-peak calls.
+extern "C" int coolmic_group_set_correlation(coolmic_group_t *self, int on)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_set_correlation(self->batch, on);
+}
+
+extern "C" int coolmic_group_correlation_set_pairs(coolmic_group_t *self, unsigned int n, const unsigned char pairs[][2])
+{
+    if (!self || !pairs)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_corr_set_pairs(self->batch, n, pairs);
+}
+
+extern "C" int coolmic_group_correlation(coolmic_group_t *self, unsigned int slot, coolmic_correlation_result_t *result)
+{
+    if (!self || !result)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= self->streams->size())
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_corr_result(self->batch, slot, result);
+}
+
+extern "C" int coolmic_group_correlations(coolmic_group_t *self, coolmic_correlation_result_t *results, int *rc)
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return cmhip_batch_corr_results(self->batch, results, rc);
+    if (!self->corr_rc) {
+        try {
+            if (!self->corr_out)
+                self->corr_out = new std::vector<coolmic_correlation_result_t>(self->max_streams);
+            self->corr_rc = new std::vector<int>(self->max_streams);
+        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
+            return COOLMIC_ERROR_NOMEM;
+        }
+    }
+    const int r = cmhip_batch_corr_results(self->batch, self->corr_out->data(), self->corr_rc->data());
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        if ((*self->corr_rc)[i] == COOLMIC_ERROR_NONE)
+            results[i] = (*self->corr_out)[i];
+        if (rc)
+            rc[i] = (*self->corr_rc)[i];
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int coolmic_group_correlation_reset(coolmic_group_t *self, long slot)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= (long)self->streams->size() || slot < -1)
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_corr_reset(self->batch, slot);
 }
 
 extern "C" int coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights)
