@@ -1002,6 +1002,78 @@ int      cmhip_dyn_check_detector(unsigned int detector, unsigned int detector_l
 int      cmhip_dyn_design(const cmhip_dyn_curve_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
 int      cmhip_dyn_design_duck(const cmhip_dyn_duck_desc_t *c, uint16_t *curve /* [CMHIP_DYN_CURVE] */);
 
+/* ---- band split: a linear-phase FIR crossover, an object of its own beside the batch -- */
+/* A band split cuts each of S streams of C interleaved int16 channels (C in 1..16) into B bands (2..8) of the same
+ * rate, in exact integers, so that the bands add up to the input delayed by D frames -- to the bit, by construction.
+ * The signal is the raw int16 the caller hands in.  T taps per filter, odd, 3..1023; D = (T-1)/2 for every band; a run
+ * of F frames gives F frames in every band.
+ *
+ * Arithmetic, per stream, channel and frame n counted from creation or reset.  The object holds B-1 filters g_b[T],
+ *   int16, each with its own scale q_b in 14..20 (units of 2^-q_b); any int16 taps are valid.  For b < B-1:
+ *       acc_b = sum_{k<T} g_b[k] * x[n-k]            exact (|acc_b| < 2^41)
+ *       r_b   = (acc_b + 2^(q_b-1)) >> q_b           arithmetic shift (floor)
+ *       y_b   = saturate_int16(r_b)
+ *   and the last band is the residual, from the UNSATURATED r_b:
+ *       y_{B-1} = saturate_int16(x[n-D] - sum_{b<B-1} r_b)
+ *   x[i] for i < 0 is the stream's history: zero at creation and after cmhip_split_reset.  The state is the last T-1
+ *   frames per channel and nothing else; a stream that gets 0 frames in a run keeps it; outputs and clip counters do not
+ *   depend on how a stream is cut into runs.  Where no band of a sample saturates, sum_b y_b = x[n-D] exactly.
+ *   clips[S][B] (uint32, modulo 2^32, on the device) counts the saturated samples per stream and band: reconstruction
+ *   is exact iff they are zero.
+ * Output layout: `out` is band-major, int16 [B][S][out_stride]; band b of stream s starts at
+ *   out + (b*S + s) * out_stride.  out + b*S*out_stride is an ordinary S-stream input (for a cmhip_dyn_t of that band's
+ *   own time constants), the whole array a B*S-stream input (for a cmhip_bus_t that sums the bands: unity sends give
+ *   the delayed input back bit for bit while no clip counter moves).  Bands must pass stages of EQUAL delay before
+ *   they are summed.
+ * cmhip_split_run has cmhip_mix_run's contract with C_in = C_out = channels and B*S output slots: asynchronous on the
+ *   object's stream; frames_per_stream (host, S entries, may be NULL) is free on return, with cmhip_mix_run's possible
+ *   wait on the host for the fifth run queued back to back; COOLMIC_ERROR_INVAL, with nothing launched and nothing
+ *   changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or below frames * C,
+ *   frames > max_frames, a count is above frames, either array would end past the address space, or the input and the
+ *   B*S output slots share a byte; COOLMIC_ERROR_FAULT for NULL arrays.  Outputs past a stream's count are not written.
+ * The designed filters (cmhip_split_design, host only, double precision, in this order).  Crossovers
+ *   f_0 < f_1 < ... < f_{B-2} strictly inside (0, rate/2), anything else is COOLMIC_ERROR_INVAL.  For filter j, with
+ *   fc = f_j / rate and x = i - D for i in 0..T-1:
+ *       w = I0(7.5 * sqrt(max(0, 1 - (x / (D+1))^2))) / I0(7.5)          l_j[i] = 2*fc * sinc(2*fc*x) * w
+ *   (sinc and I0 as cmhip_src_design's), l_j divided by its own sum.  h_0 = l_0, h_b = l_b - l_{b-1}.
+ *   g_b = rint(h_b * 2^q); the difference to the wanted integer sum (2^q for b = 0, 0 for the others) is added to the
+ *   centre tap; q_b is the largest q in 14..20 for which every finished tap lies within +-32767.  Every filter is
+ *   symmetric; a constant input c comes out as c in band 0 and 0 in every other band, the residual included, once the
+ *   history is full.  The table's bits are not pinned across libms: whatever table the library returns is the
+ *   specification for the kernel.  g == NULL checks the arguments only; with g, q may not be NULL, cap counts g's
+ *   entries, and a cap below (B-1)*T is COOLMIC_ERROR_INVAL with nothing written.
+ * cmhip_split_new designs the filters for `rate` and crossover_hz[B-1]; cmhip_split_new_table takes the caller's
+ *   g[B-1][T] and q[B-1] (cmhip_split_check: the geometry and every q_b in 14..20).  max_frames * C may not pass 2^31
+ *   samples.  Both return NULL on failure.  cmhip_split_reset (stream -1: all) zeroes history and clip counters, on the
+ *   object's stream.  cmhip_split_clips copies the counters to clips[S][B] (host) and, with clear, zeroes them behind
+ *   the copy: a synchronous round trip on the object's stream. */
+typedef struct cmhip_split cmhip_split_t;
+typedef struct cmhip_split_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int bands;           /* B in 2..8 */
+    unsigned int taps;            /* T odd, in 3..1023 */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_split_desc_t;
+cmhip_split_t *cmhip_split_new(const cmhip_split_desc_t *d, unsigned int rate, const double *crossover_hz /* [B-1] */);
+cmhip_split_t *cmhip_split_new_table(const cmhip_split_desc_t *d, const int16_t *g /* [B-1][T] */,
+                                     const uint8_t *q /* [B-1] */);
+void     cmhip_split_free(cmhip_split_t *m);
+unsigned int cmhip_split_delay(const cmhip_split_t *m);               /* D = (T-1)/2 */
+int      cmhip_split_get_table(const cmhip_split_t *m, int16_t *g /* [B-1][T] */, uint8_t *q /* [B-1] */);
+int      cmhip_split_run(cmhip_split_t *m, const void *in, size_t in_stride, size_t frames,
+                         const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_split_reset(cmhip_split_t *m, long stream);
+int      cmhip_split_clips(cmhip_split_t *m, uint32_t *clips /* [S][B] */, int clear);
+int      cmhip_split_sync(cmhip_split_t *m);
+void    *cmhip_split_hip_stream(cmhip_split_t *m);
+/* host only, no device needed */
+int      cmhip_split_design(unsigned int rate, unsigned int bands, const double *crossover_hz /* [B-1] */,
+                            unsigned int taps, int16_t *g /* [B-1][T] */, uint8_t *q /* [B-1] */, size_t cap /* entries */);
+int      cmhip_split_check(unsigned int bands, unsigned int taps, const int16_t *g, const uint8_t *q);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

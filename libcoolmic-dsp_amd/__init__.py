@@ -136,6 +136,12 @@ class DynDesc(C.Structure):
                 ("smooth_log2", C.c_uint), ("hold", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class SplitDesc(C.Structure):
+    """cmhip_split_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("bands", C.c_uint),
+                ("taps", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
 class DynCurveDesc(C.Structure):
     """cmhip_dyn_curve_desc_t (include/coolmic_hip.h)"""
     _fields_ = [(n, C.c_double) for n in ("comp_threshold_db", "comp_ratio", "comp_knee_db", "gate_threshold_db",
@@ -255,6 +261,18 @@ SIGNATURES = {
     "cmhip_src_hip_stream": (_vp, [_vp]),
     "cmhip_src_design": (C.c_int, [C.c_uint, C.c_uint, _P(C.c_uint), _P(C.c_uint), _P(C.c_uint), _vp, C.c_size_t]),
     "cmhip_src_out_frames": (C.c_uint32, [C.c_uint, C.c_uint, C.c_uint32, C.c_uint32]),
+    "cmhip_split_new": (_vp, [_P(SplitDesc), C.c_uint, _P(C.c_double)]),
+    "cmhip_split_new_table": (_vp, [_P(SplitDesc), _vp, _vp]),
+    "cmhip_split_free": (None, [_vp]),
+    "cmhip_split_delay": (C.c_uint, [_vp]),
+    "cmhip_split_get_table": (C.c_int, [_vp, _vp, _vp]),
+    "cmhip_split_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_split_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_split_clips": (C.c_int, [_vp, _vp, C.c_int]),
+    "cmhip_split_sync": (C.c_int, [_vp]),
+    "cmhip_split_hip_stream": (_vp, [_vp]),
+    "cmhip_split_design": (C.c_int, [C.c_uint, C.c_uint, _P(C.c_double), C.c_uint, _vp, _vp, C.c_size_t]),
+    "cmhip_split_check": (C.c_int, [C.c_uint, C.c_uint, _vp, _vp]),
     "cmhip_mix_new": (_vp, [_P(MixDesc)]),
     "cmhip_mix_free": (None, [_vp]),
     "cmhip_mix_set_matrix": (C.c_int, [_vp, C.c_long, _vp]),
@@ -486,6 +504,11 @@ if hasattr(lib, "cmhip_test_plan_dynrms"):      # (not in builds older than the 
     lib.cmhip_test_plan_dynrms.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
     lib.cmhip_test_dyn_isqrt.restype = C.c_uint32
     lib.cmhip_test_dyn_isqrt.argtypes = [C.c_uint32]
+if hasattr(lib, "cmhip_test_plan_split"):       # (not in builds older than the band split)
+    lib.cmhip_test_plan_split.restype = None
+    lib.cmhip_test_plan_split.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
+    lib.cmhip_test_split_compile.restype = C.c_int
+    lib.cmhip_test_split_compile.argtypes = [C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_size_t]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -654,6 +677,57 @@ def src_design(rate_in, rate_out):
 def src_out_frames(L, M, r, frames):
     """output frames of a run of `frames` input frames for a stream at position r = (frames so far) mod M"""
     return lib.cmhip_src_out_frames(L, M, r, frames)
+
+
+class SplitPlan(C.Structure):
+    """cmhip::SplitPlan (csrc/split_plan.h): what the band split's launcher launches for a run"""
+    _fields_ = [(name, C.c_int if name == "err" else C.c_uint32)
+                for name in ("err", "fast", "grid", "block", "chunks", "tile_frames", "tp", "row", "table_words",
+                             "lds_bytes")]
+
+
+def plan_split(streams, channels, bands, taps, frames):
+    """Test hook: the launch plan of a band-split run whose longest stream has `frames` frames (host logic, needs no
+    GPU)."""
+    p = SplitPlan()
+    lib.cmhip_test_plan_split(streams, channels, bands, taps, frames, C.addressof(p))
+    return p
+
+
+def _crossovers(crossover_hz, bands):
+    f = [float(v) for v in crossover_hz]
+    assert len(f) == bands - 1
+    return (C.c_double * len(f))(*f)
+
+
+def split_design(rate, bands, crossover_hz, taps):
+    """cmhip_split_design -> (int16 [B-1][T] filters, uint8 [B-1] scales)"""
+    g = np.zeros((bands - 1, taps), dtype=np.int16)
+    q = np.zeros(bands - 1, dtype=np.uint8)
+    _check("split_design", lib.cmhip_split_design(rate, bands, _crossovers(crossover_hz, bands), taps, g.ctypes.data,
+                                                  q.ctypes.data, g.size))
+    return g, q
+
+
+def split_check(bands, taps, g, q):
+    """cmhip_split_check as it is -> error number"""
+    g = None if g is None else np.ascontiguousarray(g, dtype=np.int16)
+    q = None if q is None else np.ascontiguousarray(q, dtype=np.uint8)
+    return lib.cmhip_split_check(bands, taps, None if g is None else g.ctypes.data, None if q is None else q.ctypes.data)
+
+
+def split_compile(g, q):
+    """Test hook: the filters in the kernel's form (csrc/split_plan.h) -> (pairs uint32 [B-1][Tp/2], masks uint32
+    [B-1][Tp/8], q uint32 [B-1])"""
+    g = np.ascontiguousarray(g, dtype=np.int16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    nf, T = g.shape
+    tp = (T + 8) & ~7
+    out = np.zeros(nf * (tp // 2 + tp // 8 + 1), dtype=np.uint32)
+    n = lib.cmhip_test_split_compile(nf + 1, T, g.ctypes.data, q.ctypes.data, out.ctypes.data, out.size)
+    assert n == out.size, n
+    a, b = nf * (tp // 2), nf * (tp // 2 + tp // 8)
+    return out[:a].reshape(nf, tp // 2), out[a:b].reshape(nf, tp // 8), out[b:]
 
 
 class MixPlan(C.Structure):
@@ -1245,7 +1319,7 @@ class Batch:
 
 
 class _Stage:
-    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter): the end of the handle `h`, its
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit): the end of the handle `h`, its
     stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
 
     _stem = None
@@ -1318,6 +1392,54 @@ class Resampler(_Stage):
 
     def reset(self, stream=-1):
         _check("src_reset", lib.cmhip_src_reset(self.h, stream))
+
+
+class BandSplit(_Stage):
+    """cmhip_split_t: a linear-phase FIR crossover of S streams beside a batch: B bands that add up to the input delayed
+    by delay() frames.  Either `rate` and `crossover_hz` (the library designs the filters) or table = (int16 [B-1][T],
+    uint8 [B-1])."""
+
+    _stem = "split"
+
+    def __init__(self, streams, channels, bands, taps, max_frames, rate=None, crossover_hz=None, table=None, device=0,
+                 hip_stream=None):
+        d = SplitDesc(device, streams, channels, bands, taps, max_frames, hip_stream)
+        if table is None:
+            self.h = lib.cmhip_split_new(C.byref(d), rate, _crossovers(crossover_hz, bands))
+        else:
+            g = np.ascontiguousarray(table[0], dtype=np.int16)
+            q = np.ascontiguousarray(table[1], dtype=np.uint8)
+            assert g.shape == (bands - 1, taps) and q.shape == (bands - 1,)
+            self.h = lib.cmhip_split_new_table(C.byref(d), g.ctypes.data, q.ctypes.data)
+        if not self.h:
+            raise CoolmicError("cmhip_split_new", ERROR_INVAL)
+        self.streams, self.channels, self.bands, self.taps, self.max_frames = streams, channels, bands, taps, max_frames
+
+    def delay(self):
+        return lib.cmhip_split_delay(self.h)
+
+    def get_table(self):
+        g = np.zeros((self.bands - 1, self.taps), dtype=np.int16)
+        q = np.zeros(self.bands - 1, dtype=np.uint8)
+        _check("split_get_table", lib.cmhip_split_get_table(self.h, g.ctypes.data, q.ctypes.data))
+        return g, q
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_split_run as it is -> error number"""
+        return lib.cmhip_split_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src: S slots, dst: B * S slots, band-major)"""
+        _check("split_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        _check("split_reset", lib.cmhip_split_reset(self.h, stream))
+
+    def clips(self, clear=False):
+        """-> uint32 [S][B]: the saturated samples per stream and band (a synchronous round trip)"""
+        c = np.zeros((self.streams, self.bands), dtype=np.uint32)
+        _check("split_clips", lib.cmhip_split_clips(self.h, c.ctypes.data, 1 if clear else 0))
+        return c
 
 
 class Mixer(_Stage):

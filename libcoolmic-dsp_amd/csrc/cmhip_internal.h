@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -9,6 +9,7 @@
 
 #include "lim_plan.h"
 #include "dyn_plan.h"
+#include "split_plan.h"
 
 namespace cmhip {
 
@@ -327,6 +328,28 @@ struct DynCurveArg {
     uint32_t w[DYN_CURVE / 2];
 };
 
+// Band split (k_split.hip; the arithmetic: include/coolmic_hip.h): a run of a band split over S stream slots.
+struct SplitArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [B][S][out_stride]
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    const uint32_t *table;         // the filters in the kernel's form (csrc/split_plan.h)
+    // [2][S][C][T-1] the last T-1 input frames per channel, oldest first; the two slots of SrcArgs::hist
+    int16_t       *hist;
+    uint32_t      *clips;          // [S][B] saturated samples per stream and band
+    uint64_t       in_stride, out_stride;    // samples between slots (multiples of 8)
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       bands, taps;
+    uint32_t       parity;
+    // (the launcher fills these in)
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_frames;    // frames per tile
+    uint32_t       row;            // samples between the planes of a tile in LDS
+    uint32_t       table_words;    // dwords of the table in LDS
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -475,6 +498,8 @@ hipError_t launch_dyn_set(uint16_t *curve, uint32_t first, uint32_t count, const
 // (the key map's writer: streams first .. first + count - 1 get `key`, or each itself where own is set; both values
 // travel as kernel arguments)
 hipError_t launch_dyn_set_key(uint32_t *map, uint32_t first, uint32_t count, uint32_t key, bool own, hipStream_t st);
+// Band split (k_split.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/split_plan.h's.
+hipError_t launch_split(const SplitArgs &a, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,
