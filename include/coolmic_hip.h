@@ -1074,6 +1074,81 @@ int      cmhip_split_design(unsigned int rate, unsigned int bands, const double 
                             unsigned int taps, int16_t *g /* [B-1][T] */, uint8_t *q /* [B-1] */, size_t cap /* entries */);
 int      cmhip_split_check(unsigned int bands, unsigned int taps, const int16_t *g, const uint8_t *q);
 
+/* ---- delay: a delay line with click-free moves, an object of its own beside the batch -- */
+/* A delay gives each of S streams of C interleaved int16 channels (C in 1..16) back d_s frames later, d_s in
+ * 0..max_delay per stream, in exact integers: the consumer of cmhip_split_delay, cmhip_dyn_delay and cmhip_lim_delay
+ * (a dry path beside a compressor, bands of unequal latency in front of a bus), and the ordinary delay line of a
+ * broadcast chain (time alignment, lip sync, a profanity delay of seconds).
+ *
+ * Arithmetic, per stream, channel and frame n.  Frames are counted over everything the stream was ever given; x[i] for
+ *   i before the first frame, or before the last cmhip_delay_reset, is zero.
+ *   Steady state: y[n][c] = x[n - d][c].
+ *   History: the state is the stream's last max_delay frames and nothing else.  It does not depend on d: after a move to
+ *     a larger delay the output reads real older samples, not zeros.  A stream given 0 frames in a run keeps everything.
+ *   Step: cmhip_delay_set(m, stream, d) steps between two frames (stream -1: all streams): from the next frame on,
+ *     y[n] = x[n - d].
+ *   Crossfade: cmhip_delay_ramp(m, stream, d1, R) moves the delay from d0, the one in force, to d1 without a click, by
+ *     a crossfade between the two taps over the stream's next R frames, R in 2..2^20.  Frame k = 1..R of the ramp has
+ *     the position p = cmhip_mix_ramp_position(k, R), one per frame for all channels, and
+ *         N = x[n-d0][c] * (32768 - p) + x[n-d1][c] * p
+ *         y = (N + 16384) >> 15                          arithmetic shift (floor)
+ *     Frame R has p = 32768 and is exactly x[n - d1], and so is every later frame.  R of 0 or 1 is exactly
+ *     cmhip_delay_set.  cmhip_delay_crossfade(a, b, p) is this formula as code (p above 32768 counts as 32768).
+ *   Properties.  |N| <= 2^30, so int32 is exact: |a| (32768 - p) + |b| p <= 32768 * 32768.  The result lies in
+ *     -32768..32767 for every p and every pair of int16 samples, so nothing saturates and no clamp can hide an error:
+ *     N / 32768 is a convex combination of a and b and lies in [-32768, 32767], so (N + 16384) / 32768 lies in
+ *     [-32767.5, 32767.5] and its floor in -32768..32767.  d0 = d1 gives y = x[n - d0] at every p: then
+ *     N = 32768 a, and (32768 a + 16384) >> 15 = a.  For the implementer: the weight 32768 does not fit an int16, so
+ *     the packed dot product is not the tool; y = a + ((p * (b - a) + 16384) >> 15) is the same integer, as 32768 a is
+ *     a multiple of 2^15, and its factors fit 24 bits.
+ *   While a ramp runs another cmhip_delay_ramp on that stream is COOLMIC_ERROR_BUSY and changes nothing (for stream -1:
+ *     when any stream ramps, and no stream changes) -- a third tap is not built.  cmhip_delay_set ends the ramp and
+ *     steps.  Ramp frames are counted by the frames the stream is actually given.
+ *   Cuts: the concatenated output does not depend on how a stream is cut into runs, with sets and ramps at the same
+ *     frames.
+ *   cmhip_delay_reset (stream -1: all) zeroes the history, on the object's stream.  The delay setting and a running
+ *     ramp stay.
+ * cmhip_delay_new: NULL for C outside 1..16, S = 0, max_frames = 0, (max_delay + max_frames) * C >= 2^31, or a failed
+ *   allocation (a stream's history is a ring of max_delay + max_frames frames on the device).  max_delay = 0 is legal
+ *   and makes the object a copy.  Every stream starts with d = 0.
+ * cmhip_delay_run has cmhip_mix_run's contract with C_in = C_out = channels: asynchronous on the object's stream;
+ *   frames_per_stream (host, S entries, may be NULL) is free on return, with cmhip_mix_run's possible wait on the host
+ *   for the fifth run queued back to back; COOLMIC_ERROR_INVAL, with nothing launched and nothing changed, when a base
+ *   is not 16-byte aligned, a stride is not a multiple of 8 samples or below frames * C, frames > max_frames, a count is
+ *   above frames, either array would end past the address space, or the two arrays share a byte; COOLMIC_ERROR_FAULT
+ *   for NULL arrays.  Outputs past a stream's count are not written.
+ * cmhip_delay_set and cmhip_delay_ramp take effect at the next run queued behind them: the positions, delays and ramps
+ *   live in a host mirror that every run hands to the device with its counts, so they are ordered with the runs as the
+ *   calls are, need no host wait and touch no device memory.  COOLMIC_ERROR_INVAL for a delay above max_delay,
+ *   ramp_frames above 2^20 or a stream out of range; every refused call changes nothing.  cmhip_delay_get answers from
+ *   that mirror: *delay is the last accepted target; while the stream ramps *from is d0, *done the ramp frames so far
+ *   and *ramp_frames R; otherwise *from = *delay and the other two are 0.  from, done and ramp_frames may be NULL.
+ * cmhip_delay_ms (host only): rint(rate * ms / 1000) frames, 0 for a negative or non-finite product. */
+typedef struct cmhip_delay cmhip_delay_t;
+typedef struct cmhip_delay_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    size_t       max_delay;       /* frames; 0: the object is a copy */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_delay_desc_t;
+cmhip_delay_t *cmhip_delay_new(const cmhip_delay_desc_t *d);
+void     cmhip_delay_free(cmhip_delay_t *m);
+int      cmhip_delay_set(cmhip_delay_t *m, long stream, uint32_t delay);
+int      cmhip_delay_ramp(cmhip_delay_t *m, long stream, uint32_t delay, uint32_t ramp_frames);
+int      cmhip_delay_get(const cmhip_delay_t *m, unsigned int stream, uint32_t *delay, uint32_t *from, uint32_t *done,
+                         uint32_t *ramp_frames);
+int      cmhip_delay_run(cmhip_delay_t *m, const void *in, size_t in_stride, size_t frames,
+                         const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_delay_reset(cmhip_delay_t *m, long stream);
+int      cmhip_delay_sync(cmhip_delay_t *m);
+void    *cmhip_delay_hip_stream(cmhip_delay_t *m);
+size_t   cmhip_delay_max_delay(const cmhip_delay_t *m);
+/* host only, no device needed */
+uint32_t cmhip_delay_ms(unsigned int rate, double ms);
+int16_t  cmhip_delay_crossfade(int16_t a, int16_t b, uint32_t p);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

@@ -142,6 +142,12 @@ class SplitDesc(C.Structure):
                 ("taps", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class DelayDesc(C.Structure):
+    """cmhip_delay_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("max_delay", C.c_size_t),
+                ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
 class DynCurveDesc(C.Structure):
     """cmhip_dyn_curve_desc_t (include/coolmic_hip.h)"""
     _fields_ = [(n, C.c_double) for n in ("comp_threshold_db", "comp_ratio", "comp_knee_db", "gate_threshold_db",
@@ -273,6 +279,18 @@ SIGNATURES = {
     "cmhip_split_hip_stream": (_vp, [_vp]),
     "cmhip_split_design": (C.c_int, [C.c_uint, C.c_uint, _P(C.c_double), C.c_uint, _vp, _vp, C.c_size_t]),
     "cmhip_split_check": (C.c_int, [C.c_uint, C.c_uint, _vp, _vp]),
+    "cmhip_delay_new": (_vp, [_P(DelayDesc)]),
+    "cmhip_delay_free": (None, [_vp]),
+    "cmhip_delay_set": (C.c_int, [_vp, C.c_long, C.c_uint32]),
+    "cmhip_delay_ramp": (C.c_int, [_vp, C.c_long, C.c_uint32, C.c_uint32]),
+    "cmhip_delay_get": (C.c_int, [_vp, C.c_uint, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
+    "cmhip_delay_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_delay_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_delay_sync": (C.c_int, [_vp]),
+    "cmhip_delay_hip_stream": (_vp, [_vp]),
+    "cmhip_delay_max_delay": (C.c_size_t, [_vp]),
+    "cmhip_delay_ms": (C.c_uint32, [C.c_uint, C.c_double]),
+    "cmhip_delay_crossfade": (C.c_int16, [C.c_int16, C.c_int16, C.c_uint32]),
     "cmhip_mix_new": (_vp, [_P(MixDesc)]),
     "cmhip_mix_free": (None, [_vp]),
     "cmhip_mix_set_matrix": (C.c_int, [_vp, C.c_long, _vp]),
@@ -509,6 +527,13 @@ if hasattr(lib, "cmhip_test_plan_split"):       # (not in builds older than the 
     lib.cmhip_test_plan_split.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
     lib.cmhip_test_split_compile.restype = C.c_int
     lib.cmhip_test_split_compile.argtypes = [C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_size_t]
+if hasattr(lib, "cmhip_test_plan_delay"):       # (not in builds older than the delay stage)
+    lib.cmhip_test_plan_delay.restype = None
+    lib.cmhip_test_plan_delay.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
+    lib.cmhip_test_delay_new_dry.restype = _vp
+    lib.cmhip_test_delay_new_dry.argtypes = [_P(DelayDesc)]
+    lib.cmhip_test_delay_tap.restype = None
+    lib.cmhip_test_delay_tap.argtypes = [C.c_uint32] * 5 + [_P(C.c_uint32), _P(C.c_uint32)]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -692,6 +717,46 @@ def plan_split(streams, channels, bands, taps, frames):
     p = SplitPlan()
     lib.cmhip_test_plan_split(streams, channels, bands, taps, frames, C.addressof(p))
     return p
+
+
+class DelayPlan(C.Structure):
+    """cmhip::DelayPlan (csrc/delay_plan.h): what the delay's launcher launches for a run"""
+    _fields_ = [(name, C.c_int if name == "err" else C.c_uint32)
+                for name in ("err", "fast", "grid", "block", "chunks", "tile_frames", "tile_vecs", "ring_frames")]
+
+
+DELAY_BEHIND, DELAY_FRONT, DELAY_MIXED = 0, 1, 2     # cmhip::DelayClass
+
+
+def plan_delay(streams, channels, max_delay, max_frames, frames):
+    """Test hook: the launch plan of a delay run whose longest stream has `frames` frames, and the ring's frames (host
+    logic, needs no GPU)."""
+    p = DelayPlan()
+    lib.cmhip_test_plan_delay(streams, channels, max_delay, max_frames, frames, C.addressof(p))
+    return p
+
+
+def delay_tap(e0, length, D, P, CAP):
+    """Test hook: cmhip::delay_tap (csrc/delay_plan.h), everything in samples -> (class, first source sample)"""
+    cls, q = C.c_uint32(0), C.c_uint32(0)
+    lib.cmhip_test_delay_tap(e0, length, D, P, CAP, C.byref(cls), C.byref(q))
+    return cls.value, q.value
+
+
+def test_delay_without_device(streams, channels, max_delay, max_frames):
+    """Test hook (cmhip_test_delay_new_dry): a Delay with the host mirror and every check but no device behind it, for
+    the refusals on a machine without a GPU; a run that would launch is refused."""
+    return Delay(streams, channels, max_delay, max_frames, _new=lib.cmhip_test_delay_new_dry)
+
+
+def delay_ms(rate, ms):
+    """cmhip_delay_ms: rint(rate * ms / 1000) frames"""
+    return lib.cmhip_delay_ms(rate, ms)
+
+
+def delay_crossfade(a, b, p):
+    """cmhip_delay_crossfade: the crossfade of two samples at position p, the specification as code"""
+    return lib.cmhip_delay_crossfade(a, b, p)
 
 
 def _crossovers(crossover_hz, bands):
@@ -1319,7 +1384,7 @@ class Batch:
 
 
 class _Stage:
-    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit): the end of the handle `h`, its
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay): the end of the handle `h`, its
     stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
 
     _stem = None
@@ -1440,6 +1505,58 @@ class BandSplit(_Stage):
         c = np.zeros((self.streams, self.bands), dtype=np.uint32)
         _check("split_clips", lib.cmhip_split_clips(self.h, c.ctypes.data, 1 if clear else 0))
         return c
+
+
+class Delay(_Stage):
+    """cmhip_delay_t: a delay line of S streams beside a batch, a delay of 0..max_delay frames per stream (0 at
+    creation), moved by steps or by click-free crossfades."""
+
+    _stem = "delay"
+
+    def __init__(self, streams, channels, max_delay, max_frames, delay=None, device=0, hip_stream=None, _new=None):
+        d = DelayDesc(device, streams, channels, max_delay, max_frames, hip_stream)
+        self.h = (_new or lib.cmhip_delay_new)(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_delay_new", ERROR_INVAL)
+        self.streams, self.channels, self.max_frames = streams, channels, max_frames
+        if delay is not None:
+            self.set(-1, delay)
+
+    def max_delay(self):
+        return lib.cmhip_delay_max_delay(self.h)
+
+    def set_rc(self, stream, delay):
+        """cmhip_delay_set as it is -> error number"""
+        return lib.cmhip_delay_set(self.h, stream, delay)
+
+    def set(self, stream, delay):
+        """a step between two frames (stream -1: every stream)"""
+        _check("delay_set", self.set_rc(stream, delay))
+
+    def ramp_rc(self, stream, delay, ramp_frames):
+        """cmhip_delay_ramp as it is -> error number"""
+        return lib.cmhip_delay_ramp(self.h, stream, delay, ramp_frames)
+
+    def ramp(self, stream, delay, ramp_frames):
+        """a click-free move to `delay` over ramp_frames of the stream's frames (stream -1: every stream)"""
+        _check("delay_ramp", self.ramp_rc(stream, delay, ramp_frames))
+
+    def get(self, stream):
+        """-> (delay, from, done, ramp_frames); (delay, delay, 0, 0) when nothing ramps"""
+        v = [C.c_uint32(0) for _ in range(4)]
+        _check("delay_get", lib.cmhip_delay_get(self.h, stream, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_delay_run as it is -> error number"""
+        return lib.cmhip_delay_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers)"""
+        _check("delay_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        _check("delay_reset", lib.cmhip_delay_reset(self.h, stream))
 
 
 class Mixer(_Stage):

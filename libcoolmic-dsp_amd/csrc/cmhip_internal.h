@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -10,6 +10,7 @@
 #include "lim_plan.h"
 #include "dyn_plan.h"
 #include "split_plan.h"
+#include "delay_plan.h"
 
 namespace cmhip {
 
@@ -350,6 +351,22 @@ struct SplitArgs {
     uint32_t       table_words;    // dwords of the table in LDS
 };
 
+// Delay (k_delay.hip; the arithmetic: include/coolmic_hip.h, the geometry: csrc/delay_plan.h): a run of a delay stage
+// over S stream slots.
+struct DelayArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    int16_t       *ring;           // int16 [S][ring_samples] the streams' rings
+    const uint32_t *rec;           // [S][DELAY_REC] the run's records: count, pos, d1, d0, R, done, inc
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       ring_samples;   // CAP: samples of a stream's ring (a multiple of 8)
+    uint32_t       streams;
+    uint32_t       channels;
+    // (the launcher fills these in)
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_vecs;      // 16-byte vectors per tile
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -500,6 +517,9 @@ hipError_t launch_dyn_set(uint16_t *curve, uint32_t first, uint32_t count, const
 hipError_t launch_dyn_set_key(uint32_t *map, uint32_t first, uint32_t count, uint32_t key, bool own, hipStream_t st);
 // Band split (k_split.hip): one workgroup of 256 threads per stream and tile; the plan is csrc/split_plan.h's.
 hipError_t launch_split(const SplitArgs &a, hipStream_t st);
+// Delay (k_delay.hip): one workgroup per stream and tile; the plan is csrc/delay_plan.h's.  frames: the run's largest
+// count, max_delay and max_frames the object's.
+hipError_t launch_delay(const DelayArgs &a, uint32_t max_delay, uint32_t max_frames, uint32_t frames, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,
