@@ -1149,6 +1149,107 @@ size_t   cmhip_delay_max_delay(const cmhip_delay_t *m);
 uint32_t cmhip_delay_ms(unsigned int rate, double ms);
 int16_t  cmhip_delay_crossfade(int16_t a, int16_t b, uint32_t p);
 
+/* ---- leveller: slow automatic gain control, an object of its own beside the batch ------- */
+/* A leveller finds the gain that brings each of S streams of C interleaved int16 channels (C in 1..16) to a target
+ * level, in exact integers: the stage that chooses what the limiter's constant drive cannot.  It belongs between the
+ * sources (or a bus) and the dynamics and limiter.  The gain moves once per window of W frames and is interpolated
+ * in between; the level is the input's own (feed-forward), so nothing can hunt.  The stage adds no delay.
+ *
+ * Geometry, per object: window_log2 = w in 6..14, W = 2^w.
+ * Parameters, per stream, settable between runs (cmhip_agc_set, stream -1: all streams):
+ *     target T              1..32767    sample units: the RMS level wanted
+ *     gate Q                0..32767    a window whose level is below Q leaves the gain alone: silence is not pumped up
+ *     gain_min, gain_max    1 <= gain_min <= gain_max <= 65535, units of 2^-12, unity 4096 (the limiter's drive unit):
+ *                           at most +24.08 dB
+ *     rise, fall            0..65535    the fraction of the gain in force it may move per window, units of 2^-16;
+ *                                       0 freezes that direction
+ *     initial               gain_min..gain_max: the gain of a stream's first frames (below)
+ *
+ * Arithmetic, per stream.  Frames are counted since creation or the last cmhip_agc_reset: n, 64 bits.  Window
+ *   k = n >> w, j = n & (W - 1).
+ *   Level of a complete window k: E[k] = max over the channels c of the sum over the window's frames of x[n][c]^2;
+ *     E <= 2^44, exact in uint64.  L[k] = isqrt(E[k] >> w), the exact integer root, 0 <= L <= 32768.  The loudest
+ *     channel is used, as in the dynamics stage's RMS detector: a level means the same in both stages.
+ *   Step:
+ *     step(A, L): if L == 0 or L < Q: return A
+ *                 D = clamp((T << 12) / L, gain_min, gain_max)                integer division, below 2^27
+ *                 if D > A and rise: return min(D, A + max(1, (A * rise) >> 16))
+ *                 if D < A and fall: return max(D, A - max(1, (A * fall) >> 16))
+ *                 return A
+ *     A * rise stays below 2^32: uint32 is exact.
+ *   Gain nodes: A[0] = A[1] = initial -- the `initial` in force in the run that processes frame 0.  For k >= 1,
+ *     A[k+1] = step(A[k], L[k-1]), evaluated when frame n = k W is processed, with the parameters of the last
+ *     cmhip_agc_set queued before the run that processes that frame.  The gain of window k depends only on windows
+ *     that ended before it began: the stage is causal without a delay.
+ *   Per frame: g = A[k] + (((A[k+1] - A[k]) * j) >> w), arithmetic shift (floor); the product stays below 2^30, int32 is
+ *     exact.  Every channel of the frame: v = (x * g + 2048) >> 12, arithmetic shift; |x g| + 2048 < 2^31, int32 is
+ *     exact.  y = clamp(v, -32768, 32767), and every sample the clamp changes increments the stream's clip counter.
+ *     Gain above unity can saturate: the limiter that follows is what holds a ceiling.
+ *   Properties.  With gain_min = gain_max = initial = 4096 the output is the input, bit for bit:
+ *     (4096 x + 2048) >> 12 = x.  A stream given 0 frames in a run keeps everything.  Cuts: the concatenated output,
+ *     the clip counts and the state do not depend on how a stream is cut into runs, with the sets at the same frames
+ *     -- every sum is a sum of integers.
+ *   cmhip_agc_reset (stream -1: all): the stream's next frame is frame 0 again: the gain is `initial`, the sums of an
+ *     open window and the last level are forgotten.  The parameters and the clip counter stay.
+ * cmhip_agc_new: NULL for C outside 1..16, S = 0, window_log2 outside 6..14, max_frames = 0, max_frames * C >= 2^31,
+ *   or a failed allocation.  Every stream starts with target 3277 (-20 dB re 32768), gate 33 (-60 dB), gain_min =
+ *   gain_max = initial = 4096 and rise = fall = 0: a copy, until cmhip_agc_set says otherwise.
+ * cmhip_agc_run has cmhip_delay_run's contract: asynchronous on the object's stream; frames_per_stream (host, S entries,
+ *   may be NULL) is free on return; COOLMIC_ERROR_INVAL, with nothing launched and nothing changed, when a base is not
+ *   16-byte aligned, a stride is not a multiple of 8 samples or below frames * C, frames > max_frames, a count is above
+ *   frames, either array would end past the address space, or the two arrays share a byte; COOLMIC_ERROR_FAULT for
+ *   NULL arrays.  Outputs past a stream's count are not written.
+ * cmhip_agc_set and cmhip_agc_reset are ordered with the runs as the calls are: positions and parameters live in a host
+ *   mirror that every run hands to the device with its counts, so they need no host wait and touch no device memory.
+ *   COOLMIC_ERROR_INVAL for parameters out of range or a stream out of range; a refused call changes nothing.
+ *   cmhip_agc_get answers from that mirror.
+ * cmhip_agc_state: synchronous (it waits for the object's stream, like cmhip_lim_min_gain).  Per stream, S entries each:
+ *   gain[s] = A[k+1] of the window the stream's last frame lies in (`initial` before its first frame), level[s] = L of
+ *   its last complete window (0 before the first), clips[s] = the clip counter; clear_clips != 0 zeroes the counters
+ *   after reading them.  Any of the three pointers may be NULL.
+ * cmhip_agc_check (host only): 0 for a valid window_log2 and parameter set (params may be NULL: the window alone),
+ *   else COOLMIC_ERROR_INVAL.
+ * cmhip_agc_design (host only): parameters from a law in dB (levels re 32768, gains re unity) and dB per second:
+ *     T = rint(32768 * 10^(target_db / 20)), Q likewise from gate_db; gains rint(4096 * 10^(dB / 20));
+ *     rise = rint((10^(rise_db_per_s * W / rate / 20) - 1) * 65536),
+ *     fall = rint((1 - 10^(-fall_db_per_s * W / rate / 20)) * 65536),
+ *   each clamped to its range, initial into gain_min..gain_max.  COOLMIC_ERROR_INVAL for a non-finite input, a rate
+ *   that is not positive, a window_log2 that is no integer in 6..14, negative rates of change, or min_gain_db above
+ *   max_gain_db; COOLMIC_ERROR_FAULT for NULL.  3 dB/s and 10 dB/s at w = 12, 48 kHz give 1960 and 6132. */
+typedef struct cmhip_agc cmhip_agc_t;
+typedef struct cmhip_agc_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int window_log2;     /* w in 6..14: the gain moves once per 2^w frames */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_agc_desc_t;
+typedef struct cmhip_agc_params {
+    uint16_t target, gate, gain_min, gain_max, rise, fall, initial;
+} cmhip_agc_params_t;
+typedef struct cmhip_agc_law_desc {
+    double rate;                  /* frames per second */
+    double window_log2;           /* the object's w */
+    double target_db, gate_db;    /* dB re 32768 */
+    double max_gain_db, min_gain_db, initial_gain_db;      /* dB re unity */
+    double rise_db_per_s, fall_db_per_s;                   /* >= 0 */
+} cmhip_agc_law_desc_t;
+cmhip_agc_t *cmhip_agc_new(const cmhip_agc_desc_t *d);
+void     cmhip_agc_free(cmhip_agc_t *m);
+int      cmhip_agc_set(cmhip_agc_t *m, long stream, const cmhip_agc_params_t *p);
+int      cmhip_agc_get(const cmhip_agc_t *m, unsigned int stream, cmhip_agc_params_t *p);
+int      cmhip_agc_run(cmhip_agc_t *m, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_agc_reset(cmhip_agc_t *m, long stream);
+int      cmhip_agc_state(cmhip_agc_t *m, uint32_t *gain /* [S] */, uint32_t *level /* [S] */, uint64_t *clips /* [S] */,
+                         int clear_clips);
+int      cmhip_agc_sync(cmhip_agc_t *m);
+void    *cmhip_agc_hip_stream(cmhip_agc_t *m);
+/* host only, no device needed */
+int      cmhip_agc_check(unsigned int window_log2, const cmhip_agc_params_t *p);
+int      cmhip_agc_design(const cmhip_agc_law_desc_t *law, cmhip_agc_params_t *p);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

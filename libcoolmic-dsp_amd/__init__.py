@@ -148,6 +148,29 @@ class DelayDesc(C.Structure):
                 ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class AgcDesc(C.Structure):
+    """cmhip_agc_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("window_log2", C.c_uint),
+                ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
+AGC_PARAM_NAMES = ("target", "gate", "gain_min", "gain_max", "rise", "fall", "initial")
+
+
+class AgcParams(C.Structure):
+    """cmhip_agc_params_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_uint16) for n in AGC_PARAM_NAMES]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n in AGC_PARAM_NAMES}
+
+
+class AgcLawDesc(C.Structure):
+    """cmhip_agc_law_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("rate", "window_log2", "target_db", "gate_db", "max_gain_db", "min_gain_db",
+                                          "initial_gain_db", "rise_db_per_s", "fall_db_per_s")]
+
+
 class DynCurveDesc(C.Structure):
     """cmhip_dyn_curve_desc_t (include/coolmic_hip.h)"""
     _fields_ = [(n, C.c_double) for n in ("comp_threshold_db", "comp_ratio", "comp_knee_db", "gate_threshold_db",
@@ -291,6 +314,17 @@ SIGNATURES = {
     "cmhip_delay_max_delay": (C.c_size_t, [_vp]),
     "cmhip_delay_ms": (C.c_uint32, [C.c_uint, C.c_double]),
     "cmhip_delay_crossfade": (C.c_int16, [C.c_int16, C.c_int16, C.c_uint32]),
+    "cmhip_agc_new": (_vp, [_P(AgcDesc)]),
+    "cmhip_agc_free": (None, [_vp]),
+    "cmhip_agc_set": (C.c_int, [_vp, C.c_long, _P(AgcParams)]),
+    "cmhip_agc_get": (C.c_int, [_vp, C.c_uint, _P(AgcParams)]),
+    "cmhip_agc_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_agc_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_agc_state": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "cmhip_agc_sync": (C.c_int, [_vp]),
+    "cmhip_agc_hip_stream": (_vp, [_vp]),
+    "cmhip_agc_check": (C.c_int, [C.c_uint, _P(AgcParams)]),
+    "cmhip_agc_design": (C.c_int, [_P(AgcLawDesc), _P(AgcParams)]),
     "cmhip_mix_new": (_vp, [_P(MixDesc)]),
     "cmhip_mix_free": (None, [_vp]),
     "cmhip_mix_set_matrix": (C.c_int, [_vp, C.c_long, _vp]),
@@ -534,6 +568,19 @@ if hasattr(lib, "cmhip_test_plan_delay"):       # (not in builds older than the 
     lib.cmhip_test_delay_new_dry.argtypes = [_P(DelayDesc)]
     lib.cmhip_test_delay_tap.restype = None
     lib.cmhip_test_delay_tap.argtypes = [C.c_uint32] * 5 + [_P(C.c_uint32), _P(C.c_uint32)]
+if hasattr(lib, "cmhip_test_plan_agc"):         # (not in builds older than the leveller)
+    lib.cmhip_test_plan_agc.restype = None
+    lib.cmhip_test_plan_agc.argtypes = [C.c_uint32] * 3 + [C.c_uint64, C.c_uint32, C.c_void_p]
+    lib.cmhip_test_agc_run.restype = None
+    lib.cmhip_test_agc_run.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.cmhip_test_agc_tile.restype = None
+    lib.cmhip_test_agc_tile.argtypes = [C.c_uint32] * 6 + [C.c_void_p, C.c_void_p]
+    lib.cmhip_test_agc_new_dry.restype = _vp
+    lib.cmhip_test_agc_new_dry.argtypes = [_P(AgcDesc)]
+    lib.cmhip_test_agc_step.restype = C.c_uint32
+    lib.cmhip_test_agc_step.argtypes = [C.c_uint32, C.c_uint32, _P(AgcParams)]
+    lib.cmhip_test_agc_run_events.restype = C.c_int
+    lib.cmhip_test_agc_run_events.argtypes = [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _P(C.c_void_p)]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -747,6 +794,81 @@ def test_delay_without_device(streams, channels, max_delay, max_frames):
     """Test hook (cmhip_test_delay_new_dry): a Delay with the host mirror and every check but no device behind it, for
     the refusals on a machine without a GPU; a run that would launch is refused."""
     return Delay(streams, channels, max_delay, max_frames, _new=lib.cmhip_test_delay_new_dry)
+
+
+class AgcPlan(C.Structure):
+    """cmhip::AgcPlan (csrc/agc_plan.h): what the leveller's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_log2", "nw",
+                                                                "step_grid")]
+
+
+class AgcRun(C.Structure):
+    """cmhip::AgcRun (csrc/agc_plan.h): the windows a stream's run touches"""
+    _fields_ = [("first", C.c_uint64)] + [(n, C.c_uint32) for n in ("nwin", "complete", "head", "tail")]
+
+
+class AgcTile(C.Structure):
+    """cmhip::AgcTile (csrc/agc_plan.h)"""
+    _fields_ = [(n, C.c_uint32) for n in ("fa", "fb", "win", "j")]
+
+
+class AgcSpan(C.Structure):
+    """cmhip::AgcSpan (csrc/agc_plan.h)"""
+    _fields_ = [(n, C.c_uint32) for n in ("sa", "hend", "vb", "ve", "tb", "sb")]
+
+
+def plan_agc(streams, channels, window_log2, max_frames, frames):
+    """Test hook: the launch plan of a leveller run whose longest stream has `frames` frames (host logic, no GPU)"""
+    p = AgcPlan()
+    lib.cmhip_test_plan_agc(streams, channels, window_log2, max_frames, frames, C.addressof(p))
+    return p
+
+
+def agc_run(pos, count, window_log2):
+    """Test hook: cmhip::agc_run (csrc/agc_plan.h), the windows of a run of `count` frames from position `pos`"""
+    r = AgcRun()
+    lib.cmhip_test_agc_run(pos, count, window_log2, C.addressof(r))
+    return r
+
+
+def agc_tile(pos_lo, count, window_log2, tile_log2, t, channels):
+    """Test hook: cmhip::agc_tile and agc_tile_span (csrc/agc_plan.h) -> (AgcTile, AgcSpan)"""
+    tl, sp = AgcTile(), AgcSpan()
+    lib.cmhip_test_agc_tile(pos_lo, count, window_log2, tile_log2, t, channels, C.addressof(tl), C.addressof(sp))
+    return tl, sp
+
+
+def agc_params(**kw):
+    """an AgcParams: the creation defaults (a copy) with `kw` over them"""
+    f = dict(target=3277, gate=33, gain_min=4096, gain_max=4096, rise=0, fall=0, initial=4096)
+    f.update(kw)
+    return AgcParams(**f)
+
+
+def agc_step(A, L, params):
+    """Test hook (cmhip_test_agc_step): the header's step(A, L) as code"""
+    return lib.cmhip_test_agc_step(A, L, C.byref(params))
+
+
+def agc_check(window_log2, params=None):
+    """cmhip_agc_check -> error number"""
+    return lib.cmhip_agc_check(window_log2, C.byref(params) if params is not None else None)
+
+
+def agc_design(rate, window_log2, target_db, gate_db, max_gain_db, min_gain_db, initial_gain_db, rise_db_per_s,
+               fall_db_per_s):
+    """cmhip_agc_design -> AgcParams"""
+    law = AgcLawDesc(rate, window_log2, target_db, gate_db, max_gain_db, min_gain_db, initial_gain_db, rise_db_per_s,
+                     fall_db_per_s)
+    p = AgcParams()
+    _check("agc_design", lib.cmhip_agc_design(C.byref(law), C.byref(p)))
+    return p
+
+
+def test_agc_without_device(streams, channels, window_log2, max_frames):
+    """Test hook (cmhip_test_agc_new_dry): a Leveller with the host mirror and every check but no device behind it, for
+    the refusals on a machine without a GPU"""
+    return Leveller(streams, channels, window_log2, max_frames, _new=lib.cmhip_test_agc_new_dry)
 
 
 def delay_ms(rate, ms):
@@ -1384,7 +1506,7 @@ class Batch:
 
 
 class _Stage:
-    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay): the end of the handle `h`, its
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay, Leveller): the end of the handle `h`, its
     stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
 
     _stem = None
@@ -1557,6 +1679,56 @@ class Delay(_Stage):
 
     def reset(self, stream=-1):
         _check("delay_reset", lib.cmhip_delay_reset(self.h, stream))
+
+
+class Leveller(_Stage):
+    """cmhip_agc_t: slow automatic gain control of S streams beside a batch: the gain moves once per window of
+    2^window_log2 frames towards target / level.  `params` (an AgcParams): set for every stream at creation (default:
+    a copy)."""
+
+    _stem = "agc"
+
+    def __init__(self, streams, channels, window_log2, max_frames, params=None, device=0, hip_stream=None, _new=None):
+        d = AgcDesc(device, streams, channels, window_log2, max_frames, hip_stream)
+        self.h = (_new or lib.cmhip_agc_new)(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_agc_new", ERROR_INVAL)
+        self.streams, self.channels, self.window_log2, self.max_frames = streams, channels, window_log2, max_frames
+        if params is not None:
+            self.set(-1, params)
+
+    def set_rc(self, stream, params):
+        """cmhip_agc_set as it is -> error number"""
+        return lib.cmhip_agc_set(self.h, stream, C.byref(params))
+
+    def set(self, stream, params):
+        """the stream's parameters from its next window edge on (stream -1: every stream)"""
+        _check("agc_set", self.set_rc(stream, params))
+
+    def get(self, stream):
+        p = AgcParams()
+        _check("agc_get", lib.cmhip_agc_get(self.h, stream, C.byref(p)))
+        return p
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_agc_run as it is -> error number"""
+        return lib.cmhip_agc_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers)"""
+        _check("agc_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        _check("agc_reset", lib.cmhip_agc_reset(self.h, stream))
+
+    def state(self, clear_clips=False):
+        """-> (gain uint32 [S], level uint32 [S], clips uint64 [S]); a synchronous round trip"""
+        g = np.zeros(self.streams, dtype=np.uint32)
+        lv = np.zeros(self.streams, dtype=np.uint32)
+        c = np.zeros(self.streams, dtype=np.uint64)
+        _check("agc_state", lib.cmhip_agc_state(self.h, g.ctypes.data, lv.ctypes.data, c.ctypes.data,
+                                                1 if clear_clips else 0))
+        return g, lv, c
 
 
 class Mixer(_Stage):

@@ -13,6 +13,7 @@
 //   cmhip_bus.hip      the mix bus
 //   cmhip_lim.hip      the peak limiter
 //   cmhip_dyn.hip      the dynamics stage: compressor and gate
+//   cmhip_agc.hip      the leveller: slow automatic gain control
 #pragma once
 
 #include "cmhip_internal.h"

@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -11,6 +11,7 @@
 #include "dyn_plan.h"
 #include "split_plan.h"
 #include "delay_plan.h"
+#include "agc_plan.h"
 
 namespace cmhip {
 
@@ -367,6 +368,33 @@ struct DelayArgs {
     uint32_t       tile_vecs;      // 16-byte vectors per tile
 };
 
+// Leveller (k_agc.hip; the arithmetic: include/coolmic_hip.h, the windows and tiles: csrc/agc_plan.h).  What a stream
+// carries from run to run, written by k_agc_step alone:
+struct AgcState {
+    unsigned long long psum[16];   // the open window's sums of squares so far, per channel
+    uint32_t a_lo, a_hi;           // the gain nodes of the window the stream's last frame lies in: A[k], A[k+1]
+    uint32_t level;                // L of the last complete window
+    uint32_t pad;
+};
+// a run of a leveller over S stream slots
+struct AgcArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *rec;           // [S][AGC_REC] the run's records: count, pos, the parameters
+    unsigned long long *table;     // [S][nw][C] the run's sums of squares per window and channel; zero between runs
+    uint32_t      *nodes;          // [S][nw + 1] the run's gain nodes: window i has nodes i and i + 1
+    AgcState      *state;          // [S]
+    unsigned long long *clips;     // [S] clamped samples
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       w;              // window_log2
+    // (the launcher fills these in)
+    uint32_t       nw;             // windows per stream in the tables
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_log2;      // frames per tile, as a power of two
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -520,6 +548,10 @@ hipError_t launch_split(const SplitArgs &a, hipStream_t st);
 // Delay (k_delay.hip): one workgroup per stream and tile; the plan is csrc/delay_plan.h's.  frames: the run's largest
 // count, max_delay and max_frames the object's.
 hipError_t launch_delay(const DelayArgs &a, uint32_t max_delay, uint32_t max_frames, uint32_t frames, hipStream_t st);
+// Leveller (k_agc.hip): k_agc_energy, k_agc_step and k_agc_apply, in that order; the plan is csrc/agc_plan.h's.  frames:
+// the run's largest count, max_frames the object's.  ev: nullptr, or four events recorded in front of, between and behind
+// the three launches (tools/bench_agc.py).
+hipError_t launch_agc(const AgcArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,
