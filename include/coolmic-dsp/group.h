@@ -87,10 +87,18 @@ int                 coolmic_group_pump(coolmic_group_t *self);
  * counts; 0 or 1: the pumping thread alone, which is how a group starts).  The handles of DIFFERENT streams
  * are then read at the same time, each stream's own handle still by one thread at a time and once per pump:
  * fine for the sources of this library and for callbacks that keep their state per stream, as the reference's
- * pipelines do with one thread each (ref: src/simple.c:292-310).  Streams that were given the same handle, or
- * handles over the same backend object (one device, one tee), are recognised when they are added and stay on
- * the pumping thread, in slot order.  What the group cannot see -- read callbacks of different userdata that
- * share state behind it -- is the caller's to keep thread-safe.  COOLMIC_ERROR_INVAL above 64. */
+ * pipelines do with one thread each (ref: src/simple.c:292-310).
+ * Streams that read from one object stay on the pumping thread, in slot order, after the other threads have
+ * finished.  Recognised, when a stream is added, are: the same handle given twice; handles with the same
+ * userdata (two handles of one sound device); the reader handles of one coolmic_tee_t; and any of these behind
+ * chains of this library's transforms and tees (two transforms fed by two readers of one tee, or both fed by
+ * one device handle; a tee whose input is a reader of another tee), followed through the inputs that are
+ * attached at that moment -- a chain of 64 wrappers or more is not followed to its end and keeps its stream
+ * on the pumping thread whatever it shares.
+ * NOT recognised, and the caller's to keep thread-safe or off one group: read callbacks of different userdata
+ * that share state behind it; and whatever is attached or re-attached (coolmic_tee_attach_iohandle,
+ * coolmic_transform_attach_iohandle) upstream of a stream's handle after coolmic_group_add_stream -- attach
+ * first, add the stream afterwards.  COOLMIC_ERROR_INVAL for more than 64 threads. */
 int                 coolmic_group_set_pull_threads(coolmic_group_t *self, unsigned int threads);
 
 /* VU window of one stream since its last result; COOLMIC_ERROR_INVAL while it holds no frame */

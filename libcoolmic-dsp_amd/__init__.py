@@ -499,6 +499,11 @@ if hasattr(lib, "cmhip_test_plan_run"):         # (not in builds older than the 
     lib.cmhip_test_plan_run.restype = None
     lib.cmhip_test_plan_run.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]
+if hasattr(lib, "cmhip_test_iohandle_root"):    # (not in builds older than the group's roots of shared sources)
+    lib.cmhip_test_iohandle_root.restype = C.c_void_p
+    lib.cmhip_test_iohandle_root.argtypes = [_vp]
+    lib.cmhip_test_group_shared_source.restype = C.c_int
+    lib.cmhip_test_group_shared_source.argtypes = [_vp, C.c_uint]
 lib.cmhip_test_merge_windows.restype = C.c_int
 lib.cmhip_test_merge_windows.argtypes = [_P(C.c_uint64), C.c_uint, C.c_uint, C.c_uint, _P(VuResult)]
 if hasattr(lib, "cmhip_test_unpack_finished"):  # (not in builds older than the device-side dB finish)
@@ -2193,6 +2198,12 @@ class IoHandle:
     def refcount(self):
         return lib.coolmic_ro_refcount(self.ptr)
 
+    def root(self):
+        """Test hook (cmhip_test_iohandle_root, needs no GPU): the address of the object this handle finally reads
+        from, through the tees and transforms attached right now; None for a chain too long to walk.  Streams of
+        a group whose handles have one root stay on the pumping thread."""
+        return lib.cmhip_test_iohandle_root(self.ptr)
+
     def unref(self):
         if self.ptr:
             lib.coolmic_ro_unref(self.ptr)
@@ -2365,6 +2376,11 @@ class Group:
 
     def set_pull_threads(self, threads):
         return lib.coolmic_group_set_pull_threads(self.ptr, threads)
+
+    def shared_source(self, slot):
+        """Test hook (cmhip_test_group_shared_source): 1 when the stream was recognised as reading from the same
+        object as another stream of the group (it stays on the pumping thread), 0 when not, ERROR_INVAL: no slot"""
+        return lib.cmhip_test_group_shared_source(self.ptr, slot)
 
     def vumeter_result(self, slot):
         r = VuResult()

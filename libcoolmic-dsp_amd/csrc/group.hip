@@ -34,8 +34,10 @@ struct GroupStream {
     std::vector<unsigned char> spill;        // ... and what had to leave a set that was needed again
     size_t spill_pos;                        //     (older than every segment)
     size_t pending;                          // bytes in spill and segments together
-    bool shared_source;                      // another stream of the group reads the same handle or the same backend
-                                             // state: always pulled on the pumping thread, in slot order
+    const void *root;                        // what the source finally read from when the stream was added
+                                             // (coolmic_iohandle_root; NULL: the chain was too long to walk)
+    bool shared_source;                      // another stream of the group reads the same handle or has the same
+                                             // root (or there is no root): always pulled on the pumping thread, in slot order
 };
 
 struct coolmic_group {
@@ -204,14 +206,16 @@ extern "C" int coolmic_group_add_stream(coolmic_group_t *self, coolmic_iohandle_
     s.carry_fill = 0;
     s.spill_pos = 0;
     s.pending = 0;
-    s.shared_source = false;
-    // Two streams over one upstream object (the same handle twice, or two handles whose backend is one device,
-    // one file, one tee) would race on its state once the pump's reads run on several threads
+    // Two streams over one upstream object (the same handle twice, or two handles with one root: two handles of
+    // one device, two readers of one tee, transforms and tees chained above either -- coolmic_iohandle_root, as
+    // the chain stands now) would race on its state once the pump's reads run on several threads
     // (coolmic_group_set_pull_threads): such streams are marked and keep being read by the pumping thread
-    // alone, one after the other, as a single-threaded pump reads everything.
-    const void *backend = coolmic_iohandle_backend(source);
+    // alone, one after the other and after the helpers have finished, as a single-threaded pump reads everything.
+    // A chain too long to walk (no root) is marked on its own account: what it shares cannot be known.
+    s.root = coolmic_iohandle_root(source);
+    s.shared_source = s.root == nullptr;
     for (auto &o : *self->streams) {
-        if (o.source == source || (backend != nullptr && coolmic_iohandle_backend(o.source) == backend)) {
+        if (o.source == source || (s.root != nullptr && o.root == s.root)) {
             o.shared_source = true;
             s.shared_source = true;
         }
@@ -356,6 +360,19 @@ extern "C" int coolmic_group_set_pull_threads(coolmic_group_t *self, unsigned in
     delete self->pullers;                    // (no pump is under way: the group is driven by one thread)
     self->pullers = threads > 1 ? new WorkPool(threads - 1) : nullptr;     // the pumping thread pulls too
     return COOLMIC_ERROR_NONE;
+}
+
+// test hooks: the root a handle has right now (no GPU behind it), and whether a stream was marked as sharing
+// its source (1 / 0; COOLMIC_ERROR_INVAL: no such slot)
+extern "C" const void *cmhip_test_iohandle_root(coolmic_iohandle_t *h) { return coolmic_iohandle_root(h); }
+
+extern "C" int cmhip_test_group_shared_source(coolmic_group_t *g, unsigned slot)
+{
+    if (!g)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= g->streams->size())
+        return COOLMIC_ERROR_INVAL;
+    return (*g->streams)[slot].shared_source ? 1 : 0;
 }
 
 // One block: pull from every source straight into the input set the kernel will read, then (the

@@ -35,8 +35,16 @@ int coolmic_hip_check_device(int device);
 #pragma GCC visibility push(hidden)
 
 ssize_t coolmic_transform_handle_read(void *userdata, void *buffer, size_t len);
-const void *coolmic_iohandle_backend(const coolmic_iohandle_t *self);
 ssize_t coolmic_tee_reader_read(void *userdata, void *buffer, size_t len);
+
+/* Which streams of a group read from one object (group.hip): the root of a handle (iohandle.c), found through
+ * the input a tee (tee.c; *tee: the tee of reader handle `reader`) or a transform (transform.c) has attached
+ * right now; NULL: none */
+#define COOLMIC_IOHANDLE_ROOT_STEPS 64
+const void *coolmic_iohandle_root(coolmic_iohandle_t *self);
+coolmic_iohandle_t *coolmic_tee_reader_input(void *reader, const void **tee);
+struct coolmic_transform;
+coolmic_iohandle_t *coolmic_transform_input(struct coolmic_transform *self);
 
 /* A VU meter attached directly to a transform's handle shares the transform's launch (vumeter.c,
  * transform.c): the handle is recognised, the transform accumulates the window, the meter reads it. */

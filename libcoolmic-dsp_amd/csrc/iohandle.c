@@ -37,10 +37,33 @@ coolmic_iohandle_t *coolmic_iohandle_new(const char *name, igloo_ro_t associated
     return h;
 }
 
-/* (internal: what a handle reads from -- two handles over the same userdata share their backend's state) */
-const void *coolmic_iohandle_backend(const coolmic_iohandle_t *self)
+/* (internal: the object a handle finally reads from -- two handles with the same root share its state, and
+ * that of everything between them and it.  The walk goes down through the wrappers this library can recognise,
+ * as they are attached at the moment of the call: a tee's reader continues with the tee's input (none: the tee
+ * is the root), a transform's handle with the transform's input (none: the transform is the root); anything
+ * else ends the walk with its userdata (none: the handle itself).  NULL: no handle, or a chain longer than
+ * COOLMIC_IOHANDLE_ROOT_STEPS wrappers -- a cycle built by the caller must not hang whoever asks.) */
+const void *coolmic_iohandle_root(coolmic_iohandle_t *self)
 {
-    return self != NULL ? self->userdata : NULL;
+    unsigned int steps;
+
+    for (steps = 0; self != NULL && steps < COOLMIC_IOHANDLE_ROOT_STEPS; steps++) {
+        coolmic_iohandle_t *in;
+        const void *wrapper;
+
+        if (self->read_fn == coolmic_tee_reader_read) {
+            in = coolmic_tee_reader_input(self->userdata, &wrapper);
+        } else if (self->read_fn == coolmic_transform_handle_read) {
+            in = coolmic_transform_input(self->userdata);
+            wrapper = self->userdata;
+        } else {
+            return self->userdata != NULL ? self->userdata : (const void *)self;
+        }
+        if (in == NULL)
+            return wrapper;
+        self = in;
+    }
+    return NULL;
 }
 
 ssize_t coolmic_iohandle_read(coolmic_iohandle_t *self, void *buffer, size_t len)

@@ -202,6 +202,17 @@ coolmic_iohandle_t *coolmic_tee_get_iohandle(coolmic_tee_t *self, ssize_t index)
     return h;
 }
 
+/* ---- for the root of a reader handle (internal: iohandle.c; declared in host_internal.h) --------- */
+
+/* what the tee of reader handle `userdata` reads from right now (NULL: nothing attached), and the tee */
+coolmic_iohandle_t *coolmic_tee_reader_input(void *userdata, const void **tee)
+{
+    tee_reader_t *r = userdata;
+
+    *tee = r->tee;
+    return r->tee->in;
+}
+
 /* ---- for a VU meter on a reader handle (internal: vumeter.c; declared in host_internal.h) -------- */
 
 /* the transform right above the tee of reader handle `userdata` (NULL: none), the position of that reader's

@@ -139,6 +139,12 @@ int coolmic_transform_attach_iohandle(coolmic_transform_t *self, coolmic_iohandl
     return COOLMIC_ERROR_NONE;
 }
 
+/* (internal: iohandle.c walks through a transform to the root of its handle) */
+coolmic_iohandle_t *coolmic_transform_input(coolmic_transform_t *self)
+{
+    return self->io;
+}
+
 /* the parameters read at generation `gen` are on the device (or no device exists yet) */
 static void transform_settled(coolmic_transform_t *t, unsigned long gen)
 {

@@ -350,10 +350,12 @@ def test_stage_device_setters(gpu, oracle):
 
 def test_streams_that_share_a_source_stay_on_the_pumping_thread(gpu, oracle):
     """coolmic_group_set_pull_threads(4): streams with a source of their own are pulled on four threads; two
-    streams that were given the SAME handle, and two with different handles over one backend (two readers of one
-    tee would be that; here two get_iohandle() of one sound device), are recognised at add_stream and read by the
-    pumping thread alone, in slot order -- so what each of them gets is what a single-threaded pump gives:
-    alternating blocks of the shared source."""
+    streams that were given the SAME handle, and two with different handles of one sound device (two
+    get_iohandle() of it), are recognised at add_stream and read by the pumping thread alone, in slot order -- so
+    what each of them gets is what a single-threaded pump gives: alternating blocks of the shared source.  The
+    witness here is the data, and a device or one handle is all it covers; the readers of a tee, whose handles
+    share neither address nor userdata, and the thread that reads them:
+    test_streams_behind_one_tee_stay_on_the_pumping_thread."""
     cm = gpu
     C, N, block, blocks = 1, 20, 256, 6
     grp = cm.Group(C, N, block, queue_blocks=blocks + 2)
@@ -396,4 +398,164 @@ def test_streams_that_share_a_source_stay_on_the_pumping_thread(gpu, oracle):
         assert np.array_equal(got, oracle.gain_apply(g, want, 1)), i
     for h in handles:
         h.unref()
+    grp.unref()
+
+
+# ---- which thread reads a shared source -----------------------------------------------------------------------
+# The data cannot tell: two threads inside one tee may well deliver the right bytes, or crash once a week.  The
+# witness is the identity of the thread each upstream read came from.
+
+PT_N, PT_BLOCK, PT_PUMPS, PT_THREADS = 48, 256, 12, 4
+# The pool hands out chunks of 8 slots and the pumping thread takes chunk 0 while the helpers wake: the sources
+# of slots 0..7 sleep this long in every read, which keeps it there (about 8 ms a pump) while the helpers go
+# through chunks 1..5 -- where the streams that share a source sit.  (A helper still spinning from the pump
+# before may take chunk 0 instead; then two helpers and the pumping thread share the rest.)  1 ms is what the
+# MI355X host needed: over two runs of the five cases, between 215 and 456 of the 432 to 456 reads of slots
+# 8..47 came from a helper where a tee is in the group, 312 and 480 of 480 where none is.  The set-up assertion
+# below checks it in every run; if it ever fails, lengthen this, never relax that.
+PT_CONTROL_SLEEP_S = 0.001
+
+
+class _RecordedSource:
+    """a callback source: consecutive bytes of `pcm`, and for every read the thread it came from and what it got"""
+
+    def __init__(self, cm, pcm, sleep=0.0):
+        import threading
+        import time
+        self.pcm = pcm
+        self.data = pcm.tobytes()
+        self.pos = 0
+        self.reads = []
+
+        def read(n):
+            if sleep:
+                time.sleep(sleep)
+            k = min(n, len(self.data) - self.pos)
+            self.reads.append((threading.get_ident(), k))
+            out = self.data[self.pos:self.pos + k]
+            self.pos += k
+            return out
+
+        self.handle = cm.IoHandle.from_callbacks(read, eof=lambda: 1 if self.pos >= len(self.data) else 0)
+
+
+# case -> (readers of the tee, slot of each reader's stream, a transform between reader and group, slot added late)
+PT_CASES = {
+    "two-readers": (2, (19, 43), False, None),
+    "four-readers": (4, (11, 19, 35, 43), False, None),
+    "two-transforms": (2, (19, 43), True, None),
+    "second-reader-added-late": (2, (19, 47), False, 47),
+    "no-shared-source": (0, (), False, None),
+}
+
+
+@pytest.mark.parametrize("case", list(PT_CASES))
+def test_streams_behind_one_tee_stay_on_the_pumping_thread(gpu, oracle, case):
+    """coolmic_group_set_pull_threads(4) over 48 streams whose sources are callbacks that note the calling thread.
+    The readers of one coolmic_tee_t are different handles with different userdata over one buffer without a
+    lock: the group has to find the tee behind them (and behind transforms attached to them) when they are added,
+    mark the streams (cmhip_test_group_shared_source: 1 for exactly those slots), and read them on the pumping
+    thread.  Asserted per case: every read of the tee's upstream came from the pumping thread -- in the late case
+    from the moment the second reader is added, which also marks the first --, the upstream was read front to
+    back once, in whole blocks; every reader got ALL of it (a tee, not one handle given twice), and every
+    stream's PCM is the oracle's gain over its own source.  The run only counts if the helpers did read: at least
+    one source of slots 8..47 must have been read from another thread (set-up assertion).  The case without a
+    tee is the control: no slot marked, everything else the same."""
+    import threading
+    cm = gpu
+    readers, slots, through_transform, late = PT_CASES[case]
+    N, block, pumps = PT_N, PT_BLOCK, PT_PUMPS
+    nbytes = 2 * block
+    me = threading.get_ident()
+    grp = cm.Group(1, N, block, queue_blocks=4)
+    assert grp.set_pull_threads(PT_THREADS) == 0
+
+    up = _RecordedSource(cm, oracle.lcg(4242, block * pumps))
+    tee, shared, transforms = None, {}, []                  # shared: slot -> (handle to add, gain before the group)
+    if readers:
+        tee = cm.Tee(readers)
+        assert tee.attach(up.handle) == 0
+        for k, slot in enumerate(slots):
+            h, pre = tee.get_iohandle(k), None
+            if through_transform:
+                tr = cm.Transform(48000, 1)
+                pre = [1500, 700][k]
+                assert tr.attach(h) == 0 and tr.set_master_gain(1, 1000, [pre]) == 0
+                h.unref()
+                h = tr.get_iohandle()
+                transforms.append(tr)
+            shared[slot] = (h, pre)
+    controls, handles, gains = {}, {}, {}
+
+    def add(slot):
+        if slot in shared:
+            src = shared[slot][0]
+        else:
+            controls[slot] = _RecordedSource(cm, oracle.lcg(7000 + slot, block * pumps),
+                                             sleep=PT_CONTROL_SLEEP_S if slot < 8 else 0.0)
+            src = controls[slot].handle
+        assert grp.add_stream(src) == slot
+        gains[slot] = [700 + 37 * slot]                      # every stream its own, the sharing ones too
+        assert grp.set_master_gain(slot, 1, 1000, gains[slot]) == 0
+        handles[slot] = grp.get_iohandle(slot)
+
+    for slot in range(N):
+        if slot != late:
+            add(slot)
+    got = {slot: b"" for slot in range(N)}
+    late_mark = 0
+    for p in range(pumps):
+        if late is not None and p == pumps // 2:
+            assert [grp.shared_source(s) for s in range(N - 1)] == [0] * (N - 1)
+            late_mark = len(up.reads)
+            add(late)
+            assert grp.shared_source(slots[0]) == 1 and grp.shared_source(late) == 1    # the older stream too
+        assert grp.pump() == grp.streams()
+        for slot in range(grp.streams()):                    # (the block just pumped: no read here pumps again)
+            n, data = handles[slot].read(nbytes)
+            assert n == nbytes, (p, slot, n)
+            got[slot] += data
+        if late is not None and p < pumps // 2:              # a tee's reader that is not read stalls the others:
+            n, data = shared[late][0].read(nbytes)           # until it joins the group the test reads it, between pumps
+            assert data == up.data[p * nbytes:(p + 1) * nbytes]
+
+    # the marks: deterministic
+    assert [grp.shared_source(s) for s in range(N)] == [1 if s in shared else 0 for s in range(N)]
+    assert grp.shared_source(N) == cm.ERROR_INVAL
+    # the set-up: the helpers did pull
+    far = [t for s, c in controls.items() if s >= 8 for t, _ in c.reads]
+    off = sum(1 for t in far if t != me)
+    print("pull threads, %s: %d of %d reads of the control sources in slots 8..47 came from a helper thread "
+          "(the sources of slots 0..7 sleep %.1f ms a read)" % (case, off, len(far), 1e3 * PT_CONTROL_SLEEP_S))
+    assert off > 0, "set-up failure: every source was read by the pumping thread, the helpers never pulled"
+    # the controls: one read of a block per pump, the oracle's chain (as test_group_pull_spread_over_threads)
+    for slot, c in controls.items():
+        assert [k for _, k in c.reads] == [nbytes] * pumps, slot
+        assert np.array_equal(np.frombuffer(got[slot], np.int16), _expect(oracle, c.pcm, 1, gains[slot], None)), slot
+    if readers:
+        # the tee's upstream: only the pumping thread, front to back, once, never past the data
+        assert [t for t, _ in up.reads[late_mark:]] == [me] * (len(up.reads) - late_mark), up.reads
+        assert [k for _, k in up.reads] == [nbytes] * pumps and up.pos == len(up.data)
+        for slot, (_, pre) in shared.items():
+            first = pumps // 2 * block if slot == late else 0                # (the late reader's first half: above)
+            assert len(got[slot]) == len(up.data) - 2 * first, slot
+            x = up.pcm[first:]
+            if pre is not None:
+                _, g = oracle.gain(1, 1, 1000, [pre])
+                x = oracle.gain_apply(g, x, 1)
+            assert np.array_equal(np.frombuffer(got[slot], np.int16), _expect(oracle, x, 1, gains[slot], None)), slot
+    else:
+        assert up.reads == []
+
+    for h in handles.values():
+        h.unref()
+    for h, _ in shared.values():
+        h.unref()
+    for c in controls.values():
+        c.handle.unref()
+    for tr in transforms:
+        tr.unref()
+    if tee:
+        tee.unref()
+    up.handle.unref()
     grp.unref()

@@ -327,6 +327,111 @@ def test_tee_fanout(cm):
     a.unref(); b.unref(); tee.unref()
 
 
+def test_readers_of_one_tee_are_different_handles_with_one_root(cm):
+    """What a group compares to keep streams over one object on the pumping thread (group.h,
+    coolmic_group_set_pull_threads).  Every coolmic_tee_get_iohandle() makes a handle AND a reader record of its
+    own, so neither the handle nor its userdata says that two readers pull from one tee: the root does.  (Every
+    object stays alive until the last comparison: a freed address may come back.)"""
+    src = cm.IoHandle.from_bytes(bytes(64))
+    tee = cm.Tee(2)
+    assert tee.attach(src) == 0
+    a, b = tee.get_iohandle(0), tee.get_iohandle(1)
+    assert a.ptr != b.ptr
+    assert a.root() is not None and a.root() == b.root() == src.root()
+    assert src.root() == src.ptr                        # a callback handle without userdata is its own root
+    # nothing attached: the tee itself is the root, and another tee is another root
+    bare, other = cm.Tee(2), cm.Tee(2)
+    c, d, e = bare.get_iohandle(0), bare.get_iohandle(1), other.get_iohandle(0)
+    assert c.ptr != d.ptr
+    assert c.root() == d.root() == bare.ptr and e.root() == other.ptr
+    assert len({a.root(), c.root(), e.root()}) == 3
+    # ... as the chain stands at the moment of the question: attached now, the readers follow the input
+    assert bare.attach(src) == 0
+    assert c.root() == d.root() == src.root()
+    assert bare.attach(None) == 0
+    assert c.root() == bare.ptr
+    assert cm.lib.cmhip_test_iohandle_root(None) is None
+    for h in (a, b, c, d, e, src):
+        h.unref()
+    for t in (tee, bare, other):
+        t.unref()
+
+
+def test_roots_through_chains_of_transforms_and_tees(cm):
+    """One level down: transforms over the readers of one tee, transforms over one device handle, a tee behind a
+    tee -- different userdata in front, one object behind.  No read happens here, so no GPU is needed."""
+    src = cm.IoHandle.from_bytes(bytes(64))
+    tee = cm.Tee(2)
+    assert tee.attach(src) == 0
+    ra, rb = tee.get_iohandle(0), tee.get_iohandle(1)
+    ta, tb = cm.Transform(48000, 1), cm.Transform(48000, 1)
+    assert ta.attach(ra) == 0 and tb.attach(rb) == 0
+    ha, hb = ta.get_iohandle(), tb.get_iohandle()
+    assert ha.ptr != hb.ptr and ha.root() == hb.root() == src.root()
+    # a transform with nothing attached is its own root
+    lone = cm.Transform(48000, 1)
+    hl = lone.get_iohandle()
+    assert hl.root() == lone.ptr and hl.root() != ha.root()
+    # two transforms attached to the SAME handle of a sound device, and a second handle of that device
+    dev = cm.Snddev("sine", 48000, 1)
+    dh, dh2 = dev.get_iohandle(), dev.get_iohandle()
+    tc, td = cm.Transform(48000, 1), cm.Transform(48000, 1)
+    assert tc.attach(dh) == 0 and td.attach(dh) == 0
+    hc, hd = tc.get_iohandle(), td.get_iohandle()
+    assert hc.ptr != hd.ptr and hc.root() == hd.root() == dh.root() == dh2.root()
+    assert hc.root() != ha.root()
+    dev2 = cm.Snddev("sine", 48000, 1)                   # another device is another root
+    dh3 = dev2.get_iohandle()
+    assert dh3.root() not in (None, dh.root())
+    # tee B reads from reader 0 of tee A: B's reader and A's other reader pull from the same source
+    tee_b = cm.Tee(2)
+    assert tee_b.attach(ra) == 0
+    rb0 = tee_b.get_iohandle(0)
+    assert rb0.root() == rb.root() == src.root()
+    for h in (ra, rb, ha, hb, hl, dh, dh2, dh3, hc, hd, rb0, src):
+        h.unref()
+    for o in (ta, tb, lone, tc, td, tee, tee_b, dev, dev2):
+        o.unref()
+
+
+def test_independent_sources_have_distinct_roots(cm):
+    hs = [cm.IoHandle.from_bytes(bytes(8 + i)) for i in range(6)]
+    hs += [cm.IoHandle.from_callbacks(lambda n: 0) for _ in range(6)]
+    roots = [h.root() for h in hs]
+    assert None not in roots and len(set(roots)) == len(hs)
+    assert roots == [h.ptr for h in hs]
+    for h in hs:
+        h.unref()
+
+
+def test_root_of_a_chain_longer_than_the_walk_returns(cm):
+    """The walk is bounded (64 wrappers): a chain at the bound still has its root, a longer one -- or a cycle
+    somebody built -- comes back with no root instead of hanging, and a group keeps such a stream on the pumping
+    thread."""
+    src = cm.IoHandle.from_bytes(bytes(16))
+    tees, readers, h = [], [], src
+    for depth in range(1, 71):                           # `depth` tees between the reader and src
+        t = cm.Tee(1)
+        assert t.attach(h) == 0
+        h = t.get_iohandle(0)
+        tees.append(t); readers.append(h)
+        assert h.root() == (src.root() if depth < 64 else None), depth
+    assert readers[62].root() == src.root() and readers[63].root() is None
+    # a cycle: a tee that reads from its own reader (taken apart again, or nothing of it would ever be freed)
+    loop = cm.Tee(2)
+    r0 = loop.get_iohandle(0)
+    assert loop.attach(r0) == 0
+    assert r0.root() is None
+    assert loop.attach(None) == 0
+    assert r0.root() == loop.ptr
+    r0.unref(); loop.unref()
+    for h in readers:
+        h.unref()
+    for t in tees:
+        t.unref()
+    src.unref()
+
+
 def test_group_needs_a_gpu(cm):
     if cm.device_count() > 0:
         pytest.skip("a GPU is present")
