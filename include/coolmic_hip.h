@@ -1250,6 +1250,106 @@ void    *cmhip_agc_hip_stream(cmhip_agc_t *m);
 int      cmhip_agc_check(unsigned int window_log2, const cmhip_agc_params_t *p);
 int      cmhip_agc_design(const cmhip_agc_law_desc_t *law, cmhip_agc_params_t *p);
 
+/* ---- filter: a biquad cascade in exact integers, an object of its own beside the batch -- */
+/* A filter runs each of S streams of C interleaved int16 channels (C in 1..16) through a cascade of N second-order
+ * sections (N in 1..8), in exact integers: a low cut per microphone in front of a leveller, a gate or a bus, a
+ * de-emphasis, a shelf, a notch.  It has cmhip_agc_t's shapes: slots, strides, alignment and refusals are
+ * cmhip_agc_run's.  The stage adds no delay (its phase is the sections' own).
+ *
+ * Geometry, per object: sections = N in 1..8.
+ * Coefficients, per stream and section, settable between runs (cmhip_iir_set, stream -1: all streams): five int32
+ *   b0, b1, b2, a1, a2 in units of 2^-26 (CMHIP_IIR_ONE = 1 << 26), a0 = 1:
+ *     H(z) = (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2).
+ *   Valid (cmhip_iir_check): every |c| <= 2^28, |a2| < 2^26 and |a1| < 2^26 + a2 -- the stability triangle, tested on
+ *   the integers.
+ *
+ * Arithmetic.  A stream's channels are independent.  Every section of every channel keeps u1, u2, v1, v2 (int32) and a
+ *   remainder e, 0 <= e < 2^26.  Per frame:
+ *     section 0 input:  u = x << 12                    int16 -> 12 fraction bits, |u| <= 2^27
+ *     section k input:  u = v of section k - 1
+ *     acc = b0 u + b1 u1 + b2 u2 - a1 v1 - a2 v2 + e   int64; |c| <= 2^28 and |state| < 2^31: |acc| < 2^62, exact
+ *     e   = acc & (2^26 - 1);   v = acc >> 26          arithmetic shift: floor
+ *     v   = clamp(v, -(2^31 - 1), 2^31 - 1)            a changed v increments the stream's `overs`
+ *     u2 = u1; u1 = u; v2 = v1; v1 = v
+ *     output: y = clamp((v_last + 2048) >> 12, -32768, 32767)      a changed y increments the stream's `clips`
+ *   The remainder fed back into the next frame (first-order error feedback) is what keeps a low cut from stalling
+ *   in a dead band: with a zero on z = 1 the output and the histories v1, v2 reach exactly zero behind a constant
+ *   input and stay there (e rests at whatever value below 2^26 it has reached, where it can move nothing).
+ *   Properties.  A unity section (b0 = 2^26, the rest 0) is the identity on u, and the output step gives x back: all
+ *     sections are unity until set, so a new object is a copy bit for bit.  A stream given 0 frames in a run keeps
+ *     everything.  Cuts: the concatenated output, both counters and the state do not depend on how a stream is cut
+ *     into runs, with the sets at the same frames.
+ * cmhip_iir_new: NULL for C outside 1..16, N outside 1..8, S = 0, max_frames = 0, max_frames * C >= 2^31, or a failed
+ *   allocation.
+ * cmhip_iir_run has cmhip_agc_run's contract: asynchronous on the object's stream; frames_per_stream (host, S entries,
+ *   may be NULL) is free on return; COOLMIC_ERROR_INVAL, with nothing launched and nothing changed, when a base is not
+ *   16-byte aligned, a stride is not a multiple of 8 samples or below frames * C, frames > max_frames, a count is above
+ *   frames, either array would end past the address space, or the two arrays share a byte; COOLMIC_ERROR_FAULT for
+ *   NULL arrays.  Outputs past a stream's count are not written.
+ * cmhip_iir_set takes effect at the stream's next frame and keeps the histories and e.  It is ordered with the runs as
+ *   the calls are and does not wait for the host: the coefficients live in a host mirror, and the table goes to the
+ *   device on the object's stream with the next run's counts, only when it has changed since the last run.
+ *   COOLMIC_ERROR_INVAL for a section cmhip_iir_check refuses, or a stream or section out of range; a refused call
+ *   changes nothing.  cmhip_iir_get answers from the mirror.
+ * cmhip_iir_reset (stream -1: all) zeroes the stream's histories and e, ordered with the runs as the calls are.  The
+ *   counters and the coefficients stay.
+ * cmhip_iir_state: synchronous (it waits for the object's stream).  Per stream, S entries each: clips[s] and overs[s];
+ *   clear != 0 zeroes both counters after reading them.  Either pointer may be NULL.
+ * cmhip_iir_check (host only): 0 for a valid section, else COOLMIC_ERROR_INVAL.
+ * cmhip_iir_design (host only): one section from the Audio EQ Cookbook's formulas (R. Bristow-Johnson), w0 = 2 pi f0 /
+ *   rate, alpha = sin w0 / (2 q), A = 10^(gain_db / 40); every coefficient is rint(c / a0 * 2^26):
+ *     BYPASS      unity
+ *     HIGHPASS    b = ((1 + cos) / 2, -(1 + cos), (1 + cos) / 2), a = (1 + alpha, -2 cos, 1 - alpha)
+ *     LOWPASS     b = ((1 - cos) / 2, 1 - cos, (1 - cos) / 2), the same a
+ *     LOWSHELF, HIGHSHELF, PEAK, NOTCH      the cookbook's, the shelves' slope through q (2 sqrt(A) alpha)
+ *     HIGHPASS1   K = tan(w0 / 2): b = (1, -1, 0) / (1 + K), a1 = (K - 1) / (1 + K), b2 = a2 = 0: a DC blocker
+ *     LOWPASS1    b = (K, K, 0) / (1 + K), the same a1: a 50 / 75 us de-emphasis is f0 = 3183.1 / 2122.1 Hz
+ *   For HIGHPASS b1 := -(b0 + b2) and for HIGHPASS1 b1 := -b0 on the integers, so the zero lies on z = 1 exactly
+ *   and the DC gain is 0, not a small number.  gain_db is read by the shelves and PEAK, q by all but the one-pole
+ *   kinds and BYPASS; all four values are checked for every kind.  COOLMIC_ERROR_INVAL for non-finite inputs, f0
+ *   outside (0, rate / 2), q <= 0, an unknown kind, or a result that cmhip_iir_check refuses; COOLMIC_ERROR_FAULT for
+ *   NULL.
+ * cmhip_iir_response_db (host only): the magnitude in dB at f Hz of the cascade of the n sections AS THE INTEGERS
+ *   REALISE IT; -inf on a zero, NaN for NULL or a rate that is not positive. */
+#define CMHIP_IIR_ONE (1 << 26)
+enum {
+    CMHIP_IIR_BYPASS = 0, CMHIP_IIR_HIGHPASS = 1, CMHIP_IIR_LOWPASS = 2, CMHIP_IIR_LOWSHELF = 3, CMHIP_IIR_HIGHSHELF = 4,
+    CMHIP_IIR_PEAK = 5, CMHIP_IIR_NOTCH = 6, CMHIP_IIR_HIGHPASS1 = 7, CMHIP_IIR_LOWPASS1 = 8
+};
+typedef struct cmhip_iir cmhip_iir_t;
+typedef struct cmhip_iir_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int sections;        /* N in 1..8 */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_iir_desc_t;
+typedef struct cmhip_iir_section {
+    int32_t b0, b1, b2, a1, a2;   /* units of 2^-26 */
+} cmhip_iir_section_t;
+typedef struct cmhip_iir_design_desc {
+    int    kind;                  /* CMHIP_IIR_... */
+    double rate;                  /* frames per second */
+    double f0;                    /* Hz, inside (0, rate / 2) */
+    double q;                     /* > 0 */
+    double gain_db;               /* shelves and PEAK */
+} cmhip_iir_design_desc_t;
+cmhip_iir_t *cmhip_iir_new(const cmhip_iir_desc_t *d);
+void     cmhip_iir_free(cmhip_iir_t *m);
+int      cmhip_iir_set(cmhip_iir_t *m, long stream, unsigned int section, const cmhip_iir_section_t *c);
+int      cmhip_iir_get(const cmhip_iir_t *m, unsigned int stream, unsigned int section, cmhip_iir_section_t *c);
+int      cmhip_iir_run(cmhip_iir_t *m, const void *in, size_t in_stride, size_t frames,
+                       const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_iir_reset(cmhip_iir_t *m, long stream);
+int      cmhip_iir_state(cmhip_iir_t *m, uint64_t *clips /* [S] */, uint64_t *overs /* [S] */, int clear);
+int      cmhip_iir_sync(cmhip_iir_t *m);
+void    *cmhip_iir_hip_stream(cmhip_iir_t *m);
+/* host only, no device needed */
+int      cmhip_iir_check(const cmhip_iir_section_t *c);
+int      cmhip_iir_design(const cmhip_iir_design_desc_t *d, cmhip_iir_section_t *c);
+double   cmhip_iir_response_db(const cmhip_iir_section_t *sections, unsigned int n, double rate, double f);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

@@ -171,6 +171,32 @@ class AgcLawDesc(C.Structure):
                                           "initial_gain_db", "rise_db_per_s", "fall_db_per_s")]
 
 
+class IirDesc(C.Structure):
+    """cmhip_iir_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("sections", C.c_uint),
+                ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
+IIR_ONE = 1 << 26
+IIR_COEF_NAMES = ("b0", "b1", "b2", "a1", "a2")
+IIR_KINDS = ("BYPASS", "HIGHPASS", "LOWPASS", "LOWSHELF", "HIGHSHELF", "PEAK", "NOTCH", "HIGHPASS1", "LOWPASS1")
+(IIR_BYPASS, IIR_HIGHPASS, IIR_LOWPASS, IIR_LOWSHELF, IIR_HIGHSHELF, IIR_PEAK, IIR_NOTCH, IIR_HIGHPASS1,
+ IIR_LOWPASS1) = range(9)
+
+
+class IirSection(C.Structure):
+    """cmhip_iir_section_t (include/coolmic_hip.h): b0, b1, b2, a1, a2 in units of 2^-26"""
+    _fields_ = [(n, C.c_int32) for n in IIR_COEF_NAMES]
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n in IIR_COEF_NAMES)
+
+
+class IirDesignDesc(C.Structure):
+    """cmhip_iir_design_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("kind", C.c_int), ("rate", C.c_double), ("f0", C.c_double), ("q", C.c_double), ("gain_db", C.c_double)]
+
+
 class DynCurveDesc(C.Structure):
     """cmhip_dyn_curve_desc_t (include/coolmic_hip.h)"""
     _fields_ = [(n, C.c_double) for n in ("comp_threshold_db", "comp_ratio", "comp_knee_db", "gate_threshold_db",
@@ -325,6 +351,18 @@ SIGNATURES = {
     "cmhip_agc_hip_stream": (_vp, [_vp]),
     "cmhip_agc_check": (C.c_int, [C.c_uint, _P(AgcParams)]),
     "cmhip_agc_design": (C.c_int, [_P(AgcLawDesc), _P(AgcParams)]),
+    "cmhip_iir_new": (_vp, [_P(IirDesc)]),
+    "cmhip_iir_free": (None, [_vp]),
+    "cmhip_iir_set": (C.c_int, [_vp, C.c_long, C.c_uint, _P(IirSection)]),
+    "cmhip_iir_get": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(IirSection)]),
+    "cmhip_iir_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_iir_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_iir_state": (C.c_int, [_vp, _vp, _vp, C.c_int]),
+    "cmhip_iir_sync": (C.c_int, [_vp]),
+    "cmhip_iir_hip_stream": (_vp, [_vp]),
+    "cmhip_iir_check": (C.c_int, [_P(IirSection)]),
+    "cmhip_iir_design": (C.c_int, [_P(IirDesignDesc), _P(IirSection)]),
+    "cmhip_iir_response_db": (C.c_double, [_P(IirSection), C.c_uint, C.c_double, C.c_double]),
     "cmhip_mix_new": (_vp, [_P(MixDesc)]),
     "cmhip_mix_free": (None, [_vp]),
     "cmhip_mix_set_matrix": (C.c_int, [_vp, C.c_long, _vp]),
@@ -586,6 +624,19 @@ if hasattr(lib, "cmhip_test_plan_agc"):         # (not in builds older than the 
     lib.cmhip_test_agc_step.argtypes = [C.c_uint32, C.c_uint32, _P(AgcParams)]
     lib.cmhip_test_agc_run_events.restype = C.c_int
     lib.cmhip_test_agc_run_events.argtypes = [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _P(C.c_void_p)]
+if hasattr(lib, "cmhip_test_plan_iir"):         # (not in builds older than the filter)
+    lib.cmhip_test_plan_iir.restype = None
+    lib.cmhip_test_plan_iir.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
+    lib.cmhip_test_iir_tile_vec.restype = None
+    lib.cmhip_test_iir_tile_vec.argtypes = [C.c_uint32] * 4 + [_P(C.c_uint32), _P(C.c_uint32)]
+    lib.cmhip_test_iir_section.restype = C.c_int32
+    lib.cmhip_test_iir_section.argtypes = [_P(C.c_int32), C.c_int32, _P(C.c_int32), _P(C.c_uint32)]
+    lib.cmhip_test_iir_output.restype = C.c_int32
+    lib.cmhip_test_iir_output.argtypes = [C.c_int32, _P(C.c_uint32)]
+    lib.cmhip_test_iir_new_dry.restype = _vp
+    lib.cmhip_test_iir_new_dry.argtypes = [_P(IirDesc)]
+    lib.cmhip_test_iir_rows.restype = C.c_int
+    lib.cmhip_test_iir_rows.argtypes = [_vp, _vp]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -874,6 +925,72 @@ def test_agc_without_device(streams, channels, window_log2, max_frames):
     """Test hook (cmhip_test_agc_new_dry): a Leveller with the host mirror and every check but no device behind it, for
     the refusals on a machine without a GPU"""
     return Leveller(streams, channels, window_log2, max_frames, _new=lib.cmhip_test_agc_new_dry)
+
+
+class IirPlan(C.Structure):
+    """cmhip::IirPlan (csrc/iir_plan.h): what the filter's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "np", "spw", "grid", "block", "tile", "tiles",
+                                                                "lds_bytes")]
+
+
+def plan_iir(streams, channels, sections, frames):
+    """Test hook: the launch plan of a filter run whose longest stream has `frames` frames (host logic, no GPU)"""
+    p = IirPlan()
+    lib.cmhip_test_plan_iir(streams, channels, sections, frames, C.addressof(p))
+    return p
+
+
+def iir_tile_vec(count, channels, t, q):
+    """Test hook: cmhip::iir_tile_vec (csrc/iir_plan.h) -> (first sample in the slot, samples below the count)"""
+    off, n = C.c_uint32(), C.c_uint32()
+    lib.cmhip_test_iir_tile_vec(count, channels, t, q, C.byref(off), C.byref(n))
+    return off.value, n.value
+
+
+def iir_section_step(sec, u, state):
+    """Test hook: cmhip::iir_section (csrc/iir_plan.h): one frame through one section.  sec: five ints, state: a list
+    [u1, u2, v1, v2, e] updated in place -> (v, over)"""
+    cs, st, over = (C.c_int32 * 5)(*sec), (C.c_int32 * 5)(*state), C.c_uint32()
+    v = lib.cmhip_test_iir_section(cs, u, st, C.byref(over))
+    state[:] = list(st)
+    return v, over.value
+
+
+def iir_output(v):
+    """Test hook: cmhip::iir_output (csrc/iir_plan.h) -> (y, clip)"""
+    clip = C.c_uint32()
+    y = lib.cmhip_test_iir_output(v, C.byref(clip))
+    return y, clip.value
+
+
+def iir_section(b0=IIR_ONE, b1=0, b2=0, a1=0, a2=0):
+    """an IirSection: unity with the arguments over it"""
+    return IirSection(b0, b1, b2, a1, a2)
+
+
+def iir_check(section):
+    """cmhip_iir_check -> error number"""
+    return lib.cmhip_iir_check(C.byref(section))
+
+
+def iir_design(kind, rate, f0, q=0.7071067811865476, gain_db=0.0):
+    """cmhip_iir_design -> IirSection"""
+    d = IirDesignDesc(kind, rate, f0, q, gain_db)
+    s = IirSection()
+    _check("iir_design", lib.cmhip_iir_design(C.byref(d), C.byref(s)))
+    return s
+
+
+def iir_response_db(sections, rate, f):
+    """cmhip_iir_response_db: the magnitude in dB at f of the cascade of the sections' integers"""
+    arr = (IirSection * len(sections))(*sections)
+    return lib.cmhip_iir_response_db(arr, len(sections), rate, f)
+
+
+def test_iir_without_device(streams, channels, sections, max_frames):
+    """Test hook (cmhip_test_iir_new_dry): a Filter with the host mirror and every check but no device behind it, for
+    the refusals on a machine without a GPU"""
+    return Filter(streams, channels, sections, max_frames, _new=lib.cmhip_test_iir_new_dry)
 
 
 def delay_ms(rate, ms):
@@ -1511,7 +1628,7 @@ class Batch:
 
 
 class _Stage:
-    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay, Leveller): the end of the handle `h`, its
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay, Leveller, Filter): the end of the handle `h`, its
     stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
 
     _stem = None
@@ -1734,6 +1851,57 @@ class Leveller(_Stage):
         _check("agc_state", lib.cmhip_agc_state(self.h, g.ctypes.data, lv.ctypes.data, c.ctypes.data,
                                                 1 if clear_clips else 0))
         return g, lv, c
+
+
+class Filter(_Stage):
+    """cmhip_iir_t: a cascade of `sections` biquads in exact integers over S streams beside a batch; every section is
+    unity (a copy) until set."""
+
+    _stem = "iir"
+
+    def __init__(self, streams, channels, sections, max_frames, device=0, hip_stream=None, _new=None):
+        d = IirDesc(device, streams, channels, sections, max_frames, hip_stream)
+        self.h = (_new or lib.cmhip_iir_new)(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_iir_new", ERROR_INVAL)
+        self.streams, self.channels, self.sections, self.max_frames = streams, channels, sections, max_frames
+
+    def set_rc(self, stream, section, sec):
+        """cmhip_iir_set as it is -> error number"""
+        return lib.cmhip_iir_set(self.h, stream, section, C.byref(sec))
+
+    def set(self, stream, section, sec):
+        """the stream's section from its next frame on (stream -1: every stream)"""
+        _check("iir_set", self.set_rc(stream, section, sec))
+
+    def get(self, stream, section):
+        s = IirSection()
+        _check("iir_get", lib.cmhip_iir_get(self.h, stream, section, C.byref(s)))
+        return s
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_iir_run as it is -> error number"""
+        return lib.cmhip_iir_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers)"""
+        _check("iir_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        _check("iir_reset", lib.cmhip_iir_reset(self.h, stream))
+
+    def state(self, clear=False):
+        """-> (clips uint64 [S], overs uint64 [S]); a synchronous round trip"""
+        c = np.zeros(self.streams, dtype=np.uint64)
+        o = np.zeros(self.streams, dtype=np.uint64)
+        _check("iir_state", lib.cmhip_iir_state(self.h, c.ctypes.data, o.ctypes.data, 1 if clear else 0))
+        return c, o
+
+    def rows(self):
+        """Test hook: the rows' sections as the device holds them -> int32 [S * C][N][5] (u1, u2, v1, v2, e)"""
+        r = np.zeros((self.streams * self.channels, self.sections, 5), dtype=np.int32)
+        _check("iir_rows", lib.cmhip_test_iir_rows(self.h, r.ctypes.data))
+        return r
 
 
 class Mixer(_Stage):

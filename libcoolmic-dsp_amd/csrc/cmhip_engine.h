@@ -14,6 +14,7 @@
 //   cmhip_lim.hip      the peak limiter
 //   cmhip_dyn.hip      the dynamics stage: compressor and gate
 //   cmhip_agc.hip      the leveller: slow automatic gain control
+//   cmhip_iir.hip      the filter: a biquad cascade in exact integers
 #pragma once
 
 #include "cmhip_internal.h"

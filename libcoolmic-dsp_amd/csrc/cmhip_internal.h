@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -12,6 +12,7 @@
 #include "split_plan.h"
 #include "delay_plan.h"
 #include "agc_plan.h"
+#include "iir_plan.h"
 
 namespace cmhip {
 
@@ -395,6 +396,22 @@ struct AgcArgs {
     uint32_t       tile_log2;      // frames per tile, as a power of two
 };
 
+// Filter (k_iir.hip; the arithmetic: include/coolmic_hip.h, the tiles: csrc/iir_plan.h): a run of a biquad cascade over
+// S stream slots
+struct IirArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *counts;        // [S] the run's frames per stream
+    const int32_t *coef;           // [S][N][5] b0, b1, b2, a1, a2 in units of 2^-26
+    IirState      *state;          // [S * C][N] the rows' sections between two runs
+    unsigned long long *clips;     // [S] outputs the last clamp changed
+    unsigned long long *overs;     // [S] section results the inner clamp changed
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       sections;       // N
+};
+
 struct GenArgs {
     int16_t *dst;
     uint32_t streams, channels, frames;
@@ -552,6 +569,8 @@ hipError_t launch_delay(const DelayArgs &a, uint32_t max_delay, uint32_t max_fra
 // the run's largest count, max_frames the object's.  ev: nullptr, or four events recorded in front of, between and behind
 // the three launches (tools/bench_agc.py).
 hipError_t launch_agc(const AgcArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
+// Filter (k_iir.hip): one launch, a workgroup per iir_plan's spw streams.  frames: the run's largest count.
+hipError_t launch_iir(const IirArgs &a, uint32_t frames, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

@@ -1,6 +1,6 @@
 // cmhip_stage.h -- a stage object beside the batch, on the HIP side (not part of the C ABI; cmhip_engine.h includes it
 // once fail and HIP_TRY exist): the ring a run's counts travel through, the device / stream / counts every stage owns
-// (cmhip_src.hip, cmhip_mix.hip, cmhip_bus.hip, cmhip_lim.hip, cmhip_dyn.hip, cmhip_split.hip, cmhip_delay.hip, cmhip_agc.hip embed StageBase), and the refusals of csrc/stage_io.h's
+// (cmhip_src.hip, cmhip_mix.hip, cmhip_bus.hip, cmhip_lim.hip, cmhip_dyn.hip, cmhip_split.hip, cmhip_delay.hip, cmhip_agc.hip, cmhip_iir.hip embed StageBase), and the refusals of csrc/stage_io.h's
 // checks as the caller reads them in cmhip_last_error().
 #pragma once
 
