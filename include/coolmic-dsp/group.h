@@ -169,6 +169,24 @@ int                 coolmic_group_correlation(coolmic_group_t *self, unsigned in
 int                 coolmic_group_correlations(coolmic_group_t *self, coolmic_correlation_result_t *results, int *rc);
 int                 coolmic_group_correlation_reset(coolmic_group_t *self, long slot);
 
+/* The spectrum of every stream's selected channels, opt-in: cmhip_batch_set_spectrum() of <coolmic_hip.h> on the
+ * group's engine, with its return values and its specification (mono groups included).  While it is on every block
+ * runs the spectrum kernel ahead of the block kernel, beside the other meters' kernels; as with correlation the input
+ * set is read once more over PCIe.  It measures the transformed stream, not the equaliser's result: the two exclude
+ * each other with COOLMIC_ERROR_INVAL both ways round. */
+int                 coolmic_group_set_spectrum(coolmic_group_t *self, int on);
+/* cmhip_batch_spec_configure for the group's engine: block size, band table and channels are the same for every
+ * slot, and change only while the meter is off (COOLMIC_ERROR_BUSY otherwise). */
+int                 coolmic_group_spectrum_configure(coolmic_group_t *self, unsigned int fft_log2, unsigned int nb,
+                                                     const uint16_t *edges, unsigned int nch, const unsigned char *channels);
+/* One slot's spectrum window since its last result, and all of them at once (results[] and rc[], which may be NULL,
+ * have coolmic_group_streams() entries): the slot handling of coolmic_group_correlation(s) --
+ * COOLMIC_ERROR_INVAL with the result left alone and the window kept for a window without a completed block.
+ * coolmic_group_spectrum_reset clears a slot's window, state and position, or with -1 those of every slot. */
+int                 coolmic_group_spectrum(coolmic_group_t *self, unsigned int slot, coolmic_spectrum_result_t *result);
+int                 coolmic_group_spectra(coolmic_group_t *self, coolmic_spectrum_result_t *results, int *rc);
+int                 coolmic_group_spectrum_reset(coolmic_group_t *self, long slot);
+
 unsigned int        coolmic_group_streams(coolmic_group_t *self);
 
 #ifdef __cplusplus

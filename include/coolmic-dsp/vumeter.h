@@ -91,6 +91,27 @@ typedef struct {
     double balance_db[8];
 } coolmic_correlation_result_t;
 
+/* Result of one spectrum window, as the batch engine (cmhip_batch_spec_result, <coolmic_hip.h>) and the group
+ * (coolmic_group_spectrum, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  The window
+ * accounted `frames` frames and summed `blocks` blocks of 2^fft_log2 frames that completed in it.  For each of the
+ * `selected` transformed channels channel[c] and each of `bands` bands -- band k holds the bins edges[k] <= bin <
+ * edges[k + 1] -- power[c][k] is the exact integer sum of the blocks' bin powers and db[c][k] its level,
+ * cmhip_spec_db(power, blocks): 0 dB is a full-scale sine whose main lobe lies in the band, -inf an empty band.  The
+ * arithmetic is specified to the bit in <coolmic_hip.h>.  Entries beyond what is in use are zero.  4208 bytes on LP64. */
+typedef struct {
+    uint_least32_t rate;
+    unsigned int channels;
+    size_t frames;
+    size_t blocks;
+    unsigned int fft_log2;
+    unsigned int bands;
+    unsigned int selected;
+    uint16_t edges[33];
+    unsigned char channel[8];
+    uint64_t power[8][32];
+    double db[8][32];
+} coolmic_spectrum_result_t;
+
 /* Programme loudness of one stream (ITU-R BS.1770 / EBU R128: K-weighting, 100 ms sub-blocks, 400 ms momentary,
  * 3 s short-term, gated integrated loudness), as the batch engine (cmhip_batch_loud_result, <coolmic_hip.h>) and the
  * group (coolmic_group_loudness, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  The

@@ -295,6 +295,83 @@ int    cmhip_batch_corr_reset(cmhip_batch_t *b, long stream);
 double cmhip_corr_value(uint64_t energy_a, uint64_t energy_b, int64_t cross);
 double cmhip_corr_balance_db(uint64_t energy_a, uint64_t energy_b);
 
+/* ---- spectrum, opt-in ---------------------------------------------------------- */
+/* Where in frequency the energy lies: band levels from a Hann-windowed FFT in fixed point, for up to
+ * CMHIP_SPEC_MAX_CHANNELS channels per stream and up to CMHIP_SPEC_MAX_BANDS bands.  Specified, and held, to the bit:
+ *
+ * Signal.  The TRANSFORMED stream (after channel map, gain and saturation), exactly as for true peak and correlation.
+ *   The pass reads the run's input slots and transforms them itself, so an in-place batch needs nothing special.
+ * Geometry.  N = 2^n frames per block, n = fft_log2 in 8..12 (default 10), hop H = N / 2.  Block j of a stream covers
+ *   its frames [j H, j H + N), counted from 0 where the meter was turned on or the stream last reset, and is computed
+ *   in the run in which its last frame arrives.  Blocks are anchored to the stream's position, so the result does not
+ *   depend on how the stream is cut into runs, per-stream counts included.  A stream that gets 0 frames in a run
+ *   keeps everything.
+ * Channels.  1 to CMHIP_SPEC_MAX_CHANNELS distinct transformed channels, the same for all streams; the default is
+ *   channel 0, and channel 1 too where the batch has one.  Mono batches are allowed.
+ * Window.  win[i] = min(32767, rint(32768 * 0.5 * (1 - cos(2 pi i / N)))) as int16, the upper half mirrored from the
+ *   lower (win[N - i] = win[i]); cmhip_spec_window returns it.  v[i] = x[i] * win[i], exact in int32, |v| < 2^30.
+ * Twiddles.  Wr[k] = llround(2^30 cos(2 pi k / N)), Wi[k] = llround(-2^30 sin(2 pi k / N)) for k < N / 2 as int32,
+ *   one octant computed and mirrored: k = 0 is exactly (2^30, 0), k = N / 4 exactly (0, -2^30), Wr[N / 4 - k] =
+ *   -Wi[k], W[k + N / 4] = (Wi[k], -Wr[k]).  cmhip_spec_twiddles returns them; a model takes them from there.
+ * Transform.  Radix-2 decimation in time: z[bitrev(i)] = (v[i], 0), then for stage s = 1..n with m = 2^s, for
+ *   a = z[g m + j], b = z[g m + j + m / 2] and W = W[j N / m]:
+ *       Pr = br Wr - bi Wi        Pi = br Wi + bi Wr                                  (exact in int64)
+ *       a'r = (ar 2^30 + Pr + 2^30) >> 31       b'r = (ar 2^30 - Pr + 2^30) >> 31     (and the imaginary parts likewise)
+ *   with an arithmetic shift of the exact int64 sum: one rounding per butterfly output, a factor 1/2 per stage, so X
+ *   is the DFT of v divided by N.  |a'| <= (|a| + |b|) / 2 + 1 bounds every component by 2^30 + n (int32 storage
+ *   leaves 2^31; measured components stay below 2^29) and every int64 intermediate by 2^63.  An implementation may
+ *   fuse stages, skip the trivial twiddles (those entries are exact) or use another radix that reproduces every
+ *   stage's rounded values; nothing else may differ.
+ * Power and bands.  p[k] = (uint64)(re^2 + im^2) >> 16 for the bins k = 0..N / 2.  A band table has nb in
+ *   1..CMHIP_SPEC_MAX_BANDS bands with edges 0 <= e[0] < e[1] < ... < e[nb] <= N / 2 + 1; band b is the sum of p[k]
+ *   over e[b] <= k < e[b + 1].  The default table is the bin octaves 1, 2, 4, ..., N / 2, N / 2 + 1: n bands, no DC.
+ *   A window's value per stream, channel and band is the uint64 sum over the blocks completed since it opened; a
+ *   block that straddles a window's close belongs to the window in which it completes.  One block's total over all
+ *   bins is at most 2^42.4 (DC or Nyquist at -32768), so a window is exact for 2^21 blocks -- 6 hours at N = 1024
+ *   and 48 kHz.  The bound is not enforced, as with correlation.
+ * Band design, no device needed.  cmhip_spec_design_bands(rate, fft_log2, per_octave, edges) gives fractional-octave
+ *   bands around 1 kHz, per_octave in 1..3: with f(i) = 1000.0 * pow(2.0, (2 i - 1) / (2.0 * per_octave)) for every
+ *   integer i, the bin edge is ceil(f(i) * (double)N / (double)rate) clamped to 1..N / 2 + 1, and the table is the
+ *   strictly ascending list of the distinct values (bands narrower than a bin merge upwards, the DC bin is left out;
+ *   the table always starts at 1 and ends at N / 2 + 1).  Returns the band count; COOLMIC_ERROR_INVAL for more than
+ *   32 bands, rate 0 or an argument out of range.
+ * Host finish, no device needed.  cmhip_spec_db(power, blocks) = 10.0 * log10((double)power / ((double)blocks *
+ *   1649267441664.0)) -- the constant is 1.5 * 2^40 -- which is -inf for power 0; 0.0 for blocks 0.  0 dB is a
+ *   full-scale sine whose three main-lobe bins lie in one band.
+ * State.  Per stream and selected channel the last N - 1 transformed samples, in two slots that the runs alternate
+ *   between (a run reads one and writes the other, so a run longer than N overwrites nothing a block still reads).
+ *   The state belongs to the stream, not to the window: closing a window leaves it alone, and so does a change of
+ *   gain or map.  cmhip_batch_spec_reset clears window, state and position (stream -1: all).
+ *
+ * cmhip_batch_spec_configure(b, fft_log2, nb, edges, nch, channels) sets the geometry, only while the meter is off
+ * (COOLMIC_ERROR_BUSY otherwise): nb == 0 takes the default table of that fft_log2 (edges may be NULL then), nch == 0
+ * the default channels (channels may be NULL then).  COOLMIC_ERROR_FAULT for NULL otherwise, COOLMIC_ERROR_INVAL for
+ * fft_log2 outside 8..12, a bad band table, more than 8 channels, a channel twice or out of range; nothing changes
+ * then.  cmhip_batch_set_spectrum(b, 1), between runs (it waits for the batch's stream), allocates windows, state and
+ * tables for the geometry in force and opens empty windows at position 0; from then on every cmhip_batch_run /
+ * _run_slots launches the spectrum kernel on the batch's stream AHEAD of the block kernel, beside the other meters'
+ * passes.  (b, 0) stops that and discards windows and state; the geometry is kept.  The spectrum of the equaliser's
+ * result is not measured: COOLMIC_ERROR_INVAL while the batch's equaliser has sections, and cmhip_batch_set_eq with
+ * nsec > 0 returns COOLMIC_ERROR_INVAL while the meter is on.
+ * The result calls follow correlation's: COOLMIC_ERROR_INVAL with `out` left alone and the window KEPT for a window
+ * without a completed block (per stream in rc[] for _results, rc may be NULL), and for a batch without the meter; a
+ * window is closed on success, by these calls only.  `frames` of a result counts the frames since the window opened.
+ * The pass is queued, and its frames are counted, before the block kernel is launched: see correlation on a run that
+ * returns an error. */
+#define CMHIP_SPEC_MAX_CHANNELS 8
+#define CMHIP_SPEC_MAX_BANDS 32
+int    cmhip_batch_set_spectrum(cmhip_batch_t *b, int on);
+int    cmhip_batch_get_spectrum(const cmhip_batch_t *b);      /* 0 / 1, negative error */
+int    cmhip_batch_spec_configure(cmhip_batch_t *b, unsigned int fft_log2, unsigned int nb, const uint16_t *edges,
+                                  unsigned int nch, const unsigned char *channels);
+int    cmhip_batch_spec_result(cmhip_batch_t *b, unsigned int stream, coolmic_spectrum_result_t *out);
+int    cmhip_batch_spec_results(cmhip_batch_t *b, coolmic_spectrum_result_t *out, int *rc);
+int    cmhip_batch_spec_reset(cmhip_batch_t *b, long stream);
+int    cmhip_spec_window(unsigned int fft_log2, int16_t *win);                 /* win[N] */
+int    cmhip_spec_twiddles(unsigned int fft_log2, int32_t *wr, int32_t *wi);   /* wr[N / 2], wi[N / 2] */
+int    cmhip_spec_design_bands(unsigned int rate, unsigned int fft_log2, unsigned int per_octave, uint16_t edges[33]);
+double cmhip_spec_db(uint64_t power, uint64_t blocks);
+
 /* ---- programme loudness (ITU-R BS.1770 / EBU R128), opt-in -------------------- */
 /* Momentary, short-term and gated integrated loudness of the TRANSFORMED stream (after channel map, gain and
  * saturation: the samples the VU window accounts, as for true peak).  The arithmetic is specified to the bit:

@@ -89,6 +89,29 @@ class CorrResult(C.Structure):
         return d
 
 
+SPEC_MAX_CHANNELS = 8
+SPEC_MAX_BANDS = 32
+SPEC_DB_REF = 1649267441664.0           # 1.5 * 2^40
+
+
+class SpecResult(C.Structure):
+    """coolmic_spectrum_result_t (include/coolmic-dsp/vumeter.h): exact integer band sums per selected channel and
+    their levels in double"""
+    _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t), ("blocks", C.c_size_t),
+                ("fft_log2", C.c_uint), ("bands", C.c_uint), ("selected", C.c_uint),
+                ("edges", C.c_uint16 * (SPEC_MAX_BANDS + 1)), ("channel", C.c_ubyte * SPEC_MAX_CHANNELS),
+                ("power", (C.c_uint64 * SPEC_MAX_BANDS) * SPEC_MAX_CHANNELS),
+                ("db", (C.c_double * SPEC_MAX_BANDS) * SPEC_MAX_CHANNELS)]
+
+    def as_dict(self):
+        nb, nc = self.bands, self.selected
+        return {"rate": self.rate, "channels": self.channels, "frames": self.frames, "blocks": self.blocks,
+                "fft_log2": self.fft_log2, "bands": nb, "selected": nc,
+                "edges": [self.edges[i] for i in range(nb + 1)], "channel": [self.channel[i] for i in range(nc)],
+                "power": [[self.power[c][k] for k in range(nb)] for c in range(nc)],
+                "db": [[self.db[c][k] for k in range(nb)] for c in range(nc)]}
+
+
 class LoudnessResult(C.Structure):
     """coolmic_loudness_result_t (include/coolmic-dsp/vumeter.h): LUFS doubles, -inf while there is nothing to report"""
     _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t), ("blocks", C.c_size_t),
@@ -295,6 +318,16 @@ SIGNATURES = {
     "cmhip_batch_corr_reset": (C.c_int, [_vp, C.c_long]),
     "cmhip_corr_value": (C.c_double, [C.c_uint64, C.c_uint64, C.c_int64]),
     "cmhip_corr_balance_db": (C.c_double, [C.c_uint64, C.c_uint64]),
+    "cmhip_batch_set_spectrum": (C.c_int, [_vp, C.c_int]),
+    "cmhip_batch_get_spectrum": (C.c_int, [_vp]),
+    "cmhip_batch_spec_configure": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_uint, _vp]),
+    "cmhip_batch_spec_result": (C.c_int, [_vp, C.c_uint, _P(SpecResult)]),
+    "cmhip_batch_spec_results": (C.c_int, [_vp, _vp, _vp]),
+    "cmhip_batch_spec_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_spec_window": (C.c_int, [C.c_uint, _vp]),
+    "cmhip_spec_twiddles": (C.c_int, [C.c_uint, _vp, _vp]),
+    "cmhip_spec_design_bands": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, _vp]),
+    "cmhip_spec_db": (C.c_double, [C.c_uint64, C.c_uint64]),
     "cmhip_batch_set_loudness": (C.c_int, [_vp, C.c_int]),
     "cmhip_batch_get_loudness": (C.c_int, [_vp]),
     "cmhip_batch_loud_set_weights": (C.c_int, [_vp, C.c_long, _vp]),
@@ -517,6 +550,11 @@ SIGNATURES = {
     "coolmic_group_correlation": (C.c_int, [_vp, C.c_uint, _P(CorrResult)]),
     "coolmic_group_correlations": (C.c_int, [_vp, _vp, _vp]),
     "coolmic_group_correlation_reset": (C.c_int, [_vp, C.c_long]),
+    "coolmic_group_set_spectrum": (C.c_int, [_vp, C.c_int]),
+    "coolmic_group_spectrum_configure": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, C.c_uint, _vp]),
+    "coolmic_group_spectrum": (C.c_int, [_vp, C.c_uint, _P(SpecResult)]),
+    "coolmic_group_spectra": (C.c_int, [_vp, _vp, _vp]),
+    "coolmic_group_spectrum_reset": (C.c_int, [_vp, C.c_long]),
     "coolmic_group_streams": (C.c_uint, [_vp]),
 }
 MISSING = []        # entry points this build of the library lacks (an older build under tools/ab_two_libs.py)
@@ -559,6 +597,13 @@ if hasattr(lib, "cmhip_test_plan_corr"):        # (not in builds older than phas
     lib.cmhip_test_plan_corr.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
     lib.cmhip_debug_corr_count.restype = C.c_ulonglong
     lib.cmhip_debug_corr_count.argtypes = []
+if hasattr(lib, "cmhip_test_plan_spec"):        # (not in builds older than the spectrum)
+    lib.cmhip_test_plan_spec.restype = None
+    lib.cmhip_test_plan_spec.argtypes = [C.c_uint32] * 7 + [C.c_void_p]
+    lib.cmhip_test_spec_block.restype = C.c_int
+    lib.cmhip_test_spec_block.argtypes = [C.c_uint, _vp, _vp]
+    lib.cmhip_debug_spec_count.restype = C.c_ulonglong
+    lib.cmhip_debug_spec_count.argtypes = []
 if hasattr(lib, "cmhip_test_plan_loud"):        # (not in builds older than loudness)
     lib.cmhip_test_plan_loud.restype = None
     lib.cmhip_test_plan_loud.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -716,6 +761,13 @@ def tp_coefficients():
     return h.reshape(4, 12)
 
 
+def _spec_geometry(edges, channels):
+    """(nb, edges array or None, nch, channels array or None) as cmhip_batch_spec_configure takes them"""
+    e = (C.c_uint16 * len(edges))(*[int(v) for v in edges]) if edges is not None else None
+    c = (C.c_ubyte * len(channels))(*[int(v) for v in channels]) if channels is not None else None
+    return (len(edges) - 1 if edges is not None else 0, e, len(channels) if channels is not None else 0, c)
+
+
 class CorrPlan(C.Structure):
     """cmhip::CorrPlan (csrc/cmhip_internal.h): what the correlation launcher launches for a run"""
     _fields_ = [("err", C.c_int), ("fast", C.c_uint32), ("grid", C.c_uint32), ("block", C.c_uint32),
@@ -744,6 +796,56 @@ def _corr_pairs(pairs):
     if len(flat) != 2 * len(pairs):
         raise ValueError("corr_set_pairs: every pair is two channels")
     return (C.c_ubyte * max(len(flat), 2))(*flat)
+
+
+class SpecPlan(C.Structure):
+    """cmhip::SpecPlan (csrc/cmhip_internal.h): what the spectrum launcher launches for a run"""
+    _fields_ = [("err", C.c_int), ("grid", C.c_uint32), ("block", C.c_uint32), ("chunks", C.c_uint32)]
+
+
+def plan_spec(streams, channels, frames, fft_log2=10, nch=1, nb=10, max_blocks=0):
+    """Test hook: the spectrum launcher's plan for a run whose streams complete at most max_blocks blocks (host logic,
+    needs no GPU)"""
+    p = SpecPlan()
+    lib.cmhip_test_plan_spec(streams, channels, frames, fft_log2, nch, nb, max_blocks, C.addressof(p))
+    return p
+
+
+def spec_window(fft_log2):
+    """the spectrum's Hann window, int16 [N]"""
+    w = np.zeros(1 << fft_log2, dtype=np.int16)
+    _check("spec_window", lib.cmhip_spec_window(fft_log2, w.ctypes.data))
+    return w
+
+
+def spec_twiddles(fft_log2):
+    """the spectrum's twiddles in units of 2^-30 -> (wr, wi), int32 [N / 2] each"""
+    wr = np.zeros(1 << (fft_log2 - 1), dtype=np.int32)
+    wi = np.zeros_like(wr)
+    _check("spec_twiddles", lib.cmhip_spec_twiddles(fft_log2, wr.ctypes.data, wi.ctypes.data))
+    return wr, wi
+
+
+def spec_design_bands(rate, fft_log2, per_octave):
+    """fractional-octave bands around 1 kHz -> the list of nb + 1 bin edges, or the negative error number"""
+    e = np.zeros(SPEC_MAX_BANDS + 1, dtype=np.uint16)
+    nb = lib.cmhip_spec_design_bands(rate, fft_log2, per_octave, e.ctypes.data)
+    return nb if nb < 0 else [int(v) for v in e[:nb + 1]]
+
+
+def spec_db(power, blocks):
+    """the host finish of a band: 10 * log10(power / (blocks * 1.5 * 2^40)), -inf for power 0, 0.0 for blocks 0"""
+    return lib.cmhip_spec_db(power, blocks)
+
+
+def spec_block(fft_log2, x):
+    """Test hook: the library's plain reference of one block, int16 x[N] -> uint64 p[N / 2 + 1] (needs no GPU)"""
+    x = np.ascontiguousarray(x, dtype=np.int16)
+    if x.shape != (1 << fft_log2,):
+        raise ValueError("spec_block: x holds N samples")
+    p = np.zeros((1 << (fft_log2 - 1)) + 1, dtype=np.uint64)
+    _check("spec_block", lib.cmhip_test_spec_block(fft_log2, x.ctypes.data, p.ctypes.data))
+    return p
 
 
 class LoudPlan(C.Structure):
@@ -1545,6 +1647,33 @@ class Batch:
 
     def corr_reset(self, stream=-1):
         _check("corr_reset", lib.cmhip_batch_corr_reset(self.h, stream))
+
+    # spectrum (opt-in)
+    def set_spectrum(self, on):
+        """the error number (INVAL while the equaliser has sections)"""
+        return lib.cmhip_batch_set_spectrum(self.h, int(bool(on)))
+
+    def get_spectrum(self):
+        return lib.cmhip_batch_get_spectrum(self.h)
+
+    def spec_configure(self, fft_log2=10, edges=None, channels=None):
+        """edges: the nb + 1 bin edges (None: the bin octaves), channels: the transformed channels (None: 0, and 1
+        where the batch has it) -> the error number (BUSY while the meter is on)"""
+        return lib.cmhip_batch_spec_configure(self.h, fft_log2, *_spec_geometry(edges, channels))
+
+    def spec_result(self, stream, out=None):
+        r = out if out is not None else SpecResult()
+        rc = lib.cmhip_batch_spec_result(self.h, stream, C.byref(r))
+        return rc, r
+
+    def spec_results(self, out=None):
+        out = out if out is not None else (SpecResult * self.streams)()
+        rc = (C.c_int * self.streams)()
+        _check("spec_results", lib.cmhip_batch_spec_results(self.h, out, rc))
+        return out, list(rc)
+
+    def spec_reset(self, stream=-1):
+        _check("spec_reset", lib.cmhip_batch_spec_reset(self.h, stream))
 
     # loudness (opt-in)
     def set_loudness(self, on):
@@ -2603,6 +2732,28 @@ class Group:
 
     def correlation_reset(self, slot=-1):
         return lib.coolmic_group_correlation_reset(self.ptr, slot)
+
+    def set_spectrum(self, on):
+        return lib.coolmic_group_set_spectrum(self.ptr, int(bool(on)))
+
+    def spectrum_configure(self, fft_log2=10, edges=None, channels=None):
+        return lib.coolmic_group_spectrum_configure(self.ptr, fft_log2, *_spec_geometry(edges, channels))
+
+    def spectrum(self, slot, out=None):
+        r = out if out is not None else SpecResult()
+        rc = lib.coolmic_group_spectrum(self.ptr, slot, C.byref(r))
+        return rc, r
+
+    def spectra(self, out=None):
+        """every slot's spectrum window at once -> (SpecResult array, rc list); `out`: the array to fill"""
+        n = self.streams()
+        out = out if out is not None else (SpecResult * n)()
+        rc = (C.c_int * n)()
+        _check("group_spectra", lib.coolmic_group_spectra(self.ptr, out, rc))
+        return out, list(rc)
+
+    def spectrum_reset(self, slot=-1):
+        return lib.coolmic_group_spectrum_reset(self.ptr, slot)
 
     def set_loudness(self, on):
         return lib.coolmic_group_set_loudness(self.ptr, int(bool(on)))

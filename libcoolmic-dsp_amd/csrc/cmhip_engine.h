@@ -4,6 +4,7 @@
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
 //   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
 //   cmhip_corr.hip     phase correlation: the opt-in state and pairs, its launch ahead of a run, results
+//   cmhip_spec.hip     spectrum: the opt-in state and geometry, its launch ahead of a run, results
 //   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
@@ -146,6 +147,24 @@ struct cmhip_batch {
     unsigned char corr_a[CORR_MAX_PAIRS] = {0}, corr_b[CORR_MAX_PAIRS] = {1};
     std::vector<unsigned long long> corr_frames; // frames accounted per stream since its window opened
     std::vector<unsigned long long> corr_host;   // [S][8][3] staging of a result call
+    // spectrum (cmhip_spec.hip), all of it but the geometry unused until cmhip_batch_set_spectrum(b, 1)
+    bool spec_on = false;
+    unsigned long long *d_spec = nullptr;  // [S][8][32] window sums per selected channel and band
+    int16_t *d_spec_hist = nullptr;        // [2][S][nch][N] the streams' last N - 1 samples, slot spec_parity current
+    uint32_t *d_spec_back = nullptr;       // [2][S] the streams' back (csrc/spec_plan.h), slot spec_parity current
+    int32_t *d_spec_table = nullptr;       // Wr[N/2], Wi[N/2], win[N], edges[33]
+    size_t spec_hist_words = 0, spec_table_words = 0;   // what the two arrays were allocated for
+    unsigned int spec_parity = 0;
+    // the geometry, the same for all streams (kept across off / on); spec_nb 0 / spec_nch 0: the defaults, filled in
+    // when the meter is turned on
+    unsigned int spec_log2 = SPEC_DEFAULT_LOG2;
+    unsigned int spec_nb = 0, spec_nch = 0;
+    uint16_t spec_edges[SPEC_MAX_BANDS + 1] = {};
+    unsigned char spec_ch[SPEC_MAX_CH] = {};
+    std::vector<uint32_t> spec_back;             // host mirror of the current back per stream
+    std::vector<unsigned long long> spec_frames; // frames accounted per stream since its window opened
+    std::vector<unsigned long long> spec_blocks; // blocks summed per stream since its window opened
+    std::vector<unsigned long long> spec_host;   // [S][8][32] staging of a result call
     // loudness (cmhip_loud.hip), all of it unused until cmhip_batch_set_loudness(b, 1)
     bool loud_on = false;
     LoudState *d_loud = nullptr;           // [S][C] the rows' filter history and open sub-block
@@ -183,6 +202,10 @@ CMHIP_INTERNAL int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size
 // cmhip_corr.hip: the correlation pass of a run over `in`, queued on the batch's stream ahead of the block kernel
 // (only called while b->corr_on; frames_per_stream as for cmhip_engine_tp_run)
 CMHIP_INTERNAL int cmhip_engine_corr_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
+                                         const uint32_t *frames_per_stream);
+// cmhip_spec.hip: the spectrum pass of a run over `in`, queued on the batch's stream ahead of the block kernel
+// (only called while b->spec_on; frames_per_stream as for cmhip_engine_tp_run)
+CMHIP_INTERNAL int cmhip_engine_spec_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                          const uint32_t *frames_per_stream);
 // cmhip_loud.hip: the loudness pass of a run over `in`, queued on the batch's stream ahead of the block kernel (only
 // called while b->loud_on; drains the ring first when the run could overflow it).  Returns an error number.

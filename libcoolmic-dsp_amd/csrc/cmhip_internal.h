@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip, k_spec.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -13,6 +13,7 @@
 #include "delay_plan.h"
 #include "agc_plan.h"
 #include "iir_plan.h"
+#include "spec_plan.h"
 
 namespace cmhip {
 
@@ -168,6 +169,33 @@ struct CorrArgs {
     uint8_t        a[CORR_MAX_PAIRS], b[CORR_MAX_PAIRS];     // transformed channels of pair i (for k_corr_any)
     uint64_t       stride;         // samples between stream slots (multiple of 8)
     uint32_t       chunks;         // tiles per stream (the launcher fills it in)
+};
+
+// Spectrum (k_spec.hip; the specification: include/coolmic_hip.h, the bookkeeping: csrc/spec_plan.h): per stream,
+// selected channel and band the window sums of the blocks' bin powers over the TRANSFORMED stream, exact 64-bit integers
+// merged by integer atomics.
+struct SpecArgs {
+    const int16_t *in;             // the run's INPUT slots: the kernel applies map and gain itself
+    const StreamParam *param;
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    unsigned long long *sums;      // [S][SPEC_MAX_CH][SPEC_MAX_BANDS] the windows
+    // [2][S][nch][N] the last N - 1 transformed samples per selected channel, oldest first (entry N - 1 unused), and
+    // [2][S] the streams' back (spec_plan.h).  Two slots each: a run reads slot `parity`, the state workgroups write
+    // slot `parity ^ 1` (as TpArgs::hist); the host flips parity per run.
+    int16_t       *hist;
+    uint32_t      *back;
+    // the tables, made when the meter is turned on: Wr[N / 2], Wi[N / 2], win[N] (as int32), edges[nb + 1]
+    const int32_t *table;
+    uint64_t       chpack;         // the selected channels, channel i in byte i
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       log2n;          // n
+    uint32_t       nch, nb;        // selected channels, bands
+    uint32_t       parity;
+    uint64_t       stride;         // samples between stream slots (multiple of 8)
+    // workgroups per stream and channel: the run's largest block count + 1 (the launcher fills it in)
+    uint32_t       chunks;
 };
 
 // Loudness (ITU-R BS.1770 K-weighting, 100 ms sub-block sums): one row is one channel of one stream.
@@ -468,6 +496,16 @@ struct CorrPlan {
 };
 CorrPlan plan_corr(const CorrArgs &a);
 hipError_t launch_corr(const CorrArgs &a, hipStream_t st);
+// Spectrum (k_spec.hip): one workgroup of 256 threads per stream, selected channel and block of the run, and one more
+// per stream and channel that writes the state the run leaves.  max_blocks: the largest block count of the run's streams
+// (spec_run_blocks over the host's mirror of the streams' back).
+struct SpecPlan {
+    hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups
+    uint32_t   grid, block;        // grid 0: nothing to launch (or refused)
+    uint32_t   chunks;             // SpecArgs::chunks
+};
+SpecPlan plan_spec(const SpecArgs &a, uint32_t max_blocks);
+hipError_t launch_spec(const SpecArgs &a, uint32_t max_blocks, hipStream_t st);
 // Loudness (k_loud.hip): one lane per row, one wave per workgroup.
 struct LoudPlan {
     hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups

@@ -68,6 +68,8 @@ struct coolmic_group {
     std::vector<coolmic_loudness_result_t> *loud_out;    // and for coolmic_group_loudnesses
     std::vector<coolmic_correlation_result_t> *corr_out; // and for coolmic_group_correlations
     std::vector<int> *corr_rc;
+    std::vector<coolmic_spectrum_result_t> *spec_out;    // and for coolmic_group_spectra
+    std::vector<int> *spec_rc;
 };
 
 struct GroupHandle {
@@ -86,6 +88,8 @@ static void group_destroy(void *self)
     delete g->loud_out;
     delete g->corr_out;
     delete g->corr_rc;
+    delete g->spec_out;
+    delete g->spec_rc;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -713,6 +717,68 @@ extern "C" int coolmic_group_correlation_reset(coolmic_group_t *self, long slot)
     if (slot >= (long)self->streams->size() || slot < -1)
         return COOLMIC_ERROR_INVAL;
     return cmhip_batch_corr_reset(self->batch, slot);
+}
+
+// Spectrum: thin wrappers over the engine (cmhip_spec.hip), with the slot handling of the correlation calls.
+extern "C" int coolmic_group_set_spectrum(coolmic_group_t *self, int on)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_set_spectrum(self->batch, on);
+}
+
+extern "C" int coolmic_group_spectrum_configure(coolmic_group_t *self, unsigned int fft_log2, unsigned int nb,
+                                                const uint16_t *edges, unsigned int nch, const unsigned char *channels)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_spec_configure(self->batch, fft_log2, nb, edges, nch, channels);
+}
+
+extern "C" int coolmic_group_spectrum(coolmic_group_t *self, unsigned int slot, coolmic_spectrum_result_t *result)
+{
+    if (!self || !result)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= self->streams->size())
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_spec_result(self->batch, slot, result);
+}
+
+extern "C" int coolmic_group_spectra(coolmic_group_t *self, coolmic_spectrum_result_t *results, int *rc)
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return cmhip_batch_spec_results(self->batch, results, rc);
+    if (!self->spec_rc) {
+        try {
+            if (!self->spec_out)
+                self->spec_out = new std::vector<coolmic_spectrum_result_t>(self->max_streams);
+            self->spec_rc = new std::vector<int>(self->max_streams);
+        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
+            return COOLMIC_ERROR_NOMEM;
+        }
+    }
+    const int r = cmhip_batch_spec_results(self->batch, self->spec_out->data(), self->spec_rc->data());
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        if ((*self->spec_rc)[i] == COOLMIC_ERROR_NONE)
+            results[i] = (*self->spec_out)[i];
+        if (rc)
+            rc[i] = (*self->spec_rc)[i];
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int coolmic_group_spectrum_reset(coolmic_group_t *self, long slot)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= (long)self->streams->size() || slot < -1)
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_spec_reset(self->batch, slot);
 }
 
 extern "C" int coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights)
