@@ -187,6 +187,25 @@ int                 coolmic_group_spectrum(coolmic_group_t *self, unsigned int s
 int                 coolmic_group_spectra(coolmic_group_t *self, coolmic_spectrum_result_t *results, int *rc);
 int                 coolmic_group_spectrum_reset(coolmic_group_t *self, long slot);
 
+/* The signal watch -- dead air, clipping, DC offset of every stream -- opt-in: cmhip_batch_set_watch() of
+ * <coolmic_hip.h> on the group's engine, with its return values and its specification (mono groups included).  While
+ * it is on every block runs the watch's two kernels ahead of the block kernel, beside the other meters' kernels; as
+ * with correlation the input set is read once more over PCIe.  Run lengths continue from block to block and from
+ * window to window.  It measures the transformed stream, not the equaliser's result: the two exclude each other with
+ * COOLMIC_ERROR_INVAL both ways round. */
+int                 coolmic_group_set_watch(coolmic_group_t *self, int on);
+/* cmhip_batch_watch_configure for the group's engine: the thresholds are the same for every slot, and change only
+ * while every window is empty (COOLMIC_ERROR_BUSY otherwise); a change clears every slot's run state. */
+int                 coolmic_group_watch_configure(coolmic_group_t *self, unsigned int quiet, unsigned int rail,
+                                                  unsigned int clip_run);
+/* One slot's watch window since its last result, and all of them at once (results[] and rc[], which may be NULL, have
+ * coolmic_group_streams() entries): the slot handling of coolmic_group_correlation(s) -- COOLMIC_ERROR_INVAL with the
+ * result left alone for a window without a frame.  A result closes the window and keeps the run state;
+ * coolmic_group_watch_reset clears a slot's window and state, or with -1 those of every slot. */
+int                 coolmic_group_watch(coolmic_group_t *self, unsigned int slot, coolmic_watch_result_t *result);
+int                 coolmic_group_watches(coolmic_group_t *self, coolmic_watch_result_t *results, int *rc);
+int                 coolmic_group_watch_reset(coolmic_group_t *self, long slot);
+
 unsigned int        coolmic_group_streams(coolmic_group_t *self);
 
 #ifdef __cplusplus

@@ -112,6 +112,30 @@ typedef struct {
     double db[8][32];
 } coolmic_spectrum_result_t;
 
+/* Result of one signal-watch window, as the batch engine (cmhip_batch_watch_result, <coolmic_hip.h>) and the group
+ * (coolmic_group_watch, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  Over the window's
+ * `frames` frames of the transformed stream, with the batch's thresholds quiet, rail and clip_run (K) as they were:
+ * dead air (every channel quiet), per channel the quiet frames, and per channel the samples at the rail -- each as the
+ * number of such frames, the longest run of consecutive ones (a run that began before the window counts with its full
+ * length if it continues into it) and, for dead air and quiet, the run still going at the window's last frame;
+ * clip_events counts the runs at the rail that reached K frames in this window, each once.  sum is the exact sum of
+ * the channel's samples and dc = (double)sum / (double)frames / 32768.0.  All integers are exact and independent of
+ * how the stream was cut into runs; the arithmetic is specified in <coolmic_hip.h>.  Entries at and beyond `channels`
+ * are zero.  1080 bytes on LP64. */
+typedef struct {
+    uint_least32_t rate;
+    unsigned int channels;
+    size_t frames;
+    unsigned int quiet, rail, clip_run;
+    uint64_t dead_frames, dead_longest, dead_current;
+    uint64_t quiet_frames[COOLMIC_DSP_VUMETER_MAX_CHANNELS], quiet_longest[COOLMIC_DSP_VUMETER_MAX_CHANNELS],
+             quiet_current[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
+    uint64_t clip_samples[COOLMIC_DSP_VUMETER_MAX_CHANNELS], clip_events[COOLMIC_DSP_VUMETER_MAX_CHANNELS],
+             clip_longest[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
+    int64_t sum[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
+    double dc[COOLMIC_DSP_VUMETER_MAX_CHANNELS];
+} coolmic_watch_result_t;
+
 /* Programme loudness of one stream (ITU-R BS.1770 / EBU R128: K-weighting, 100 ms sub-blocks, 400 ms momentary,
  * 3 s short-term, gated integrated loudness), as the batch engine (cmhip_batch_loud_result, <coolmic_hip.h>) and the
  * group (coolmic_group_loudness, group.h) report it; the per-stream coolmic_vumeter_t does not measure it.  The

@@ -372,6 +372,60 @@ int    cmhip_spec_twiddles(unsigned int fft_log2, int32_t *wr, int32_t *wi);   /
 int    cmhip_spec_design_bands(unsigned int rate, unsigned int fft_log2, unsigned int per_octave, uint16_t edges[33]);
 double cmhip_spec_db(uint64_t power, uint64_t blocks);
 
+/* ---- signal watch: dead air, clipping, DC offset; opt-in ---------------------- */
+/* Which streams are dead and for how long, which are clipped, which carry DC: run-length and sum statistics of the
+ * stream, exact in integers and independent of how a stream is cut into runs.  Specified, and held, to the bit:
+ *
+ * Signal.  The TRANSFORMED stream (after channel map, gain and saturation), exactly as for true peak and correlation.
+ *   The pass reads the run's input slots and transforms them itself, so an in-place batch needs nothing special.  All
+ *   channels of the stream are covered, C = 1..16; mono is allowed.
+ * Parameters, per batch and the same for all streams; cmhip_batch_watch_configure(b, quiet, rail, clip_run) sets them:
+ *   quiet in 0..32767 (default 32, -60.2 dBFS): a sample x is QUIET iff -quiet <= x <= quiet.
+ *   rail in 1..32767 (default 32767): a sample is AT THE RAIL iff x >= rail || x <= -rail; -32768 is at every rail.
+ *   clip_run = K in 1..16 (default 3).
+ *   Out of range: COOLMIC_ERROR_INVAL, nothing changes.  Configuring is allowed with the watch on or off, but only
+ *   while every window is empty (COOLMIC_ERROR_BUSY otherwise: result or reset first).  A successful configure also
+ *   clears every stream's run state (below): the predicates have changed.
+ *   cmhip_watch_level(db) = lround(32768 * 10^(db / 20)) clamped to 0..32767, a host helper that needs no device
+ *   (-60 dB gives 33, 0 dB and above 32767, -inf 0).
+ * Predicates, per frame n -- the stream's absolute frame index since its state was last cleared:
+ *   Q(c, n): channel c is quiet.   R(c, n): channel c is at the rail.   D(n): every channel is quiet (dead air).
+ *   For each predicate P the run length is l_P(n) = l_P(n - 1) + 1 if P(n), else 0, with l_P(-1) = 0.  l continues
+ *   across runs and across windows: it is the STATE, a uint64 per stream and predicate, C + C + 1 of them per stream.
+ * Window: the frames accounted since the last result or reset.
+ *   dead_frames, quiet_frames[c], clip_samples[c]     the number of window frames with D, Q(c), R(c)
+ *   dead_longest, quiet_longest[c], clip_longest[c]   max of l(n) over the window's frames
+ *   dead_current, quiet_current[c]                    l at the window's last frame: "silent for this long, now"
+ *   clip_events[c]                                    the number of window frames with l_R(c, n) == K
+ *   sum[c]                                            sum of x_c as int64; |sum| <= 2^15 * frames
+ *   A run that began before the window counts in *_longest with its full length, but only if it continues into the
+ *   window: a window whose first frame is not P takes nothing from the state for that predicate.  clip_events counts
+ *   each run once, at the frame where it reaches K, wherever cuts and windows fall.
+ *   Host finish: dc[c] = (double)sum[c] / (double)frames / 32768.0 -- conversions and both quotients correctly
+ *   rounded, one fixed double.
+ *   Nothing depends on the order tiles finish in, on the tile size, or on how the stream is cut into runs.  A stream
+ *   that gets 0 frames in a run keeps its window and state.
+ *
+ * cmhip_batch_set_watch(b, 1), between runs (it waits for the batch's stream), allocates the windows and the state on
+ * first use and opens empty windows with cleared state; from then on every cmhip_batch_run / _run_slots launches the
+ * watch's two kernels on the batch's stream AHEAD of the block kernel, beside the other meters' passes: a tile pass
+ * that writes one run-length summary per stream, tile and predicate into a scratch array (grown on need) and adds the
+ * channel sums, and a fold that walks every stream's summaries in stream order.  (b, 0) stops that and discards windows
+ * and state; the parameters are kept.  The equaliser's result is not measured: COOLMIC_ERROR_INVAL while the batch's
+ * equaliser has sections, and cmhip_batch_set_eq with nsec > 0 returns COOLMIC_ERROR_INVAL while the watch is on.
+ * cmhip_batch_watch_result / _results close windows and KEEP the state; one device round trip serves all streams.
+ * They return COOLMIC_ERROR_INVAL, with `out` left alone, for a window without a frame (per stream in rc[] for
+ * _results, rc may be NULL) and for a batch without the watch.  cmhip_batch_watch_reset clears window and state
+ * (stream -1: all).  The pass is queued, and its frames are counted, before the block kernel is launched: see
+ * correlation on a run that returns an error. */
+int    cmhip_batch_set_watch(cmhip_batch_t *b, int on);
+int    cmhip_batch_get_watch(const cmhip_batch_t *b);         /* 0 / 1, negative error */
+int    cmhip_batch_watch_configure(cmhip_batch_t *b, unsigned int quiet, unsigned int rail, unsigned int clip_run);
+int    cmhip_batch_watch_result(cmhip_batch_t *b, unsigned int stream, coolmic_watch_result_t *out);
+int    cmhip_batch_watch_results(cmhip_batch_t *b, coolmic_watch_result_t *out, int *rc);
+int    cmhip_batch_watch_reset(cmhip_batch_t *b, long stream);
+unsigned int cmhip_watch_level(double db);
+
 /* ---- programme loudness (ITU-R BS.1770 / EBU R128), opt-in -------------------- */
 /* Momentary, short-term and gated integrated loudness of the TRANSFORMED stream (after channel map, gain and
  * saturation: the samples the VU window accounts, as for true peak).  The arithmetic is specified to the bit:

@@ -112,6 +112,28 @@ class SpecResult(C.Structure):
                 "db": [[self.db[c][k] for k in range(nb)] for c in range(nc)]}
 
 
+class WatchResult(C.Structure):
+    """coolmic_watch_result_t (include/coolmic-dsp/vumeter.h): dead air, quiet channels, samples at the rail and the
+    channel sums of one window, exact integers, and the DC finish in double"""
+    _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t),
+                ("quiet", C.c_uint), ("rail", C.c_uint), ("clip_run", C.c_uint),
+                ("dead_frames", C.c_uint64), ("dead_longest", C.c_uint64), ("dead_current", C.c_uint64),
+                ("quiet_frames", C.c_uint64 * MAX_CH), ("quiet_longest", C.c_uint64 * MAX_CH),
+                ("quiet_current", C.c_uint64 * MAX_CH),
+                ("clip_samples", C.c_uint64 * MAX_CH), ("clip_events", C.c_uint64 * MAX_CH),
+                ("clip_longest", C.c_uint64 * MAX_CH),
+                ("sum", C.c_int64 * MAX_CH), ("dc", C.c_double * MAX_CH)]
+
+    def as_dict(self):
+        ch = self.channels
+        d = {n: getattr(self, n) for n in ("rate", "channels", "frames", "quiet", "rail", "clip_run", "dead_frames",
+                                           "dead_longest", "dead_current")}
+        for name in ("quiet_frames", "quiet_longest", "quiet_current", "clip_samples", "clip_events", "clip_longest",
+                     "sum", "dc"):
+            d[name] = [getattr(self, name)[i] for i in range(ch)]
+        return d
+
+
 class LoudnessResult(C.Structure):
     """coolmic_loudness_result_t (include/coolmic-dsp/vumeter.h): LUFS doubles, -inf while there is nothing to report"""
     _fields_ = [("rate", C.c_uint32), ("channels", C.c_uint), ("frames", C.c_size_t), ("blocks", C.c_size_t),
@@ -316,6 +338,13 @@ SIGNATURES = {
     "cmhip_batch_corr_result": (C.c_int, [_vp, C.c_uint, _P(CorrResult)]),
     "cmhip_batch_corr_results": (C.c_int, [_vp, _vp, _vp]),
     "cmhip_batch_corr_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_batch_set_watch": (C.c_int, [_vp, C.c_int]),
+    "cmhip_batch_get_watch": (C.c_int, [_vp]),
+    "cmhip_batch_watch_configure": (C.c_int, [_vp, C.c_uint, C.c_uint, C.c_uint]),
+    "cmhip_batch_watch_result": (C.c_int, [_vp, C.c_uint, _P(WatchResult)]),
+    "cmhip_batch_watch_results": (C.c_int, [_vp, _vp, _vp]),
+    "cmhip_batch_watch_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_watch_level": (C.c_uint, [C.c_double]),
     "cmhip_corr_value": (C.c_double, [C.c_uint64, C.c_uint64, C.c_int64]),
     "cmhip_corr_balance_db": (C.c_double, [C.c_uint64, C.c_uint64]),
     "cmhip_batch_set_spectrum": (C.c_int, [_vp, C.c_int]),
@@ -545,6 +574,11 @@ SIGNATURES = {
     "coolmic_group_loudnesses": (C.c_int, [_vp, _vp, _vp]),
     "coolmic_group_loudness_set_weights": (C.c_int, [_vp, C.c_long, _vp]),
     "coolmic_group_loudness_reset": (C.c_int, [_vp, C.c_long]),
+    "coolmic_group_set_watch": (C.c_int, [_vp, C.c_int]),
+    "coolmic_group_watch_configure": (C.c_int, [_vp, C.c_uint, C.c_uint, C.c_uint]),
+    "coolmic_group_watch": (C.c_int, [_vp, C.c_uint, _P(WatchResult)]),
+    "coolmic_group_watches": (C.c_int, [_vp, _vp, _vp]),
+    "coolmic_group_watch_reset": (C.c_int, [_vp, C.c_long]),
     "coolmic_group_set_correlation": (C.c_int, [_vp, C.c_int]),
     "coolmic_group_correlation_set_pairs": (C.c_int, [_vp, C.c_uint, _vp]),
     "coolmic_group_correlation": (C.c_int, [_vp, C.c_uint, _P(CorrResult)]),
@@ -604,6 +638,13 @@ if hasattr(lib, "cmhip_test_plan_spec"):        # (not in builds older than the 
     lib.cmhip_test_spec_block.argtypes = [C.c_uint, _vp, _vp]
     lib.cmhip_debug_spec_count.restype = C.c_ulonglong
     lib.cmhip_debug_spec_count.argtypes = []
+if hasattr(lib, "cmhip_test_plan_watch"):       # (not in builds older than the signal watch)
+    lib.cmhip_test_plan_watch.restype = None
+    lib.cmhip_test_plan_watch.argtypes = [C.c_uint32] * 3 + [C.c_void_p]
+    lib.cmhip_debug_watch_count.restype = C.c_ulonglong
+    lib.cmhip_debug_watch_count.argtypes = []
+    lib.cmhip_test_watch_time.restype = C.c_int
+    lib.cmhip_test_watch_time.argtypes = [_vp, C.c_size_t, _vp]
 if hasattr(lib, "cmhip_test_plan_loud"):        # (not in builds older than loudness)
     lib.cmhip_test_plan_loud.restype = None
     lib.cmhip_test_plan_loud.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -779,6 +820,33 @@ def plan_corr(streams, channels, frames, npairs=1):
     p = CorrPlan()
     lib.cmhip_test_plan_corr(streams, channels, frames, npairs, C.addressof(p))
     return p
+
+
+class WatchPlan(C.Structure):
+    """cmhip::WatchPlan (csrc/watch_plan.h): what the watch's launcher launches for a run"""
+    _fields_ = [("refused", C.c_int32), ("fast", C.c_uint32), ("tile_frames", C.c_uint32), ("chunks", C.c_uint32),
+                ("grid", C.c_uint32), ("block", C.c_uint32), ("fold_grid", C.c_uint32), ("fold_block", C.c_uint32),
+                ("scratch", C.c_uint64)]
+
+
+def plan_watch(streams, channels, frames):
+    """Test hook: the watch launcher's plan for a run (host logic, needs no GPU)"""
+    p = WatchPlan()
+    lib.cmhip_test_plan_watch(streams, channels, frames, C.addressof(p))
+    return p
+
+
+def watch_time(batch, frames):
+    """Measurement hook (tools/bench_watch.py): the watch's two kernels alone over the batch's own input slots, timed
+    between events -> (tile pass ms, fold ms).  The frames are accounted as a run's are: reset afterwards."""
+    ms = (C.c_float * 2)()
+    _check("watch_time", lib.cmhip_test_watch_time(batch.h, frames, ms))
+    return ms[0], ms[1]
+
+
+def watch_level(db):
+    """a threshold for watch_configure from a level in dBFS: lround(32768 * 10^(db / 20)) clamped to 0..32767"""
+    return lib.cmhip_watch_level(db)
 
 
 def corr_value(energy_a, energy_b, cross):
@@ -1674,6 +1742,32 @@ class Batch:
 
     def spec_reset(self, stream=-1):
         _check("spec_reset", lib.cmhip_batch_spec_reset(self.h, stream))
+
+    # signal watch (opt-in)
+    def set_watch(self, on):
+        """the error number (INVAL while the equaliser has sections)"""
+        return lib.cmhip_batch_set_watch(self.h, int(bool(on)))
+
+    def get_watch(self):
+        return lib.cmhip_batch_get_watch(self.h)
+
+    def watch_configure(self, quiet=32, rail=32767, clip_run=3):
+        """the thresholds of all streams -> the error number (BUSY while a window holds frames)"""
+        return lib.cmhip_batch_watch_configure(self.h, quiet, rail, clip_run)
+
+    def watch_result(self, stream, out=None):
+        r = out if out is not None else WatchResult()
+        rc = lib.cmhip_batch_watch_result(self.h, stream, C.byref(r))
+        return rc, r
+
+    def watch_results(self, out=None):
+        out = out if out is not None else (WatchResult * self.streams)()
+        rc = (C.c_int * self.streams)()
+        _check("watch_results", lib.cmhip_batch_watch_results(self.h, out, rc))
+        return out, list(rc)
+
+    def watch_reset(self, stream=-1):
+        _check("watch_reset", lib.cmhip_batch_watch_reset(self.h, stream))
 
     # loudness (opt-in)
     def set_loudness(self, on):
@@ -2754,6 +2848,28 @@ class Group:
 
     def spectrum_reset(self, slot=-1):
         return lib.coolmic_group_spectrum_reset(self.ptr, slot)
+
+    def set_watch(self, on):
+        return lib.coolmic_group_set_watch(self.ptr, int(bool(on)))
+
+    def watch_configure(self, quiet=32, rail=32767, clip_run=3):
+        return lib.coolmic_group_watch_configure(self.ptr, quiet, rail, clip_run)
+
+    def watch(self, slot, out=None):
+        r = out if out is not None else WatchResult()
+        rc = lib.coolmic_group_watch(self.ptr, slot, C.byref(r))
+        return rc, r
+
+    def watches(self, out=None):
+        """every slot's watch window at once -> (WatchResult array, rc list); `out`: the array to fill"""
+        n = self.streams()
+        out = out if out is not None else (WatchResult * n)()
+        rc = (C.c_int * n)()
+        _check("group_watches", lib.coolmic_group_watches(self.ptr, out, rc))
+        return out, list(rc)
+
+    def watch_reset(self, slot=-1):
+        return lib.coolmic_group_watch_reset(self.ptr, slot)
 
     def set_loudness(self, on):
         return lib.coolmic_group_set_loudness(self.ptr, int(bool(on)))

@@ -220,6 +220,8 @@ extern "C" void cmhip_batch_free(cmhip_batch_t *b)
     (void)hipFree(b->d_spec_hist);
     (void)hipFree(b->d_spec_back);
     (void)hipFree(b->d_spec_table);
+    (void)hipFree(b->d_watch);
+    (void)hipFree(b->d_watch_scratch);
     (void)hipFree(b->d_loud);
     (void)hipFree(b->d_loud_ring);
     if (b->h_ring)
@@ -474,6 +476,8 @@ extern "C" int cmhip_batch_set_eq(cmhip_batch_t *b, long stream, unsigned int ns
         return fail(COOLMIC_ERROR_INVAL, "set_eq: correlation is on, and it does not measure the equaliser's result");
     if (nsec && b->spec_on)
         return fail(COOLMIC_ERROR_INVAL, "set_eq: the spectrum is on, and it does not measure the equaliser's result");
+    if (nsec && b->watch_on)
+        return fail(COOLMIC_ERROR_INVAL, "set_eq: the watch is on, and it does not measure the equaliser's result");
     if (stream >= 0 && nsec != b->nsec)
         return fail(COOLMIC_ERROR_INVAL,
                     "set_eq: the section count is a batch property (%u); set it with stream -1",
@@ -952,7 +956,7 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
                                           frames_per_stream ? b->d_nframes : nullptr, vu ? window : nullptr, parity);
         a.done_flag = flag;
         a.done_seq = flag_seq;
-        // True peak, loudness, correlation and the spectrum, when the batch has them on (then the equaliser has no sections: this branch):
+        // True peak, loudness, correlation, the spectrum and the watch, when the batch has them on (then the equaliser has no sections: this branch):
         // passes of their own over the input slots, queued AHEAD of the block kernel.  The stream runs them in order,
         // so the end of the block kernel -- its completion flag included -- still marks the end of all.  (A run the
         // block kernels' plan refuses launches nothing, these passes included.)  A pass that has been queued has
@@ -960,7 +964,7 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
         // behind it: after a run that returns an error the meters that were on may or may not hold its frames --
         // cmhip_batch_loud_reset / cmhip_batch_tp_reset / cmhip_batch_corr_reset / cmhip_batch_spec_reset before the run
         // is tried again.
-        if (b->tp_on || b->loud_on || b->corr_on || b->spec_on) {
+        if (b->tp_on || b->loud_on || b->corr_on || b->spec_on || b->watch_on) {
             if (plan_run(a).err != hipSuccess)
                 return fail(COOLMIC_ERROR_GENERIC, "run: the grid would reach 2^31 workgroups");
             if (b->loud_on) {
@@ -973,6 +977,8 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
             if (b->corr_on && cmhip_engine_corr_run(b, slots_in, frames, frames_per_stream))
                 return COOLMIC_ERROR_GENERIC;
             if (b->spec_on && cmhip_engine_spec_run(b, slots_in, frames, frames_per_stream))
+                return COOLMIC_ERROR_GENERIC;
+            if (b->watch_on && cmhip_engine_watch_run(b, slots_in, frames, frames_per_stream))
                 return COOLMIC_ERROR_GENERIC;
         }
         HIP_TRY(launch_run(a, b->stream, ev.a, ev.b, &flagged));

@@ -5,6 +5,7 @@
 //   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
 //   cmhip_corr.hip     phase correlation: the opt-in state and pairs, its launch ahead of a run, results
 //   cmhip_spec.hip     spectrum: the opt-in state and geometry, its launch ahead of a run, results
+//   cmhip_watch.hip    signal watch: the opt-in state and thresholds, its launch ahead of a run, results
 //   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
@@ -165,6 +166,14 @@ struct cmhip_batch {
     std::vector<unsigned long long> spec_frames; // frames accounted per stream since its window opened
     std::vector<unsigned long long> spec_blocks; // blocks summed per stream since its window opened
     std::vector<unsigned long long> spec_host;   // [S][8][32] staging of a result call
+    // signal watch (cmhip_watch.hip), all of it but the thresholds unused until cmhip_batch_set_watch(b, 1)
+    bool watch_on = false;
+    unsigned long long *d_watch = nullptr; // [S][WATCH_WINDOW_WORDS] windows, then [S][WATCH_SLOTS] state
+    WatchSum *d_watch_scratch = nullptr;   // [S][tiles][2C + 1] a run's tile summaries, grown on need
+    uint64_t watch_scratch_n = 0;          // summaries d_watch_scratch holds
+    unsigned int watch_quiet = WATCH_DEFAULT_QUIET, watch_rail = WATCH_DEFAULT_RAIL, watch_run = WATCH_DEFAULT_RUN;
+    std::vector<unsigned long long> watch_frames; // frames accounted per stream since its window opened
+    std::vector<unsigned long long> watch_host;   // staging of a result call: windows, then state
     // loudness (cmhip_loud.hip), all of it unused until cmhip_batch_set_loudness(b, 1)
     bool loud_on = false;
     LoudState *d_loud = nullptr;           // [S][C] the rows' filter history and open sub-block
@@ -207,6 +216,10 @@ CMHIP_INTERNAL int cmhip_engine_corr_run(cmhip_batch_t *b, const int16_t *in, si
 // (only called while b->spec_on; frames_per_stream as for cmhip_engine_tp_run)
 CMHIP_INTERNAL int cmhip_engine_spec_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                          const uint32_t *frames_per_stream);
+// cmhip_watch.hip: the watch's tile pass and fold of a run over `in`, queued on the batch's stream ahead of the block
+// kernel (only called while b->watch_on; frames_per_stream as for cmhip_engine_tp_run)
+CMHIP_INTERNAL int cmhip_engine_watch_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
+                                          const uint32_t *frames_per_stream);
 // cmhip_loud.hip: the loudness pass of a run over `in`, queued on the batch's stream ahead of the block kernel (only
 // called while b->loud_on; drains the ring first when the run could overflow it).  Returns an error number.
 CMHIP_INTERNAL int cmhip_engine_loud_run(cmhip_batch_t *b, const int16_t *in, size_t frames,

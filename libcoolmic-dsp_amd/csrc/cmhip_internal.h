@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip, k_spec.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip, k_spec.hip, k_watch.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -14,6 +14,7 @@
 #include "agc_plan.h"
 #include "iir_plan.h"
 #include "spec_plan.h"
+#include "watch_plan.h"
 
 namespace cmhip {
 
@@ -167,6 +168,25 @@ struct CorrArgs {
     uint32_t       channels;
     uint32_t       npairs;
     uint8_t        a[CORR_MAX_PAIRS], b[CORR_MAX_PAIRS];     // transformed channels of pair i (for k_corr_any)
+    uint64_t       stride;         // samples between stream slots (multiple of 8)
+    uint32_t       chunks;         // tiles per stream (the launcher fills it in)
+};
+
+// Signal watch (k_watch.hip; the specification: include/coolmic_hip.h, the arithmetic: csrc/watch_plan.h): per stream
+// the run-length and sum statistics of dead air, quiet channels and samples at the rail over the TRANSFORMED stream.
+// The tile pass writes one summary per stream, tile and predicate and adds the channel sums by integer atomics; the
+// fold walks a stream's summaries in order.  No workgroup waits for another: the stream orders the two kernels.
+struct WatchArgs {
+    const int16_t *in;             // the run's INPUT slots: the kernel applies map and gain itself
+    const StreamParam *param;
+    const uint32_t *nframes;       // per-stream frame counts or nullptr
+    unsigned long long *words;     // [S][WATCH_WINDOW_WORDS] the windows
+    unsigned long long *state;     // [S][WATCH_SLOTS] the run lengths the streams brought along
+    WatchSum      *scratch;        // [S][chunks][2C + 1] the run's tile summaries
+    uint32_t       frames;         // uniform count when nframes == nullptr
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       quiet, rail, clip_run;
     uint64_t       stride;         // samples between stream slots (multiple of 8)
     uint32_t       chunks;         // tiles per stream (the launcher fills it in)
 };
@@ -506,6 +526,10 @@ struct SpecPlan {
 };
 SpecPlan plan_spec(const SpecArgs &a, uint32_t max_blocks);
 hipError_t launch_spec(const SpecArgs &a, uint32_t max_blocks, hipStream_t st);
+// Signal watch (k_watch.hip): the plan is csrc/watch_plan.h's, shared with the CPU tests.  launch_watch queues the
+// tile pass and the fold; a.scratch holds at least plan.scratch summaries.  ev: nullptr, or three events recorded
+// ahead of the tile pass, between the two kernels and behind the fold (the measurement of tools/bench_watch.py).
+hipError_t launch_watch(const WatchArgs &a, const WatchPlan &p, hipStream_t st, hipEvent_t *ev = nullptr);
 // Loudness (k_loud.hip): one lane per row, one wave per workgroup.
 struct LoudPlan {
     hipError_t err;                // hipErrorInvalidValue: refused, the grid would reach 2^31 workgroups

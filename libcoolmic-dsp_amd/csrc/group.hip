@@ -70,6 +70,8 @@ struct coolmic_group {
     std::vector<int> *corr_rc;
     std::vector<coolmic_spectrum_result_t> *spec_out;    // and for coolmic_group_spectra
     std::vector<int> *spec_rc;
+    std::vector<coolmic_watch_result_t> *watch_out;      // and for coolmic_group_watches
+    std::vector<int> *watch_rc;
 };
 
 struct GroupHandle {
@@ -90,6 +92,8 @@ static void group_destroy(void *self)
     delete g->corr_rc;
     delete g->spec_out;
     delete g->spec_rc;
+    delete g->watch_out;
+    delete g->watch_rc;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -779,6 +783,68 @@ extern "C" int coolmic_group_spectrum_reset(coolmic_group_t *self, long slot)
     if (slot >= (long)self->streams->size() || slot < -1)
         return COOLMIC_ERROR_INVAL;
     return cmhip_batch_spec_reset(self->batch, slot);
+}
+
+// Signal watch: thin wrappers over the engine (cmhip_watch.hip), with the slot handling of the correlation calls.
+extern "C" int coolmic_group_set_watch(coolmic_group_t *self, int on)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_set_watch(self->batch, on);
+}
+
+extern "C" int coolmic_group_watch_configure(coolmic_group_t *self, unsigned int quiet, unsigned int rail,
+                                             unsigned int clip_run)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_watch_configure(self->batch, quiet, rail, clip_run);
+}
+
+extern "C" int coolmic_group_watch(coolmic_group_t *self, unsigned int slot, coolmic_watch_result_t *result)
+{
+    if (!self || !result)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= self->streams->size())
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_watch_result(self->batch, slot, result);
+}
+
+extern "C" int coolmic_group_watches(coolmic_group_t *self, coolmic_watch_result_t *results, int *rc)
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return cmhip_batch_watch_results(self->batch, results, rc);
+    if (!self->watch_rc) {
+        try {
+            if (!self->watch_out)
+                self->watch_out = new std::vector<coolmic_watch_result_t>(self->max_streams);
+            self->watch_rc = new std::vector<int>(self->max_streams);
+        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
+            return COOLMIC_ERROR_NOMEM;
+        }
+    }
+    const int r = cmhip_batch_watch_results(self->batch, self->watch_out->data(), self->watch_rc->data());
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        if ((*self->watch_rc)[i] == COOLMIC_ERROR_NONE)
+            results[i] = (*self->watch_out)[i];
+        if (rc)
+            rc[i] = (*self->watch_rc)[i];
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int coolmic_group_watch_reset(coolmic_group_t *self, long slot)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= (long)self->streams->size() || slot < -1)
+        return COOLMIC_ERROR_INVAL;
+    return cmhip_batch_watch_reset(self->batch, slot);
 }
 
 extern "C" int coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights)
