@@ -1527,6 +1527,20 @@ def eq3(rate=48000.0):
 # the batch engine
 
 
+def _one_result(fn, handle, index, T, out=None):
+    """one stream's (slot's) window through `fn` -> (error number, T); `out`: the T to fill"""
+    r = out if out is not None else T()
+    return fn(handle, index, C.byref(r)), r
+
+
+def _all_results(what, fn, handle, n, T, out=None):
+    """every stream's (slot's) window at once through `fn` -> (T array, rc list); `out`: the array to fill"""
+    out = out if out is not None else (T * n)()
+    rc = (C.c_int * n)()
+    _check(what, fn(handle, out, rc))
+    return out, list(rc)
+
+
 class Batch:
     def __init__(self, streams, channels, max_frames, flags=OUT_PCM | VU, rate=48000, device=0,
                  hip_stream=None):
@@ -1631,15 +1645,10 @@ class Batch:
 
     # VU
     def vu_result(self, stream):
-        r = VuResult()
-        rc = lib.cmhip_batch_vu_result(self.h, stream, C.byref(r))
-        return rc, r
+        return _one_result(lib.cmhip_batch_vu_result, self.h, stream, VuResult)
 
     def vu_results(self):
-        out = (VuResult * self.streams)()
-        rc = (C.c_int * self.streams)()
-        _check("vu_results", lib.cmhip_batch_vu_results(self.h, out, rc))
-        return out, list(rc)
+        return _all_results("vu_results", lib.cmhip_batch_vu_results, self.h, self.streams, VuResult)
 
     def vu_snapshot(self):
         _check("vu_snapshot", lib.cmhip_batch_vu_snapshot(self.h))
@@ -1677,15 +1686,10 @@ class Batch:
         return lib.cmhip_batch_get_true_peak(self.h)
 
     def tp_result(self, stream):
-        r = TruePeakResult()
-        rc = lib.cmhip_batch_tp_result(self.h, stream, C.byref(r))
-        return rc, r
+        return _one_result(lib.cmhip_batch_tp_result, self.h, stream, TruePeakResult)
 
     def tp_results(self):
-        out = (TruePeakResult * self.streams)()
-        rc = (C.c_int * self.streams)()
-        _check("tp_results", lib.cmhip_batch_tp_results(self.h, out, rc))
-        return out, list(rc)
+        return _all_results("tp_results", lib.cmhip_batch_tp_results, self.h, self.streams, TruePeakResult)
 
     def tp_reset(self, stream=-1):
         _check("tp_reset", lib.cmhip_batch_tp_reset(self.h, stream))
@@ -1703,15 +1707,10 @@ class Batch:
         return lib.cmhip_batch_corr_set_pairs(self.h, len(pairs), _corr_pairs(pairs))
 
     def corr_result(self, stream, out=None):
-        r = out if out is not None else CorrResult()
-        rc = lib.cmhip_batch_corr_result(self.h, stream, C.byref(r))
-        return rc, r
+        return _one_result(lib.cmhip_batch_corr_result, self.h, stream, CorrResult, out)
 
     def corr_results(self, out=None):
-        out = out if out is not None else (CorrResult * self.streams)()
-        rc = (C.c_int * self.streams)()
-        _check("corr_results", lib.cmhip_batch_corr_results(self.h, out, rc))
-        return out, list(rc)
+        return _all_results("corr_results", lib.cmhip_batch_corr_results, self.h, self.streams, CorrResult, out)
 
     def corr_reset(self, stream=-1):
         _check("corr_reset", lib.cmhip_batch_corr_reset(self.h, stream))
@@ -1730,15 +1729,10 @@ class Batch:
         return lib.cmhip_batch_spec_configure(self.h, fft_log2, *_spec_geometry(edges, channels))
 
     def spec_result(self, stream, out=None):
-        r = out if out is not None else SpecResult()
-        rc = lib.cmhip_batch_spec_result(self.h, stream, C.byref(r))
-        return rc, r
+        return _one_result(lib.cmhip_batch_spec_result, self.h, stream, SpecResult, out)
 
     def spec_results(self, out=None):
-        out = out if out is not None else (SpecResult * self.streams)()
-        rc = (C.c_int * self.streams)()
-        _check("spec_results", lib.cmhip_batch_spec_results(self.h, out, rc))
-        return out, list(rc)
+        return _all_results("spec_results", lib.cmhip_batch_spec_results, self.h, self.streams, SpecResult, out)
 
     def spec_reset(self, stream=-1):
         _check("spec_reset", lib.cmhip_batch_spec_reset(self.h, stream))
@@ -1756,15 +1750,10 @@ class Batch:
         return lib.cmhip_batch_watch_configure(self.h, quiet, rail, clip_run)
 
     def watch_result(self, stream, out=None):
-        r = out if out is not None else WatchResult()
-        rc = lib.cmhip_batch_watch_result(self.h, stream, C.byref(r))
-        return rc, r
+        return _one_result(lib.cmhip_batch_watch_result, self.h, stream, WatchResult, out)
 
     def watch_results(self, out=None):
-        out = out if out is not None else (WatchResult * self.streams)()
-        rc = (C.c_int * self.streams)()
-        _check("watch_results", lib.cmhip_batch_watch_results(self.h, out, rc))
-        return out, list(rc)
+        return _all_results("watch_results", lib.cmhip_batch_watch_results, self.h, self.streams, WatchResult, out)
 
     def watch_reset(self, stream=-1):
         _check("watch_reset", lib.cmhip_batch_watch_reset(self.h, stream))
@@ -1785,15 +1774,10 @@ class Batch:
         return lib.cmhip_batch_loud_set_weights(self.h, stream, w)
 
     def loud_result(self, stream):
-        r = LoudnessResult()
-        rc = lib.cmhip_batch_loud_result(self.h, stream, C.byref(r))
-        return rc, r
+        return _one_result(lib.cmhip_batch_loud_result, self.h, stream, LoudnessResult)
 
     def loud_results(self):
-        out = (LoudnessResult * self.streams)()
-        rc = (C.c_int * self.streams)()
-        _check("loud_results", lib.cmhip_batch_loud_results(self.h, out, rc))
-        return out, list(rc)
+        return _all_results("loud_results", lib.cmhip_batch_loud_results, self.h, self.streams, LoudnessResult)
 
     def loud_raw(self, stream, cap=30):
         """the trailing min(cap, 30) complete sub-blocks' per-channel sums, oldest first -> ([n][channels] array,
@@ -2773,18 +2757,15 @@ class Group:
         object as another stream of the group (it stays on the pumping thread), 0 when not, ERROR_INVAL: no slot"""
         return lib.cmhip_test_group_shared_source(self.ptr, slot)
 
+    def _results(self, call, T, out):
+        return _all_results("group_" + call, getattr(lib, "coolmic_group_" + call), self.ptr, self.streams(), T, out)
+
     def vumeter_result(self, slot):
-        r = VuResult()
-        rc = lib.coolmic_group_vumeter_result(self.ptr, slot, C.byref(r))
-        return rc, r
+        return _one_result(lib.coolmic_group_vumeter_result, self.ptr, slot, VuResult)
 
     def vumeter_results(self, out=None):
         """every slot's window in one snapshot and collect -> (VuResult array, rc list); `out`: the array to fill"""
-        n = self.streams()
-        out = out if out is not None else (VuResult * n)()
-        rc = (C.c_int * n)()
-        _check("group_vumeter_results", lib.coolmic_group_vumeter_results(self.ptr, out, rc))
-        return out, list(rc)
+        return self._results("vumeter_results", VuResult, out)
 
     def set_vu_finish(self, where):
         return lib.coolmic_group_set_vu_finish(self.ptr, where)
@@ -2793,17 +2774,11 @@ class Group:
         return lib.coolmic_group_set_true_peak(self.ptr, int(bool(on)))
 
     def true_peak(self, slot):
-        r = TruePeakResult()
-        rc = lib.coolmic_group_true_peak(self.ptr, slot, C.byref(r))
-        return rc, r
+        return _one_result(lib.coolmic_group_true_peak, self.ptr, slot, TruePeakResult)
 
     def true_peaks(self, out=None):
         """every slot's true-peak window at once -> (TruePeakResult array, rc list); `out`: the array to fill"""
-        n = self.streams()
-        out = out if out is not None else (TruePeakResult * n)()
-        rc = (C.c_int * n)()
-        _check("group_true_peaks", lib.coolmic_group_true_peaks(self.ptr, out, rc))
-        return out, list(rc)
+        return self._results("true_peaks", TruePeakResult, out)
 
     def set_correlation(self, on):
         return lib.coolmic_group_set_correlation(self.ptr, int(bool(on)))
@@ -2812,17 +2787,11 @@ class Group:
         return lib.coolmic_group_correlation_set_pairs(self.ptr, len(pairs), _corr_pairs(pairs))
 
     def correlation(self, slot, out=None):
-        r = out if out is not None else CorrResult()
-        rc = lib.coolmic_group_correlation(self.ptr, slot, C.byref(r))
-        return rc, r
+        return _one_result(lib.coolmic_group_correlation, self.ptr, slot, CorrResult, out)
 
     def correlations(self, out=None):
         """every slot's correlation window at once -> (CorrResult array, rc list); `out`: the array to fill"""
-        n = self.streams()
-        out = out if out is not None else (CorrResult * n)()
-        rc = (C.c_int * n)()
-        _check("group_correlations", lib.coolmic_group_correlations(self.ptr, out, rc))
-        return out, list(rc)
+        return self._results("correlations", CorrResult, out)
 
     def correlation_reset(self, slot=-1):
         return lib.coolmic_group_correlation_reset(self.ptr, slot)
@@ -2834,17 +2803,11 @@ class Group:
         return lib.coolmic_group_spectrum_configure(self.ptr, fft_log2, *_spec_geometry(edges, channels))
 
     def spectrum(self, slot, out=None):
-        r = out if out is not None else SpecResult()
-        rc = lib.coolmic_group_spectrum(self.ptr, slot, C.byref(r))
-        return rc, r
+        return _one_result(lib.coolmic_group_spectrum, self.ptr, slot, SpecResult, out)
 
     def spectra(self, out=None):
         """every slot's spectrum window at once -> (SpecResult array, rc list); `out`: the array to fill"""
-        n = self.streams()
-        out = out if out is not None else (SpecResult * n)()
-        rc = (C.c_int * n)()
-        _check("group_spectra", lib.coolmic_group_spectra(self.ptr, out, rc))
-        return out, list(rc)
+        return self._results("spectra", SpecResult, out)
 
     def spectrum_reset(self, slot=-1):
         return lib.coolmic_group_spectrum_reset(self.ptr, slot)
@@ -2856,17 +2819,11 @@ class Group:
         return lib.coolmic_group_watch_configure(self.ptr, quiet, rail, clip_run)
 
     def watch(self, slot, out=None):
-        r = out if out is not None else WatchResult()
-        rc = lib.coolmic_group_watch(self.ptr, slot, C.byref(r))
-        return rc, r
+        return _one_result(lib.coolmic_group_watch, self.ptr, slot, WatchResult, out)
 
     def watches(self, out=None):
         """every slot's watch window at once -> (WatchResult array, rc list); `out`: the array to fill"""
-        n = self.streams()
-        out = out if out is not None else (WatchResult * n)()
-        rc = (C.c_int * n)()
-        _check("group_watches", lib.coolmic_group_watches(self.ptr, out, rc))
-        return out, list(rc)
+        return self._results("watches", WatchResult, out)
 
     def watch_reset(self, slot=-1):
         return lib.coolmic_group_watch_reset(self.ptr, slot)
@@ -2875,17 +2832,11 @@ class Group:
         return lib.coolmic_group_set_loudness(self.ptr, int(bool(on)))
 
     def loudness(self, slot):
-        r = LoudnessResult()
-        rc = lib.coolmic_group_loudness(self.ptr, slot, C.byref(r))
-        return rc, r
+        return _one_result(lib.coolmic_group_loudness, self.ptr, slot, LoudnessResult)
 
     def loudnesses(self, out=None):
         """every slot's loudness at once -> (LoudnessResult array, rc list); `out`: the array to fill"""
-        n = self.streams()
-        out = out if out is not None else (LoudnessResult * n)()
-        rc = (C.c_int * n)()
-        _check("group_loudnesses", lib.coolmic_group_loudnesses(self.ptr, out, rc))
-        return out, list(rc)
+        return self._results("loudnesses", LoudnessResult, out)
 
     def loudness_set_weights(self, slot, weights):
         if len(weights) != self.channels:

@@ -213,17 +213,10 @@ extern "C" void cmhip_batch_free(cmhip_batch_t *b)
     (void)hipFree(b->d_sink);
     (void)hipFree(b->d_node_scratch);
     (void)hipFree(b->d_ring);
-    (void)hipFree(b->d_tp_peak);
-    (void)hipFree(b->d_tp_hist);
-    (void)hipFree(b->d_corr);
-    (void)hipFree(b->d_spec);
-    (void)hipFree(b->d_spec_hist);
-    (void)hipFree(b->d_spec_back);
-    (void)hipFree(b->d_spec_table);
-    (void)hipFree(b->d_watch);
-    (void)hipFree(b->d_watch_scratch);
-    (void)hipFree(b->d_loud);
-    (void)hipFree(b->d_loud_ring);
+    for (void *p : {b->tp.d, b->corr.d, b->spec.d, b->watch.d, (void *)b->d_tp_hist, (void *)b->d_spec_hist,
+                    (void *)b->d_spec_back, (void *)b->d_spec_table, (void *)b->d_watch_scratch, (void *)b->d_loud,
+                    (void *)b->d_loud_ring})
+        (void)hipFree(p);
     if (b->h_ring)
         (void)hipHostFree(b->h_ring);
     for (int i = 0; i < 3; i++)
@@ -456,6 +449,141 @@ extern "C" int cmhip_batch_set_chmap(cmhip_batch_t *b, long stream, const uint8_
     return COOLMIC_ERROR_NONE;
 }
 
+// ---------------------------------------------------------------------------
+// the opt-in meters
+
+// Every meter that measures the transformed input with a pass of its own, in the order a run launches them.  None
+// measures the equaliser's result: sections and a meter that is on exclude each other.
+struct BatchMeter {
+    const char *name;                        // the meter in a sentence
+    bool (*on)(const cmhip_batch_t *b);
+    int (*run)(cmhip_batch_t *b, const int16_t *in, size_t frames, const uint32_t *frames_per_stream);
+};
+static const BatchMeter METERS[] = {
+    {"loudness", [](const cmhip_batch_t *b) { return b->loud_on; }, cmhip_engine_loud_run},
+    {"true peak", [](const cmhip_batch_t *b) { return b->tp.on; }, cmhip_engine_tp_run},
+    {"correlation", [](const cmhip_batch_t *b) { return b->corr.on; }, cmhip_engine_corr_run},
+    {"the spectrum", [](const cmhip_batch_t *b) { return b->spec.on; }, cmhip_engine_spec_run},
+    {"the watch", [](const cmhip_batch_t *b) { return b->watch.on; }, cmhip_engine_watch_run},
+};
+
+// The window meters' shared lifecycle (csrc/cmhip_meter.h).
+
+int cmhip_meter_switch(cmhip_batch_t *b, const MeterKind &k, int on)
+{
+    if (!b)
+        return fail(COOLMIC_ERROR_FAULT, "set_%s: batch is NULL", k.sw);
+    if (on && b->nsec)
+        return fail(COOLMIC_ERROR_INVAL, "set_%s: the equaliser has sections, and %s does not measure its result", k.sw,
+                    k.name);
+    if (use(b))
+        return COOLMIC_ERROR_GENERIC;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    WindowMeter &m = b->*k.meter;
+    if (!on) {
+        m.on = false;                        // (windows and state are cleared when it is turned on again; settings stay)
+        return COOLMIC_ERROR_NONE;
+    }
+    if (m.on)
+        return COOLMIC_ERROR_NONE;
+    if (k.turn_on) {
+        const int rc = k.turn_on(b);
+        if (rc != COOLMIC_ERROR_NONE)
+            return rc;
+    }
+    const size_t S = b->d.streams, all = S * (m.bytes + m.state_bytes);
+    if (!m.d) {
+        HIP_TRY(hipMalloc(&m.d, all));
+        m.host.assign(all / sizeof(unsigned long long), 0);
+    }
+    HIP_TRY(hipMemsetAsync(m.d, 0, all, b->stream));
+    m.frames.assign(S, 0);
+    m.on = true;
+    return COOLMIC_ERROR_NONE;
+}
+
+int cmhip_meter_get(const cmhip_batch_t *b, const MeterKind &k)
+{
+    if (!b)
+        return fail(COOLMIC_ERROR_FAULT, "get_%s: batch is NULL", k.sw);
+    return (b->*k.meter).on ? 1 : 0;
+}
+
+int cmhip_meter_fetch_one(cmhip_batch_t *b, const MeterKind &k, unsigned int stream, void *out)
+{
+    if (!b || !out)
+        return fail(COOLMIC_ERROR_FAULT, "%s_result: NULL argument", k.tag);
+    WindowMeter &m = b->*k.meter;
+    if (!m.on || stream >= b->d.streams)
+        return fail(COOLMIC_ERROR_INVAL, "%s_result: stream out of range or batch without %s", k.tag, k.name);
+    if (m.frames[stream] == 0)
+        return fail(COOLMIC_ERROR_INVAL, "%s_result: the window holds no frame", k.tag);
+    if (use(b))
+        return COOLMIC_ERROR_GENERIC;
+    // (the first bytes of the staging serve: no results call is under way)
+    unsigned char *const host = (unsigned char *)m.host.data(), *const window = m.windows<unsigned char>() + stream * m.bytes;
+    HIP_TRY(hipMemcpyAsync(host, window, m.bytes, hipMemcpyDeviceToHost, b->stream));
+    if (m.state_bytes)
+        HIP_TRY(hipMemcpyAsync(host + m.bytes, m.state<unsigned char>(b->d.streams) + stream * m.state_bytes,
+                               m.state_bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    const int rc = k.finish(b, stream, host, host + m.bytes, out);
+    HIP_TRY(hipMemsetAsync(window, 0, m.bytes, b->stream));          // the window; the state stays
+    m.frames[stream] = 0;
+    return rc;
+}
+
+int cmhip_meter_fetch_all(cmhip_batch_t *b, const MeterKind &k, void *out, int *rc)
+{
+    if (!b || !out)
+        return fail(COOLMIC_ERROR_FAULT, "%s_results: NULL argument", k.tag);
+    WindowMeter &m = b->*k.meter;
+    if (!m.on)
+        return fail(COOLMIC_ERROR_INVAL, "%s_results: batch without %s", k.tag, k.name);
+    if (use(b))
+        return COOLMIC_ERROR_GENERIC;
+    // one round trip for all streams: behind what the stream has queued, read windows and state, clear the windows on
+    // the stream (the state behind them stays)
+    const size_t S = b->d.streams;
+    HIP_TRY(hipMemcpyAsync(m.host.data(), m.d, S * (m.bytes + m.state_bytes), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemsetAsync(m.d, 0, S * m.bytes, b->stream));
+    const unsigned char *const windows = (const unsigned char *)m.host.data(), *const state = windows + S * m.bytes;
+    for (size_t s = 0; s < S; s++) {
+        const int r = k.finish(b, s, windows + s * m.bytes, state + s * m.state_bytes, (unsigned char *)out + s * k.out_size);
+        if (rc)
+            rc[s] = r;
+        // A refused window held nothing to close: no frame, which leaves nothing to zero, or -- the spectrum -- frames
+        // short of a block, which the next window accounts (its sums were still zero).
+        if (r == COOLMIC_ERROR_NONE)
+            m.frames[s] = 0;
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+int cmhip_meter_clear_range(cmhip_batch_t *b, const MeterKind &k, long stream, size_t *lo, size_t *n)
+{
+    if (!b)
+        return fail(COOLMIC_ERROR_FAULT, "%s_reset: batch is NULL", k.tag);
+    const StreamRange sr = stream_range(stream, b->d.streams);
+    WindowMeter &m = b->*k.meter;
+    if (!m.on || !sr.ok)
+        return fail(COOLMIC_ERROR_INVAL, "%s_reset: stream %ld out of range or batch without %s", k.tag, stream, k.name);
+    if (use(b))
+        return COOLMIC_ERROR_GENERIC;
+    if (lo)
+        *lo = sr.lo;
+    if (n)
+        *n = sr.n;
+    HIP_TRY(hipMemsetAsync(m.windows<unsigned char>() + sr.lo * m.bytes, 0, sr.n * m.bytes, b->stream));
+    if (m.state_bytes)
+        HIP_TRY(hipMemsetAsync(m.state<unsigned char>(b->d.streams) + sr.lo * m.state_bytes, 0, sr.n * m.state_bytes,
+                               b->stream));
+    for (size_t s = sr.lo; s < sr.lo + sr.n; s++)
+        m.frames[s] = 0;
+    return COOLMIC_ERROR_NONE;
+}
+
 extern "C" int cmhip_batch_set_eq(cmhip_batch_t *b, long stream, unsigned int nsec,
                                   const float *coef)
 {
@@ -468,16 +596,9 @@ extern "C" int cmhip_batch_set_eq(cmhip_batch_t *b, long stream, unsigned int ns
     const StreamRange sr = stream_range(stream, b->d.streams);
     if (!sr.ok)
         return fail(COOLMIC_ERROR_INVAL, "set_eq: stream %ld out of range", stream);
-    if (nsec && b->tp_on)
-        return fail(COOLMIC_ERROR_INVAL, "set_eq: true peak is on, and it does not measure the equaliser's result");
-    if (nsec && b->loud_on)
-        return fail(COOLMIC_ERROR_INVAL, "set_eq: loudness is on, and it does not measure the equaliser's result");
-    if (nsec && b->corr_on)
-        return fail(COOLMIC_ERROR_INVAL, "set_eq: correlation is on, and it does not measure the equaliser's result");
-    if (nsec && b->spec_on)
-        return fail(COOLMIC_ERROR_INVAL, "set_eq: the spectrum is on, and it does not measure the equaliser's result");
-    if (nsec && b->watch_on)
-        return fail(COOLMIC_ERROR_INVAL, "set_eq: the watch is on, and it does not measure the equaliser's result");
+    for (const BatchMeter &m : METERS)
+        if (nsec && m.on(b))
+            return fail(COOLMIC_ERROR_INVAL, "set_eq: %s is on, and it does not measure the equaliser's result", m.name);
     if (stream >= 0 && nsec != b->nsec)
         return fail(COOLMIC_ERROR_INVAL,
                     "set_eq: the section count is a batch property (%u); set it with stream -1",
@@ -956,30 +1077,24 @@ static int batch_run(cmhip_batch_t *b, size_t frames, const uint32_t *frames_per
                                           frames_per_stream ? b->d_nframes : nullptr, vu ? window : nullptr, parity);
         a.done_flag = flag;
         a.done_seq = flag_seq;
-        // True peak, loudness, correlation, the spectrum and the watch, when the batch has them on (then the equaliser has no sections: this branch):
-        // passes of their own over the input slots, queued AHEAD of the block kernel.  The stream runs them in order,
-        // so the end of the block kernel -- its completion flag included -- still marks the end of all.  (A run the
-        // block kernels' plan refuses launches nothing, these passes included.)  A pass that has been queued has
-        // taken the run's frames, on the device and in the host's counts alike, whatever happens to the launches
-        // behind it: after a run that returns an error the meters that were on may or may not hold its frames --
-        // cmhip_batch_loud_reset / cmhip_batch_tp_reset / cmhip_batch_corr_reset / cmhip_batch_spec_reset before the run
-        // is tried again.
-        if (b->tp_on || b->loud_on || b->corr_on || b->spec_on || b->watch_on) {
-            if (plan_run(a).err != hipSuccess)
+        // The meters the batch has on (METERS; then the equaliser has no sections: this branch): passes of their own
+        // over the input slots, queued AHEAD of the block kernel.  The stream runs them in order, so the end of the
+        // block kernel -- its completion flag included -- still marks the end of all.  (A run the block kernels' plan
+        // refuses launches nothing, these passes included.)  A pass that has been queued has taken the run's frames,
+        // on the device and in the host's counts alike, whatever happens to the launches behind it: after a run that
+        // returns an error the meters that were on may or may not hold its frames -- cmhip_batch_loud_reset /
+        // cmhip_batch_tp_reset / cmhip_batch_corr_reset / cmhip_batch_spec_reset / cmhip_batch_watch_reset before the
+        // run is tried again.
+        bool planned = false;
+        for (const BatchMeter &m : METERS) {
+            if (!m.on(b))
+                continue;
+            if (!planned && plan_run(a).err != hipSuccess)
                 return fail(COOLMIC_ERROR_GENERIC, "run: the grid would reach 2^31 workgroups");
-            if (b->loud_on) {
-                const int rc = cmhip_engine_loud_run(b, slots_in, frames, frames_per_stream);
-                if (rc != COOLMIC_ERROR_NONE)
-                    return rc;
-            }
-            if (b->tp_on && cmhip_engine_tp_run(b, slots_in, frames, frames_per_stream))
-                return COOLMIC_ERROR_GENERIC;
-            if (b->corr_on && cmhip_engine_corr_run(b, slots_in, frames, frames_per_stream))
-                return COOLMIC_ERROR_GENERIC;
-            if (b->spec_on && cmhip_engine_spec_run(b, slots_in, frames, frames_per_stream))
-                return COOLMIC_ERROR_GENERIC;
-            if (b->watch_on && cmhip_engine_watch_run(b, slots_in, frames, frames_per_stream))
-                return COOLMIC_ERROR_GENERIC;
+            planned = true;
+            const int rc = m.run(b, slots_in, frames, frames_per_stream);    // (the window meters' is GENERIC)
+            if (rc != COOLMIC_ERROR_NONE)
+                return rc;
         }
         HIP_TRY(launch_run(a, b->stream, ev.a, ev.b, &flagged));
         b->in_flight = true;

@@ -1,11 +1,12 @@
 // cmhip_engine.h -- the batch object and what the engine's translation units share (not part of the C ABI):
-//   cmhip_batch.hip    the object, parameters, transfers, the run
+//   cmhip_batch.hip    the object, parameters, transfers, the run, the list of meters and the window meters' shared
+//                      lifecycle (csrc/cmhip_meter.h)
 //   cmhip_place.hip    the opt-in placement search for a batch's two PCM arrays
 //   cmhip_vu.hip       VU windows: results, packed snapshots and their collect, window records, node records
-//   cmhip_tp.hip       true peak: the opt-in state, its launch ahead of a run, results
-//   cmhip_corr.hip     phase correlation: the opt-in state and pairs, its launch ahead of a run, results
-//   cmhip_spec.hip     spectrum: the opt-in state and geometry, its launch ahead of a run, results
-//   cmhip_watch.hip    signal watch: the opt-in state and thresholds, its launch ahead of a run, results
+//   cmhip_tp.hip       true peak: its kind and history, its launch ahead of a run, the finish
+//   cmhip_corr.hip     phase correlation: its kind and pairs, its launch ahead of a run, the finish
+//   cmhip_spec.hip     spectrum: its kind, geometry and state, its launch ahead of a run, the finish
+//   cmhip_watch.hip    signal watch: its kind and thresholds, its launch ahead of a run, the finish
 //   cmhip_loud.hip     loudness: the opt-in state, its launch ahead of a run, the ring's drain, results
 //   cmhip_measure.hip  kernel timing and the plain HBM ceilings
 //   node.hip           the node-global VU exchange over RCCL (cmhip_node_*)
@@ -15,6 +16,8 @@
 //   cmhip_bus.hip      the mix bus
 //   cmhip_lim.hip      the peak limiter
 //   cmhip_dyn.hip      the dynamics stage: compressor and gate
+//   cmhip_split.hip    the band split: an FIR crossover
+//   cmhip_delay.hip    the delay line
 //   cmhip_agc.hip      the leveller: slow automatic gain control
 //   cmhip_iir.hip      the filter: a biquad cascade in exact integers
 #pragma once
@@ -44,6 +47,7 @@ CMHIP_INTERNAL int cmhip_fail(int code, const char *fmt, ...) __attribute__((for
     } while (0)
 
 #include "cmhip_stage.h"
+#include "cmhip_meter.h"
 
 constexpr unsigned STAGE_SLOTS = 4;
 constexpr size_t STAGE_BYTES = 64 * 1024;
@@ -134,23 +138,17 @@ struct cmhip_batch {
     cmhip_placement_t place = {0, 2, 0, 1, 0, 0, 0, 0, 0, 0};
     bool vu_off;                           // runs leave the windows alone for now (cmhip_batch_vu_pause)
 
+    // The window meters (csrc/cmhip_meter.h), each with what it keeps beside its windows.
     // true peak (cmhip_tp.hip), all of it unused until cmhip_batch_set_true_peak(b, 1)
-    bool tp_on = false;
-    uint32_t *d_tp_peak = nullptr;         // [S][16] window maxima of |y|
+    WindowMeter tp{MAX_CH * sizeof(uint32_t)};             // [S][16] window maxima of |y|
     int16_t *d_tp_hist = nullptr;          // [2][S][16][11] the streams' filter history, slot tp_parity current
     unsigned int tp_parity = 0;
-    std::vector<unsigned long long> tp_frames;   // frames accounted per stream since its window opened
-    std::vector<uint32_t> tp_host;         // [S][16] staging of a result call
     // phase correlation (cmhip_corr.hip), all of it but the pairs unused until cmhip_batch_set_correlation(b, 1)
-    bool corr_on = false;
-    unsigned long long *d_corr = nullptr;  // [S][8][3] window sums: energy_a, energy_b, cross
+    WindowMeter corr{CORR_MAX_PAIRS * CORR_SUMS * sizeof(unsigned long long)};     // [S][8][3] energy_a, energy_b, cross
     unsigned int corr_npairs = 1;          // the channel pairs, the same for all streams (kept across off / on)
     unsigned char corr_a[CORR_MAX_PAIRS] = {0}, corr_b[CORR_MAX_PAIRS] = {1};
-    std::vector<unsigned long long> corr_frames; // frames accounted per stream since its window opened
-    std::vector<unsigned long long> corr_host;   // [S][8][3] staging of a result call
     // spectrum (cmhip_spec.hip), all of it but the geometry unused until cmhip_batch_set_spectrum(b, 1)
-    bool spec_on = false;
-    unsigned long long *d_spec = nullptr;  // [S][8][32] window sums per selected channel and band
+    WindowMeter spec{SPEC_MAX_CH * SPEC_MAX_BANDS * sizeof(unsigned long long)};   // [S][8][32] sums per selected channel and band
     int16_t *d_spec_hist = nullptr;        // [2][S][nch][N] the streams' last N - 1 samples, slot spec_parity current
     uint32_t *d_spec_back = nullptr;       // [2][S] the streams' back (csrc/spec_plan.h), slot spec_parity current
     int32_t *d_spec_table = nullptr;       // Wr[N/2], Wi[N/2], win[N], edges[33]
@@ -163,17 +161,12 @@ struct cmhip_batch {
     uint16_t spec_edges[SPEC_MAX_BANDS + 1] = {};
     unsigned char spec_ch[SPEC_MAX_CH] = {};
     std::vector<uint32_t> spec_back;             // host mirror of the current back per stream
-    std::vector<unsigned long long> spec_frames; // frames accounted per stream since its window opened
     std::vector<unsigned long long> spec_blocks; // blocks summed per stream since its window opened
-    std::vector<unsigned long long> spec_host;   // [S][8][32] staging of a result call
     // signal watch (cmhip_watch.hip), all of it but the thresholds unused until cmhip_batch_set_watch(b, 1)
-    bool watch_on = false;
-    unsigned long long *d_watch = nullptr; // [S][WATCH_WINDOW_WORDS] windows, then [S][WATCH_SLOTS] state
+    WindowMeter watch{WATCH_WINDOW_WORDS * sizeof(unsigned long long), WATCH_SLOTS * sizeof(unsigned long long)};
     WatchSum *d_watch_scratch = nullptr;   // [S][tiles][2C + 1] a run's tile summaries, grown on need
     uint64_t watch_scratch_n = 0;          // summaries d_watch_scratch holds
     unsigned int watch_quiet = WATCH_DEFAULT_QUIET, watch_rail = WATCH_DEFAULT_RAIL, watch_run = WATCH_DEFAULT_RUN;
-    std::vector<unsigned long long> watch_frames; // frames accounted per stream since its window opened
-    std::vector<unsigned long long> watch_host;   // staging of a result call: windows, then state
     // loudness (cmhip_loud.hip), all of it unused until cmhip_batch_set_loudness(b, 1)
     bool loud_on = false;
     LoudState *d_loud = nullptr;           // [S][C] the rows' filter history and open sub-block
@@ -205,19 +198,19 @@ CMHIP_INTERNAL int cmhip_engine_flush_params(cmhip_batch_t *b);
 CMHIP_INTERNAL RunArgs cmhip_engine_run_args(const cmhip_batch_t *b, const int16_t *in, int16_t *out, size_t frames,
                                              const uint32_t *nframes, VuState *window, uint32_t parity);
 // cmhip_tp.hip: the true-peak pass of a run over `in`, queued on the batch's stream ahead of the block kernel
-// (only called while b->tp_on; frames_per_stream: the run's host array or nullptr, already uploaded to d_nframes)
+// (only called while b->tp.on; frames_per_stream: the run's host array or nullptr, already uploaded to d_nframes)
 CMHIP_INTERNAL int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                        const uint32_t *frames_per_stream);
 // cmhip_corr.hip: the correlation pass of a run over `in`, queued on the batch's stream ahead of the block kernel
-// (only called while b->corr_on; frames_per_stream as for cmhip_engine_tp_run)
+// (only called while b->corr.on; frames_per_stream as for cmhip_engine_tp_run)
 CMHIP_INTERNAL int cmhip_engine_corr_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                          const uint32_t *frames_per_stream);
 // cmhip_spec.hip: the spectrum pass of a run over `in`, queued on the batch's stream ahead of the block kernel
-// (only called while b->spec_on; frames_per_stream as for cmhip_engine_tp_run)
+// (only called while b->spec.on; frames_per_stream as for cmhip_engine_tp_run)
 CMHIP_INTERNAL int cmhip_engine_spec_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                          const uint32_t *frames_per_stream);
 // cmhip_watch.hip: the watch's tile pass and fold of a run over `in`, queued on the batch's stream ahead of the block
-// kernel (only called while b->watch_on; frames_per_stream as for cmhip_engine_tp_run)
+// kernel (only called while b->watch.on; frames_per_stream as for cmhip_engine_tp_run)
 CMHIP_INTERNAL int cmhip_engine_watch_run(cmhip_batch_t *b, const int16_t *in, size_t frames,
                                           const uint32_t *frames_per_stream);
 // cmhip_loud.hip: the loudness pass of a run over `in`, queued on the batch's stream ahead of the block kernel (only

@@ -6,7 +6,8 @@
 // sums per stream and selected channel; the streams' last N - 1 transformed samples per selected channel and their
 // `back` (csrc/spec_plan.h), each in two slots that the runs alternate between, as true peak keeps its history; the
 // tables.  Positions, block counts and the frames a window accounts are mirrored on the host, where every run's counts
-// are known.  The VU, true-peak, loudness and correlation windows know nothing of this.
+// are known.  The VU, true-peak, loudness and correlation windows know nothing of this.  The windows' lifecycle is the
+// shared one of csrc/cmhip_meter.h; a window here closes on its completed blocks, not on its frames.
 #include "cmhip_engine.h"
 
 #include <math.h>
@@ -97,7 +98,7 @@ extern "C" int cmhip_batch_spec_configure(cmhip_batch_t *b, unsigned int fft_log
 {
     if (!b || (nb && !edges) || (nch && !channels))
         return fail(COOLMIC_ERROR_FAULT, "spec_configure: NULL argument");
-    if (b->spec_on)
+    if (b->spec.on)
         return fail(COOLMIC_ERROR_BUSY, "spec_configure: the spectrum is on (turn it off first)");
     if (!spec_log2_ok(fft_log2))
         return fail(COOLMIC_ERROR_INVAL, "spec_configure: fft_log2 %u outside 8..12", fft_log2);
@@ -125,29 +126,14 @@ extern "C" int cmhip_batch_spec_configure(cmhip_batch_t *b, unsigned int fft_log
     return COOLMIC_ERROR_NONE;
 }
 
-extern "C" int cmhip_batch_set_spectrum(cmhip_batch_t *b, int on)
+// beside the windows: the defaults, the state and tables for the geometry in force, the state cleared
+static int spec_turn_on(cmhip_batch_t *b)
 {
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "set_spectrum: batch is NULL");
-    if (on && b->nsec)
-        return fail(COOLMIC_ERROR_INVAL, "set_spectrum: the equaliser has sections, and the spectrum does not measure its result");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (!on) {
-        b->spec_on = false;                  // (windows and state are cleared when it is turned on again; the geometry stays)
-        return COOLMIC_ERROR_NONE;
-    }
-    if (b->spec_on)
-        return COOLMIC_ERROR_NONE;
     spec_fill_defaults(b);
     const size_t S = b->d.streams, N = (size_t)1 << b->spec_log2;
     const size_t hist_words = 2 * S * b->spec_nch * N, table_words = 2 * N + SPEC_MAX_BANDS + 1;
-    if (!b->d_spec) {
-        HIP_TRY(hipMalloc((void **)&b->d_spec, S * SPEC_WORDS * sizeof(unsigned long long)));
+    if (!b->d_spec_back)
         HIP_TRY(hipMalloc((void **)&b->d_spec_back, 2 * S * sizeof(uint32_t)));
-        b->spec_host.assign(S * SPEC_WORDS, 0);
-    }
     if (b->spec_hist_words != hist_words) {  // (the geometry changed while the meter was off)
         (void)hipFree(b->d_spec_hist);
         b->d_spec_hist = nullptr;
@@ -172,23 +158,13 @@ extern "C" int cmhip_batch_set_spectrum(cmhip_batch_t *b, int on)
     for (unsigned i = 0; i <= b->spec_nb; i++)
         table[2 * N + i] = b->spec_edges[i];
     HIP_TRY(hipMemcpyAsync(b->d_spec_table, table.data(), table_words * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemsetAsync(b->d_spec, 0, S * SPEC_WORDS * sizeof(unsigned long long), b->stream));
     HIP_TRY(hipMemsetAsync(b->d_spec_hist, 0, hist_words * sizeof(int16_t), b->stream));
     HIP_TRY(hipMemsetAsync(b->d_spec_back, 0, 2 * S * sizeof(uint32_t), b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));        // (the table is a local)
     b->spec_parity = 0;
     b->spec_back.assign(S, 0);
-    b->spec_frames.assign(S, 0);
     b->spec_blocks.assign(S, 0);
-    b->spec_on = true;
     return COOLMIC_ERROR_NONE;
-}
-
-extern "C" int cmhip_batch_get_spectrum(const cmhip_batch_t *b)
-{
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "get_spectrum: batch is NULL");
-    return b->spec_on ? 1 : 0;
 }
 
 int cmhip_engine_spec_run(cmhip_batch_t *b, const int16_t *in, size_t frames, const uint32_t *frames_per_stream)
@@ -198,7 +174,7 @@ int cmhip_engine_spec_run(cmhip_batch_t *b, const int16_t *in, size_t frames, co
     a.in = in;
     a.param = b->d_param;
     a.nframes = frames_per_stream ? b->d_nframes : nullptr;
-    a.sums = b->d_spec;
+    a.sums = b->spec.windows<unsigned long long>();
     a.hist = b->d_spec_hist;
     a.back = b->d_spec_back;
     a.table = b->d_spec_table;
@@ -228,21 +204,23 @@ int cmhip_engine_spec_run(cmhip_batch_t *b, const int16_t *in, size_t frames, co
         const uint32_t f = frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
         b->spec_blocks[s] += spec_run_blocks(b->spec_log2, b->spec_back[s], f);
         b->spec_back[s] = spec_next_back(b->spec_log2, b->spec_back[s], f);
-        b->spec_frames[s] += f;
     }
+    b->spec.account(frames, frames_per_stream);
     return COOLMIC_ERROR_NONE;
 }
 
 // one window's result from its sums; out is left alone while the window holds no block
-static int spec_finish(const cmhip_batch_t *b, unsigned long long frames, unsigned long long blocks,
-                       const unsigned long long *sums, coolmic_spectrum_result_t *out)
+static int spec_finish(const cmhip_batch_t *b, size_t s, const void *window, const void *, void *result)
 {
+    const unsigned long long blocks = b->spec_blocks[s];
     if (blocks == 0)
         return COOLMIC_ERROR_INVAL;
+    const unsigned long long *const sums = (const unsigned long long *)window;
+    coolmic_spectrum_result_t *const out = (coolmic_spectrum_result_t *)result;
     memset(out, 0, sizeof(*out));
     out->rate = b->d.rate;
     out->channels = b->d.channels;
-    out->frames = (size_t)frames;
+    out->frames = (size_t)b->spec.frames[s];
     out->blocks = (size_t)blocks;
     out->fft_log2 = b->spec_log2;
     out->bands = b->spec_nb;
@@ -257,72 +235,50 @@ static int spec_finish(const cmhip_batch_t *b, unsigned long long frames, unsign
     return COOLMIC_ERROR_NONE;
 }
 
+static const MeterKind SPEC = {"spec", "spectrum", "the spectrum", &cmhip_batch::spec, sizeof(coolmic_spectrum_result_t),
+                               spec_finish, spec_turn_on};
+
+extern "C" int cmhip_batch_set_spectrum(cmhip_batch_t *b, int on)
+{
+    return cmhip_meter_switch(b, SPEC, on);  // (the geometry stays across off and on)
+}
+
+extern "C" int cmhip_batch_get_spectrum(const cmhip_batch_t *b) { return cmhip_meter_get(b, SPEC); }
+
+// A window closes on its blocks, not its frames: frames short of a block give no result and are kept.
 extern "C" int cmhip_batch_spec_result(cmhip_batch_t *b, unsigned int stream, coolmic_spectrum_result_t *out)
 {
-    if (!b || !out)
-        return fail(COOLMIC_ERROR_FAULT, "spec_result: NULL argument");
-    if (!b->spec_on || stream >= b->d.streams)
-        return fail(COOLMIC_ERROR_INVAL, "spec_result: stream out of range or batch without the spectrum");
-    if (b->spec_blocks[stream] == 0)
+    if (b && out && b->spec.on && stream < b->d.streams && b->spec_blocks[stream] == 0)
         return fail(COOLMIC_ERROR_INVAL, "spec_result: the window holds no completed block");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    unsigned long long sums[SPEC_WORDS];
-    unsigned long long *const window = b->d_spec + (size_t)stream * SPEC_WORDS;
-    HIP_TRY(hipMemcpyAsync(sums, window, sizeof(sums), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    const int rc = spec_finish(b, b->spec_frames[stream], b->spec_blocks[stream], sums, out);
-    HIP_TRY(hipMemsetAsync(window, 0, sizeof(sums), b->stream));
-    b->spec_frames[stream] = 0;
-    b->spec_blocks[stream] = 0;
+    const int rc = cmhip_meter_fetch_one(b, SPEC, stream, out);
+    if (rc == COOLMIC_ERROR_NONE)
+        b->spec_blocks[stream] = 0;
     return rc;
 }
 
 extern "C" int cmhip_batch_spec_results(cmhip_batch_t *b, coolmic_spectrum_result_t *out, int *rc)
 {
-    if (!b || !out)
-        return fail(COOLMIC_ERROR_FAULT, "spec_results: NULL argument");
-    if (!b->spec_on)
-        return fail(COOLMIC_ERROR_INVAL, "spec_results: batch without the spectrum");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    // one round trip for all streams: behind what the stream has queued, read the windows, then clear on the stream
-    // those that closed (a window without a completed block is kept: it holds no sum, only its frames on the host)
-    const size_t S = b->d.streams, bytes = S * SPEC_WORDS * sizeof(unsigned long long);
-    HIP_TRY(hipMemcpyAsync(b->spec_host.data(), b->d_spec, bytes, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemsetAsync(b->d_spec, 0, bytes, b->stream));
-    for (size_t s = 0; s < S; s++) {
-        const int r = spec_finish(b, b->spec_frames[s], b->spec_blocks[s], &b->spec_host[s * SPEC_WORDS], &out[s]);
-        if (rc)
-            rc[s] = r;
-        if (r == COOLMIC_ERROR_NONE) {
-            b->spec_frames[s] = 0;
-            b->spec_blocks[s] = 0;
-        }
-    }
-    return COOLMIC_ERROR_NONE;
+    const int r = cmhip_meter_fetch_all(b, SPEC, out, rc);
+    // every window that held a block has closed, frames and all; the others keep their frames and had no block
+    if (r == COOLMIC_ERROR_NONE)
+        b->spec_blocks.assign(b->d.streams, 0);
+    return r;
 }
 
 extern "C" int cmhip_batch_spec_reset(cmhip_batch_t *b, long stream)
 {
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "spec_reset: batch is NULL");
-    const StreamRange sr = stream_range(stream, b->d.streams);
-    if (!b->spec_on || !sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "spec_reset: stream %ld out of range or batch without the spectrum", stream);
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    const size_t lo = sr.lo, n = sr.n, S = b->d.streams;
+    size_t lo, n;
+    const int rc = cmhip_meter_clear_range(b, SPEC, stream, &lo, &n);
+    if (rc != COOLMIC_ERROR_NONE)
+        return rc;
+    const size_t S = b->d.streams;
     const size_t row = (size_t)b->spec_nch << b->spec_log2;      // state samples per stream and slot
-    HIP_TRY(hipMemsetAsync(b->d_spec + lo * SPEC_WORDS, 0, n * SPEC_WORDS * sizeof(unsigned long long), b->stream));
     for (size_t slot = 0; slot < 2; slot++) {
         HIP_TRY(hipMemsetAsync(b->d_spec_hist + (slot * S + lo) * row, 0, n * row * sizeof(int16_t), b->stream));
         HIP_TRY(hipMemsetAsync(b->d_spec_back + slot * S + lo, 0, n * sizeof(uint32_t), b->stream));
     }
     for (size_t s = lo; s < lo + n; s++) {
         b->spec_back[s] = 0;
-        b->spec_frames[s] = 0;
         b->spec_blocks[s] = 0;
     }
     return COOLMIC_ERROR_NONE;

@@ -1,10 +1,11 @@
-// cmhip_tp.hip -- true peak (ITU-R BS.1770 Annex 2 / EBU R128) of a batch on the host side: the opt-in state, the
-// launch of k_tpeak.hip's kernel ahead of a run's block kernel, the windows' results with the dBTP finish in double.
+// cmhip_tp.hip -- true peak (ITU-R BS.1770 Annex 2 / EBU R128) of a batch on the host side: the meter's kind, the
+// launch of k_tpeak.hip's kernel ahead of a run's block kernel, the windows' finish with dBTP in double.
 //
 // Device state (made on the first cmhip_batch_set_true_peak(b, 1)): the windows, uint32 [S][16] maxima of |y|, and
 // the streams' filter history, int16 [2][S][16][11], two slots selected by a parity the host flips per run (the
 // mechanism of VuState::samples).  The frames a window accounts are counted on the host, where every run's counts
-// are known.  The VU windows, their snapshots and records know nothing of this.
+// are known.  The VU windows, their snapshots and records know nothing of this.  The windows' lifecycle is the shared
+// one of csrc/cmhip_meter.h.
 #include "cmhip_engine.h"
 
 #include <math.h>
@@ -32,40 +33,14 @@ extern "C" void cmhip_tp_coefficients(int16_t h[48])
             h[p * TP_TAPS + k] = tp_h(p, k);
 }
 
-extern "C" int cmhip_batch_set_true_peak(cmhip_batch_t *b, int on)
+// beside the windows: both history slots, made once and cleared
+static int tp_turn_on(cmhip_batch_t *b)
 {
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "set_true_peak: batch is NULL");
-    if (on && b->nsec)
-        return fail(COOLMIC_ERROR_INVAL, "set_true_peak: the equaliser has sections, and true peak does not measure its result");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (!on) {
-        b->tp_on = false;                    // (windows and history are cleared when it is turned on again)
-        return COOLMIC_ERROR_NONE;
-    }
-    if (b->tp_on)
-        return COOLMIC_ERROR_NONE;
-    const size_t S = b->d.streams;
-    if (!b->d_tp_peak) {
-        HIP_TRY(hipMalloc((void **)&b->d_tp_peak, S * MAX_CH * sizeof(uint32_t)));
+    if (!b->d_tp_hist)
         HIP_TRY(hipMalloc((void **)&b->d_tp_hist, 2 * tp_hist_words(b) * sizeof(int16_t)));
-        b->tp_host.assign(S * MAX_CH, 0);
-    }
-    HIP_TRY(hipMemsetAsync(b->d_tp_peak, 0, S * MAX_CH * sizeof(uint32_t), b->stream));
     HIP_TRY(hipMemsetAsync(b->d_tp_hist, 0, 2 * tp_hist_words(b) * sizeof(int16_t), b->stream));
-    b->tp_frames.assign(S, 0);
     b->tp_parity = 0;
-    b->tp_on = true;
     return COOLMIC_ERROR_NONE;
-}
-
-extern "C" int cmhip_batch_get_true_peak(const cmhip_batch_t *b)
-{
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "get_true_peak: batch is NULL");
-    return b->tp_on ? 1 : 0;
 }
 
 int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames, const uint32_t *frames_per_stream)
@@ -75,7 +50,7 @@ int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames, cons
     a.in = in;
     a.param = b->d_param;
     a.nframes = frames_per_stream ? b->d_nframes : nullptr;
-    a.peak = b->d_tp_peak;
+    a.peak = b->tp.windows<uint32_t>();
     a.hist = b->d_tp_hist;
     a.frames = (uint32_t)frames;
     a.streams = b->d.streams;
@@ -87,17 +62,18 @@ int cmhip_engine_tp_run(cmhip_batch_t *b, const int16_t *in, size_t frames, cons
         return fail(COOLMIC_ERROR_GENERIC, "run: the true-peak pass: %s", hipGetErrorString(e));
     g_tp_runs.fetch_add(1, std::memory_order_relaxed);
     b->tp_parity ^= 1u;                      // the kernel wrote the other history slot
-    for (unsigned s = 0; s < b->d.streams; s++)
-        b->tp_frames[s] += frames_per_stream ? frames_per_stream[s] : frames;
+    b->tp.account(frames, frames_per_stream);
     return COOLMIC_ERROR_NONE;
 }
 
 // one window's result from its maxima; out is left alone while the window holds no frame
-static int tp_finish(const cmhip_batch_t *b, unsigned long long frames, const uint32_t *peak,
-                     coolmic_truepeak_result_t *out)
+static int tp_finish(const cmhip_batch_t *b, size_t s, const void *window, const void *, void *result)
 {
+    const unsigned long long frames = b->tp.frames[s];
     if (frames == 0)
         return COOLMIC_ERROR_INVAL;
+    const uint32_t *const peak = (const uint32_t *)window;
+    coolmic_truepeak_result_t *const out = (coolmic_truepeak_result_t *)result;
     const unsigned C = b->d.channels;
     memset(out, 0, sizeof(*out));
     out->rate = b->d.rate;
@@ -115,63 +91,30 @@ static int tp_finish(const cmhip_batch_t *b, unsigned long long frames, const ui
     return COOLMIC_ERROR_NONE;
 }
 
+static const MeterKind TP = {"tp", "true_peak", "true peak", &cmhip_batch::tp, sizeof(coolmic_truepeak_result_t),
+                             tp_finish, tp_turn_on};
+
+extern "C" int cmhip_batch_set_true_peak(cmhip_batch_t *b, int on) { return cmhip_meter_switch(b, TP, on); }
+extern "C" int cmhip_batch_get_true_peak(const cmhip_batch_t *b) { return cmhip_meter_get(b, TP); }
+
 extern "C" int cmhip_batch_tp_result(cmhip_batch_t *b, unsigned int stream, coolmic_truepeak_result_t *out)
 {
-    if (!b || !out)
-        return fail(COOLMIC_ERROR_FAULT, "tp_result: NULL argument");
-    if (!b->tp_on || stream >= b->d.streams)
-        return fail(COOLMIC_ERROR_INVAL, "tp_result: stream out of range or batch without true peak");
-    if (b->tp_frames[stream] == 0)
-        return fail(COOLMIC_ERROR_INVAL, "tp_result: the window holds no frame");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    uint32_t peak[MAX_CH];
-    uint32_t *const window = b->d_tp_peak + (size_t)stream * MAX_CH;
-    HIP_TRY(hipMemcpyAsync(peak, window, sizeof(peak), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    const int rc = tp_finish(b, b->tp_frames[stream], peak, out);
-    HIP_TRY(hipMemsetAsync(window, 0, sizeof(peak), b->stream));
-    b->tp_frames[stream] = 0;
-    return rc;
+    return cmhip_meter_fetch_one(b, TP, stream, out);
 }
 
 extern "C" int cmhip_batch_tp_results(cmhip_batch_t *b, coolmic_truepeak_result_t *out, int *rc)
 {
-    if (!b || !out)
-        return fail(COOLMIC_ERROR_FAULT, "tp_results: NULL argument");
-    if (!b->tp_on)
-        return fail(COOLMIC_ERROR_INVAL, "tp_results: batch without true peak");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    // one round trip for all streams: behind what the stream has queued, read the windows, clear them on the stream
-    const size_t S = b->d.streams, bytes = S * MAX_CH * sizeof(uint32_t);
-    HIP_TRY(hipMemcpyAsync(b->tp_host.data(), b->d_tp_peak, bytes, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemsetAsync(b->d_tp_peak, 0, bytes, b->stream));
-    for (size_t s = 0; s < S; s++) {
-        const int r = tp_finish(b, b->tp_frames[s], &b->tp_host[s * MAX_CH], &out[s]);
-        if (rc)
-            rc[s] = r;
-        b->tp_frames[s] = 0;
-    }
-    return COOLMIC_ERROR_NONE;
+    return cmhip_meter_fetch_all(b, TP, out, rc);
 }
 
 extern "C" int cmhip_batch_tp_reset(cmhip_batch_t *b, long stream)
 {
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "tp_reset: batch is NULL");
-    const StreamRange sr = stream_range(stream, b->d.streams);
-    if (!b->tp_on || !sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "tp_reset: stream %ld out of range or batch without true peak", stream);
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    const size_t lo = sr.lo, n = sr.n;
-    HIP_TRY(hipMemsetAsync(b->d_tp_peak + lo * MAX_CH, 0, n * MAX_CH * sizeof(uint32_t), b->stream));
+    size_t lo, n;
+    const int rc = cmhip_meter_clear_range(b, TP, stream, &lo, &n);
+    if (rc != COOLMIC_ERROR_NONE)
+        return rc;
     for (unsigned slot = 0; slot < 2; slot++)
         HIP_TRY(hipMemsetAsync(b->d_tp_hist + slot * tp_hist_words(b) + lo * MAX_CH * TP_HIST, 0,
                                n * MAX_CH * TP_HIST * sizeof(int16_t), b->stream));
-    for (size_t s = lo; s < lo + n; s++)
-        b->tp_frames[s] = 0;
     return COOLMIC_ERROR_NONE;
 }

@@ -5,7 +5,8 @@
 // [S][WATCH_WINDOW_WORDS] (frames, longest run and events per predicate, the channel sums) and behind them the state
 // [S][WATCH_SLOTS], the run lengths the streams brought along (csrc/watch_plan.h); and a scratch array of tile
 // summaries sized by the launch plan and grown on need.  The frames a window accounts are counted on the host, where
-// every run's counts are known.
+// every run's counts are known.  The windows' lifecycle is the shared one of csrc/cmhip_meter.h, the state its
+// state_bytes.
 #include "cmhip_engine.h"
 
 #include <math.h>
@@ -32,54 +33,6 @@ extern "C" unsigned int cmhip_watch_level(double db)
     return (unsigned int)lround(v);
 }
 
-static unsigned long long *watch_state(const cmhip_batch_t *b)
-{
-    return b->d_watch + (size_t)b->d.streams * WATCH_WINDOW_WORDS;
-}
-
-static bool watch_windows_empty(const cmhip_batch_t *b)
-{
-    if (!b->watch_on)
-        return true;
-    for (unsigned long long f : b->watch_frames)
-        if (f)
-            return false;
-    return true;
-}
-
-extern "C" int cmhip_batch_set_watch(cmhip_batch_t *b, int on)
-{
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "set_watch: batch is NULL");
-    if (on && b->nsec)
-        return fail(COOLMIC_ERROR_INVAL, "set_watch: the equaliser has sections, and the watch does not measure its result");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (!on) {
-        b->watch_on = false;                 // (windows and state are cleared when it is turned on again)
-        return COOLMIC_ERROR_NONE;
-    }
-    if (b->watch_on)
-        return COOLMIC_ERROR_NONE;
-    const size_t S = b->d.streams;
-    if (!b->d_watch) {
-        HIP_TRY(hipMalloc((void **)&b->d_watch, S * WATCH_WORDS * WORD));
-        b->watch_host.assign(S * WATCH_WORDS, 0);
-    }
-    HIP_TRY(hipMemsetAsync(b->d_watch, 0, S * WATCH_WORDS * WORD, b->stream));
-    b->watch_frames.assign(S, 0);
-    b->watch_on = true;
-    return COOLMIC_ERROR_NONE;
-}
-
-extern "C" int cmhip_batch_get_watch(const cmhip_batch_t *b)
-{
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "get_watch: batch is NULL");
-    return b->watch_on ? 1 : 0;
-}
-
 extern "C" int cmhip_batch_watch_configure(cmhip_batch_t *b, unsigned int quiet, unsigned int rail, unsigned int clip_run)
 {
     if (!b)
@@ -87,12 +40,12 @@ extern "C" int cmhip_batch_watch_configure(cmhip_batch_t *b, unsigned int quiet,
     if (quiet > 32767 || rail < 1 || rail > 32767 || clip_run < 1 || clip_run > WATCH_MAX_RUN)
         return fail(COOLMIC_ERROR_INVAL, "watch_configure: quiet 0..32767, rail 1..32767, clip_run 1..%u (got %u, %u, %u)",
                     WATCH_MAX_RUN, quiet, rail, clip_run);
-    if (!watch_windows_empty(b))
+    if (!b->watch.windows_empty())
         return fail(COOLMIC_ERROR_BUSY, "watch_configure: a window holds frames (result or reset first)");
-    if (b->watch_on) {                       // the predicates change: no run continues across that
+    if (b->watch.on) {                       // the predicates change: no run continues across that
         if (use(b))
             return COOLMIC_ERROR_GENERIC;
-        HIP_TRY(hipMemsetAsync(b->d_watch, 0, (size_t)b->d.streams * WATCH_WORDS * WORD, b->stream));
+        HIP_TRY(hipMemsetAsync(b->watch.d, 0, (size_t)b->d.streams * WATCH_WORDS * WORD, b->stream));
     }
     b->watch_quiet = quiet;
     b->watch_rail = rail;
@@ -118,8 +71,8 @@ static int watch_launch(cmhip_batch_t *b, const int16_t *in, size_t frames, cons
     a.in = in;
     a.param = b->d_param;
     a.nframes = frames_per_stream ? b->d_nframes : nullptr;
-    a.words = b->d_watch;
-    a.state = watch_state(b);
+    a.words = b->watch.windows<unsigned long long>();
+    a.state = b->watch.state<unsigned long long>(b->d.streams);
     a.scratch = b->d_watch_scratch;
     a.frames = (uint32_t)frames;
     a.streams = b->d.streams;
@@ -132,8 +85,7 @@ static int watch_launch(cmhip_batch_t *b, const int16_t *in, size_t frames, cons
     if (e != hipSuccess)
         return fail(COOLMIC_ERROR_GENERIC, "run: the watch pass: %s", hipGetErrorString(e));
     g_watch_runs.fetch_add(1, std::memory_order_relaxed);
-    for (unsigned s = 0; s < b->d.streams; s++)
-        b->watch_frames[s] += frames_per_stream ? frames_per_stream[s] : frames;
+    b->watch.account(frames, frames_per_stream);
     return COOLMIC_ERROR_NONE;
 }
 
@@ -149,7 +101,7 @@ extern "C" int cmhip_test_watch_time(cmhip_batch_t *b, size_t frames, float ms[2
 {
     if (!b || !ms)
         return fail(COOLMIC_ERROR_FAULT, "watch_time: NULL argument");
-    if (!b->watch_on || !b->d_in || frames == 0 || frames > b->d.max_frames)
+    if (!b->watch.on || !b->d_in || frames == 0 || frames > b->d.max_frames)
         return fail(COOLMIC_ERROR_INVAL, "watch_time: a batch with the watch on and slots of its own, 1..max_frames frames");
     if (use(b) || cmhip_engine_flush_params(b))
         return COOLMIC_ERROR_GENERIC;
@@ -166,12 +118,14 @@ extern "C" int cmhip_test_watch_time(cmhip_batch_t *b, size_t frames, float ms[2
     return rc;
 }
 
-// one window's result from its words; out is left alone while the window holds no frame
-static int watch_finish(const cmhip_batch_t *b, unsigned long long frames, const unsigned long long *w,
-                        const unsigned long long *st, coolmic_watch_result_t *out)
+// one window's result from its words and the stream's state; out is left alone while the window holds no frame
+static int watch_finish(const cmhip_batch_t *b, size_t s, const void *window, const void *state, void *result)
 {
+    const unsigned long long frames = b->watch.frames[s];
     if (frames == 0)
         return COOLMIC_ERROR_INVAL;
+    const unsigned long long *const w = (const unsigned long long *)window, *const st = (const unsigned long long *)state;
+    coolmic_watch_result_t *const out = (coolmic_watch_result_t *)result;
     const unsigned C = b->d.channels;
     memset(out, 0, sizeof(*out));
     out->rate = b->d.rate;
@@ -198,64 +152,22 @@ static int watch_finish(const cmhip_batch_t *b, unsigned long long frames, const
     return COOLMIC_ERROR_NONE;
 }
 
+// (a result clears the window and keeps the state; on, reset and a configure while on clear both)
+static const MeterKind WATCH = {"watch", "watch", "the watch", &cmhip_batch::watch, sizeof(coolmic_watch_result_t),
+                                watch_finish, nullptr};
+
+extern "C" int cmhip_batch_set_watch(cmhip_batch_t *b, int on) { return cmhip_meter_switch(b, WATCH, on); }
+extern "C" int cmhip_batch_get_watch(const cmhip_batch_t *b) { return cmhip_meter_get(b, WATCH); }
+
 extern "C" int cmhip_batch_watch_result(cmhip_batch_t *b, unsigned int stream, coolmic_watch_result_t *out)
 {
-    if (!b || !out)
-        return fail(COOLMIC_ERROR_FAULT, "watch_result: NULL argument");
-    if (!b->watch_on || stream >= b->d.streams)
-        return fail(COOLMIC_ERROR_INVAL, "watch_result: stream out of range or batch without the watch");
-    if (b->watch_frames[stream] == 0)
-        return fail(COOLMIC_ERROR_INVAL, "watch_result: the window holds no frame");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    unsigned long long w[WATCH_WINDOW_WORDS], st[WATCH_SLOTS];
-    unsigned long long *const window = b->d_watch + (size_t)stream * WATCH_WINDOW_WORDS;
-    HIP_TRY(hipMemcpyAsync(w, window, sizeof(w), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(st, watch_state(b) + (size_t)stream * WATCH_SLOTS, sizeof(st), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    const int rc = watch_finish(b, b->watch_frames[stream], w, st, out);
-    HIP_TRY(hipMemsetAsync(window, 0, sizeof(w), b->stream));      // the window; the state stays
-    b->watch_frames[stream] = 0;
-    return rc;
+    return cmhip_meter_fetch_one(b, WATCH, stream, out);
 }
 
 extern "C" int cmhip_batch_watch_results(cmhip_batch_t *b, coolmic_watch_result_t *out, int *rc)
 {
-    if (!b || !out)
-        return fail(COOLMIC_ERROR_FAULT, "watch_results: NULL argument");
-    if (!b->watch_on)
-        return fail(COOLMIC_ERROR_INVAL, "watch_results: batch without the watch");
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    // one round trip for all streams: behind what the stream has queued, read windows and state, clear the windows
-    // on the stream (the state behind them stays)
-    const size_t S = b->d.streams;
-    HIP_TRY(hipMemcpyAsync(b->watch_host.data(), b->d_watch, S * WATCH_WORDS * WORD, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemsetAsync(b->d_watch, 0, S * WATCH_WINDOW_WORDS * WORD, b->stream));
-    const unsigned long long *const host_state = b->watch_host.data() + S * WATCH_WINDOW_WORDS;
-    for (size_t s = 0; s < S; s++) {
-        const int r = watch_finish(b, b->watch_frames[s], &b->watch_host[s * WATCH_WINDOW_WORDS], host_state + s * WATCH_SLOTS, &out[s]);
-        if (rc)
-            rc[s] = r;
-        b->watch_frames[s] = 0;
-    }
-    return COOLMIC_ERROR_NONE;
+    return cmhip_meter_fetch_all(b, WATCH, out, rc);
 }
 
-extern "C" int cmhip_batch_watch_reset(cmhip_batch_t *b, long stream)
-{
-    if (!b)
-        return fail(COOLMIC_ERROR_FAULT, "watch_reset: batch is NULL");
-    const StreamRange sr = stream_range(stream, b->d.streams);
-    if (!b->watch_on || !sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "watch_reset: stream %ld out of range or batch without the watch", stream);
-    if (use(b))
-        return COOLMIC_ERROR_GENERIC;
-    const size_t lo = sr.lo, n = sr.n;
-    HIP_TRY(hipMemsetAsync(b->d_watch + lo * WATCH_WINDOW_WORDS, 0, n * WATCH_WINDOW_WORDS * WORD, b->stream));
-    HIP_TRY(hipMemsetAsync(watch_state(b) + lo * WATCH_SLOTS, 0, n * WATCH_SLOTS * WORD, b->stream));
-    for (size_t s = lo; s < lo + n; s++)
-        b->watch_frames[s] = 0;
-    return COOLMIC_ERROR_NONE;
-}
+extern "C" int cmhip_batch_watch_reset(cmhip_batch_t *b, long stream) { return cmhip_meter_clear_range(b, WATCH, stream); }
+

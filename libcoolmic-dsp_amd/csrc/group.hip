@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <deque>
+#include <memory>
 #include <vector>
 
 #define COOLMIC_COMPONENT "libcoolmic-dsp/group"
@@ -61,17 +62,23 @@ struct coolmic_group {
     std::vector<uint32_t> *flight;           // ... of the block on the GPU
     bool in_flight;                          // a block's launch is queued
     WorkPool *pullers;                       // helpers for the pull of a pump (coolmic_group_set_pull_threads)
-    std::vector<coolmic_vumeter_result_t> *vu_out;   // coolmic_group_vumeter_results of a group that is not full:
-    std::vector<int> *vu_rc;                 // the engine's max_streams results and codes (made on first use)
-    std::vector<coolmic_truepeak_result_t> *tp_out;  // the same for coolmic_group_true_peaks
-    std::vector<int> *tp_rc;
-    std::vector<coolmic_loudness_result_t> *loud_out;    // and for coolmic_group_loudnesses
-    std::vector<coolmic_correlation_result_t> *corr_out; // and for coolmic_group_correlations
-    std::vector<int> *corr_rc;
-    std::vector<coolmic_spectrum_result_t> *spec_out;    // and for coolmic_group_spectra
-    std::vector<int> *spec_rc;
-    std::vector<coolmic_watch_result_t> *watch_out;      // and for coolmic_group_watches
-    std::vector<int> *watch_rc;
+    struct GroupStaging *staging;            // the results calls of a group that is not full (made on first use)
+};
+
+// A results call of a group that is not full: the engine's max_streams results and codes land here, and the slots'
+// go on to the caller.  Each pair of arrays is made by the first call that needs it.
+template <class R> struct Staged {
+    std::unique_ptr<R[]> out;
+    std::unique_ptr<int[]> rc;
+};
+
+struct __attribute__((visibility("hidden"))) GroupStaging {
+    Staged<coolmic_vumeter_result_t> vu;
+    Staged<coolmic_truepeak_result_t> tp;
+    Staged<coolmic_loudness_result_t> loud;
+    Staged<coolmic_correlation_result_t> corr;
+    Staged<coolmic_spectrum_result_t> spec;
+    Staged<coolmic_watch_result_t> watch;
 };
 
 struct GroupHandle {
@@ -83,17 +90,7 @@ static void group_destroy(void *self)
 {
     coolmic_group_t *g = (coolmic_group_t *)self;
     delete g->pullers;
-    delete g->vu_out;
-    delete g->vu_rc;
-    delete g->tp_out;
-    delete g->tp_rc;
-    delete g->loud_out;
-    delete g->corr_out;
-    delete g->corr_rc;
-    delete g->spec_out;
-    delete g->spec_rc;
-    delete g->watch_out;
-    delete g->watch_rc;
+    delete g->staging;
     if (g->streams) {
         for (auto &s : *g->streams)
             coolmic_ro_unref(s.source);
@@ -529,322 +526,119 @@ extern "C" coolmic_iohandle_t *coolmic_group_get_iohandle(coolmic_group_t *self,
     return io;
 }
 
-extern "C" int coolmic_group_vumeter_result(coolmic_group_t *self, unsigned int slot,
-                                            coolmic_vumeter_result_t *result)
+// ---------------------------------------------------------------------------
+// The meters: thin wrappers over the engine (cmhip_vu.hip, cmhip_tp.hip, cmhip_loud.hip, cmhip_corr.hip,
+// cmhip_spec.hip, cmhip_watch.hip), which check the group and the slot and pass the engine's word through.  The
+// group's blocks lie in host memory, so a meter's pass reads the input set once more over PCIe.
+
+// a setting of the whole group
+template <class F, class... A> static int group_forward(coolmic_group_t *self, F engine, A... args)
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    return engine(self->batch, args...);
+}
+
+// one slot's result
+template <class R>
+static int group_result(coolmic_group_t *self, unsigned int slot, R *result, int (*engine)(cmhip_batch_t *, unsigned int, R *))
 {
     if (!self || !result)
         return COOLMIC_ERROR_FAULT;
     if (slot >= self->streams->size())
         return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_vu_result(self->batch, slot, result);
+    return engine(self->batch, slot, result);
+}
+
+// one slot's reset, or with -1 every slot's
+static int group_reset(coolmic_group_t *self, long slot, int (*engine)(cmhip_batch_t *, long))
+{
+    if (!self)
+        return COOLMIC_ERROR_FAULT;
+    if (slot >= (long)self->streams->size() || slot < -1)
+        return COOLMIC_ERROR_INVAL;
+    return engine(self->batch, slot);
+}
+
+// every slot's result at once
+template <class R>
+static int group_results(coolmic_group_t *self, Staged<R> GroupStaging::*which, R *results, int *rc,
+                         int (*engine)(cmhip_batch_t *, R *, int *))
+{
+    if (!self || !results)
+        return COOLMIC_ERROR_FAULT;
+    const size_t n = self->streams->size();
+    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
+        return engine(self->batch, results, rc);
+    try {
+        if (!self->staging)
+            self->staging = new GroupStaging();
+        Staged<R> &made = self->staging->*which;
+        if (!made.out)
+            made.out.reset(new R[self->max_streams]());
+        if (!made.rc)
+            made.rc.reset(new int[self->max_streams]());
+    } catch (const std::bad_alloc &) {       // (nothing C++ leaves through the C interface)
+        return COOLMIC_ERROR_NOMEM;
+    }
+    const Staged<R> &st = self->staging->*which;
+    const int r = engine(self->batch, st.out.get(), st.rc.get());
+    if (r != COOLMIC_ERROR_NONE)
+        return r;
+    for (size_t i = 0; i < n; i++) {
+        if (st.rc[i] == COOLMIC_ERROR_NONE)
+            results[i] = st.out[i];
+        if (rc)
+            rc[i] = st.rc[i];
+    }
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int coolmic_group_vumeter_result(coolmic_group_t *self, unsigned int slot,
+                                            coolmic_vumeter_result_t *result)
+{
+    return group_result(self, slot, result, cmhip_batch_vu_result);
 }
 
 extern "C" int coolmic_group_vumeter_results(coolmic_group_t *self, coolmic_vumeter_result_t *results, int *rc)
 {
-    if (!self || !results)
-        return COOLMIC_ERROR_FAULT;
-    const size_t n = self->streams->size();
-    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
-        return cmhip_batch_vu_results(self->batch, results, rc);
-    if (!self->vu_rc) {
-        try {
-            if (!self->vu_out)
-                self->vu_out = new std::vector<coolmic_vumeter_result_t>(self->max_streams);
-            self->vu_rc = new std::vector<int>(self->max_streams);
-        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
-            return COOLMIC_ERROR_NOMEM;
-        }
-    }
-    const int r = cmhip_batch_vu_results(self->batch, self->vu_out->data(), self->vu_rc->data());
-    if (r != COOLMIC_ERROR_NONE)
-        return r;
-    for (size_t i = 0; i < n; i++) {
-        if ((*self->vu_rc)[i] == COOLMIC_ERROR_NONE)
-            results[i] = (*self->vu_out)[i];
-        if (rc)
-            rc[i] = (*self->vu_rc)[i];
-    }
-    return COOLMIC_ERROR_NONE;
+    return group_results(self, &GroupStaging::vu, results, rc, cmhip_batch_vu_results);
 }
 
 extern "C" int coolmic_group_set_vu_finish(coolmic_group_t *self, int where)
 {
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_vu_set_finish(self->batch, where);
+    return group_forward(self, cmhip_batch_vu_set_finish, where);
 }
 
-// True peak: thin wrappers over the engine (cmhip_tp.hip).  The group's blocks lie in host memory, so the true-peak
-// kernel's pass reads the input set a second time over PCIe.
 extern "C" int coolmic_group_set_true_peak(coolmic_group_t *self, int on)
 {
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_set_true_peak(self->batch, on);
+    return group_forward(self, cmhip_batch_set_true_peak, on);
 }
 
 extern "C" int coolmic_group_true_peak(coolmic_group_t *self, unsigned int slot, coolmic_truepeak_result_t *result)
 {
-    if (!self || !result)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= self->streams->size())
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_tp_result(self->batch, slot, result);
+    return group_result(self, slot, result, cmhip_batch_tp_result);
 }
 
 extern "C" int coolmic_group_true_peaks(coolmic_group_t *self, coolmic_truepeak_result_t *results, int *rc)
 {
-    if (!self || !results)
-        return COOLMIC_ERROR_FAULT;
-    const size_t n = self->streams->size();
-    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
-        return cmhip_batch_tp_results(self->batch, results, rc);
-    if (!self->tp_rc) {
-        try {
-            if (!self->tp_out)
-                self->tp_out = new std::vector<coolmic_truepeak_result_t>(self->max_streams);
-            self->tp_rc = new std::vector<int>(self->max_streams);
-        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
-            return COOLMIC_ERROR_NOMEM;
-        }
-    }
-    const int r = cmhip_batch_tp_results(self->batch, self->tp_out->data(), self->tp_rc->data());
-    if (r != COOLMIC_ERROR_NONE)
-        return r;
-    for (size_t i = 0; i < n; i++) {
-        if ((*self->tp_rc)[i] == COOLMIC_ERROR_NONE)
-            results[i] = (*self->tp_out)[i];
-        if (rc)
-            rc[i] = (*self->tp_rc)[i];
-    }
-    return COOLMIC_ERROR_NONE;
+    return group_results(self, &GroupStaging::tp, results, rc, cmhip_batch_tp_results);
 }
 
-// Loudness: thin wrappers over the engine (cmhip_loud.hip), with the slot handling of the true-peak calls.
 extern "C" int coolmic_group_set_loudness(coolmic_group_t *self, int on)
 {
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_set_loudness(self->batch, on);
+    return group_forward(self, cmhip_batch_set_loudness, on);
 }
 
 extern "C" int coolmic_group_loudness(coolmic_group_t *self, unsigned int slot, coolmic_loudness_result_t *result)
 {
-    if (!self || !result)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= self->streams->size())
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_loud_result(self->batch, slot, result);
+    return group_result(self, slot, result, cmhip_batch_loud_result);
 }
 
+// (the engine reports every stream's loudness, so every code is COOLMIC_ERROR_NONE and every slot is copied)
 extern "C" int coolmic_group_loudnesses(coolmic_group_t *self, coolmic_loudness_result_t *results, int *rc)
 {
-    if (!self || !results)
-        return COOLMIC_ERROR_FAULT;
-    const size_t n = self->streams->size();
-    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
-        return cmhip_batch_loud_results(self->batch, results, rc);
-    if (!self->loud_out) {
-        try {
-            self->loud_out = new std::vector<coolmic_loudness_result_t>(self->max_streams);
-        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
-            return COOLMIC_ERROR_NOMEM;
-        }
-    }
-    const int r = cmhip_batch_loud_results(self->batch, self->loud_out->data(), nullptr);
-    if (r != COOLMIC_ERROR_NONE)
-        return r;
-    for (size_t i = 0; i < n; i++) {
-        results[i] = (*self->loud_out)[i];
-        if (rc)
-            rc[i] = COOLMIC_ERROR_NONE;
-    }
-    return COOLMIC_ERROR_NONE;
-}
-
-// Phase correlation: thin wrappers over the engine (cmhip_corr.hip), with the slot handling of the true-peak calls.
-extern "C" int coolmic_group_set_correlation(coolmic_group_t *self, int on)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_set_correlation(self->batch, on);
-}
-
-extern "C" int coolmic_group_correlation_set_pairs(coolmic_group_t *self, unsigned int n, const unsigned char pairs[][2])
-{
-    if (!self || !pairs)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_corr_set_pairs(self->batch, n, pairs);
-}
-
-extern "C" int coolmic_group_correlation(coolmic_group_t *self, unsigned int slot, coolmic_correlation_result_t *result)
-{
-    if (!self || !result)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= self->streams->size())
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_corr_result(self->batch, slot, result);
-}
-
-extern "C" int coolmic_group_correlations(coolmic_group_t *self, coolmic_correlation_result_t *results, int *rc)
-{
-    if (!self || !results)
-        return COOLMIC_ERROR_FAULT;
-    const size_t n = self->streams->size();
-    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
-        return cmhip_batch_corr_results(self->batch, results, rc);
-    if (!self->corr_rc) {
-        try {
-            if (!self->corr_out)
-                self->corr_out = new std::vector<coolmic_correlation_result_t>(self->max_streams);
-            self->corr_rc = new std::vector<int>(self->max_streams);
-        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
-            return COOLMIC_ERROR_NOMEM;
-        }
-    }
-    const int r = cmhip_batch_corr_results(self->batch, self->corr_out->data(), self->corr_rc->data());
-    if (r != COOLMIC_ERROR_NONE)
-        return r;
-    for (size_t i = 0; i < n; i++) {
-        if ((*self->corr_rc)[i] == COOLMIC_ERROR_NONE)
-            results[i] = (*self->corr_out)[i];
-        if (rc)
-            rc[i] = (*self->corr_rc)[i];
-    }
-    return COOLMIC_ERROR_NONE;
-}
-
-extern "C" int coolmic_group_correlation_reset(coolmic_group_t *self, long slot)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= (long)self->streams->size() || slot < -1)
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_corr_reset(self->batch, slot);
-}
-
-// Spectrum: thin wrappers over the engine (cmhip_spec.hip), with the slot handling of the correlation calls.
-extern "C" int coolmic_group_set_spectrum(coolmic_group_t *self, int on)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_set_spectrum(self->batch, on);
-}
-
-extern "C" int coolmic_group_spectrum_configure(coolmic_group_t *self, unsigned int fft_log2, unsigned int nb,
-                                                const uint16_t *edges, unsigned int nch, const unsigned char *channels)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_spec_configure(self->batch, fft_log2, nb, edges, nch, channels);
-}
-
-extern "C" int coolmic_group_spectrum(coolmic_group_t *self, unsigned int slot, coolmic_spectrum_result_t *result)
-{
-    if (!self || !result)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= self->streams->size())
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_spec_result(self->batch, slot, result);
-}
-
-extern "C" int coolmic_group_spectra(coolmic_group_t *self, coolmic_spectrum_result_t *results, int *rc)
-{
-    if (!self || !results)
-        return COOLMIC_ERROR_FAULT;
-    const size_t n = self->streams->size();
-    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
-        return cmhip_batch_spec_results(self->batch, results, rc);
-    if (!self->spec_rc) {
-        try {
-            if (!self->spec_out)
-                self->spec_out = new std::vector<coolmic_spectrum_result_t>(self->max_streams);
-            self->spec_rc = new std::vector<int>(self->max_streams);
-        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
-            return COOLMIC_ERROR_NOMEM;
-        }
-    }
-    const int r = cmhip_batch_spec_results(self->batch, self->spec_out->data(), self->spec_rc->data());
-    if (r != COOLMIC_ERROR_NONE)
-        return r;
-    for (size_t i = 0; i < n; i++) {
-        if ((*self->spec_rc)[i] == COOLMIC_ERROR_NONE)
-            results[i] = (*self->spec_out)[i];
-        if (rc)
-            rc[i] = (*self->spec_rc)[i];
-    }
-    return COOLMIC_ERROR_NONE;
-}
-
-extern "C" int coolmic_group_spectrum_reset(coolmic_group_t *self, long slot)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= (long)self->streams->size() || slot < -1)
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_spec_reset(self->batch, slot);
-}
-
-// Signal watch: thin wrappers over the engine (cmhip_watch.hip), with the slot handling of the correlation calls.
-extern "C" int coolmic_group_set_watch(coolmic_group_t *self, int on)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_set_watch(self->batch, on);
-}
-
-extern "C" int coolmic_group_watch_configure(coolmic_group_t *self, unsigned int quiet, unsigned int rail,
-                                             unsigned int clip_run)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    return cmhip_batch_watch_configure(self->batch, quiet, rail, clip_run);
-}
-
-extern "C" int coolmic_group_watch(coolmic_group_t *self, unsigned int slot, coolmic_watch_result_t *result)
-{
-    if (!self || !result)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= self->streams->size())
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_watch_result(self->batch, slot, result);
-}
-
-extern "C" int coolmic_group_watches(coolmic_group_t *self, coolmic_watch_result_t *results, int *rc)
-{
-    if (!self || !results)
-        return COOLMIC_ERROR_FAULT;
-    const size_t n = self->streams->size();
-    if (n == self->max_streams)              // the engine's streams are the group's slots: straight into the caller's
-        return cmhip_batch_watch_results(self->batch, results, rc);
-    if (!self->watch_rc) {
-        try {
-            if (!self->watch_out)
-                self->watch_out = new std::vector<coolmic_watch_result_t>(self->max_streams);
-            self->watch_rc = new std::vector<int>(self->max_streams);
-        } catch (const std::bad_alloc &) {   // (nothing C++ leaves through the C interface)
-            return COOLMIC_ERROR_NOMEM;
-        }
-    }
-    const int r = cmhip_batch_watch_results(self->batch, self->watch_out->data(), self->watch_rc->data());
-    if (r != COOLMIC_ERROR_NONE)
-        return r;
-    for (size_t i = 0; i < n; i++) {
-        if ((*self->watch_rc)[i] == COOLMIC_ERROR_NONE)
-            results[i] = (*self->watch_out)[i];
-        if (rc)
-            rc[i] = (*self->watch_rc)[i];
-    }
-    return COOLMIC_ERROR_NONE;
-}
-
-extern "C" int coolmic_group_watch_reset(coolmic_group_t *self, long slot)
-{
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= (long)self->streams->size() || slot < -1)
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_watch_reset(self->batch, slot);
+    return group_results(self, &GroupStaging::loud, results, rc, cmhip_batch_loud_results);
 }
 
 extern "C" int coolmic_group_loudness_set_weights(coolmic_group_t *self, long slot, const double *weights)
@@ -858,9 +652,85 @@ extern "C" int coolmic_group_loudness_set_weights(coolmic_group_t *self, long sl
 
 extern "C" int coolmic_group_loudness_reset(coolmic_group_t *self, long slot)
 {
-    if (!self)
-        return COOLMIC_ERROR_FAULT;
-    if (slot >= (long)self->streams->size() || slot < -1)
-        return COOLMIC_ERROR_INVAL;
-    return cmhip_batch_loud_reset(self->batch, slot);
+    return group_reset(self, slot, cmhip_batch_loud_reset);
 }
+
+extern "C" int coolmic_group_set_correlation(coolmic_group_t *self, int on)
+{
+    return group_forward(self, cmhip_batch_set_correlation, on);
+}
+
+extern "C" int coolmic_group_correlation_set_pairs(coolmic_group_t *self, unsigned int n, const unsigned char pairs[][2])
+{
+    if (!self || !pairs)
+        return COOLMIC_ERROR_FAULT;
+    return cmhip_batch_corr_set_pairs(self->batch, n, pairs);
+}
+
+extern "C" int coolmic_group_correlation(coolmic_group_t *self, unsigned int slot, coolmic_correlation_result_t *result)
+{
+    return group_result(self, slot, result, cmhip_batch_corr_result);
+}
+
+extern "C" int coolmic_group_correlations(coolmic_group_t *self, coolmic_correlation_result_t *results, int *rc)
+{
+    return group_results(self, &GroupStaging::corr, results, rc, cmhip_batch_corr_results);
+}
+
+extern "C" int coolmic_group_correlation_reset(coolmic_group_t *self, long slot)
+{
+    return group_reset(self, slot, cmhip_batch_corr_reset);
+}
+
+extern "C" int coolmic_group_set_spectrum(coolmic_group_t *self, int on)
+{
+    return group_forward(self, cmhip_batch_set_spectrum, on);
+}
+
+extern "C" int coolmic_group_spectrum_configure(coolmic_group_t *self, unsigned int fft_log2, unsigned int nb,
+                                                const uint16_t *edges, unsigned int nch, const unsigned char *channels)
+{
+    return group_forward(self, cmhip_batch_spec_configure, fft_log2, nb, edges, nch, channels);
+}
+
+extern "C" int coolmic_group_spectrum(coolmic_group_t *self, unsigned int slot, coolmic_spectrum_result_t *result)
+{
+    return group_result(self, slot, result, cmhip_batch_spec_result);
+}
+
+extern "C" int coolmic_group_spectra(coolmic_group_t *self, coolmic_spectrum_result_t *results, int *rc)
+{
+    return group_results(self, &GroupStaging::spec, results, rc, cmhip_batch_spec_results);
+}
+
+extern "C" int coolmic_group_spectrum_reset(coolmic_group_t *self, long slot)
+{
+    return group_reset(self, slot, cmhip_batch_spec_reset);
+}
+
+extern "C" int coolmic_group_set_watch(coolmic_group_t *self, int on)
+{
+    return group_forward(self, cmhip_batch_set_watch, on);
+}
+
+extern "C" int coolmic_group_watch_configure(coolmic_group_t *self, unsigned int quiet, unsigned int rail,
+                                             unsigned int clip_run)
+{
+    return group_forward(self, cmhip_batch_watch_configure, quiet, rail, clip_run);
+}
+
+extern "C" int coolmic_group_watch(coolmic_group_t *self, unsigned int slot, coolmic_watch_result_t *result)
+{
+    return group_result(self, slot, result, cmhip_batch_watch_result);
+}
+
+extern "C" int coolmic_group_watches(coolmic_group_t *self, coolmic_watch_result_t *results, int *rc)
+{
+    return group_results(self, &GroupStaging::watch, results, rc, cmhip_batch_watch_results);
+}
+
+extern "C" int coolmic_group_watch_reset(coolmic_group_t *self, long slot)
+{
+    return group_reset(self, slot, cmhip_batch_watch_reset);
+}
+
