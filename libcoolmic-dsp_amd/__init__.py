@@ -1835,8 +1835,11 @@ class Batch:
 
 
 class _Stage:
-    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay, Leveller, Filter): the end of the handle `h`, its
-    stream, and a run's counts.  `_stem` names the object's C functions: cmhip_<stem>_free, _sync, _hip_stream."""
+    """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay,
+    Leveller, Filter): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
+    object's C functions: cmhip_<stem>_free, _sync, _hip_stream, _run, _reset.  The Mixer and the Bus have no state to
+    reset and the library no cmhip_mix_reset or cmhip_bus_reset: their reset() raises AttributeError, as the lookup of
+    any symbol the library lacks does."""
 
     _stem = None
 
@@ -1856,6 +1859,19 @@ class _Stage:
 
     def hip_stream(self):
         return getattr(lib, "cmhip_%s_hip_stream" % self._stem)(self.h) or 0
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_<stem>_run as it is -> error number"""
+        return getattr(lib, "cmhip_%s_run" % self._stem)(self.h, src, in_stride, frames, self._counts(frames_per_stream),
+                                                         dst, out_stride)
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers; the band split's dst: B * S slots, band-major)"""
+        _check(self._stem + "_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
+
+    def reset(self, stream=-1):
+        """the stream's state as at creation (stream -1: every stream); ordered with the runs"""
+        _check(self._stem + "_reset", getattr(lib, "cmhip_%s_reset" % self._stem)(self.h, stream))
 
     def _counts(self, frames_per_stream):
         """-> the run's frames_per_stream argument: None, or the uint32 array as ctypes passes it (it holds the array)"""
@@ -1906,9 +1922,6 @@ class Resampler(_Stage):
         _check("src_run", rc)
         return got
 
-    def reset(self, stream=-1):
-        _check("src_reset", lib.cmhip_src_reset(self.h, stream))
-
 
 class BandSplit(_Stage):
     """cmhip_split_t: a linear-phase FIR crossover of S streams beside a batch: B bands that add up to the input delayed
@@ -1939,17 +1952,6 @@ class BandSplit(_Stage):
         q = np.zeros(self.bands - 1, dtype=np.uint8)
         _check("split_get_table", lib.cmhip_split_get_table(self.h, g.ctypes.data, q.ctypes.data))
         return g, q
-
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_split_run as it is -> error number"""
-        return lib.cmhip_split_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src: S slots, dst: B * S slots, band-major)"""
-        _check("split_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
-
-    def reset(self, stream=-1):
-        _check("split_reset", lib.cmhip_split_reset(self.h, stream))
 
     def clips(self, clear=False):
         """-> uint32 [S][B]: the saturated samples per stream and band (a synchronous round trip)"""
@@ -1998,17 +2000,6 @@ class Delay(_Stage):
         _check("delay_get", lib.cmhip_delay_get(self.h, stream, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_delay_run as it is -> error number"""
-        return lib.cmhip_delay_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src, dst: device pointers)"""
-        _check("delay_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
-
-    def reset(self, stream=-1):
-        _check("delay_reset", lib.cmhip_delay_reset(self.h, stream))
-
 
 class Leveller(_Stage):
     """cmhip_agc_t: slow automatic gain control of S streams beside a batch: the gain moves once per window of
@@ -2038,17 +2029,6 @@ class Leveller(_Stage):
         p = AgcParams()
         _check("agc_get", lib.cmhip_agc_get(self.h, stream, C.byref(p)))
         return p
-
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_agc_run as it is -> error number"""
-        return lib.cmhip_agc_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src, dst: device pointers)"""
-        _check("agc_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
-
-    def reset(self, stream=-1):
-        _check("agc_reset", lib.cmhip_agc_reset(self.h, stream))
 
     def state(self, clear_clips=False):
         """-> (gain uint32 [S], level uint32 [S], clips uint64 [S]); a synchronous round trip"""
@@ -2085,17 +2065,6 @@ class Filter(_Stage):
         s = IirSection()
         _check("iir_get", lib.cmhip_iir_get(self.h, stream, section, C.byref(s)))
         return s
-
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_iir_run as it is -> error number"""
-        return lib.cmhip_iir_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src, dst: device pointers)"""
-        _check("iir_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
-
-    def reset(self, stream=-1):
-        _check("iir_reset", lib.cmhip_iir_reset(self.h, stream))
 
     def state(self, clear=False):
         """-> (clips uint64 [S], overs uint64 [S]); a synchronous round trip"""
@@ -2158,14 +2127,6 @@ class Mixer(_Stage):
         w = np.zeros((self.channels_out, self.channels_in), dtype=np.int16)
         _check("mix_ramp_state", lib.cmhip_mix_ramp_state(self.h, stream, C.byref(done), C.byref(total), w.ctypes.data))
         return done.value, total.value, w
-
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_mix_run as it is -> error number"""
-        return lib.cmhip_mix_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src, dst: device pointers)"""
-        _check("mix_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
 
 
 class Bus(_Stage):
@@ -2279,17 +2240,6 @@ class Limiter(_Stage):
         _check("lim_get", lib.cmhip_lim_get(self.h, stream, C.byref(t), C.byref(d)))
         return t.value, d.value
 
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_lim_run as it is -> error number"""
-        return lib.cmhip_lim_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src, dst: device pointers)"""
-        _check("lim_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
-
-    def reset(self, stream=-1):
-        _check("lim_reset", lib.cmhip_lim_reset(self.h, stream))
-
     def min_gain(self, reset=False):
         """waits for the stream -> the streams' gain-reduction meters, uint32 [S] in Q15"""
         out = np.zeros(self.streams, dtype=np.uint32)
@@ -2353,17 +2303,6 @@ class Dynamics(_Stage):
         k = C.c_long()
         _check("dyn_get_key", lib.cmhip_dyn_get_key(self.h, stream, C.byref(k)))
         return k.value
-
-    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """cmhip_dyn_run as it is -> error number"""
-        return lib.cmhip_dyn_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride)
-
-    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
-        """one run over device arrays (src, dst: device pointers)"""
-        _check("dyn_run", self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream))
-
-    def reset(self, stream=-1):
-        _check("dyn_reset", lib.cmhip_dyn_reset(self.h, stream))
 
     def min_gain(self, reset=False):
         """waits for the stream -> the streams' gain meters, uint32 [S] in Q15"""

@@ -13,8 +13,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <new>
-
 static_assert(sizeof(cmhip_agc_params_t) == sizeof(AgcParams) && sizeof(AgcParams) == 14, "cmhip_agc_params_t is AgcParams");
 static_assert(offsetof(cmhip_agc_params_t, initial) == offsetof(AgcParams, initial), "cmhip_agc_params_t is AgcParams");
 
@@ -26,7 +24,6 @@ struct cmhip_agc : StageBase {
     AgcState *d_state;                 // [S]
     unsigned long long *d_clips;       // [S]
     AgcMirror mirror;
-    bool dry;                          // cmhip_test_agc_new_dry: the mirror and the checks, no device behind them
 };
 
 static const AgcParams AGC_DEFAULT = {3277, 33, AGC_UNITY, AGC_UNITY, 0, 0, AGC_UNITY};
@@ -91,49 +88,25 @@ extern "C" uint32_t cmhip_test_agc_step(uint32_t A, uint32_t L, const cmhip_agc_
     return p ? agc_step(A, L, agc_from(p)) : 0u;
 }
 
-extern "C" void cmhip_agc_free(cmhip_agc_t *m)
-{
-    if (!m)
-        return;
-    if (!m->dry) {
-        m->close();
-        (void)hipFree(m->d_table);
-        (void)hipFree(m->d_nodes);
-        (void)hipFree(m->d_state);
-        (void)hipFree(m->d_clips);
-    }
-    delete m;
-}
+extern "C" void cmhip_agc_free(cmhip_agc_t *m) { stage_free(m); }
 
-static int agc_init(cmhip_agc_t *m)
+// device false (cmhip_test_agc_new_dry): the mirror and the checks, no device behind them
+static int agc_init(cmhip_agc_t *m, bool device)
 {
     const cmhip_agc_desc_t &d = m->d;
     const size_t S = d.streams;
-    try {
-        m->mirror.init(S, AGC_DEFAULT);
-    } catch (const std::bad_alloc &) {
-        return fail(COOLMIC_ERROR_NOMEM, "agc_new: out of memory");
-    }
-    if (m->dry)
+    m->mirror.init(S, AGC_DEFAULT);
+    if (!device)
         return COOLMIC_ERROR_NONE;
-    if (m->open(d.device, d.hip_stream, S * AGC_REC))
+    if (m->open("agc_new", d.device, d.hip_stream, S * AGC_REC) ||
+        m->array("agc_new", &m->d_table, S * m->nw * d.channels) ||
+        m->array("agc_new", &m->d_nodes, S * ((size_t)m->nw + 1u)) || m->array("agc_new", &m->d_state, S) ||
+        m->array("agc_new", &m->d_clips, S))
         return COOLMIC_ERROR_GENERIC;
-    const size_t table = S * m->nw * d.channels * sizeof(unsigned long long);
-    const size_t nodes = S * ((size_t)m->nw + 1u) * sizeof(uint32_t);
-    if (hipMalloc((void **)&m->d_table, table) != hipSuccess || hipMalloc((void **)&m->d_nodes, nodes) != hipSuccess ||
-        hipMalloc((void **)&m->d_state, S * sizeof(AgcState)) != hipSuccess ||
-        hipMalloc((void **)&m->d_clips, S * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(COOLMIC_ERROR_NOMEM, "agc_new: no device memory for %zu bytes of tables", table + nodes);
-    }
-    HIP_TRY(hipMemsetAsync(m->d_table, 0, table, m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_nodes, 0, nodes, m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_state, 0, S * sizeof(AgcState), m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_clips, 0, S * sizeof(unsigned long long), m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
-static cmhip_agc_t *agc_new(const cmhip_agc_desc_t *d, bool dry)
+static cmhip_agc_t *agc_new(const cmhip_agc_desc_t *d, bool device)
 {
     if (!d) {
         fail(COOLMIC_ERROR_FAULT, "agc_new: NULL argument");
@@ -144,38 +117,31 @@ static cmhip_agc_t *agc_new(const cmhip_agc_desc_t *d, bool dry)
              "below 2^31) out of range", AGC_W_MIN, AGC_W_MAX);
         return nullptr;
     }
-    cmhip_agc_t *m = new (std::nothrow) cmhip_agc();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "agc_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    m->dry = dry;
-    m->nw = agc_table_windows(d->max_frames, d->window_log2);
-    if (agc_init(m)) {
-        cmhip_agc_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_agc>("agc_new", [&](cmhip_agc_t *m) {
+        m->d = *d;
+        m->nw = agc_table_windows(d->max_frames, d->window_log2);
+        return agc_init(m, device);
+    });
 }
 
-extern "C" cmhip_agc_t *cmhip_agc_new(const cmhip_agc_desc_t *d) { return agc_new(d, false); }
+extern "C" cmhip_agc_t *cmhip_agc_new(const cmhip_agc_desc_t *d) { return agc_new(d, true); }
 
 // test hook: an object with its mirror and every check but no device behind it, for the refusals and the mirror's
 // answers on a machine without a GPU; a run that would launch is refused
-extern "C" cmhip_agc_t *cmhip_test_agc_new_dry(const cmhip_agc_desc_t *d) { return agc_new(d, true); }
+extern "C" cmhip_agc_t *cmhip_test_agc_new_dry(const cmhip_agc_desc_t *d) { return agc_new(d, false); }
 
 extern "C" void *cmhip_agc_hip_stream(cmhip_agc_t *m) { return m ? (void *)m->stream : nullptr; }
 
-extern "C" int cmhip_agc_sync(cmhip_agc_t *m) { return m && m->dry ? COOLMIC_ERROR_NONE : stage_sync(m, "agc_sync"); }
+extern "C" int cmhip_agc_sync(cmhip_agc_t *m) { return stage_sync(m, "agc_sync"); }
 
 extern "C" int cmhip_agc_set(cmhip_agc_t *m, long stream, const cmhip_agc_params_t *p)
 {
-    if (!m || !p)
+    if (!p)
         return fail(COOLMIC_ERROR_FAULT, "agc_set: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "agc_set: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "agc_set", stream, &sr);
+    if (rc)
+        return rc;
     const AgcParams q = agc_from(p);
     if (!agc_params_ok(q))
         return fail(COOLMIC_ERROR_INVAL,
@@ -203,22 +169,17 @@ static int agc_run_on(cmhip_agc_t *m, const void *in, size_t in_stride, size_t f
     const unsigned S = m->d.streams, C = m->d.channels;
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
                         STAGE_APART};
-    const int refused = stage_run_refusal("agc_run", r);
-    if (refused)
-        return refused;
-    // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    if (m->dry)
-        return fail(COOLMIC_ERROR_INVAL, "agc_run: the object has no device");
-    HIP_TRY(hipSetDevice(m->d.device));
+    int rc;
+    if (!stage_run_begin(m, "agc_run", r, &rc))
+        return rc;
     if (plan_agc(S, C, m->d.window_log2, m->d.max_frames, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "agc_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S, frames);
+    // nothing was touched so far; from here on the run happens
     // the run's records: the counts, and beside each the stream's position and parameters
     uint32_t *block;
     HIP_TRY(m->counts.take(&block));
     for (unsigned s = 0; s < S; s++)
-        m->mirror.record(s, frames_per_stream ? frames_per_stream[s] : (uint32_t)frames, block + (size_t)s * AGC_REC);
+        m->mirror.record(s, stage_count(frames_per_stream, s, frames), block + (size_t)s * AGC_REC);
     HIP_TRY(m->counts.send(m->d_counts, (size_t)S * AGC_REC, m->stream));
     AgcArgs a;
     memset(&a, 0, sizeof(a));
@@ -234,12 +195,10 @@ static int agc_run_on(cmhip_agc_t *m, const void *in, size_t in_stride, size_t f
     a.streams = S;
     a.channels = C;
     a.w = m->d.window_log2;
-    const hipError_t e = launch_agc(a, m->d.max_frames, (uint32_t)frames, m->stream, ev);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "agc_run: %s", hipGetErrorString(e));
-    for (unsigned s = 0; s < S; s++)
-        m->mirror.pos[s] += frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
-    return COOLMIC_ERROR_NONE;
+    rc = stage_launched("agc_run", launch_agc(a, m->d.max_frames, (uint32_t)frames, m->stream, ev));
+    for (unsigned s = 0; s < S && !rc; s++)
+        m->mirror.pos[s] += stage_count(frames_per_stream, s, frames);
+    return rc;
 }
 
 extern "C" int cmhip_agc_run(cmhip_agc_t *m, const void *in, size_t in_stride, size_t frames,
@@ -260,11 +219,10 @@ extern "C" int cmhip_test_agc_run_events(cmhip_agc_t *m, const void *in, size_t 
 
 extern "C" int cmhip_agc_reset(cmhip_agc_t *m, long stream)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "agc_reset: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "agc_reset: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "agc_reset", stream, &sr);
+    if (rc)
+        return rc;
     for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
         m->mirror.pos[s] = 0;                        // the next record says so, and k_agc_step starts afresh
     return COOLMIC_ERROR_NONE;
@@ -274,32 +232,19 @@ extern "C" int cmhip_agc_state(cmhip_agc_t *m, uint32_t *gain, uint32_t *level, 
 {
     if (!m)
         return fail(COOLMIC_ERROR_FAULT, "agc_state: NULL argument");
-    const size_t S = m->d.streams;
-    std::vector<AgcState> st;
-    try {
-        st.resize(S);
-    } catch (const std::bad_alloc &) {
-        return fail(COOLMIC_ERROR_NOMEM, "agc_state: out of memory");
-    }
-    if (!m->dry) {
-        HIP_TRY(hipSetDevice(m->d.device));
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        HIP_TRY(hipMemcpy(st.data(), m->d_state, S * sizeof(AgcState), hipMemcpyDeviceToHost));
-        if (clips)
-            HIP_TRY(hipMemcpy(clips, m->d_clips, S * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (clear_clips) {
-            HIP_TRY(hipMemsetAsync(m->d_clips, 0, S * sizeof(uint64_t), m->stream));
-            HIP_TRY(hipStreamSynchronize(m->stream));
+    return stage_guard("agc_state", [&] {
+        const size_t S = m->d.streams;
+        std::vector<AgcState> st(S);
+        if (stage_read(m, st.data(), m->d_state, S * sizeof(AgcState), false) ||
+            stage_read(m, clips, m->d_clips, S * sizeof(uint64_t), clear_clips != 0))
+            return COOLMIC_ERROR_GENERIC;
+        for (size_t s = 0; s < S; s++) {
+            const bool fresh = !m->opened || m->mirror.pos[s] == 0;  // before frame 0: what the device holds is stale
+            if (gain)
+                gain[s] = fresh ? m->mirror.par[s].initial : st[s].a_hi;
+            if (level)
+                level[s] = fresh ? 0u : st[s].level;
         }
-    } else if (clips) {
-        memset(clips, 0, S * sizeof(uint64_t));
-    }
-    for (size_t s = 0; s < S; s++) {
-        const bool fresh = m->dry || m->mirror.pos[s] == 0;          // before frame 0: what the device holds is stale
-        if (gain)
-            gain[s] = fresh ? m->mirror.par[s].initial : st[s].a_hi;
-        if (level)
-            level[s] = fresh ? 0u : st[s].level;
-    }
-    return COOLMIC_ERROR_NONE;
+        return COOLMIC_ERROR_NONE;
+    });
 }

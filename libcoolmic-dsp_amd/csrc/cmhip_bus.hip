@@ -24,7 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
+#include <memory>
 
 #include "bus_ramp.h"
 #include "bus_route.h"
@@ -43,10 +43,19 @@ struct cmhip_bus : StageBase {         // d_counts and its ring hold [S] streams
     BusTable t;                        // ... and compiled
     uint32_t *d_ramp;                  // the sends' ramp records in compiled order, allocated by the first ramp
     uint32_t *h_ramp;                  // pinned, the same layout: staged with the table, under table_ev
-    BusRampMirror *ramp;               // ... and their mirror, in the caller's order
+    std::unique_ptr<BusRampMirror> ramp;       // ... and their mirror, in the caller's order
     std::vector<uint32_t> pos;         // compiled position of the caller's send j (while ramp != nullptr)
     std::vector<uint32_t> bound;       // the split's bounds [n][C_out] (scratch of a compile)
     std::vector<uint32_t> bus_count;   // a ramp run's count per bus (scratch of a run)
+
+    // the pinned staging blocks and their event are the bus's own (stage_free: behind close(), the device current)
+    ~cmhip_bus()
+    {
+        (void)hipHostFree(h_table);
+        (void)hipHostFree(h_ramp);
+        if (table_ev)
+            (void)hipEventDestroy(table_ev);
+    }
 };
 
 static size_t bus_nw(const cmhip_bus_t *m) { return (size_t)m->d.channels_out * ((m->d.channels_in + 1) / 2); }
@@ -124,32 +133,17 @@ static int bus_init(cmhip_bus_t *m)
 {
     const cmhip_bus_desc_t &d = m->d;
     const size_t B = d.buses, S = d.streams, words = B + 1 + d.max_sends * (1 + bus_nw(m));
-    if (m->open(d.device, d.hip_stream, S + B))
+    if (m->open("bus_new", d.device, d.hip_stream, S + B) || m->array("bus_new", &m->d_table, words))
         return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipMalloc((void **)&m->d_table, words * sizeof(uint32_t)));
     HIP_TRY(hipHostMalloc((void **)&m->h_table, words * sizeof(uint32_t), hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&m->table_ev, hipEventDisableTiming));
     m->bus_count.assign(B, 0);
     // routing at creation: empty
     bus_route_compile(d.buses, d.channels_in, d.channels_out, 0, nullptr, nullptr, nullptr, m->t);
-    HIP_TRY(hipMemsetAsync(m->d_table, 0, (B + 1) * sizeof(uint32_t), m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
-extern "C" void cmhip_bus_free(cmhip_bus_t *m)
-{
-    if (!m)
-        return;
-    m->close();
-    (void)hipFree(m->d_table);
-    (void)hipHostFree(m->h_table);
-    (void)hipFree(m->d_ramp);
-    (void)hipHostFree(m->h_ramp);
-    delete m->ramp;
-    if (m->table_ev)
-        (void)hipEventDestroy(m->table_ev);
-    delete m;
-}
+extern "C" void cmhip_bus_free(cmhip_bus_t *m) { stage_free(m); }
 
 extern "C" cmhip_bus_t *cmhip_bus_new(const cmhip_bus_desc_t *d)
 {
@@ -174,17 +168,10 @@ extern "C" cmhip_bus_t *cmhip_bus_new(const cmhip_bus_desc_t *d)
              d->streams, d->buses, d->max_sends);
         return nullptr;
     }
-    cmhip_bus_t *m = new (std::nothrow) cmhip_bus();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "bus_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    if (bus_init(m)) {
-        cmhip_bus_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_bus>("bus_new", [&](cmhip_bus_t *m) {
+        m->d = *d;
+        return bus_init(m);
+    });
 }
 
 // The table in force (m->bus, m->strm, m->w) compiled and on its way to the device; the caller has waited for the
@@ -226,7 +213,7 @@ extern "C" int cmhip_bus_set_routing(cmhip_bus_t *m, size_t n, const uint32_t *b
                                      const int16_t *W)
 {
     if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "bus_set_routing: bus is NULL");
+        return fail(COOLMIC_ERROR_FAULT, "bus_set_routing: NULL argument");
     if (n > m->d.max_sends)
         return fail(COOLMIC_ERROR_INVAL, "bus_set_routing: %zu sends above max_sends %zu", n, m->d.max_sends);
     const unsigned B = m->d.buses, CI = m->d.channels_in, CO = m->d.channels_out;
@@ -239,18 +226,15 @@ extern "C" int cmhip_bus_set_routing(cmhip_bus_t *m, size_t n, const uint32_t *b
         HIP_TRY(hipEventSynchronize(m->table_ev));
         m->table_busy = false;
     }
-    if (m->ramp) {                                   // every ramp ends: all sends at rest on the new table
-        try {
+    return stage_guard("bus_set_routing", [&] {
+        if (m->ramp)                                 // every ramp ends: all sends at rest on the new table
             m->ramp->init(n, (size_t)CO * CI, bus, W);
-        } catch (const std::bad_alloc &) {
-            return fail(COOLMIC_ERROR_NOMEM, "bus_set_routing: out of memory");
-        }
-    }
-    // nothing of the table was touched so far; from here on it changes
-    m->bus.assign(bus, bus + n);
-    m->strm.assign(stream, stream + n);
-    m->w.assign(W, W + n * CO * CI);
-    return bus_upload(m, false);
+        // nothing of the table was touched so far; from here on it changes
+        m->bus.assign(bus, bus + n);
+        m->strm.assign(stream, stream + n);
+        m->w.assign(W, W + n * CO * CI);
+        return bus_upload(m, false);
+    });
 }
 
 extern "C" size_t cmhip_bus_sends(const cmhip_bus_t *m) { return m ? m->bus.size() : 0; }
@@ -258,7 +242,7 @@ extern "C" size_t cmhip_bus_sends(const cmhip_bus_t *m) { return m ? m->bus.size
 extern "C" int cmhip_bus_get_routing(const cmhip_bus_t *m, size_t cap, uint32_t *bus, uint32_t *stream, int16_t *W)
 {
     if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "bus_get_routing: bus is NULL");
+        return fail(COOLMIC_ERROR_FAULT, "bus_get_routing: NULL argument");
     const size_t n = m->bus.size();
     if (cap < n)
         return fail(COOLMIC_ERROR_INVAL, "bus_get_routing: room for %zu sends, the table has %zu", cap, n);
@@ -275,42 +259,26 @@ extern "C" int cmhip_bus_get_routing(const cmhip_bus_t *m, size_t cap, uint32_t 
 // the ramp records, their staging copy and the mirror, on first use: every send at rest on its matrix
 static int bus_ramp_alloc(cmhip_bus_t *m)
 {
-    const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
-    const size_t bytes = m->d.max_sends * bus_ramp_record_dwords(CI, CO) * sizeof(uint32_t);
-    BusRampMirror *mirror = new (std::nothrow) BusRampMirror();
-    if (!mirror)
-        return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: out of memory");
-    try {
+    return stage_guard("bus_ramp_sends", [&] {
+        const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
+        const size_t words = m->d.max_sends * bus_ramp_record_dwords(CI, CO);
+        auto mirror = std::make_unique<BusRampMirror>();
         mirror->init(m->bus.size(), (size_t)CO * CI, m->bus.data(), m->w.data());
-    } catch (const std::bad_alloc &) {
-        delete mirror;
-        return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: out of memory");
-    }
-    uint32_t *d = nullptr, *h = nullptr;
-    if (hipMalloc((void **)&d, bytes) != hipSuccess || hipHostMalloc((void **)&h, bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(d);
-        delete mirror;
-        return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: no memory for %zu bytes of ramp state", bytes);
-    }
-    const hipError_t e = hipMemsetAsync(d, 0, bytes, m->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        (void)hipHostFree(h);
-        delete mirror;
-        return fail(COOLMIC_ERROR_GENERIC, "bus_ramp_sends: %s", hipGetErrorString(e));
-    }
-    m->d_ramp = d;
-    m->h_ramp = h;
-    m->ramp = mirror;
-    return COOLMIC_ERROR_NONE;
+        if (!m->h_ramp && hipHostMalloc((void **)&m->h_ramp, words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            m->h_ramp = nullptr;
+            return fail(COOLMIC_ERROR_NOMEM, "bus_ramp_sends: no pinned memory for %zu bytes", words * sizeof(uint32_t));
+        }
+        const int rc = m->array("bus_ramp_sends", &m->d_ramp, words);
+        if (!rc)
+            m->ramp = std::move(mirror);
+        return rc;
+    });
 }
 
 extern "C" int cmhip_bus_ramp_sends(cmhip_bus_t *m, size_t first, size_t count, const int16_t *W, uint32_t ramp_frames)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "bus_ramp_sends: bus is NULL");
-    if (count && !W)
+    if (!m || (count && !W))
         return fail(COOLMIC_ERROR_FAULT, "bus_ramp_sends: NULL argument");
     const size_t n = m->bus.size();
     if (first > n || count > n - first)
@@ -331,9 +299,9 @@ extern "C" int cmhip_bus_ramp_sends(cmhip_bus_t *m, size_t first, size_t count, 
         }
     HIP_TRY(hipSetDevice(m->d.device));
     if (ramp_frames >= 2 && !m->ramp) {
-        const int ra = bus_ramp_alloc(m);
-        if (ra)
-            return ra;
+        const int rc = bus_ramp_alloc(m);
+        if (rc)
+            return rc;
     }
     if (m->table_busy) {                             // the staging area is still the source of the last table's copy
         HIP_TRY(hipEventSynchronize(m->table_ev));
@@ -390,14 +358,15 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
     const unsigned S = m->d.streams, B = m->d.buses, CI = m->d.channels_in, CO = m->d.channels_out;
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, B, CI, frames, CO,
                         STAGE_APART};
-    const int refused = stage_run_refusal("bus_run", r);
-    if (refused)
-        return refused;
+    int rc;
+    const bool go = stage_run_begin(m, "bus_run", r, &rc);
+    if (rc)
+        return rc;
     BusArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_counts : nullptr;
+    a.nframes = m->counts_arg(frames_per_stream);
     a.bus_frames = m->d_counts + S;
     a.first = m->d_table;
     a.send = m->d_table + B + 1;
@@ -410,16 +379,15 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
     a.channels_out = CO;
     a.nt_loads = m->nt_loads ? 1u : 0u;
     const bool ramps = m->ramp && m->ramp->any();    // (the ramp kernels' tile may be the finer one)
-    if ((ramps ? plan_busramp(a) : plan_bus(a)).err != hipSuccess)
+    if (go && (ramps ? plan_busramp(a) : plan_bus(a)).err != hipSuccess)
         return fail(COOLMIC_ERROR_INVAL, "bus_run: %u buses of %zu frames: the grid would reach 2^31 workgroups", B,
                     frames);
     // nothing was touched so far; from here on the run happens
     if (out_frames)
         for (unsigned b = 0; b < B; b++)
             out_frames[b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
-    if (frames == 0 || m->bus.empty())
+    if (!go || m->bus.empty())
         return COOLMIC_ERROR_NONE;
-    HIP_TRY(hipSetDevice(m->d.device));
     if (frames_per_stream) {
         uint32_t *h;
         HIP_TRY(m->counts.take(&h));
@@ -428,12 +396,8 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
             h[S + b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
         HIP_TRY(m->counts.send(m->d_counts, (size_t)S + B, m->stream));
     }
-    if (!ramps) {                                    // nobody ramps: the plain kernels, as ever
-        const hipError_t e = launch_bus(a, m->stream);
-        if (e != hipSuccess)
-            return fail(COOLMIC_ERROR_GENERIC, "bus_run: %s", hipGetErrorString(e));
-        return COOLMIC_ERROR_NONE;
-    }
+    if (!ramps)                                      // nobody ramps: the plain kernels, as ever
+        return stage_launched("bus_run", launch_bus(a, m->stream));
     // somebody ramps: the ramp kernels, then every ramping send moves on by its bus's count, there and here
     BusRampArgs ra;
     ra.b = a;
@@ -442,8 +406,9 @@ extern "C" int cmhip_bus_run(cmhip_bus_t *m, const void *in, size_t in_stride, s
     if (e == hipSuccess)
         e = launch_busramp_advance(m->d_ramp, a.nframes ? a.bus_frames : nullptr, a.frames, (uint32_t)m->bus.size(), CI,
                                    CO, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "bus_run: %s", hipGetErrorString(e));
+    rc = stage_launched("bus_run", e);
+    if (rc)
+        return rc;
     for (unsigned b = 0; b < B; b++)
         m->bus_count[b] = bus_out_frames(m->t, b, frames_per_stream, (uint32_t)frames);
     m->ramp->advance(m->bus_count.data());

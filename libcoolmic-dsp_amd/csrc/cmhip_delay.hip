@@ -11,14 +11,11 @@
 #include <math.h>
 #include <string.h>
 
-#include <new>
-
 struct cmhip_delay : StageBase {
     cmhip_delay_desc_t d;
     int16_t *d_ring;
     uint32_t cap;                      // frames of a stream's ring
     DelayMirror mirror;
-    bool dry;                          // cmhip_test_delay_new_dry: the mirror and the checks, no device behind them
 };
 
 extern "C" uint32_t cmhip_delay_ms(unsigned rate, double ms)
@@ -35,41 +32,23 @@ extern "C" int16_t cmhip_delay_crossfade(int16_t a, int16_t b, uint32_t p)
     return (int16_t)((N + 16384) >> 15);
 }
 
-extern "C" void cmhip_delay_free(cmhip_delay_t *m)
-{
-    if (!m)
-        return;
-    if (!m->dry) {
-        m->close();
-        (void)hipFree(m->d_ring);
-    }
-    delete m;
-}
+extern "C" void cmhip_delay_free(cmhip_delay_t *m) { stage_free(m); }
 
-static int delay_init(cmhip_delay_t *m)
+// device false (cmhip_test_delay_new_dry): the mirror and the checks, no device behind them
+static int delay_init(cmhip_delay_t *m, bool device)
 {
     const cmhip_delay_desc_t &d = m->d;
     const size_t S = d.streams;
-    try {
-        m->mirror.init(S, m->cap);
-    } catch (const std::bad_alloc &) {
-        return fail(COOLMIC_ERROR_NOMEM, "delay_new: out of memory");
-    }
-    if (m->dry)
+    m->mirror.init(S, m->cap);
+    if (!device)
         return COOLMIC_ERROR_NONE;
-    if (m->open(d.device, d.hip_stream, S * DELAY_REC))
+    if (m->open("delay_new", d.device, d.hip_stream, S * DELAY_REC) ||
+        m->array("delay_new", &m->d_ring, S * (size_t)m->cap * d.channels))
         return COOLMIC_ERROR_GENERIC;
-    const size_t bytes = S * (size_t)m->cap * d.channels * sizeof(int16_t);
-    if (hipMalloc((void **)&m->d_ring, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        m->d_ring = nullptr;
-        return fail(COOLMIC_ERROR_NOMEM, "delay_new: no device memory for %zu bytes of rings", bytes);
-    }
-    HIP_TRY(hipMemsetAsync(m->d_ring, 0, bytes, m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
-static cmhip_delay_t *delay_new(const cmhip_delay_desc_t *d, bool dry)
+static cmhip_delay_t *delay_new(const cmhip_delay_desc_t *d, bool device)
 {
     if (!d) {
         fail(COOLMIC_ERROR_FAULT, "delay_new: NULL argument");
@@ -84,40 +63,31 @@ static cmhip_delay_t *delay_new(const cmhip_delay_desc_t *d, bool dry)
              d->max_frames);
         return nullptr;
     }
-    cmhip_delay_t *m = new (std::nothrow) cmhip_delay();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "delay_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    m->dry = dry;
-    m->cap = (uint32_t)delay_ring_frames(d->max_delay, d->max_frames);
-    if (delay_init(m)) {
-        cmhip_delay_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_delay>("delay_new", [&](cmhip_delay_t *m) {
+        m->d = *d;
+        m->cap = (uint32_t)delay_ring_frames(d->max_delay, d->max_frames);
+        return delay_init(m, device);
+    });
 }
 
-extern "C" cmhip_delay_t *cmhip_delay_new(const cmhip_delay_desc_t *d) { return delay_new(d, false); }
+extern "C" cmhip_delay_t *cmhip_delay_new(const cmhip_delay_desc_t *d) { return delay_new(d, true); }
 
 // test hook: an object with its mirror and every check but no device behind it, for the refusals and the mirror's
 // answers on a machine without a GPU; a run that would launch is refused
-extern "C" cmhip_delay_t *cmhip_test_delay_new_dry(const cmhip_delay_desc_t *d) { return delay_new(d, true); }
+extern "C" cmhip_delay_t *cmhip_test_delay_new_dry(const cmhip_delay_desc_t *d) { return delay_new(d, false); }
 
 extern "C" size_t cmhip_delay_max_delay(const cmhip_delay_t *m) { return m ? m->d.max_delay : 0; }
 
 extern "C" void *cmhip_delay_hip_stream(cmhip_delay_t *m) { return m ? (void *)m->stream : nullptr; }
 
-extern "C" int cmhip_delay_sync(cmhip_delay_t *m) { return m && m->dry ? COOLMIC_ERROR_NONE : stage_sync(m, "delay_sync"); }
+extern "C" int cmhip_delay_sync(cmhip_delay_t *m) { return stage_sync(m, "delay_sync"); }
 
 extern "C" int cmhip_delay_set(cmhip_delay_t *m, long stream, uint32_t delay)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "delay_set: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "delay_set: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "delay_set", stream, &sr);
+    if (rc)
+        return rc;
     if (delay > m->d.max_delay)
         return fail(COOLMIC_ERROR_INVAL, "delay_set: %u frames above the object's %zu", delay, m->d.max_delay);
     for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
@@ -127,11 +97,10 @@ extern "C" int cmhip_delay_set(cmhip_delay_t *m, long stream, uint32_t delay)
 
 extern "C" int cmhip_delay_ramp(cmhip_delay_t *m, long stream, uint32_t delay, uint32_t ramp_frames)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "delay_ramp: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "delay_ramp: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "delay_ramp", stream, &sr);
+    if (rc)
+        return rc;
     if (delay > m->d.max_delay)
         return fail(COOLMIC_ERROR_INVAL, "delay_ramp: %u frames above the object's %zu", delay, m->d.max_delay);
     if (ramp_frames > DELAY_RAMP_MAX)
@@ -174,22 +143,17 @@ extern "C" int cmhip_delay_run(cmhip_delay_t *m, const void *in, size_t in_strid
     const unsigned S = m->d.streams, C = m->d.channels;
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
                         STAGE_APART};
-    const int refused = stage_run_refusal("delay_run", r);
-    if (refused)
-        return refused;
-    // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    if (m->dry)
-        return fail(COOLMIC_ERROR_INVAL, "delay_run: the object has no device");
-    HIP_TRY(hipSetDevice(m->d.device));
+    int rc;
+    if (!stage_run_begin(m, "delay_run", r, &rc))
+        return rc;
     if (plan_delay(S, C, (uint32_t)m->d.max_delay, (uint32_t)m->d.max_frames, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "delay_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S, frames);
+    // nothing was touched so far; from here on the run happens
     // the run's records: the counts, and beside each the stream's position, taps and place in its ramp
     uint32_t *block;
     HIP_TRY(m->counts.take(&block));
     for (unsigned s = 0; s < S; s++)
-        m->mirror.record(s, frames_per_stream ? frames_per_stream[s] : (uint32_t)frames, block + (size_t)s * DELAY_REC);
+        m->mirror.record(s, stage_count(frames_per_stream, s, frames), block + (size_t)s * DELAY_REC);
     HIP_TRY(m->counts.send(m->d_counts, (size_t)S * DELAY_REC, m->stream));
     DelayArgs a;
     memset(&a, 0, sizeof(a));
@@ -202,23 +166,19 @@ extern "C" int cmhip_delay_run(cmhip_delay_t *m, const void *in, size_t in_strid
     a.ring_samples = m->cap * C;
     a.streams = S;
     a.channels = C;
-    const hipError_t e = launch_delay(a, (uint32_t)m->d.max_delay, (uint32_t)m->d.max_frames, (uint32_t)frames, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "delay_run: %s", hipGetErrorString(e));
-    for (unsigned s = 0; s < S; s++)                 // the kernel wrote every stream's frames behind its position
-        m->mirror.advance(s, frames_per_stream ? frames_per_stream[s] : (uint32_t)frames);
-    return COOLMIC_ERROR_NONE;
+    rc = stage_launched("delay_run", launch_delay(a, (uint32_t)m->d.max_delay, (uint32_t)m->d.max_frames, (uint32_t)frames,
+                                                  m->stream));
+    for (unsigned s = 0; s < S && !rc; s++)          // the kernel wrote every stream's frames behind its position
+        m->mirror.advance(s, stage_count(frames_per_stream, s, frames));
+    return rc;
 }
 
 extern "C" int cmhip_delay_reset(cmhip_delay_t *m, long stream)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "delay_reset: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "delay_reset: stream %ld out of range", stream);
-    if (m->dry)
-        return COOLMIC_ERROR_NONE;
+    StreamRange sr;
+    const int rc = stage_streams(m, "delay_reset", stream, &sr);
+    if (rc || !m->opened)
+        return rc;
     HIP_TRY(hipSetDevice(m->d.device));
     const size_t per = (size_t)m->cap * m->d.channels;
     HIP_TRY(hipMemsetAsync(m->d_ring + sr.lo * per, 0, sr.n * per * sizeof(int16_t), m->stream));

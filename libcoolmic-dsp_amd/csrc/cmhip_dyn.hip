@@ -3,8 +3,8 @@
 // ones for an object with the RMS detector), the curves, the keys, reset, the gain meter and the curve designers.
 //
 // Device state of a dynamics stage: one curve of DYN_CURVE uint16 entries per stream, the streams' history, int16
-// [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
-// cmhip_lim.hip's d_hist), the meter, uint32 [S], and the key map, uint32 [S]: the stream whose level steers stream s,
+// [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (HistoryPair,
+// csrc/cmhip_stage.h), the meter, uint32 [S], and the key map, uint32 [S]: the stream whose level steers stream s,
 // s itself where no key is set.  The host keeps a mirror of the curves and of the map; cmhip_dyn_get_curve and
 // cmhip_dyn_get_key answer from them, and the mirror's count of keyed streams chooses a run's kernels.  A new curve or
 // key reaches the device inside a kernel's arguments (k_dyn_set, k_dynk_set), so it is ordered with the runs by the
@@ -14,8 +14,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <new>
-
 constexpr uint64_t DYN_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
 struct cmhip_dyn : StageBase {
@@ -24,8 +22,7 @@ struct cmhip_dyn : StageBase {
     uint32_t detector;                 // DYN_DETECT_*, fixed at creation
     uint16_t *d_curve;
     uint32_t *d_gmin;
-    int16_t *d_hist;
-    unsigned parity;
+    HistoryPair hist;                  // [2][S][halo * C]
     uint32_t *d_key;
     std::vector<uint16_t> curve;       // the mirror: [S][DYN_CURVE]
     std::vector<uint32_t> key;         // the mirror: [S], s where stream s follows its own level
@@ -35,8 +32,6 @@ struct cmhip_dyn : StageBase {
 static_assert(CMHIP_DYN_CURVE == DYN_CURVE, "the header's curve length is the kernels'");
 static_assert(CMHIP_DYN_DETECT_MEAN == DYN_DETECT_MEAN && CMHIP_DYN_DETECT_RMS == DYN_DETECT_RMS,
               "the header's detectors are the kernels'");
-
-static size_t dyn_slot(const cmhip_dyn_t *m) { return (size_t)m->g.halo * m->d.channels; }     // samples per stream
 
 extern "C" int cmhip_dyn_check(unsigned detector_log2, unsigned smooth_log2, unsigned hold)
 {
@@ -128,39 +123,21 @@ static int dyn_init(cmhip_dyn_t *m)
 {
     const cmhip_dyn_desc_t &d = m->d;
     const size_t S = d.streams;
-    if (m->open(d.device, d.hip_stream, S))
+    if (m->open("dyn_new", d.device, d.hip_stream, S) || m->array("dyn_new", &m->d_curve, S * DYN_CURVE) ||
+        m->array("dyn_new", &m->d_gmin, S, DYN_UNITY) || m->array("dyn_new", &m->d_key, S) ||
+        m->hist.init(*m, "dyn_new", S, (size_t)m->g.halo * d.channels))
         return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipMalloc((void **)&m->d_curve, S * DYN_CURVE * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * dyn_slot(m) * sizeof(int16_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_key, S * sizeof(uint32_t)));
-    HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * dyn_slot(m) * sizeof(int16_t), m->stream));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)DYN_UNITY, S, m->stream));
     m->curve.assign(S * DYN_CURVE, (uint16_t)DYN_UNITY);         // at creation: unity everywhere, a pure delay
-    const hipError_t e = launch_dyn_set(m->d_curve, 0, d.streams, m->curve.data(), m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "dyn_new: %s", hipGetErrorString(e));
+    if (stage_launched("dyn_new", launch_dyn_set(m->d_curve, 0, d.streams, m->curve.data(), m->stream)))
+        return COOLMIC_ERROR_GENERIC;
     m->key.resize(S);                                            // at creation: every stream is its own key
     for (size_t s = 0; s < S; s++)
         m->key[s] = (uint32_t)s;
     m->keyed = 0;
-    const hipError_t k = launch_dyn_set_key(m->d_key, 0, d.streams, 0, true, m->stream);
-    if (k != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "dyn_new: %s", hipGetErrorString(k));
-    return COOLMIC_ERROR_NONE;
+    return stage_launched("dyn_new", launch_dyn_set_key(m->d_key, 0, d.streams, 0, true, m->stream));
 }
 
-extern "C" void cmhip_dyn_free(cmhip_dyn_t *m)
-{
-    if (!m)
-        return;
-    m->close();
-    (void)hipFree(m->d_curve);
-    (void)hipFree(m->d_gmin);
-    (void)hipFree(m->d_hist);
-    (void)hipFree(m->d_key);
-    delete m;
-}
+extern "C" void cmhip_dyn_free(cmhip_dyn_t *m) { stage_free(m); }
 
 extern "C" cmhip_dyn_t *cmhip_dyn_new_detector(const cmhip_dyn_desc_t *d, unsigned detector)
 {
@@ -187,19 +164,12 @@ extern "C" cmhip_dyn_t *cmhip_dyn_new_detector(const cmhip_dyn_desc_t *d, unsign
         fail(COOLMIC_ERROR_INVAL, "dyn_new: %u streams: the history would pass 2^31 samples", d->streams);
         return nullptr;
     }
-    cmhip_dyn_t *m = new (std::nothrow) cmhip_dyn();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "dyn_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    m->g = g;
-    m->detector = detector;
-    if (dyn_init(m)) {
-        cmhip_dyn_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_dyn>("dyn_new", [&](cmhip_dyn_t *m) {
+        m->d = *d;
+        m->g = g;
+        m->detector = detector;
+        return dyn_init(m);
+    });
 }
 
 extern "C" cmhip_dyn_t *cmhip_dyn_new(const cmhip_dyn_desc_t *d) { return cmhip_dyn_new_detector(d, DYN_DETECT_MEAN); }
@@ -210,17 +180,18 @@ extern "C" unsigned cmhip_dyn_delay(const cmhip_dyn_t *m) { return m ? m->g.D : 
 
 extern "C" int cmhip_dyn_set_curve(cmhip_dyn_t *m, long stream, const uint16_t *curve)
 {
-    if (!m || !curve)
+    if (!curve)
         return fail(COOLMIC_ERROR_FAULT, "dyn_set_curve: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "dyn_set_curve: stream %ld out of range", stream);
+    StreamRange sr;
+    int rc = stage_streams(m, "dyn_set_curve", stream, &sr);
+    if (rc)
+        return rc;
     if (!dyn_curve_ok(curve))
         return fail(COOLMIC_ERROR_INVAL, "dyn_set_curve: an entry of 0..%u is above 32768", DYN_CURVE_USED - 1u);
     HIP_TRY(hipSetDevice(m->d.device));
-    const hipError_t e = launch_dyn_set(m->d_curve, sr.lo, sr.n, curve, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "dyn_set_curve: %s", hipGetErrorString(e));
+    rc = stage_launched("dyn_set_curve", launch_dyn_set(m->d_curve, sr.lo, sr.n, curve, m->stream));
+    if (rc)
+        return rc;
     for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
         memcpy(&m->curve[s * DYN_CURVE], curve, DYN_CURVE * sizeof(uint16_t));
     return COOLMIC_ERROR_NONE;
@@ -238,18 +209,17 @@ extern "C" int cmhip_dyn_get_curve(const cmhip_dyn_t *m, unsigned stream, uint16
 
 extern "C" int cmhip_dyn_set_key(cmhip_dyn_t *m, long stream, long key)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "dyn_set_key: stage is NULL");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "dyn_set_key: stream %ld out of range", stream);
+    StreamRange sr;
+    int rc = stage_streams(m, "dyn_set_key", stream, &sr);
+    if (rc)
+        return rc;
     if (key < -1 || (key >= 0 && (unsigned long)key >= m->d.streams))
         return fail(COOLMIC_ERROR_INVAL, "dyn_set_key: key %ld out of range", key);
     HIP_TRY(hipSetDevice(m->d.device));
     const bool own = key < 0;
-    const hipError_t e = launch_dyn_set_key(m->d_key, sr.lo, sr.n, own ? 0u : (uint32_t)key, own, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "dyn_set_key: %s", hipGetErrorString(e));
+    rc = stage_launched("dyn_set_key", launch_dyn_set_key(m->d_key, sr.lo, sr.n, own ? 0u : (uint32_t)key, own, m->stream));
+    if (rc)
+        return rc;
     for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++) {
         const uint32_t k = own ? (uint32_t)s : (uint32_t)key;
         if (m->key[s] != s)
@@ -277,17 +247,13 @@ extern "C" int cmhip_dyn_sync(cmhip_dyn_t *m) { return stage_sync(m, "dyn_sync")
 
 extern "C" int cmhip_dyn_reset(cmhip_dyn_t *m, long stream)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "dyn_reset: stage is NULL");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "dyn_reset: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "dyn_reset", stream, &sr);
+    if (rc)
+        return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    const size_t lo = sr.lo, n = sr.n, per = dyn_slot(m);
-    // (the slot the next run reads; the other one is rewritten by that run)
-    HIP_TRY(hipMemsetAsync(m->d_hist + ((size_t)m->parity * m->d.streams + lo) * per, 0, n * per * sizeof(int16_t),
-                           m->stream));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->d_gmin + lo), (int)DYN_UNITY, n, m->stream));
+    HIP_TRY(m->hist.reset(sr.lo, sr.n, m->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->d_gmin + sr.lo), (int)DYN_UNITY, sr.n, m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
@@ -295,12 +261,7 @@ extern "C" int cmhip_dyn_min_gain(cmhip_dyn_t *m, uint32_t *out, int reset)
 {
     if (!m || !out)
         return fail(COOLMIC_ERROR_FAULT, "dyn_min_gain: NULL argument");
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipMemcpyAsync(out, m->d_gmin, m->d.streams * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (reset)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)DYN_UNITY, m->d.streams, m->stream));
-    return COOLMIC_ERROR_NONE;
+    return stage_read(m, out, m->d_gmin, m->d.streams * sizeof(uint32_t), reset != 0, DYN_UNITY);
 }
 
 extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, size_t frames,
@@ -313,9 +274,9 @@ extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, s
     // written them)
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
                         STAGE_APART};
-    const int refused = stage_run_refusal("dyn_run", r);
-    if (refused)
-        return refused;
+    int rc;
+    if (!stage_run_begin(m, "dyn_run", r, &rc))
+        return rc;
     if (plan_dyn(S, C, m->g.a, m->g.b, m->g.H, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "dyn_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
@@ -328,32 +289,26 @@ extern "C" int cmhip_dyn_run(cmhip_dyn_t *m, const void *in, size_t in_stride, s
                             frames_per_stream[s], k, frames_per_stream[k]);
         }
     // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    HIP_TRY(hipSetDevice(m->d.device));
     DynArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_counts : nullptr;
     a.curve = m->d_curve;
-    a.hist = m->d_hist;
+    a.hist = m->hist.d;
     a.gmin = m->d_gmin;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
     a.frames = (uint32_t)frames;
     a.streams = S;
     a.channels = C;
-    a.parity = m->parity;
+    a.parity = m->hist.parity();
     a.a = m->g.a;
     a.b = m->g.b;
     a.W = m->g.W;
-    if (frames_per_stream)
-        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
+    HIP_TRY(m->send_counts(frames_per_stream, S, &a.nframes));
     // (the keyed kernels only while a key is set)
-    const hipError_t e = launch_dyn(a, m->detector, m->keyed ? m->d_key : nullptr, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "dyn_run: %s", hipGetErrorString(e));
-    m->parity ^= 1u;                         // the kernel wrote the other slots
-    return COOLMIC_ERROR_NONE;
+    rc = stage_launched("dyn_run", launch_dyn(a, m->detector, m->keyed ? m->d_key : nullptr, m->stream));
+    if (!rc)
+        m->hist.flip();                      // the kernel wrote the other slots
+    return rc;
 }

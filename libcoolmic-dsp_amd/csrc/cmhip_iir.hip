@@ -11,9 +11,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <new>
-#include <vector>
-
 static_assert(sizeof(cmhip_iir_section_t) == sizeof(IirSec) && sizeof(IirSec) == 20, "cmhip_iir_section_t is IirSec");
 static_assert(offsetof(cmhip_iir_section_t, a1) == offsetof(IirSec, a1), "cmhip_iir_section_t is IirSec");
 static_assert(CMHIP_IIR_ONE == IIR_ONE, "the coefficient unit");
@@ -25,7 +22,6 @@ struct cmhip_iir : StageBase {
     IirState *d_state;                 // [S * C][N]
     unsigned long long *d_clips;       // [S]
     unsigned long long *d_overs;       // [S]
-    bool dry;                          // cmhip_test_iir_new_dry: the mirror and the checks, no device behind them
 };
 
 static IirSec iir_from(const cmhip_iir_section_t *p)
@@ -133,49 +129,27 @@ extern "C" double cmhip_iir_response_db(const cmhip_iir_section_t *sec, unsigned
     return db;
 }
 
-extern "C" void cmhip_iir_free(cmhip_iir_t *m)
-{
-    if (!m)
-        return;
-    if (!m->dry) {
-        m->close();
-        (void)hipFree(m->d_state);
-        (void)hipFree(m->d_clips);
-        (void)hipFree(m->d_overs);
-    }
-    delete m;
-}
+extern "C" void cmhip_iir_free(cmhip_iir_t *m) { stage_free(m); }
 
 static size_t iir_table_words(const cmhip_iir_desc_t &d) { return (size_t)d.streams * d.sections * IIR_SEC_WORDS; }
 
-static int iir_init(cmhip_iir_t *m)
+// device false (cmhip_test_iir_new_dry): the mirror and the checks, no device behind them
+static int iir_init(cmhip_iir_t *m, bool device)
 {
     const cmhip_iir_desc_t &d = m->d;
     const size_t S = d.streams;
-    try {
-        m->coef.assign(S * d.sections, IIR_UNITY);
-    } catch (const std::bad_alloc &) {
-        return fail(COOLMIC_ERROR_NOMEM, "iir_new: out of memory");
-    }
+    m->coef.assign(S * d.sections, IIR_UNITY);
     m->dirty = true;
-    if (m->dry)
+    if (!device)
         return COOLMIC_ERROR_NONE;
-    if (m->open(d.device, d.hip_stream, S + iir_table_words(d)))
+    if (m->open("iir_new", d.device, d.hip_stream, S + iir_table_words(d)) ||
+        m->array("iir_new", &m->d_state, S * d.channels * d.sections) || m->array("iir_new", &m->d_clips, S) ||
+        m->array("iir_new", &m->d_overs, S))
         return COOLMIC_ERROR_GENERIC;
-    const size_t state = S * d.channels * d.sections * sizeof(IirState);
-    if (hipMalloc((void **)&m->d_state, state) != hipSuccess ||
-        hipMalloc((void **)&m->d_clips, S * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&m->d_overs, S * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(COOLMIC_ERROR_NOMEM, "iir_new: no device memory for %zu bytes of state", state);
-    }
-    HIP_TRY(hipMemsetAsync(m->d_state, 0, state, m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_clips, 0, S * sizeof(unsigned long long), m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_overs, 0, S * sizeof(unsigned long long), m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
-static cmhip_iir_t *iir_new(const cmhip_iir_desc_t *d, bool dry)
+static cmhip_iir_t *iir_new(const cmhip_iir_desc_t *d, bool device)
 {
     if (!d) {
         fail(COOLMIC_ERROR_FAULT, "iir_new: NULL argument");
@@ -186,37 +160,30 @@ static cmhip_iir_t *iir_new(const cmhip_iir_desc_t *d, bool dry)
              "2^31) out of range");
         return nullptr;
     }
-    cmhip_iir_t *m = new (std::nothrow) cmhip_iir();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "iir_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    m->dry = dry;
-    if (iir_init(m)) {
-        cmhip_iir_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_iir>("iir_new", [&](cmhip_iir_t *m) {
+        m->d = *d;
+        return iir_init(m, device);
+    });
 }
 
-extern "C" cmhip_iir_t *cmhip_iir_new(const cmhip_iir_desc_t *d) { return iir_new(d, false); }
+extern "C" cmhip_iir_t *cmhip_iir_new(const cmhip_iir_desc_t *d) { return iir_new(d, true); }
 
 // test hook: an object with its mirror and every check but no device behind it, for the refusals and the mirror's
 // answers on a machine without a GPU; a run that would launch is refused
-extern "C" cmhip_iir_t *cmhip_test_iir_new_dry(const cmhip_iir_desc_t *d) { return iir_new(d, true); }
+extern "C" cmhip_iir_t *cmhip_test_iir_new_dry(const cmhip_iir_desc_t *d) { return iir_new(d, false); }
 
 extern "C" void *cmhip_iir_hip_stream(cmhip_iir_t *m) { return m ? (void *)m->stream : nullptr; }
 
-extern "C" int cmhip_iir_sync(cmhip_iir_t *m) { return m && m->dry ? COOLMIC_ERROR_NONE : stage_sync(m, "iir_sync"); }
+extern "C" int cmhip_iir_sync(cmhip_iir_t *m) { return stage_sync(m, "iir_sync"); }
 
 extern "C" int cmhip_iir_set(cmhip_iir_t *m, long stream, unsigned int section, const cmhip_iir_section_t *c)
 {
-    if (!m || !c)
+    if (!c)
         return fail(COOLMIC_ERROR_FAULT, "iir_set: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "iir_set: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "iir_set", stream, &sr);
+    if (rc)
+        return rc;
     if (section >= m->d.sections)
         return fail(COOLMIC_ERROR_INVAL, "iir_set: section %u of %u", section, m->d.sections);
     const IirSec q = iir_from(c);
@@ -246,20 +213,15 @@ extern "C" int cmhip_iir_run(cmhip_iir_t *m, const void *in, size_t in_stride, s
     const unsigned S = m->d.streams, C = m->d.channels;
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
                         STAGE_APART};
-    const int refused = stage_run_refusal("iir_run", r);
-    if (refused)
-        return refused;
+    int rc;
+    if (!stage_run_begin(m, "iir_run", r, &rc))
+        return rc;
     // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    if (m->dry)
-        return fail(COOLMIC_ERROR_INVAL, "iir_run: the object has no device");
-    HIP_TRY(hipSetDevice(m->d.device));
     // the run's counts and, behind a set, the coefficient table behind them
     uint32_t *block;
     HIP_TRY(m->counts.take(&block));
     for (unsigned s = 0; s < S; s++)
-        block[s] = frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
+        block[s] = stage_count(frames_per_stream, s, frames);
     const size_t words = m->dirty ? iir_table_words(m->d) : 0;
     if (words)
         memcpy(block + S, m->coef.data(), words * sizeof(uint32_t));
@@ -279,21 +241,15 @@ extern "C" int cmhip_iir_run(cmhip_iir_t *m, const void *in, size_t in_stride, s
     a.streams = S;
     a.channels = C;
     a.sections = m->d.sections;
-    const hipError_t e = launch_iir(a, (uint32_t)frames, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "iir_run: %s", hipGetErrorString(e));
-    return COOLMIC_ERROR_NONE;
+    return stage_launched("iir_run", launch_iir(a, (uint32_t)frames, m->stream));
 }
 
 extern "C" int cmhip_iir_reset(cmhip_iir_t *m, long stream)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "iir_reset: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "iir_reset: stream %ld out of range", stream);
-    if (m->dry)
-        return COOLMIC_ERROR_NONE;
+    StreamRange sr;
+    const int rc = stage_streams(m, "iir_reset", stream, &sr);
+    if (rc || !m->opened)
+        return rc;
     HIP_TRY(hipSetDevice(m->d.device));
     const size_t per = (size_t)m->d.channels * m->d.sections;            // a stream's sections, all rows
     HIP_TRY(hipMemsetAsync(m->d_state + (size_t)sr.lo * per, 0, (size_t)sr.n * per * sizeof(IirState), m->stream));
@@ -305,25 +261,8 @@ extern "C" int cmhip_iir_state(cmhip_iir_t *m, uint64_t *clips, uint64_t *overs,
     if (!m)
         return fail(COOLMIC_ERROR_FAULT, "iir_state: NULL argument");
     const size_t bytes = (size_t)m->d.streams * sizeof(uint64_t);
-    if (m->dry) {
-        if (clips)
-            memset(clips, 0, bytes);
-        if (overs)
-            memset(overs, 0, bytes);
-        return COOLMIC_ERROR_NONE;
-    }
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (clips)
-        HIP_TRY(hipMemcpy(clips, m->d_clips, bytes, hipMemcpyDeviceToHost));
-    if (overs)
-        HIP_TRY(hipMemcpy(overs, m->d_overs, bytes, hipMemcpyDeviceToHost));
-    if (clear) {
-        HIP_TRY(hipMemsetAsync(m->d_clips, 0, bytes, m->stream));
-        HIP_TRY(hipMemsetAsync(m->d_overs, 0, bytes, m->stream));
-        HIP_TRY(hipStreamSynchronize(m->stream));
-    }
-    return COOLMIC_ERROR_NONE;
+    const int rc = stage_read(m, clips, m->d_clips, bytes, clear != 0);
+    return rc ? rc : stage_read(m, overs, m->d_overs, bytes, clear != 0);
 }
 
 // test hook: the rows' sections as the device holds them, int32 [S * C][N][5] (u1, u2, v1, v2, e); synchronous
@@ -331,13 +270,5 @@ extern "C" int cmhip_test_iir_rows(cmhip_iir_t *m, int32_t *rows)
 {
     if (!m || !rows)
         return fail(COOLMIC_ERROR_FAULT, "iir_rows: NULL argument");
-    const size_t bytes = (size_t)m->d.streams * m->d.channels * m->d.sections * sizeof(IirState);
-    if (m->dry) {
-        memset(rows, 0, bytes);
-        return COOLMIC_ERROR_NONE;
-    }
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    HIP_TRY(hipMemcpy(rows, m->d_state, bytes, hipMemcpyDeviceToHost));
-    return COOLMIC_ERROR_NONE;
+    return stage_read(m, rows, m->d_state, (size_t)m->d.streams * m->d.channels * m->d.sections * sizeof(IirState), false);
 }

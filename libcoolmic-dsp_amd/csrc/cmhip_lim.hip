@@ -4,16 +4,14 @@
 // (release_log2 >= 1, fixed at creation), parameters, reset and the gain-reduction meter.
 //
 // Device state of a limiter: one parameter word per stream (threshold | drive << 16), the streams' history, int16
-// [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (the mechanism of
-// cmhip_src.hip's d_hist), and the meter, uint32 [S].  The host keeps a mirror of the parameters; cmhip_lim_get answers
+// [2][S][halo * C] raw input frames, two slots selected by a parity the host flips per run (HistoryPair,
+// csrc/cmhip_stage.h), and the meter, uint32 [S].  The host keeps a mirror of the parameters; cmhip_lim_get answers
 // from it.  New parameters reach the device inside a kernel's arguments (k_lim_set), so they are ordered with the runs
 // by the stream alone and no staging memory outlives the call.
 #include "cmhip_engine.h"
 
 #include <math.h>
 #include <string.h>
-
-#include <new>
 
 constexpr uint64_t LIM_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
@@ -24,12 +22,9 @@ struct cmhip_lim : StageBase {
     unsigned rho;                      // release_log2; 0: no release stage
     uint32_t *d_par;
     uint32_t *d_gmin;
-    int16_t *d_hist;
-    unsigned parity;
+    HistoryPair hist;                  // [2][S][halo * C]
     std::vector<uint32_t> par;         // the mirror: threshold | drive << 16
 };
-
-static size_t lim_slot(const cmhip_lim_t *m) { return (size_t)m->g.halo * m->d.channels; }     // samples per stream
 
 extern "C" int cmhip_lim_check(unsigned lookahead_log2, unsigned hold, unsigned threshold, unsigned drive)
 {
@@ -81,30 +76,14 @@ static int lim_init(cmhip_lim_t *m)
 {
     const cmhip_lim_desc_t &d = m->d;
     const size_t S = d.streams;
-    if (m->open(d.device, d.hip_stream, S))
+    if (m->open("lim_new", d.device, d.hip_stream, S) || m->array("lim_new", &m->d_par, S) ||
+        m->array("lim_new", &m->d_gmin, S, LIM_UNITY) || m->hist.init(*m, "lim_new", S, (size_t)m->g.halo * d.channels))
         return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipMalloc((void **)&m->d_par, S * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_gmin, S * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * S * lim_slot(m) * sizeof(int16_t)));
-    HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * S * lim_slot(m) * sizeof(int16_t), m->stream));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)LIM_UNITY, S, m->stream));
     m->par.assign(S, LIM_T_MAX | 4096u << 16);       // at creation: no limiting below full scale, unity drive
-    const hipError_t e = launch_lim_set(m->d_par, 0, d.streams, LIM_T_MAX, 4096u, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "lim_new: %s", hipGetErrorString(e));
-    return COOLMIC_ERROR_NONE;
+    return stage_launched("lim_new", launch_lim_set(m->d_par, 0, d.streams, LIM_T_MAX, 4096u, m->stream));
 }
 
-extern "C" void cmhip_lim_free(cmhip_lim_t *m)
-{
-    if (!m)
-        return;
-    m->close();
-    (void)hipFree(m->d_par);
-    (void)hipFree(m->d_gmin);
-    (void)hipFree(m->d_hist);
-    delete m;
-}
+extern "C" void cmhip_lim_free(cmhip_lim_t *m) { stage_free(m); }
 
 extern "C" cmhip_lim_t *cmhip_lim_new(const cmhip_lim_desc_t *d)
 {
@@ -153,20 +132,13 @@ extern "C" cmhip_lim_t *cmhip_lim_new_release(const cmhip_lim_desc_t *d, unsigne
         fail(COOLMIC_ERROR_INVAL, "lim_new: %u streams: the history would pass 2^31 samples", d->streams);
         return nullptr;
     }
-    cmhip_lim_t *m = new (std::nothrow) cmhip_lim();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "lim_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    m->g = g;
-    m->detector = detector;
-    m->rho = release_log2;
-    if (lim_init(m)) {
-        cmhip_lim_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_lim>("lim_new", [&](cmhip_lim_t *m) {
+        m->d = *d;
+        m->g = g;
+        m->detector = detector;
+        m->rho = release_log2;
+        return lim_init(m);
+    });
 }
 
 extern "C" unsigned cmhip_lim_delay(const cmhip_lim_t *m) { return m ? m->g.D : 0u; }
@@ -177,18 +149,16 @@ extern "C" unsigned cmhip_lim_release(const cmhip_lim_t *m) { return m ? m->rho 
 
 extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, unsigned drive)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "lim_set: limiter is NULL");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "lim_set: stream %ld out of range", stream);
-    const int rc = cmhip_lim_check_detector(m->detector, m->g.a, m->g.H, threshold, drive);
+    StreamRange sr;
+    int rc = stage_streams(m, "lim_set", stream, &sr);
+    if (!rc)
+        rc = cmhip_lim_check_detector(m->detector, m->g.a, m->g.H, threshold, drive);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    const hipError_t e = launch_lim_set(m->d_par, sr.lo, sr.n, threshold, drive, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "lim_set: %s", hipGetErrorString(e));
+    rc = stage_launched("lim_set", launch_lim_set(m->d_par, sr.lo, sr.n, threshold, drive, m->stream));
+    if (rc)
+        return rc;
     for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
         m->par[s] = threshold | drive << 16;
     return COOLMIC_ERROR_NONE;
@@ -197,7 +167,7 @@ extern "C" int cmhip_lim_set(cmhip_lim_t *m, long stream, unsigned threshold, un
 extern "C" int cmhip_lim_get(const cmhip_lim_t *m, unsigned stream, unsigned *threshold, unsigned *drive)
 {
     if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "lim_get: limiter is NULL");
+        return fail(COOLMIC_ERROR_FAULT, "lim_get: NULL argument");
     if (stream >= m->d.streams)
         return fail(COOLMIC_ERROR_INVAL, "lim_get: stream %u out of range", stream);
     if (threshold)
@@ -213,17 +183,13 @@ extern "C" int cmhip_lim_sync(cmhip_lim_t *m) { return stage_sync(m, "lim_sync")
 
 extern "C" int cmhip_lim_reset(cmhip_lim_t *m, long stream)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "lim_reset: limiter is NULL");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "lim_reset: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "lim_reset", stream, &sr);
+    if (rc)
+        return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    const size_t lo = sr.lo, n = sr.n, per = lim_slot(m);
-    // (the slot the next run reads; the other one is rewritten by that run)
-    HIP_TRY(hipMemsetAsync(m->d_hist + ((size_t)m->parity * m->d.streams + lo) * per, 0, n * per * sizeof(int16_t),
-                           m->stream));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->d_gmin + lo), (int)LIM_UNITY, n, m->stream));
+    HIP_TRY(m->hist.reset(sr.lo, sr.n, m->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(m->d_gmin + sr.lo), (int)LIM_UNITY, sr.n, m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
@@ -231,12 +197,7 @@ extern "C" int cmhip_lim_min_gain(cmhip_lim_t *m, uint32_t *out, int reset)
 {
     if (!m || !out)
         return fail(COOLMIC_ERROR_FAULT, "lim_min_gain: NULL argument");
-    HIP_TRY(hipSetDevice(m->d.device));
-    HIP_TRY(hipMemcpyAsync(out, m->d_gmin, m->d.streams * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (reset)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m->d_gmin, (int)LIM_UNITY, m->d.streams, m->stream));
-    return COOLMIC_ERROR_NONE;
+    return stage_read(m, out, m->d_gmin, m->d.streams * sizeof(uint32_t), reset != 0, LIM_UNITY);
 }
 
 extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, size_t frames,
@@ -249,37 +210,31 @@ extern "C" int cmhip_lim_run(cmhip_lim_t *m, const void *in, size_t in_stride, s
     // written them)
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, C, frames, C,
                         STAGE_APART};
-    const int refused = stage_run_refusal("lim_run", r);
-    if (refused)
-        return refused;
+    int rc;
+    if (!stage_run_begin(m, "lim_run", r, &rc))
+        return rc;
     if (plan_limrel(m->detector, S, C, m->g.a, m->g.H, m->rho, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "lim_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
     // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    HIP_TRY(hipSetDevice(m->d.device));
     LimArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_counts : nullptr;
     a.par = m->d_par;
-    a.hist = m->d_hist;
+    a.hist = m->hist.d;
     a.gmin = m->d_gmin;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
     a.frames = (uint32_t)frames;
     a.streams = S;
     a.channels = C;
-    a.parity = m->parity;
+    a.parity = m->hist.parity();
     a.a = m->g.a;
     a.W = m->g.W;
-    if (frames_per_stream)
-        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    const hipError_t e = launch_limrel(a, m->detector, m->rho, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "lim_run: %s", hipGetErrorString(e));
-    m->parity ^= 1u;                         // the kernel wrote the other slots
-    return COOLMIC_ERROR_NONE;
+    HIP_TRY(m->send_counts(frames_per_stream, S, &a.nframes));
+    rc = stage_launched("lim_run", launch_limrel(a, m->detector, m->rho, m->stream));
+    if (!rc)
+        m->hist.flip();                      // the kernel wrote the other slots
+    return rc;
 }

@@ -16,7 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
+#include <memory>
 
 constexpr uint64_t MIX_MAX_SAMPLES = 1ull << 31;     // per slot and run: the kernels index a slot in 32 bits
 
@@ -25,7 +25,7 @@ struct cmhip_mix : StageBase {
     uint32_t *d_wk;
     std::vector<int16_t> w;            // the mirror: [S][C_out][C_in]
     uint32_t *d_ramp;                  // the streams' ramp records, allocated by the first ramp
-    MixRampMirror *ramp;               // ... and their mirror
+    std::unique_ptr<MixRampMirror> ramp;       // ... and their mirror
 };
 
 static bool mix_channels_ok(unsigned ci, unsigned co) { return ci >= 1 && ci <= MAX_CH && co >= 1 && co <= MAX_CH; }
@@ -82,9 +82,8 @@ static int mix_init(cmhip_mix_t *m)
 {
     const cmhip_mix_desc_t &d = m->d;
     const size_t S = d.streams, CI = d.channels_in, CO = d.channels_out, n = CO * ((CI + 1) / 2);
-    if (m->open(d.device, d.hip_stream, S))
+    if (m->open("mix_new", d.device, d.hip_stream, S) || m->array("mix_new", &m->d_wk, S * n))
         return COOLMIC_ERROR_GENERIC;
-    HIP_TRY(hipMalloc((void **)&m->d_wk, S * n * sizeof(uint32_t)));
     // the matrix at creation: the leading channels kept, silence in extra outputs
     std::vector<int16_t> w0(CO * CI, 0);
     for (size_t o = 0; o < (CI < CO ? CI : CO); o++)
@@ -92,22 +91,11 @@ static int mix_init(cmhip_mix_t *m)
     m->w.resize(S * CO * CI);
     for (size_t s = 0; s < S; s++)
         memcpy(&m->w[s * CO * CI], w0.data(), CO * CI * sizeof(int16_t));
-    const hipError_t e = launch_mix_set(m->d_wk, 0, d.streams, d.channels_in, d.channels_out, w0.data(), m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "mix_new: %s", hipGetErrorString(e));
-    return COOLMIC_ERROR_NONE;
+    return stage_launched("mix_new", launch_mix_set(m->d_wk, 0, d.streams, d.channels_in, d.channels_out, w0.data(),
+                                                    m->stream));
 }
 
-extern "C" void cmhip_mix_free(cmhip_mix_t *m)
-{
-    if (!m)
-        return;
-    m->close();
-    (void)hipFree(m->d_wk);
-    (void)hipFree(m->d_ramp);
-    delete m->ramp;
-    delete m;
-}
+extern "C" void cmhip_mix_free(cmhip_mix_t *m) { stage_free(m); }
 
 extern "C" cmhip_mix_t *cmhip_mix_new(const cmhip_mix_desc_t *d)
 {
@@ -128,39 +116,33 @@ extern "C" cmhip_mix_t *cmhip_mix_new(const cmhip_mix_desc_t *d)
         fail(COOLMIC_ERROR_INVAL, "mix_new: %u streams: the matrix table would pass 2^31 entries", d->streams);
         return nullptr;
     }
-    cmhip_mix_t *m = new (std::nothrow) cmhip_mix();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "mix_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    if (mix_init(m)) {
-        cmhip_mix_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_mix>("mix_new", [&](cmhip_mix_t *m) {
+        m->d = *d;
+        return mix_init(m);
+    });
 }
 
 extern "C" int cmhip_mix_set_matrix(cmhip_mix_t *m, long stream, const int16_t *W)
 {
-    if (!m || !W)
+    if (!W)
         return fail(COOLMIC_ERROR_FAULT, "mix_set_matrix: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "mix_set_matrix: stream %ld out of range", stream);
+    StreamRange sr;
+    int rc = stage_streams(m, "mix_set_matrix", stream, &sr);
+    if (rc)
+        return rc;
     const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
-    const int rc = cmhip_mix_check(CI, CO, W);
+    rc = cmhip_mix_check(CI, CO, W);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(m->d.device));
     const uint32_t lo = sr.lo, n = sr.n;
-    const hipError_t e = launch_mix_set(m->d_wk, lo, n, CI, CO, W, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "mix_set_matrix: %s", hipGetErrorString(e));
+    rc = stage_launched("mix_set_matrix", launch_mix_set(m->d_wk, lo, n, CI, CO, W, m->stream));
+    if (rc)
+        return rc;
     if (m->ramp) {                     // a step ends whatever ramp runs
-        const hipError_t ec = launch_mixramp_cancel(m->d_ramp, lo, n, CI, CO, m->stream);
-        if (ec != hipSuccess)
-            return fail(COOLMIC_ERROR_GENERIC, "mix_set_matrix: %s", hipGetErrorString(ec));
+        rc = stage_launched("mix_set_matrix", launch_mixramp_cancel(m->d_ramp, lo, n, CI, CO, m->stream));
+        if (rc)
+            return rc;
         for (size_t s = lo; s < (size_t)lo + n; s++)
             m->ramp->cancel(s, W);
     }
@@ -172,59 +154,40 @@ extern "C" int cmhip_mix_set_matrix(cmhip_mix_t *m, long stream, const int16_t *
 // the ramp records and their mirror, on first use: every stream at rest (R = 0) on its matrix
 static int mix_ramp_alloc(cmhip_mix_t *m)
 {
-    const size_t S = m->d.streams, n = (size_t)m->d.channels_out * m->d.channels_in;
-    const size_t bytes = S * mixramp_record_dwords(m->d.channels_in, m->d.channels_out) * sizeof(uint32_t);
-    MixRampMirror *mirror = new (std::nothrow) MixRampMirror();
-    if (!mirror)
-        return fail(COOLMIC_ERROR_NOMEM, "mix_ramp_matrix: out of memory");
-    try {
+    return stage_guard("mix_ramp_matrix", [&] {
+        const size_t S = m->d.streams, n = (size_t)m->d.channels_out * m->d.channels_in;
+        auto mirror = std::make_unique<MixRampMirror>();
         mirror->init(S, n, m->w.data());
-    } catch (const std::bad_alloc &) {
-        delete mirror;
-        return fail(COOLMIC_ERROR_NOMEM, "mix_ramp_matrix: out of memory");
-    }
-    uint32_t *d = nullptr;
-    if (hipMalloc((void **)&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        delete mirror;
-        return fail(COOLMIC_ERROR_NOMEM, "mix_ramp_matrix: no device memory for %zu bytes of ramp state", bytes);
-    }
-    const hipError_t e = hipMemsetAsync(d, 0, bytes, m->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        delete mirror;
-        return fail(COOLMIC_ERROR_GENERIC, "mix_ramp_matrix: %s", hipGetErrorString(e));
-    }
-    m->d_ramp = d;
-    m->ramp = mirror;
-    return COOLMIC_ERROR_NONE;
+        const int rc = m->array("mix_ramp_matrix", &m->d_ramp, S * mixramp_record_dwords(m->d.channels_in, m->d.channels_out));
+        if (!rc)
+            m->ramp = std::move(mirror);
+        return rc;
+    });
 }
 
 extern "C" int cmhip_mix_ramp_matrix(cmhip_mix_t *m, long stream, const int16_t *W, uint32_t ramp_frames)
 {
-    if (!m || !W)
+    if (!W)
         return fail(COOLMIC_ERROR_FAULT, "mix_ramp_matrix: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "mix_ramp_matrix: stream %ld out of range", stream);
+    StreamRange sr;
+    int rc = stage_streams(m, "mix_ramp_matrix", stream, &sr);
+    if (rc)
+        return rc;
     if (ramp_frames > MIX_RAMP_MAX)
         return fail(COOLMIC_ERROR_INVAL, "mix_ramp_matrix: %u frames above %u", ramp_frames, MIX_RAMP_MAX);
     if (ramp_frames < 2)
         return cmhip_mix_set_matrix(m, stream, W);
     const unsigned CI = m->d.channels_in, CO = m->d.channels_out;
-    const int rc = cmhip_mix_check(CI, CO, W);
+    rc = cmhip_mix_check(CI, CO, W);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    if (!m->ramp) {
-        const int ra = mix_ramp_alloc(m);
-        if (ra)
-            return ra;
-    }
+    if (!m->ramp && (rc = mix_ramp_alloc(m)) != 0)
+        return rc;
     const uint32_t lo = sr.lo, n = sr.n;
-    const hipError_t e = launch_mixramp_start(m->d_ramp, m->d_wk, lo, n, CI, CO, W, ramp_frames, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "mix_ramp_matrix: %s", hipGetErrorString(e));
+    rc = stage_launched("mix_ramp_matrix", launch_mixramp_start(m->d_ramp, m->d_wk, lo, n, CI, CO, W, ramp_frames, m->stream));
+    if (rc)
+        return rc;
     for (size_t s = lo; s < (size_t)lo + n; s++) {
         m->ramp->start(s, W, ramp_frames);
         memcpy(&m->w[s * CO * CI], W, (size_t)CO * CI * sizeof(int16_t));
@@ -281,18 +244,13 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
     // (the two arrays may not share a byte: a narrower output written over the input would race between tiles)
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, S, CI, frames, CO,
                         STAGE_APART};
-    const int refused = stage_run_refusal("mix_run", r);
-    if (refused)
-        return refused;
-    // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    HIP_TRY(hipSetDevice(m->d.device));
+    int rc;
+    if (!stage_run_begin(m, "mix_run", r, &rc))
+        return rc;
     MixArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_counts : nullptr;
     a.wk = m->d_wk;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
@@ -303,14 +261,10 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
     if (plan_mix(a).err != hipSuccess)
         return fail(COOLMIC_ERROR_INVAL, "mix_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S,
                     frames);
-    if (frames_per_stream)
-        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
-    if (!m->ramp || !m->ramp->any()) {               // nobody ramps: the plain kernels, as ever
-        const hipError_t e = launch_mix(a, m->stream);
-        if (e != hipSuccess)
-            return fail(COOLMIC_ERROR_GENERIC, "mix_run: %s", hipGetErrorString(e));
-        return COOLMIC_ERROR_NONE;
-    }
+    // nothing was touched so far; from here on the run happens
+    HIP_TRY(m->send_counts(frames_per_stream, S, &a.nframes));
+    if (!m->ramp || !m->ramp->any())                 // nobody ramps: the plain kernels, as ever
+        return stage_launched("mix_run", launch_mix(a, m->stream));
     // somebody ramps: the ramp kernels, then every stream's position moves on by its count, there and here
     MixRampArgs ra;
     ra.m = a;
@@ -318,9 +272,8 @@ extern "C" int cmhip_mix_run(cmhip_mix_t *m, const void *in, size_t in_stride, s
     hipError_t e = launch_mixramp(ra, m->stream);
     if (e == hipSuccess)
         e = launch_mixramp_advance(m->d_ramp, a.nframes, a.frames, S, CI, CO, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "mix_run: %s", hipGetErrorString(e));
-    for (unsigned s = 0; s < S; s++)
-        m->ramp->advance(s, frames_per_stream ? frames_per_stream[s] : (uint32_t)frames);
-    return COOLMIC_ERROR_NONE;
+    rc = stage_launched("mix_run", e);
+    for (unsigned s = 0; s < S && !rc; s++)
+        m->ramp->advance(s, stage_count(frames_per_stream, s, frames));
+    return rc;
 }

@@ -2,15 +2,13 @@
 // its validation, the launch of k_split.hip's kernels, the design of the filters and the table check.
 //
 // Device state of a band split: the filters in the kernel's form (csrc/split_plan.h), the streams' history, int16
-// [2][S][C][T-1], two slots selected by a parity the host flips per run (the resampler's mechanism), and the clip
+// [2][S][C][T-1], two slots selected by a parity the host flips per run (HistoryPair, csrc/cmhip_stage.h), and the clip
 // counters, uint32 [S][B].  The host keeps the filters as the caller gave them; cmhip_split_get_table answers from them.
 #include "cmhip_engine.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-
-#include <new>
 
 constexpr uint64_t SPLIT_MAX_SAMPLES = 1ull << 31;   // per slot and run: the kernels index a slot in 32 bits
 
@@ -19,12 +17,9 @@ struct cmhip_split : StageBase {
     std::vector<int16_t> g;            // [B-1][T] as the caller gave them
     std::vector<uint8_t> q;            // [B-1]
     uint32_t *d_table;
-    int16_t *d_hist;
-    uint32_t *d_clips;
-    unsigned parity;
+    HistoryPair hist;                  // [2][S][C * (T-1)]
+    uint32_t *d_clips;                 // [S][B]
 };
-
-static size_t split_hist_words(const cmhip_split_t *m) { return (size_t)m->d.streams * m->d.channels * (m->d.taps - 1); }
 
 static int split_geometry(const char *who, unsigned bands, unsigned taps)
 {
@@ -60,8 +55,9 @@ static double split_i0(double x)
     }
 }
 
-extern "C" int cmhip_split_design(unsigned rate, unsigned bands, const double *crossover_hz, unsigned taps, int16_t *g,
-                                  uint8_t *q, size_t cap)
+// (the body of cmhip_split_design: its vectors may throw)
+static int split_design(unsigned rate, unsigned bands, const double *crossover_hz, unsigned taps, int16_t *g, uint8_t *q,
+                        size_t cap)
 {
     const int rc = split_geometry("split_design", bands, taps);
     if (rc)
@@ -130,33 +126,27 @@ extern "C" int cmhip_split_design(unsigned rate, unsigned bands, const double *c
     return COOLMIC_ERROR_NONE;
 }
 
+extern "C" int cmhip_split_design(unsigned rate, unsigned bands, const double *crossover_hz, unsigned taps, int16_t *g,
+                                  uint8_t *q, size_t cap)
+{
+    return stage_guard("split_design", [&] { return split_design(rate, bands, crossover_hz, taps, g, q, cap); });
+}
+
 static int split_init(cmhip_split_t *m)
 {
     const cmhip_split_desc_t &d = m->d;
     const size_t S = d.streams;
-    if (m->open(d.device, d.hip_stream, S))
-        return COOLMIC_ERROR_GENERIC;
     std::vector<uint32_t> tab((split_table_words(d.bands, d.taps) + 3u) & ~3u, 0);
     split_compile(d.bands, d.taps, m->g.data(), m->q.data(), tab.data());
-    HIP_TRY(hipMalloc((void **)&m->d_table, tab.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_hist, 2 * split_hist_words(m) * sizeof(int16_t)));
-    HIP_TRY(hipMalloc((void **)&m->d_clips, S * d.bands * sizeof(uint32_t)));
+    if (m->open("split_new", d.device, d.hip_stream, S) || m->alloc("split_new", &m->d_table, tab.size()) ||
+        m->array("split_new", &m->d_clips, S * d.bands) ||
+        m->hist.init(*m, "split_new", S, (size_t)d.channels * (d.taps - 1)))
+        return COOLMIC_ERROR_GENERIC;
     HIP_TRY(hipMemcpy(m->d_table, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(m->d_hist, 0, 2 * split_hist_words(m) * sizeof(int16_t), m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_clips, 0, S * d.bands * sizeof(uint32_t), m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
-extern "C" void cmhip_split_free(cmhip_split_t *m)
-{
-    if (!m)
-        return;
-    m->close();
-    (void)hipFree(m->d_table);
-    (void)hipFree(m->d_hist);
-    (void)hipFree(m->d_clips);
-    delete m;
-}
+extern "C" void cmhip_split_free(cmhip_split_t *m) { stage_free(m); }
 
 extern "C" cmhip_split_t *cmhip_split_new_table(const cmhip_split_desc_t *d, const int16_t *g, const uint8_t *q)
 {
@@ -178,20 +168,13 @@ extern "C" cmhip_split_t *cmhip_split_new_table(const cmhip_split_desc_t *d, con
         fail(COOLMIC_ERROR_INVAL, "split_new: %u streams of %u bands: the output would pass 2^31 slots", d->streams, d->bands);
         return nullptr;
     }
-    cmhip_split_t *m = new (std::nothrow) cmhip_split();
-    if (!m) {
-        fail(COOLMIC_ERROR_NOMEM, "split_new: out of memory");
-        return nullptr;
-    }
-    m->d = *d;
-    const size_t nf = d->bands - 1;
-    m->g.assign(g, g + nf * d->taps);
-    m->q.assign(q, q + nf);
-    if (split_init(m)) {
-        cmhip_split_free(m);
-        return nullptr;
-    }
-    return m;
+    return stage_new<cmhip_split>("split_new", [&](cmhip_split_t *m) {
+        m->d = *d;
+        const size_t nf = d->bands - 1;
+        m->g.assign(g, g + nf * d->taps);
+        m->q.assign(q, q + nf);
+        return split_init(m);
+    });
 }
 
 extern "C" cmhip_split_t *cmhip_split_new(const cmhip_split_desc_t *d, unsigned rate, const double *crossover_hz)
@@ -202,11 +185,15 @@ extern "C" cmhip_split_t *cmhip_split_new(const cmhip_split_desc_t *d, unsigned 
     }
     if (split_geometry("split_new", d->bands, d->taps))
         return nullptr;
-    std::vector<int16_t> g((size_t)(d->bands - 1) * d->taps);
-    std::vector<uint8_t> q(d->bands - 1);
-    if (cmhip_split_design(rate, d->bands, crossover_hz, d->taps, g.data(), q.data(), g.size()))
-        return nullptr;
-    return cmhip_split_new_table(d, g.data(), q.data());
+    cmhip_split_t *m = nullptr;
+    (void)stage_guard("split_new", [&] {
+        std::vector<int16_t> g((size_t)(d->bands - 1) * d->taps);
+        std::vector<uint8_t> q(d->bands - 1);
+        if (!split_design(rate, d->bands, crossover_hz, d->taps, g.data(), q.data(), g.size()))
+            m = cmhip_split_new_table(d, g.data(), q.data());
+        return 0;
+    });
+    return m;
 }
 
 extern "C" unsigned cmhip_split_delay(const cmhip_split_t *m) { return m ? (m->d.taps - 1) / 2 : 0; }
@@ -232,24 +219,19 @@ extern "C" int cmhip_split_run(cmhip_split_t *m, const void *in, size_t in_strid
     const unsigned S = m->d.streams, C = m->d.channels, B = m->d.bands;
     const StageRun r = {in, out, in_stride, out_stride, frames, m->d.max_frames, frames_per_stream, S, (size_t)B * S, C,
                         frames, C, STAGE_APART};
-    const int refused = stage_run_refusal("split_run", r);
-    if (refused)
-        return refused;
-    // nothing was touched so far; from here on the run happens
-    if (frames == 0)
-        return COOLMIC_ERROR_NONE;
-    HIP_TRY(hipSetDevice(m->d.device));
+    int rc;
+    if (!stage_run_begin(m, "split_run", r, &rc))
+        return rc;
     if (plan_split(S, C, B, m->d.taps, (uint32_t)frames).err)
         return fail(COOLMIC_ERROR_INVAL, "split_run: %u streams of %zu frames: the grid would reach 2^31 workgroups", S, frames);
-    if (frames_per_stream)
-        HIP_TRY(m->counts.upload(m->d_counts, frames_per_stream, S, m->stream));
+    // nothing was touched so far; from here on the run happens
     SplitArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
     a.out = (int16_t *)out;
-    a.nframes = frames_per_stream ? m->d_counts : nullptr;
+    HIP_TRY(m->send_counts(frames_per_stream, S, &a.nframes));
     a.table = m->d_table;
-    a.hist = m->d_hist;
+    a.hist = m->hist.d;
     a.clips = m->d_clips;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
@@ -258,27 +240,23 @@ extern "C" int cmhip_split_run(cmhip_split_t *m, const void *in, size_t in_strid
     a.channels = C;
     a.bands = B;
     a.taps = m->d.taps;
-    a.parity = m->parity;
-    const hipError_t e = launch_split(a, m->stream);
-    if (e != hipSuccess)
-        return fail(COOLMIC_ERROR_GENERIC, "split_run: %s", hipGetErrorString(e));
-    m->parity ^= 1u;                         // the kernel wrote the other slot
-    return COOLMIC_ERROR_NONE;
+    a.parity = m->hist.parity();
+    rc = stage_launched("split_run", launch_split(a, m->stream));
+    if (!rc)
+        m->hist.flip();                      // the kernel wrote the other slot
+    return rc;
 }
 
 extern "C" int cmhip_split_reset(cmhip_split_t *m, long stream)
 {
-    if (!m)
-        return fail(COOLMIC_ERROR_FAULT, "split_reset: NULL argument");
-    const StreamRange sr = stream_range(stream, m->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "split_reset: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(m, "split_reset", stream, &sr);
+    if (rc)
+        return rc;
     HIP_TRY(hipSetDevice(m->d.device));
-    const size_t per = (size_t)m->d.channels * (m->d.taps - 1), B = m->d.bands;
-    const size_t lo = sr.lo, n = sr.n;
-    for (unsigned slot = 0; slot < 2; slot++)
-        HIP_TRY(hipMemsetAsync(m->d_hist + slot * split_hist_words(m) + lo * per, 0, n * per * sizeof(int16_t), m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_clips + lo * B, 0, n * B * sizeof(uint32_t), m->stream));
+    const size_t B = m->d.bands;
+    HIP_TRY(m->hist.reset(sr.lo, sr.n, m->stream));
+    HIP_TRY(hipMemsetAsync(m->d_clips + sr.lo * B, 0, sr.n * B * sizeof(uint32_t), m->stream));
     return COOLMIC_ERROR_NONE;
 }
 
@@ -286,11 +264,5 @@ extern "C" int cmhip_split_clips(cmhip_split_t *m, uint32_t *clips, int clear)
 {
     if (!m || !clips)
         return fail(COOLMIC_ERROR_FAULT, "split_clips: NULL argument");
-    HIP_TRY(hipSetDevice(m->d.device));
-    const size_t bytes = (size_t)m->d.streams * m->d.bands * sizeof(uint32_t);
-    HIP_TRY(hipMemcpyAsync(clips, m->d_clips, bytes, hipMemcpyDeviceToHost, m->stream));
-    if (clear)
-        HIP_TRY(hipMemsetAsync(m->d_clips, 0, bytes, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return COOLMIC_ERROR_NONE;
+    return stage_read(m, clips, m->d_clips, (size_t)m->d.streams * m->d.bands * sizeof(uint32_t), clear != 0);
 }

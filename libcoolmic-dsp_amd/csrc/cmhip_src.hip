@@ -4,7 +4,7 @@
 //
 // Device state of a resampler: the table in the kernel's form (SrcArgs::table), the streams' history, int16
 // [2][S][C][T-1], and their positions r = (frames so far) mod M, uint32 [2][S]; two slots each, selected by a parity
-// the host flips per run (the mechanism of the true-peak history).  The host keeps a mirror of every r: it knows each
+// the host flips per run (HistoryPair, csrc/cmhip_stage.h; the positions follow its parity).  The host keeps a mirror of every r: it knows each
 // run's counts, so a run's output counts are known before the call returns, without a device wait.
 #include "cmhip_engine.h"
 
@@ -12,7 +12,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
 #include <numeric>
 
 constexpr unsigned SRC_MAX_LM = 640, SRC_MAX_T = 192;
@@ -23,13 +22,10 @@ struct cmhip_src : StageBase {
     unsigned L, M, T;
     size_t max_out;                    // floor(max_in_frames * L / M) + 1
     int16_t *d_table;
-    int16_t *d_hist;
-    uint32_t *d_rpos;
-    unsigned parity;
+    HistoryPair hist;                  // [2][S][C * (T-1)]
+    uint32_t *d_rpos;                  // [2][S], the slots of hist
     std::vector<uint32_t> r;           // the mirror of the device's current r per stream
 };
-
-static size_t src_hist_words(const cmhip_src_t *r) { return (size_t)r->d.streams * r->d.channels * (r->T - 1); }
 
 extern "C" uint32_t cmhip_src_out_frames(unsigned L, unsigned M, uint32_t r, uint32_t frames)
 {
@@ -83,8 +79,8 @@ static double src_i0(double x)
     }
 }
 
-extern "C" int cmhip_src_design(unsigned rate_in, unsigned rate_out, unsigned *L, unsigned *M, unsigned *T, int16_t *h,
-                                size_t cap)
+// (the body of cmhip_src_design: its vectors may throw)
+static int src_design(unsigned rate_in, unsigned rate_out, unsigned *L, unsigned *M, unsigned *T, int16_t *h, size_t cap)
 {
     unsigned l, m, t;
     const int rc = src_geometry(rate_in, rate_out, &l, &m, &t);
@@ -139,11 +135,16 @@ extern "C" int cmhip_src_design(unsigned rate_in, unsigned rate_out, unsigned *L
     return COOLMIC_ERROR_NONE;
 }
 
+extern "C" int cmhip_src_design(unsigned rate_in, unsigned rate_out, unsigned *L, unsigned *M, unsigned *T, int16_t *h,
+                                size_t cap)
+{
+    return stage_guard("src_design", [&] { return src_design(rate_in, rate_out, L, M, T, h, cap); });
+}
+
 static int src_init(cmhip_src_t *r, const int16_t *h)
 {
     const cmhip_src_desc_t &d = r->d;
-    if (r->open(d.device, d.hip_stream, d.streams))
-        return COOLMIC_ERROR_GENERIC;
+    const size_t S = d.streams;
     // the table as the kernel reads it (SrcArgs::table)
     const unsigned T8 = (r->T + 7u) & ~7u, krow = T8 + 8u;
     std::vector<int16_t> tab((size_t)r->L * krow, 0);
@@ -152,27 +153,15 @@ static int src_init(cmhip_src_t *r, const int16_t *h)
             tab[(size_t)p * krow + k] = h[(size_t)p * r->T + k + 1];
             tab[(size_t)p * krow + k + 1] = h[(size_t)p * r->T + k];
         }
-    const size_t S = d.streams;
-    HIP_TRY(hipMalloc((void **)&r->d_table, tab.size() * sizeof(int16_t)));
-    HIP_TRY(hipMalloc((void **)&r->d_hist, 2 * src_hist_words(r) * sizeof(int16_t)));
-    HIP_TRY(hipMalloc((void **)&r->d_rpos, 2 * S * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(r->d_table, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(r->d_hist, 0, 2 * src_hist_words(r) * sizeof(int16_t), r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_rpos, 0, 2 * S * sizeof(uint32_t), r->stream));
     r->r.assign(S, 0);
+    if (r->open("src_new", d.device, d.hip_stream, S) || r->alloc("src_new", &r->d_table, tab.size()) ||
+        r->array("src_new", &r->d_rpos, 2 * S) || r->hist.init(*r, "src_new", S, (size_t)d.channels * (r->T - 1)))
+        return COOLMIC_ERROR_GENERIC;
+    HIP_TRY(hipMemcpy(r->d_table, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     return COOLMIC_ERROR_NONE;
 }
 
-extern "C" void cmhip_src_free(cmhip_src_t *r)
-{
-    if (!r)
-        return;
-    r->close();
-    (void)hipFree(r->d_table);
-    (void)hipFree(r->d_hist);
-    (void)hipFree(r->d_rpos);
-    delete r;
-}
+extern "C" void cmhip_src_free(cmhip_src_t *r) { stage_free(r); }
 
 extern "C" cmhip_src_t *cmhip_src_new_table(const cmhip_src_desc_t *d, unsigned L, unsigned M, unsigned T,
                                             const int16_t *h)
@@ -192,21 +181,14 @@ extern "C" cmhip_src_t *cmhip_src_new_table(const cmhip_src_desc_t *d, unsigned 
         fail(COOLMIC_ERROR_INVAL, "src_new: max_in_frames %zu: a slot of a run would pass 2^31 samples", d->max_in_frames);
         return nullptr;
     }
-    cmhip_src_t *r = new (std::nothrow) cmhip_src();
-    if (!r) {
-        fail(COOLMIC_ERROR_NOMEM, "src_new: out of memory");
-        return nullptr;
-    }
-    r->d = *d;
-    r->L = L;
-    r->M = M;
-    r->T = T;
-    r->max_out = (size_t)max_out;
-    if (src_init(r, h)) {
-        cmhip_src_free(r);
-        return nullptr;
-    }
-    return r;
+    return stage_new<cmhip_src>("src_new", [&](cmhip_src_t *r) {
+        r->d = *d;
+        r->L = L;
+        r->M = M;
+        r->T = T;
+        r->max_out = (size_t)max_out;
+        return src_init(r, h);
+    });
 }
 
 extern "C" cmhip_src_t *cmhip_src_new(const cmhip_src_desc_t *d)
@@ -218,16 +200,20 @@ extern "C" cmhip_src_t *cmhip_src_new(const cmhip_src_desc_t *d)
     unsigned L, M, T;
     if (src_geometry(d->rate_in, d->rate_out, &L, &M, &T))
         return nullptr;
-    std::vector<int16_t> h((size_t)L * T);
-    if (cmhip_src_design(d->rate_in, d->rate_out, nullptr, nullptr, nullptr, h.data(), h.size()))
-        return nullptr;
-    return cmhip_src_new_table(d, L, M, T, h.data());
+    cmhip_src_t *r = nullptr;
+    (void)stage_guard("src_new", [&] {
+        std::vector<int16_t> h((size_t)L * T);
+        if (!src_design(d->rate_in, d->rate_out, nullptr, nullptr, nullptr, h.data(), h.size()))
+            r = cmhip_src_new_table(d, L, M, T, h.data());
+        return 0;
+    });
+    return r;
 }
 
 extern "C" int cmhip_src_geometry(const cmhip_src_t *r, unsigned *L, unsigned *M, unsigned *T)
 {
     if (!r)
-        return fail(COOLMIC_ERROR_FAULT, "src_geometry: resampler is NULL");
+        return fail(COOLMIC_ERROR_FAULT, "src_geometry: NULL argument");
     if (L)
         *L = r->L;
     if (M)
@@ -251,46 +237,43 @@ extern "C" int cmhip_src_run(cmhip_src_t *r, const void *in, size_t in_stride, s
     // what the run gives its longest stream (pure arithmetic on counts the check below has yet to judge)
     uint32_t most = 0;
     for (unsigned s = 0; s < S; s++) {
-        const uint32_t f = frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
-        const uint32_t k = cmhip_src_out_frames(r->L, r->M, r->r[s], f);
+        const uint32_t k = cmhip_src_out_frames(r->L, r->M, r->r[s], stage_count(frames_per_stream, s, frames));
         if (k > most)
             most = k;
     }
     const StageRun run = {in, out, in_stride, out_stride, frames, r->d.max_in_frames, frames_per_stream, S, S, C, most, C,
                           STAGE_NOT_IN_PLACE};
-    const int refused = stage_run_refusal("src_run", run);
-    if (refused)
-        return refused;
-    // nothing was touched so far; from here on the run happens
-    HIP_TRY(hipSetDevice(r->d.device));
-    if (frames > 0) {
-        if (frames_per_stream)
-            HIP_TRY(r->counts.upload(r->d_counts, frames_per_stream, S, r->stream));
+    int rc;
+    const bool go = stage_run_begin(r, "src_run", run, &rc);
+    if (rc)
+        return rc;
+    // nothing was touched so far; from here on the run happens (one of no frames in the mirror alone)
+    if (go) {
         SrcArgs a;
         memset(&a, 0, sizeof(a));
         a.in = (const int16_t *)in;
         a.out = (int16_t *)out;
-        a.nframes = frames_per_stream ? r->d_counts : nullptr;
+        HIP_TRY(r->send_counts(frames_per_stream, S, &a.nframes));
         a.table = r->d_table;
-        a.hist = r->d_hist;
+        a.hist = r->hist.d;
         a.rpos = r->d_rpos;
         a.in_stride = in_stride;
         a.out_stride = out_stride;
         a.frames = (uint32_t)frames;
         a.streams = S;
         a.channels = C;
-        a.parity = r->parity;
+        a.parity = r->hist.parity();
         a.L = r->L;
         a.M = r->M;
         a.T = r->T;
         // (a run that gives no stream an output still moves history and r: one workgroup per stream)
-        const hipError_t e = launch_src(a, most ? most : 1u, r->stream);
-        if (e != hipSuccess)
-            return fail(COOLMIC_ERROR_GENERIC, "src_run: %s", hipGetErrorString(e));
-        r->parity ^= 1u;                     // the kernel wrote the other slots
+        rc = stage_launched("src_run", launch_src(a, most ? most : 1u, r->stream));
+        if (rc)
+            return rc;
+        r->hist.flip();                      // the kernel wrote the other slots
     }
     for (unsigned s = 0; s < S; s++) {
-        const uint32_t f = frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
+        const uint32_t f = stage_count(frames_per_stream, s, frames);
         if (out_frames)
             out_frames[s] = cmhip_src_out_frames(r->L, r->M, r->r[s], f);
         r->r[s] = (uint32_t)(((uint64_t)r->r[s] + f) % r->M);
@@ -300,19 +283,14 @@ extern "C" int cmhip_src_run(cmhip_src_t *r, const void *in, size_t in_stride, s
 
 extern "C" int cmhip_src_reset(cmhip_src_t *r, long stream)
 {
-    if (!r)
-        return fail(COOLMIC_ERROR_FAULT, "src_reset: resampler is NULL");
-    const StreamRange sr = stream_range(stream, r->d.streams);
-    if (!sr.ok)
-        return fail(COOLMIC_ERROR_INVAL, "src_reset: stream %ld out of range", stream);
+    StreamRange sr;
+    const int rc = stage_streams(r, "src_reset", stream, &sr);
+    if (rc)
+        return rc;
     HIP_TRY(hipSetDevice(r->d.device));
-    const size_t S = r->d.streams, per = (size_t)r->d.channels * (r->T - 1);
-    const size_t lo = sr.lo, n = sr.n;
-    for (unsigned slot = 0; slot < 2; slot++) {
-        HIP_TRY(hipMemsetAsync(r->d_hist + slot * src_hist_words(r) + lo * per, 0, n * per * sizeof(int16_t), r->stream));
-        HIP_TRY(hipMemsetAsync(r->d_rpos + slot * S + lo, 0, n * sizeof(uint32_t), r->stream));
-    }
-    for (size_t s = lo; s < lo + n; s++)
+    HIP_TRY(r->hist.reset(sr.lo, sr.n, r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_rpos + r->hist.slots.at(sr.lo, 1), 0, sr.n * sizeof(uint32_t), r->stream));
+    for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
         r->r[s] = 0;
     return COOLMIC_ERROR_NONE;
 }

@@ -1,7 +1,8 @@
 // stage_io.h -- what every object that runs over the slots of device arrays checks before it touches anything
-// (include/coolmic_hip.h: the resampler, the mixer, the mix bus, the limiter, and the batch's "stream -1 means every
-// stream"): the range of streams a call names, and a run's pointers, strides and counts.  Host only, plain C++17, no
-// HIP: tests/cpp/stage_io_test.cpp compiles it with g++ alone.  Nothing is dereferenced but the counts.
+// (include/coolmic_hip.h: the stage objects beside the batch, and the batch's "stream -1 means every stream"): the range
+// of streams a call names, a run's pointers, strides and counts, and which of a history's two slots a run reads.  Host
+// only, plain C++17, no HIP: tests/cpp/stage_io_test.cpp compiles it with g++ alone.  Nothing is dereferenced but the
+// counts.
 #ifndef CMHIP_STAGE_IO_H
 #define CMHIP_STAGE_IO_H
 
@@ -23,6 +24,22 @@ static inline StreamRange stream_range(long stream, unsigned streams)
         return {false, 0u, 0u};
     return {true, (uint32_t)stream, 1u};
 }
+
+// the frames of stream s in a run: its count, or `frames` where the run has no counts
+static inline uint32_t stage_count(const uint32_t *frames_per_stream, size_t s, size_t frames)
+{
+    return frames_per_stream ? frames_per_stream[s] : (uint32_t)frames;
+}
+
+// Which of the two slots of a per-stream history [2][streams][per] a run reads: slot `parity`.  The kernel writes the
+// other slot and the host flips the parity after the launch, so the next run reads what this one wrote.
+struct HistorySlots {
+    size_t   streams = 0;
+    unsigned parity = 0;
+    // the element where stream s begins in the slot the next run reads
+    size_t at(size_t s, size_t per) const { return ((size_t)parity * streams + s) * per; }
+    void flip() { parity ^= 1u; }
+};
 
 // A run: in_slots slots of in_stride int16 samples at `in`, out_slots slots of out_stride samples at `out`.  Every
 // input slot holds `frames` frames of in_channels samples, every output slot out_frames frames of out_channels.

@@ -195,10 +195,28 @@ static int test_stream_range()
     return 0;
 }
 
+// the two slots of a history [2][S][per]: a run reads slot `parity`, the flip after it makes that the slot it wrote
+static int test_history_slots()
+{
+    HistorySlots h;
+    h.streams = 5;
+    CHECK(h.parity == 0 && h.at(0, 7) == 0 && h.at(3, 7) == 21);
+    h.flip();
+    CHECK(h.parity == 1 && h.at(0, 7) == 35 && h.at(3, 7) == 56 && h.at(4, 1) == 9);   // (per 1: the resampler's positions)
+    h.flip();
+    CHECK(h.parity == 0 && h.at(4, 7) == 28);
+    // the last element of the slot a run reads lies inside [2][S][per] whatever the parity
+    for (int i = 0; i < 2; i++, h.flip())
+        CHECK(h.at(4, 7) + 7 <= 2 * 5 * 7);
+    const uint32_t counts[2] = {3, 0};
+    CHECK(stage_count(counts, 0, 9) == 3 && stage_count(counts, 1, 9) == 0 && stage_count(nullptr, 1, 9) == 9);
+    return 0;
+}
+
 int main(void)
 {
     if (test_limiter_refusals() || test_bus_refusals() || test_overlap_edges() || test_resampler_rule() || test_counts() ||
-        test_wrap_around() || test_stream_range())
+        test_wrap_around() || test_stream_range() || test_history_slots())
         return 1;
     printf("stage io ok: %lu checks\n", checks);
     return 0;
