@@ -1421,9 +1421,48 @@ int      cmhip_agc_design(const cmhip_agc_law_desc_t *law, cmhip_agc_params_t *p
  *   the calls are and does not wait for the host: the coefficients live in a host mirror, and the table goes to the
  *   device on the object's stream with the next run's counts, only when it has changed since the last run.
  *   COOLMIC_ERROR_INVAL for a section cmhip_iir_check refuses, or a stream or section out of range; a refused call
- *   changes nothing.  cmhip_iir_get answers from the mirror.
+ *   changes nothing.  cmhip_iir_get answers from the mirror.  A move that does not click: cmhip_iir_ramp, below.
  * cmhip_iir_reset (stream -1: all) zeroes the stream's histories and e, ordered with the runs as the calls are.  The
- *   counters and the coefficients stay.
+ *   counters, the coefficients and the ramps stay.
+ *
+ * Coefficient ramps (cmhip_iir_ramp): a section moves to its new coefficients over ramp_frames frames instead of
+ *   between two frames, so that a low cut turned from 40 to 80 Hz or a peak pulled down by 6 dB does not click.  Every
+ *   (stream, section) has a ramp of its own: two ends c0, c1 (five int32 each), `done` and R; R = 0: at rest on c1.
+ *   Position.  A section ramps while done < R.  Frame f (from 0) of its stream's next run uses the section
+ *     c(p(done + f + 1)) with p(n) = cmhip_mix_ramp_position(n, R), the mixer's, in units of 2^-15; frames past the
+ *     ramp use c1.  After a run of n frames done = min(done + n, R); a section whose ramp is over is at rest
+ *     (done = R = 0).  A stream given 0 frames does not advance.  R in 2..2^20 (CMHIP_IIR_RAMP_MAX).
+ *   The section at position p, 0 <= p <= 32768.  For a pair of ends (x0, x1) let N(x0, x1) = x0 (32768 - p) + x1 p,
+ *     int64, |N| < 2^45.
+ *       b0(p), b2(p), a1(p) = sgn(N) (|N| >> 15)         truncated towards zero, as the mixer truncates
+ *       a2(p)               = -((-N) >> 15)              rounded up
+ *       s(p)                = sgn(N) (|N| >> 15) of the ends s0 = b0 + b1 + b2 of c0 and s1 of c1 (|s| <= 3 * 2^28)
+ *       b1(p)               = clamp(s(p) - b0(p) - b2(p), -2^28, 2^28)
+ *   Why these roundings.  c(0) = c0 and c(32768) = c1 exactly.  |a1(p)| does not exceed the exact convex combination of
+ *     the ends and a2(p) is not below it, so every c(p) passes cmhip_iir_check whenever both ends do: the stability
+ *     triangle is convex, and rounding a1 and a2 each to nearest could not promise that on its edge.  Where both ends
+ *     have b0 + b1 + b2 = 0 -- every HIGHPASS and HIGHPASS1 of cmhip_iir_design -- s(p) = 0, b1(p) = -(b0(p) + b2(p))
+ *     and the clamp does not act: the zero stays on z = 1 exactly through a whole low-cut sweep.  The clamp acts only
+ *     in corners of the coefficient range, where the unclamped b1 can pass 2^28 by one.
+ *   The arithmetic of a frame does not change: the section runs with that frame's c(p), e and the histories carry on,
+ *     and |c| <= 2^28 still gives |acc| < 2^62.  A SECTION VALID AT EVERY FRAME DOES NOT MAKE A TIME-VARYING FILTER
+ *     BOUNDED: stability of each frozen c(p) says nothing about the filter that moves through them.  What bounds it is
+ *     the inner clamp, and `overs` counts where it acted.
+ *   cmhip_iir_ramp (stream -1: all streams) starts from the section IN FORCE, which is c(p(done)) while a ramp runs: a
+ *     retarget in the middle of a ramp is allowed and is itself click-free, and a long sweep is a chain of short ramps.
+ *     ramp_frames 0 or 1 is exactly cmhip_iir_set.  COOLMIC_ERROR_INVAL for ramp_frames above 2^20, a target that
+ *     cmhip_iir_check refuses, or a stream or section out of range; COOLMIC_ERROR_FAULT for NULL; a refused call changes
+ *     nothing.  cmhip_iir_set on a ramping section ends that ramp with a step.  cmhip_iir_get returns the section in
+ *     force.  cmhip_iir_ramp_state: done and R of a section (0, 0 at rest); either pointer may be NULL.
+ *   Ordering.  Like a set, a ramp touches the host mirror only, needs no host wait and is ordered with the runs as the
+ *     calls are.  The host sees every run's counts and advances the mirror by them, so cmhip_iir_ramp_state and
+ *     cmhip_iir_get ask no device.  While any section ramps, or the table has changed, the table travels behind the
+ *     run's counts; in a run at whose start a section ramps it holds both ends, done and R of every section.  A filter
+ *     that never ramps launches what it always did.
+ *   Cuts.  Output, `clips`, `overs` and every section's state do not depend on how a stream is cut into runs, with the
+ *     sets, ramps and resets at the same frames.
+ *   cmhip_iir_ramp_section (host only): c(p) between two sections, p above 32768 counting as 32768; an end's coefficient
+ *     outside +-2^28, which no valid section has, counts as the bound.  NULL: nothing is written.
  * cmhip_iir_state: synchronous (it waits for the object's stream).  Per stream, S entries each: clips[s] and overs[s];
  *   clear != 0 zeroes both counters after reading them.  Either pointer may be NULL.
  * cmhip_iir_check (host only): 0 for a valid section, else COOLMIC_ERROR_INVAL.
@@ -1443,6 +1482,7 @@ int      cmhip_agc_design(const cmhip_agc_law_desc_t *law, cmhip_agc_params_t *p
  * cmhip_iir_response_db (host only): the magnitude in dB at f Hz of the cascade of the n sections AS THE INTEGERS
  *   REALISE IT; -inf on a zero, NaN for NULL or a rate that is not positive. */
 #define CMHIP_IIR_ONE (1 << 26)
+#define CMHIP_IIR_RAMP_MAX (1u << 20)
 enum {
     CMHIP_IIR_BYPASS = 0, CMHIP_IIR_HIGHPASS = 1, CMHIP_IIR_LOWPASS = 2, CMHIP_IIR_LOWSHELF = 3, CMHIP_IIR_HIGHSHELF = 4,
     CMHIP_IIR_PEAK = 5, CMHIP_IIR_NOTCH = 6, CMHIP_IIR_HIGHPASS1 = 7, CMHIP_IIR_LOWPASS1 = 8
@@ -1470,6 +1510,10 @@ cmhip_iir_t *cmhip_iir_new(const cmhip_iir_desc_t *d);
 void     cmhip_iir_free(cmhip_iir_t *m);
 int      cmhip_iir_set(cmhip_iir_t *m, long stream, unsigned int section, const cmhip_iir_section_t *c);
 int      cmhip_iir_get(const cmhip_iir_t *m, unsigned int stream, unsigned int section, cmhip_iir_section_t *c);
+int      cmhip_iir_ramp(cmhip_iir_t *m, long stream, unsigned int section, const cmhip_iir_section_t *target,
+                        uint32_t ramp_frames);
+int      cmhip_iir_ramp_state(const cmhip_iir_t *m, unsigned int stream, unsigned int section, uint32_t *done,
+                              uint32_t *ramp_frames);                   /* either may be NULL */
 int      cmhip_iir_run(cmhip_iir_t *m, const void *in, size_t in_stride, size_t frames,
                        const uint32_t *frames_per_stream, void *out, size_t out_stride);
 int      cmhip_iir_reset(cmhip_iir_t *m, long stream);
@@ -1480,6 +1524,8 @@ void    *cmhip_iir_hip_stream(cmhip_iir_t *m);
 int      cmhip_iir_check(const cmhip_iir_section_t *c);
 int      cmhip_iir_design(const cmhip_iir_design_desc_t *d, cmhip_iir_section_t *c);
 double   cmhip_iir_response_db(const cmhip_iir_section_t *sections, unsigned int n, double rate, double f);
+void     cmhip_iir_ramp_section(const cmhip_iir_section_t *c0, const cmhip_iir_section_t *c1, uint32_t p,
+                                cmhip_iir_section_t *out);              /* c(p) */
 
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of

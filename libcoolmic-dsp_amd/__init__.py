@@ -417,6 +417,9 @@ SIGNATURES = {
     "cmhip_iir_free": (None, [_vp]),
     "cmhip_iir_set": (C.c_int, [_vp, C.c_long, C.c_uint, _P(IirSection)]),
     "cmhip_iir_get": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(IirSection)]),
+    "cmhip_iir_ramp": (C.c_int, [_vp, C.c_long, C.c_uint, _P(IirSection), C.c_uint32]),
+    "cmhip_iir_ramp_state": (C.c_int, [_vp, C.c_uint, C.c_uint, _P(C.c_uint32), _P(C.c_uint32)]),
+    "cmhip_iir_ramp_section": (None, [_P(IirSection), _P(IirSection), C.c_uint32, _P(IirSection)]),
     "cmhip_iir_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
     "cmhip_iir_reset": (C.c_int, [_vp, C.c_long]),
     "cmhip_iir_state": (C.c_int, [_vp, _vp, _vp, C.c_int]),
@@ -723,6 +726,10 @@ if hasattr(lib, "cmhip_test_plan_iir"):         # (not in builds older than the 
     lib.cmhip_test_iir_new_dry.argtypes = [_P(IirDesc)]
     lib.cmhip_test_iir_rows.restype = C.c_int
     lib.cmhip_test_iir_rows.argtypes = [_vp, _vp]
+if hasattr(lib, "cmhip_test_iir_ramp_at"):      # (not in builds older than the filter's ramps)
+    lib.cmhip_test_iir_ramp_at.restype = None
+    lib.cmhip_test_iir_ramp_at.argtypes = [_P(C.c_int32), _P(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32,
+                                           _P(C.c_int32), _P(C.c_uint32)]
 lib.cmhip_debug_run_count.restype = C.c_ulonglong
 lib.cmhip_debug_run_count.argtypes = []
 lib.coolmic_debug_vumeter_mode.restype = C.c_int
@@ -1155,6 +1162,24 @@ def iir_response_db(sections, rate, f):
     """cmhip_iir_response_db: the magnitude in dB at f of the cascade of the sections' integers"""
     arr = (IirSection * len(sections))(*sections)
     return lib.cmhip_iir_response_db(arr, len(sections), rate, f)
+
+
+IIR_RAMP_MAX = 1 << 20
+
+
+def iir_ramp_section(c0, c1, p):
+    """cmhip_iir_ramp_section: the section at position p (0..32768) between two IirSections -> IirSection"""
+    out = IirSection()
+    lib.cmhip_iir_ramp_section(C.byref(c0), C.byref(c1), p, C.byref(out))
+    return out
+
+
+def iir_ramp_at(c0, c1, done, R, f):
+    """Test hook: the section and the position that the ramp kernels compute for frame f of a run that a section with
+    the ends c0, c1 (five ints each), `done` and R enters -> (five ints, p)"""
+    a, b, out, p = (C.c_int32 * 5)(*c0), (C.c_int32 * 5)(*c1), (C.c_int32 * 5)(), C.c_uint32()
+    lib.cmhip_test_iir_ramp_at(a, b, done, R, f, out, C.byref(p))
+    return tuple(out), p.value
 
 
 def test_iir_without_device(streams, channels, sections, max_frames):
@@ -2062,9 +2087,25 @@ class Filter(_Stage):
         _check("iir_set", self.set_rc(stream, section, sec))
 
     def get(self, stream, section):
+        """the section in force: between its ends while it ramps"""
         s = IirSection()
         _check("iir_get", lib.cmhip_iir_get(self.h, stream, section, C.byref(s)))
         return s
+
+    def ramp_rc(self, stream, section, target, ramp_frames):
+        """cmhip_iir_ramp as it is -> error number"""
+        return lib.cmhip_iir_ramp(self.h, stream, section, C.byref(target), ramp_frames)
+
+    def ramp(self, stream, section, target, ramp_frames):
+        """the stream's section moves to `target` over its next ramp_frames frames, from the section in force (stream
+        -1: every stream; 0 or 1 frames: set)"""
+        _check("iir_ramp", self.ramp_rc(stream, section, target, ramp_frames))
+
+    def ramp_state(self, stream, section):
+        """-> (done, ramp_frames) of the section's ramp, (0, 0) at rest; from the host mirror"""
+        done, frames = C.c_uint32(), C.c_uint32()
+        _check("iir_ramp_state", lib.cmhip_iir_ramp_state(self.h, stream, section, C.byref(done), C.byref(frames)))
+        return done.value, frames.value
 
     def state(self, clear=False):
         """-> (clips uint64 [S], overs uint64 [S]); a synchronous round trip"""

@@ -4,8 +4,13 @@
 //
 // Device state of a filter: per row and section the histories and the remainder (IirState), per stream the two
 // counters, and the coefficient table.  The table lies behind the run's counts in one device array and travels with
-// them through the counts ring, but only in a run that follows a set: a set changes the mirror alone and is ordered
-// with the runs by the order of the calls.  A reset is a memset of the stream's rows on the object's stream.
+// them through the counts ring, but only in a run that follows a set or a ramp: both change the mirror alone and are
+// ordered with the runs by the order of the calls.  A reset is a memset of the stream's rows on the object's stream.
+//
+// Coefficient ramps (csrc/iir_ramp.h): the mirror holds per section both ends, done and R, and advances by every run's
+// counts, which the host knows; the device keeps nothing of a ramp.  While any section ramps the table that travels is
+// the mirror as it is, IIR_RAMP_WORDS per section, and the kernels are k_iirramp.hip's; a run at whose start nothing
+// ramps sends the five words per section, and only if they changed, and launches what it always did.
 #include "cmhip_engine.h"
 
 #include <math.h>
@@ -17,8 +22,8 @@ static_assert(CMHIP_IIR_ONE == IIR_ONE, "the coefficient unit");
 
 struct cmhip_iir : StageBase {
     cmhip_iir_desc_t d;
-    std::vector<IirSec> coef;          // [S][N] the mirror
-    bool dirty;                        // the mirror has changed since the table last went to the device
+    IirRampMirror ramp;                // [S][N] the mirror: the sections, at rest or between two ends
+    bool dirty;                        // the sections in force are not the five-word table the device last got
     IirState *d_state;                 // [S * C][N]
     unsigned long long *d_clips;       // [S]
     unsigned long long *d_overs;       // [S]
@@ -131,18 +136,21 @@ extern "C" double cmhip_iir_response_db(const cmhip_iir_section_t *sec, unsigned
 
 extern "C" void cmhip_iir_free(cmhip_iir_t *m) { stage_free(m); }
 
-static size_t iir_table_words(const cmhip_iir_desc_t &d) { return (size_t)d.streams * d.sections * IIR_SEC_WORDS; }
+static size_t iir_table_words(const cmhip_iir_desc_t &d, bool ramp)
+{
+    return (size_t)d.streams * d.sections * (ramp ? IIR_RAMP_WORDS : IIR_SEC_WORDS);
+}
 
 // device false (cmhip_test_iir_new_dry): the mirror and the checks, no device behind them
 static int iir_init(cmhip_iir_t *m, bool device)
 {
     const cmhip_iir_desc_t &d = m->d;
     const size_t S = d.streams;
-    m->coef.assign(S * d.sections, IIR_UNITY);
+    m->ramp.init(S * d.sections);
     m->dirty = true;
     if (!device)
         return COOLMIC_ERROR_NONE;
-    if (m->open("iir_new", d.device, d.hip_stream, S + iir_table_words(d)) ||
+    if (m->open("iir_new", d.device, d.hip_stream, S + iir_table_words(d, true)) ||
         m->array("iir_new", &m->d_state, S * d.channels * d.sections) || m->array("iir_new", &m->d_clips, S) ||
         m->array("iir_new", &m->d_overs, S))
         return COOLMIC_ERROR_GENERIC;
@@ -190,9 +198,65 @@ extern "C" int cmhip_iir_set(cmhip_iir_t *m, long stream, unsigned int section, 
     if (!iir_section_ok(q))
         return fail(COOLMIC_ERROR_INVAL, "iir_set: every |c| <= 2^28, |a2| < 2^26 and |a1| < 2^26 + a2 are required");
     for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++)
-        m->coef[s * m->d.sections + section] = q;
+        m->ramp.cancel(s * m->d.sections + section, q);
     m->dirty = true;
     return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_iir_ramp(cmhip_iir_t *m, long stream, unsigned int section, const cmhip_iir_section_t *target,
+                              uint32_t ramp_frames)
+{
+    if (!target)
+        return fail(COOLMIC_ERROR_FAULT, "iir_ramp: NULL argument");
+    StreamRange sr;
+    const int rc = stage_streams(m, "iir_ramp", stream, &sr);
+    if (rc)
+        return rc;
+    if (section >= m->d.sections)
+        return fail(COOLMIC_ERROR_INVAL, "iir_ramp: section %u of %u", section, m->d.sections);
+    if (ramp_frames > IIR_RAMP_MAX)
+        return fail(COOLMIC_ERROR_INVAL, "iir_ramp: %u frames, at most %u", ramp_frames, IIR_RAMP_MAX);
+    const IirSec q = iir_from(target);
+    if (!iir_section_ok(q))
+        return fail(COOLMIC_ERROR_INVAL, "iir_ramp: every |c| <= 2^28, |a2| < 2^26 and |a1| < 2^26 + a2 are required");
+    for (size_t s = sr.lo; s < (size_t)sr.lo + sr.n; s++) {
+        const size_t i = s * m->d.sections + section;
+        if (ramp_frames < 2)
+            m->ramp.cancel(i, q);                    // a step: cmhip_iir_set
+        else
+            m->ramp.start(i, q, ramp_frames);
+    }
+    m->dirty = true;
+    return COOLMIC_ERROR_NONE;
+}
+
+extern "C" int cmhip_iir_ramp_state(const cmhip_iir_t *m, unsigned int stream, unsigned int section, uint32_t *done,
+                                    uint32_t *ramp_frames)
+{
+    if (!m)
+        return fail(COOLMIC_ERROR_FAULT, "iir_ramp_state: NULL argument");
+    if (stream >= m->d.streams || section >= m->d.sections)
+        return fail(COOLMIC_ERROR_INVAL, "iir_ramp_state: stream %u, section %u out of range", stream, section);
+    const IirRampEntry &e = m->ramp.e[(size_t)stream * m->d.sections + section];
+    if (done)
+        *done = e.done;
+    if (ramp_frames)
+        *ramp_frames = e.R;
+    return COOLMIC_ERROR_NONE;
+}
+
+// c(p) between two sections; an end's coefficient outside +-2^28, which no valid section has, counts as the bound
+extern "C" void cmhip_iir_ramp_section(const cmhip_iir_section_t *c0, const cmhip_iir_section_t *c1, uint32_t p,
+                                       cmhip_iir_section_t *out)
+{
+    if (!c0 || !c1 || !out)
+        return;
+    IirSec e[2] = {iir_from(c0), iir_from(c1)};
+    for (IirSec &c : e)
+        for (int32_t *v : {&c.b0, &c.b1, &c.b2, &c.a1, &c.a2})
+            *v = *v < -IIR_COEF_MAX ? -IIR_COEF_MAX : *v > IIR_COEF_MAX ? IIR_COEF_MAX : *v;
+    const IirSec c = iir_ramp_section(e[0], e[1], p);
+    memcpy(out, &c, sizeof(c));
 }
 
 extern "C" int cmhip_iir_get(const cmhip_iir_t *m, unsigned int stream, unsigned int section, cmhip_iir_section_t *c)
@@ -201,7 +265,8 @@ extern "C" int cmhip_iir_get(const cmhip_iir_t *m, unsigned int stream, unsigned
         return fail(COOLMIC_ERROR_FAULT, "iir_get: NULL argument");
     if (stream >= m->d.streams || section >= m->d.sections)
         return fail(COOLMIC_ERROR_INVAL, "iir_get: stream %u, section %u out of range", stream, section);
-    memcpy(c, &m->coef[(size_t)stream * m->d.sections + section], sizeof(*c));
+    const IirSec now = m->ramp.now((size_t)stream * m->d.sections + section);
+    memcpy(c, &now, sizeof(*c));
     return COOLMIC_ERROR_NONE;
 }
 
@@ -217,16 +282,27 @@ extern "C" int cmhip_iir_run(cmhip_iir_t *m, const void *in, size_t in_stride, s
     if (!stage_run_begin(m, "iir_run", r, &rc))
         return rc;
     // nothing was touched so far; from here on the run happens
-    // the run's counts and, behind a set, the coefficient table behind them
+    // the run's counts and, behind a set or while a section ramps, the coefficient table behind them
     uint32_t *block;
     HIP_TRY(m->counts.take(&block));
     for (unsigned s = 0; s < S; s++)
         block[s] = stage_count(frames_per_stream, s, frames);
-    const size_t words = m->dirty ? iir_table_words(m->d) : 0;
-    if (words)
-        memcpy(block + S, m->coef.data(), words * sizeof(uint32_t));
+    const bool ramp = m->ramp.any();
+    const size_t words = ramp || m->dirty ? iir_table_words(m->d, ramp) : 0;
+    if (ramp) {
+        memcpy(block + S, m->ramp.e.data(), words * sizeof(uint32_t));
+    } else if (words) {
+        IirSec *table = (IirSec *)(block + S);
+        for (size_t i = 0; i < m->ramp.e.size(); i++)
+            table[i] = m->ramp.e[i].c1;
+    }
     HIP_TRY(m->counts.send(m->d_counts, S + words, m->stream));
-    m->dirty = false;
+    // the mirror behind this run: every section by its stream's count; what the device holds is a ramp table then
+    m->dirty = ramp;
+    if (ramp)
+        for (unsigned s = 0; s < S; s++)
+            for (unsigned k = 0; k < m->d.sections; k++)
+                m->ramp.advance((size_t)s * m->d.sections + k, block[s]);
     IirArgs a;
     memset(&a, 0, sizeof(a));
     a.in = (const int16_t *)in;
@@ -241,7 +317,7 @@ extern "C" int cmhip_iir_run(cmhip_iir_t *m, const void *in, size_t in_stride, s
     a.streams = S;
     a.channels = C;
     a.sections = m->d.sections;
-    return stage_launched("iir_run", launch_iir(a, (uint32_t)frames, m->stream));
+    return stage_launched("iir_run", launch_iir(a, (uint32_t)frames, ramp, m->stream));
 }
 
 extern "C" int cmhip_iir_reset(cmhip_iir_t *m, long stream)

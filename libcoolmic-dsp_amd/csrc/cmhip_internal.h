@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip, k_spec.hip, k_watch.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -13,6 +13,7 @@
 #include "delay_plan.h"
 #include "agc_plan.h"
 #include "iir_plan.h"
+#include "iir_ramp.h"
 #include "spec_plan.h"
 #include "watch_plan.h"
 
@@ -450,7 +451,7 @@ struct IirArgs {
     const int16_t *in;             // int16 [S][in_stride]
     int16_t       *out;            // int16 [S][out_stride]
     const uint32_t *counts;        // [S] the run's frames per stream
-    const int32_t *coef;           // [S][N][5] b0, b1, b2, a1, a2 in units of 2^-26
+    const int32_t *coef;           // [S][N][5] b0, b1, b2, a1, a2 in units of 2^-26; in a ramp run [S][N][12], IirRampEntry
     IirState      *state;          // [S * C][N] the rows' sections between two runs
     unsigned long long *clips;     // [S] outputs the last clamp changed
     unsigned long long *overs;     // [S] section results the inner clamp changed
@@ -631,8 +632,9 @@ hipError_t launch_delay(const DelayArgs &a, uint32_t max_delay, uint32_t max_fra
 // the run's largest count, max_frames the object's.  ev: nullptr, or four events recorded in front of, between and behind
 // the three launches (tools/bench_agc.py).
 hipError_t launch_agc(const AgcArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
-// Filter (k_iir.hip): one launch, a workgroup per iir_plan's spw streams.  frames: the run's largest count.
-hipError_t launch_iir(const IirArgs &a, uint32_t frames, hipStream_t st);
+// Filter (k_iir.hip): one launch, a workgroup per iir_plan's spw streams.  frames: the run's largest count.  ramp: some
+// section ramps at the run's start, a.coef is the ramp table (csrc/iir_ramp.h) and the kernels are k_iirramp.hip's.
+hipError_t launch_iir(const IirArgs &a, uint32_t frames, bool ramp, hipStream_t st);
 hipError_t launch_generate(const GenArgs &a, int mode, hipStream_t st);
 hipError_t launch_node_partial(const VuState *vu, uint32_t streams, uint32_t channels,
                                uint32_t parity, uint64_t first_global, uint64_t global_step,

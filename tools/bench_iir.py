@@ -11,7 +11,15 @@ is expected to be bound by the latency of its dependent chain, frames x (B + NP 
 Each line reports the time per step of the recurrence in nanoseconds beside the ratio to the copy.  Also: registers,
 LDS, scratch and waves per SIMD of the nine kernels from build/k_iir.usage.txt (`make asm`) and the launcher's plan.
 
+--ramp: coefficient ramps (cmhip_iir_ramp, csrc/k_iirramp.hip).  In the same process, on the same arrays and bracketed
+the same way, every case is timed three times: the plain run, a run in which every section of every stream is in the
+middle of a ramp, and a run in which one stream in 64 is (so every workgroup of the ramp kernels holds mostly sections
+at rest).  The ramps are started anew in front of every run, outside the bracket, between the 40 Hz and a 160 Hz
+high-pass and over 2^20 frames, so that no run sees one end.  The lines are APPENDED to FILE, with the ramp kernels'
+resources from build/k_iirramp.usage.txt behind them.
+
     python tools/bench_iir.py [--steps N] [--shapes a,b] [--sections 1,2] [--out FILE]   one JSON line per case, also in FILE
+    python tools/bench_iir.py --ramp [...]                               the three timings per case, appended to FILE
     python tools/bench_iir.py --usage                                    the kernels' resources alone (no GPU needed)
 """
 import argparse
@@ -28,13 +36,13 @@ BUILD = os.path.join(ROOT, "libcoolmic-dsp_amd", "build")
 SHAPES = {"s2": (4096, 2, 65536), "m1": (8192, 1, 65536), "c6": (1365, 6, 65536)}
 
 
-def usage():
-    path = os.path.join(BUILD, "k_iir.usage.txt")
+def usage(stem="k_iir"):
+    path = os.path.join(BUILD, stem + ".usage.txt")
     if not os.path.exists(path):
         return None
     out = {}
     for m in re.finditer(r"Function Name: (\S+)(.*?)LDS Size \[bytes/block\]: (\d+)", open(path).read(), flags=re.S):
-        stem = re.search(r"k_iir_[a-z]+", m.group(1)).group(0)
+        stem = re.search(r"k_iirr?_[a-z]+", m.group(1)).group(0)
         width = re.search(r"ILi(\d)ELi(\d)E", m.group(1))
         name = "%s<%s, %s>" % (stem, width.group(1), width.group(2)) if width else stem
         f = dict(re.findall(r"remark:\s+([\w \[\]/]+): (\d+)", m.group(2)))
@@ -58,9 +66,10 @@ def main():
     ap.add_argument("--sections", default="1,2,4,8")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "iir_bench.txt"))
     ap.add_argument("--usage", action="store_true")
+    ap.add_argument("--ramp", action="store_true")
     a = ap.parse_args()
     if a.usage:
-        print(json.dumps({"k_iir": usage()}))
+        print(json.dumps({"k_iir": usage(), "k_iirramp": usage("k_iirramp")}))
         return
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
@@ -68,6 +77,7 @@ def main():
     hip = None
     lines = []
     cut = cm.iir_design(cm.IIR_HIGHPASS, 48000.0, 40.0)
+    cut160 = cm.iir_design(cm.IIR_HIGHPASS, 48000.0, 160.0)
     for name in a.shapes.split(","):
         S, Cn, F = SHAPES[name]
         src = cm.Batch(S, Cn, F, flags=cm.VU, rate=48000)
@@ -95,13 +105,17 @@ def main():
                 m.set(-1, k, cut)
             st = C.c_void_p(m.hip_stream())
 
-            def timed(fn):
+            def timed(fn, before=None):
                 t0 = time.perf_counter()
                 while time.perf_counter() - t0 < 0.15:         # the step's own launches bring the clocks up
+                    if before:
+                        before()
                     fn()
                     m.sync()
                 ts = []
                 for _ in range(a.steps):
+                    if before:
+                        before()                               # (host only, outside the bracket)
                     assert hip.hipEventRecord(ev[0], st) == 0
                     fn()
                     assert hip.hipEventRecord(ev[1], st) == 0
@@ -117,8 +131,28 @@ def main():
             def run():
                 m.run(src.dev_in, src.stride, F, dst, out_stride)
 
+            turn = [0]
+
+            def ramp_every(stride):
+                def before():                                  # every section of every stride-th stream, mid-ramp
+                    turn[0] += 1
+                    to = cut160 if turn[0] % 2 else cut
+                    for s in ([-1] if stride == 1 else range(0, S, stride)):
+                        for k in range(N):
+                            m.ramp(s, k, to, cm.IIR_RAMP_MAX)
+                return before
+
             copies, runs = timed(copy), timed(run)
             med, medc = statistics.median(runs), statistics.median(copies)
+            ramped = {}
+            if a.ramp:
+                for key, stride in (("all", 1), ("one_in_64", 64)):
+                    ts = timed(run, ramp_every(stride))
+                    assert m.ramp_state(0, 0)[1] == cm.IIR_RAMP_MAX
+                    ramped[key] = {"run_ms_median": round(statistics.median(ts), 4), "run_ms_min": round(min(ts), 4),
+                                   "run_ms_max": round(max(ts), 4), "ratio_to_plain": round(statistics.median(ts) / med, 3)}
+                    for k in range(N):
+                        m.set(-1, k, cut)
             clips, overs = m.state()
             p = cm.plan_iir(S, Cn, N, F)
             steps = p.tiles * (p.tile + p.np - 1)
@@ -129,17 +163,20 @@ def main():
                     "waves": p.grid, "clips": int(clips.sum()), "overs": int(overs.sum()),
                     "plan": {"fast": p.fast, "np": p.np, "streams_per_workgroup": p.spw, "grid": p.grid, "block": p.block,
                              "tile_frames": p.tile, "tiles": p.tiles, "lds_bytes": p.lds_bytes}}
+            if a.ramp:
+                line["ramp"] = ramped
             print(json.dumps(line), flush=True)
             lines.append(line)
             m.close()
         cm.lib.cmhip_device_free(0, dst)
         src.close()
-    lines.append({"k_iir": usage()})
+    lines.append({"k_iirramp": usage("k_iirramp")} if a.ramp else {"k_iir": usage()})
     print(json.dumps(lines[-1]))
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("# python tools/bench_iir.py --steps %d --shapes %s --sections %s\n" % (a.steps, a.shapes, a.sections))
+        with open(a.out, "a" if a.ramp else "w") as f:
+            f.write("# python tools/bench_iir.py%s --steps %d --shapes %s --sections %s\n"
+                    % (" --ramp" if a.ramp else "", a.steps, a.shapes, a.sections))
             for ln in lines:
                 f.write(json.dumps(ln) + "\n")
 
