@@ -1381,6 +1381,110 @@ void    *cmhip_agc_hip_stream(cmhip_agc_t *m);
 int      cmhip_agc_check(unsigned int window_log2, const cmhip_agc_params_t *p);
 int      cmhip_agc_design(const cmhip_agc_law_desc_t *law, cmhip_agc_params_t *p);
 
+/* ---- automixer: gain-sharing groups, an object of its own beside the batch --------------- */
+/* An automixer shares one unit of gain among the open microphones of a group, Dugan style, in exact integers: each of S
+ * streams of C interleaved int16 channels (C in 1..16) gets the share of its group's gain that its level earns.  One
+ * talker passes at unity, two equal talkers at -3 dB each, four at -6 dB; idle microphones sink towards a floor.  The
+ * sum keeps the noise and feedback margin of one open microphone however many are plugged in.  It belongs in front of
+ * the bus.  It has cmhip_agc_t's shapes: slots, strides, alignment and refusals are cmhip_agc_run's.  The gains move
+ * once per window of W frames and are interpolated in between; the stage adds no delay.
+ *
+ * Geometry, per object: window_log2 = w in 6..14, W = 2^w.
+ * Groups.  Each stream has a group id in 0..S-1, or -1 for none; every stream is in no group at creation.  A stream in
+ *   no group is copied bit for bit; its gain nodes are 4096 throughout.  A group has ONE clock: all its members have the
+ *   same position and must get the same count in every run.
+ * Parameters, per stream, settable between runs (cmhip_automix_set, stream -1: all streams):
+ *     weight u              0..4096     units of 2^-12 on power: the stream's priority, 4096 is unity
+ *     floor                 0..4096     the lowest gain, units of 2^-12 (unity 4096, the leveller's gain unit)
+ *     attack, release       0..8        the smoothing shifts of a rising and of a falling power
+ *     initial               0..4096     the gain of a stream's first frames (below)
+ *   Defaults: weight 4096, floor 0, attack 0, release 0, initial 4096.
+ *
+ * Arithmetic.  Frames are counted since creation or the last reset: n, 64 bits.  Window k = n >> w, j = n & (W - 1),
+ *   as in the leveller.  Per complete window k of stream s:
+ *     E = max over the channels c of the sum over the window's frames of x[n][c]^2; m = E >> w, so m <= 2^30: the
+ *       leveller's E and shift, to the letter.
+ *     v = (m * u) >> 12;  V = v << 8                               V <= 2^38
+ *     P[k] = P[k-1] + ((V - P[k-1]) >> sh)                          signed 64-bit, arithmetic shift (floor);
+ *       sh = attack when V > P[k-1], else release; P[-1] = 0.  0 <= P <= 2^38: a step never passes V.
+ *     Sum[k] = the sum of P_j[k] over the members j of the stream's group: exact in uint64, independent of order.
+ *     D[k] = D[k-1] when Sum[k] = 0, else max(floor, isqrt((P[k] << 24) / Sum[k]))
+ *       unsigned 64-bit division, integer; the quotient is at most 2^24, the exact integer root at most 4096.
+ *       D[-1] = initial.
+ *     The parameters used are those in force in the run in which the window completes.
+ *   Gain nodes: A[0] = A[1] = initial -- the `initial` in force in the run that processes frame 0.  For k >= 1,
+ *     A[k+1] = D[k-1], taken when frame n = k W is processed.  The gain of window k depends only on windows that ended
+ *     before it began: the stage is causal without a delay.
+ *   Per frame and sample, the leveller's lines: g = A[k] + (((A[k+1] - A[k]) * j) >> w), arithmetic shift;
+ *     y = clamp((x * g + 2048) >> 12, -32768, 32767).
+ *   Properties.  g <= 4096, so the clamp never acts and |y| <= |x|.  With floors 0 the squares of a group's D[k] sum to
+ *     at most 2^24 -- the group never has more than one microphone's gain.  A group of one member with a non-zero level
+ *     is a copy from its third window on.  n members with equal input and weights each get isqrt(2^24 / n): 4096,
+ *     2896, 2364, 2048 for n = 1..4.  Against members at digital silence one talker gets 4096 and the silent members
+ *     their floor.  A stream given 0 frames in a run keeps everything.  Cuts: the concatenated output and the state do
+ *     not depend on how the streams are cut into runs, with the sets at the same frames -- every sum is of integers.
+ * cmhip_automix_new: NULL for C outside 1..16, S = 0, window_log2 outside 6..14, max_frames = 0,
+ *   max_frames * C >= 2^31, or a failed allocation.
+ * cmhip_automix_set_group(m, stream, group): the stream joins `group` (0..S-1) or leaves its group (-1).  Every member
+ *   of the group left and of the group joined is reset, the stream included: that keeps a group on one clock.
+ *   COOLMIC_ERROR_INVAL for a stream outside 0..S-1 or a group outside -1..S-1.  cmhip_automix_get_group answers from
+ *   the mirror.
+ * cmhip_automix_reset(m, stream): the stream's whole group is reset; a stream in no group alone; stream -1: all.  A reset
+ *   stream's next frame is frame 0 again: the gain is `initial`, and P, D, the sums of an open window and the pending
+ *   node are forgotten.  Parameters and groups stay.
+ * cmhip_automix_run has cmhip_agc_run's signature and contract.  In addition: frames_per_stream that gives two members
+ *   of one group different counts is COOLMIC_ERROR_INVAL, nothing is launched and nothing changes; the message names both
+ *   streams and both counts.  Equal counts of 0 are fine.
+ * cmhip_automix_set, _set_group and _reset touch the host mirror only: they need no host wait and no device memory, and
+ *   are ordered with the runs as the calls are.  COOLMIC_ERROR_INVAL for parameters or a stream out of range; a refused
+ *   call changes nothing.  cmhip_automix_get answers from the mirror.
+ * cmhip_automix_state: synchronous (it waits for the object's stream, like cmhip_agc_state).  Per stream, S entries each:
+ *   gain[s] = A[k+1] of the window the stream's last frame lies in (`initial` before its first frame), power[s] = P of
+ *   its last complete window (0 before the first), share[s] = D of its last complete window (`initial` before the
+ *   first): the node its next window edge brings in.  A stream in no group: 4096, 0, 4096.  Any pointer may be NULL.
+ * cmhip_automix_check (host only): 0 for a valid window_log2 and parameter set (params may be NULL: the window alone),
+ *   else COOLMIC_ERROR_INVAL.
+ * cmhip_automix_design (host only): parameters from a law: weight = rint(4096 * 10^(weight_db / 10)) (weight_db <= 0);
+ *   floor and initial = rint(4096 * 10^(dB / 20)), clamped to 0..4096; attack and release =
+ *   rint(log2(ms * rate / 1000 / W)) clamped to 0..8 (0 for ms <= 0).  COOLMIC_ERROR_INVAL for a non-finite input, a
+ *   rate that is not positive, a window_log2 that is no integer in 6..14 or weight_db above 0; COOLMIC_ERROR_FAULT for
+ *   NULL. */
+typedef struct cmhip_automix cmhip_automix_t;
+typedef struct cmhip_automix_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int window_log2;     /* w in 6..14: the gains move once per 2^w frames */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_automix_desc_t;
+typedef struct cmhip_automix_params {
+    uint16_t weight, floor, attack, release, initial;
+} cmhip_automix_params_t;
+typedef struct cmhip_automix_law_desc {
+    double rate;                  /* frames per second */
+    double window_log2;           /* the object's w */
+    double weight_db;             /* <= 0, dB on power */
+    double floor_db, initial_db;  /* dB re unity */
+    double attack_ms, release_ms;
+} cmhip_automix_law_desc_t;
+cmhip_automix_t *cmhip_automix_new(const cmhip_automix_desc_t *d);
+void     cmhip_automix_free(cmhip_automix_t *m);
+int      cmhip_automix_set(cmhip_automix_t *m, long stream, const cmhip_automix_params_t *p);
+int      cmhip_automix_get(const cmhip_automix_t *m, unsigned int stream, cmhip_automix_params_t *p);
+int      cmhip_automix_set_group(cmhip_automix_t *m, long stream, long group);
+int      cmhip_automix_get_group(const cmhip_automix_t *m, unsigned int stream, long *group);
+int      cmhip_automix_run(cmhip_automix_t *m, const void *in, size_t in_stride, size_t frames,
+                           const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_automix_reset(cmhip_automix_t *m, long stream);
+int      cmhip_automix_state(cmhip_automix_t *m, uint32_t *gain /* [S] */, uint64_t *power /* [S] */,
+                             uint32_t *share /* [S] */);
+int      cmhip_automix_sync(cmhip_automix_t *m);
+void    *cmhip_automix_hip_stream(cmhip_automix_t *m);
+/* host only, no device needed */
+int      cmhip_automix_check(unsigned int window_log2, const cmhip_automix_params_t *p);
+int      cmhip_automix_design(const cmhip_automix_law_desc_t *law, cmhip_automix_params_t *p);
+
 /* ---- filter: a biquad cascade in exact integers, an object of its own beside the batch -- */
 /* A filter runs each of S streams of C interleaved int16 channels (C in 1..16) through a cascade of N second-order
  * sections (N in 1..8), in exact integers: a low cut per microphone in front of a leveller, a gate or a bus, a

@@ -216,6 +216,28 @@ class AgcLawDesc(C.Structure):
                                           "initial_gain_db", "rise_db_per_s", "fall_db_per_s")]
 
 
+class AutomixDesc(C.Structure):
+    """cmhip_automix_desc_t (include/coolmic_hip.h)"""
+    _fields_ = AgcDesc._fields_
+
+
+AUTOMIX_PARAM_NAMES = ("weight", "floor", "attack", "release", "initial")
+
+
+class AutomixParams(C.Structure):
+    """cmhip_automix_params_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_uint16) for n in AUTOMIX_PARAM_NAMES]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n in AUTOMIX_PARAM_NAMES}
+
+
+class AutomixLawDesc(C.Structure):
+    """cmhip_automix_law_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("rate", "window_log2", "weight_db", "floor_db", "initial_db", "attack_ms",
+                                          "release_ms")]
+
+
 class IirDesc(C.Structure):
     """cmhip_iir_desc_t (include/coolmic_hip.h)"""
     _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("sections", C.c_uint),
@@ -413,6 +435,19 @@ SIGNATURES = {
     "cmhip_agc_hip_stream": (_vp, [_vp]),
     "cmhip_agc_check": (C.c_int, [C.c_uint, _P(AgcParams)]),
     "cmhip_agc_design": (C.c_int, [_P(AgcLawDesc), _P(AgcParams)]),
+    "cmhip_automix_new": (_vp, [_P(AutomixDesc)]),
+    "cmhip_automix_free": (None, [_vp]),
+    "cmhip_automix_set": (C.c_int, [_vp, C.c_long, _P(AutomixParams)]),
+    "cmhip_automix_get": (C.c_int, [_vp, C.c_uint, _P(AutomixParams)]),
+    "cmhip_automix_set_group": (C.c_int, [_vp, C.c_long, C.c_long]),
+    "cmhip_automix_get_group": (C.c_int, [_vp, C.c_uint, _P(C.c_long)]),
+    "cmhip_automix_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_automix_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_automix_state": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "cmhip_automix_sync": (C.c_int, [_vp]),
+    "cmhip_automix_hip_stream": (_vp, [_vp]),
+    "cmhip_automix_check": (C.c_int, [C.c_uint, _P(AutomixParams)]),
+    "cmhip_automix_design": (C.c_int, [_P(AutomixLawDesc), _P(AutomixParams)]),
     "cmhip_iir_new": (_vp, [_P(IirDesc)]),
     "cmhip_iir_free": (None, [_vp]),
     "cmhip_iir_set": (C.c_int, [_vp, C.c_long, C.c_uint, _P(IirSection)]),
@@ -1029,6 +1064,17 @@ def test_delay_without_device(streams, channels, max_delay, max_frames):
     return Delay(streams, channels, max_delay, max_frames, _new=lib.cmhip_test_delay_new_dry)
 
 
+if hasattr(lib, "cmhip_test_automix_new_dry"):  # (not in builds older than the automixer)
+    lib.cmhip_test_automix_new_dry.restype = _vp
+    lib.cmhip_test_automix_new_dry.argtypes = [_P(AutomixDesc)]
+    lib.cmhip_test_automix_power.restype = C.c_uint64
+    lib.cmhip_test_automix_power.argtypes = [C.c_uint64, C.c_uint32, _P(AutomixParams)]
+    lib.cmhip_test_automix_share.restype = C.c_uint32
+    lib.cmhip_test_automix_share.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.cmhip_test_automix_run_events.restype = C.c_int
+    lib.cmhip_test_automix_run_events.argtypes = [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _P(C.c_void_p)]
+
+
 class AgcPlan(C.Structure):
     """cmhip::AgcPlan (csrc/agc_plan.h): what the leveller's launcher launches for a run"""
     _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_log2", "nw",
@@ -1096,6 +1142,42 @@ def agc_design(rate, window_log2, target_db, gate_db, max_gain_db, min_gain_db, 
     p = AgcParams()
     _check("agc_design", lib.cmhip_agc_design(C.byref(law), C.byref(p)))
     return p
+
+
+def automix_params(**kw):
+    """an AutomixParams: the creation defaults with `kw` over them"""
+    f = dict(weight=4096, floor=0, attack=0, release=0, initial=4096)
+    f.update(kw)
+    return AutomixParams(**f)
+
+
+def automix_power(P, m, params):
+    """Test hook (cmhip_test_automix_power): the header's P[k] from P[k-1] and the window's m, as code"""
+    return lib.cmhip_test_automix_power(P, m, C.byref(params))
+
+
+def automix_share(P, total, floor, D_before):
+    """Test hook (cmhip_test_automix_share): the header's D[k] from P[k], the group's sum, the floor and D[k-1]"""
+    return lib.cmhip_test_automix_share(P, total, floor, D_before)
+
+
+def automix_check(window_log2, params=None):
+    """cmhip_automix_check -> error number"""
+    return lib.cmhip_automix_check(window_log2, C.byref(params) if params is not None else None)
+
+
+def automix_design(rate, window_log2, weight_db=0.0, floor_db=-100.0, initial_db=0.0, attack_ms=0.0, release_ms=0.0):
+    """cmhip_automix_design -> AutomixParams"""
+    law = AutomixLawDesc(rate, window_log2, weight_db, floor_db, initial_db, attack_ms, release_ms)
+    p = AutomixParams()
+    _check("automix_design", lib.cmhip_automix_design(C.byref(law), C.byref(p)))
+    return p
+
+
+def test_automix_without_device(streams, channels, window_log2, max_frames):
+    """Test hook (cmhip_test_automix_new_dry): an Automixer with the host mirror and every check but no device behind
+    it, for the refusals and the mirror's answers on a machine without a GPU"""
+    return Automixer(streams, channels, window_log2, max_frames, _new=lib.cmhip_test_automix_new_dry)
 
 
 def test_agc_without_device(streams, channels, window_log2, max_frames):
@@ -1861,7 +1943,7 @@ class Batch:
 
 class _Stage:
     """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay,
-    Leveller, Filter): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
+    Leveller, Filter, Automixer): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
     object's C functions: cmhip_<stem>_free, _sync, _hip_stream, _run, _reset.  The Mixer and the Bus have no state to
     reset and the library no cmhip_mix_reset or cmhip_bus_reset: their reset() raises AttributeError, as the lookup of
     any symbol the library lacks does."""
@@ -2063,6 +2145,57 @@ class Leveller(_Stage):
         _check("agc_state", lib.cmhip_agc_state(self.h, g.ctypes.data, lv.ctypes.data, c.ctypes.data,
                                                 1 if clear_clips else 0))
         return g, lv, c
+
+
+class Automixer(_Stage):
+    """cmhip_automix_t: gain sharing among the streams of a group (Dugan style) beside a batch: every window of
+    2^window_log2 frames each member gets the share of one unit of gain that its level earns.  Every stream starts in no
+    group (a copy).  `params` (an AutomixParams): set for every stream at creation."""
+
+    _stem = "automix"
+
+    def __init__(self, streams, channels, window_log2, max_frames, params=None, device=0, hip_stream=None, _new=None):
+        d = AutomixDesc(device, streams, channels, window_log2, max_frames, hip_stream)
+        self.h = (_new or lib.cmhip_automix_new)(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_automix_new", ERROR_INVAL)
+        self.streams, self.channels, self.window_log2, self.max_frames = streams, channels, window_log2, max_frames
+        if params is not None:
+            self.set(-1, params)
+
+    def set_rc(self, stream, params):
+        """cmhip_automix_set as it is -> error number"""
+        return lib.cmhip_automix_set(self.h, stream, C.byref(params))
+
+    def set(self, stream, params):
+        """the stream's parameters from the next run on (stream -1: every stream)"""
+        _check("automix_set", self.set_rc(stream, params))
+
+    def get(self, stream):
+        p = AutomixParams()
+        _check("automix_get", lib.cmhip_automix_get(self.h, stream, C.byref(p)))
+        return p
+
+    def set_group_rc(self, stream, group):
+        """cmhip_automix_set_group as it is -> error number"""
+        return lib.cmhip_automix_set_group(self.h, stream, group)
+
+    def set_group(self, stream, group):
+        """the stream joins `group` (-1: leaves its group); the group left and the group joined start afresh"""
+        _check("automix_set_group", self.set_group_rc(stream, group))
+
+    def get_group(self, stream):
+        g = C.c_long()
+        _check("automix_get_group", lib.cmhip_automix_get_group(self.h, stream, C.byref(g)))
+        return g.value
+
+    def state(self):
+        """-> (gain uint32 [S], power uint64 [S], share uint32 [S]); a synchronous round trip"""
+        g = np.zeros(self.streams, dtype=np.uint32)
+        pw = np.zeros(self.streams, dtype=np.uint64)
+        sh = np.zeros(self.streams, dtype=np.uint32)
+        _check("automix_state", lib.cmhip_automix_state(self.h, g.ctypes.data, pw.ctypes.data, sh.ctypes.data))
+        return g, pw, sh
 
 
 class Filter(_Stage):

@@ -19,6 +19,7 @@
 //   cmhip_split.hip    the band split: an FIR crossover
 //   cmhip_delay.hip    the delay line
 //   cmhip_agc.hip      the leveller: slow automatic gain control
+//   cmhip_automix.hip  the automixer: gain-sharing groups
 //   cmhip_iir.hip      the filter: a biquad cascade in exact integers
 #pragma once
 

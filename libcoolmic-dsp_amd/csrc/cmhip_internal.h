@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -12,6 +12,7 @@
 #include "split_plan.h"
 #include "delay_plan.h"
 #include "agc_plan.h"
+#include "automix_plan.h"
 #include "iir_plan.h"
 #include "iir_ramp.h"
 #include "spec_plan.h"
@@ -445,6 +446,26 @@ struct AgcArgs {
     uint32_t       tile_log2;      // frames per tile, as a power of two
 };
 
+// Automixer (k_automix.hip; the arithmetic: include/coolmic_hip.h, the record and the mirror: csrc/automix_plan.h).  What
+// a stream carries from run to run: k_automix_level writes psum and power, k_automix_share the rest
+struct AutomixState {
+    unsigned long long psum[16];   // the open window's sums of squares so far, per channel
+    unsigned long long power;      // P of the last complete window
+    uint32_t a_lo, a_hi;           // the gain nodes of the window the stream's last frame lies in: A[k], A[k+1]
+    uint32_t pending;              // D of the last complete window: the node the next window edge brings in
+    uint32_t pad;
+};
+// a run of an automixer over S stream slots
+struct AutomixArgs {
+    AgcArgs        tile;           // what the leveller's tile bodies read (state: unused, nullptr); tile.rec: every stream's
+                                   // record, as the apply pass and the two lane-per-stream kernels read it
+    const uint32_t *rec_energy;    // [S][AGC_REC] the same records with count 0 for a stream in no group: the energy pass
+                                   // reads nothing of such a stream and leaves its table row alone
+    unsigned long long *power;     // [S][nw] P of the run's complete windows, level's word to share
+    unsigned long long *gsum;      // [S][nw] per group id and window of the run: the members' sum of P; zero before level
+    AutomixState  *state;          // [S]
+};
+
 // Filter (k_iir.hip; the arithmetic: include/coolmic_hip.h, the tiles: csrc/iir_plan.h): a run of a biquad cascade over
 // S stream slots
 struct IirArgs {
@@ -632,6 +653,10 @@ hipError_t launch_delay(const DelayArgs &a, uint32_t max_delay, uint32_t max_fra
 // the run's largest count, max_frames the object's.  ev: nullptr, or four events recorded in front of, between and behind
 // the three launches (tools/bench_agc.py).
 hipError_t launch_agc(const AgcArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
+// Automixer (k_automix.hip): gsum cleared, then k_automix_energy, k_automix_level, k_automix_share and k_automix_apply, in
+// that order on `st`; the plan is the leveller's.  ev: nullptr, or five events around the four launches
+// (tools/bench_automix.py); the clearing of gsum lies between the first two.
+hipError_t launch_automix(const AutomixArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
 // Filter (k_iir.hip): one launch, a workgroup per iir_plan's spw streams.  frames: the run's largest count.  ramp: some
 // section ramps at the run's start, a.coef is the ramp table (csrc/iir_ramp.h) and the kernels are k_iirramp.hip's.
 hipError_t launch_iir(const IirArgs &a, uint32_t frames, bool ramp, hipStream_t st);
