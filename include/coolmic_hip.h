@@ -1485,6 +1485,135 @@ void    *cmhip_automix_hip_stream(cmhip_automix_t *m);
 int      cmhip_automix_check(unsigned int window_log2, const cmhip_automix_params_t *p);
 int      cmhip_automix_design(const cmhip_automix_law_desc_t *law, cmhip_automix_params_t *p);
 
+/* ---- failover switch: silence-triggered source changeover, an object of its own beside the batch */
+/* A failover switch gives each of O outputs one of up to four candidate input streams, chosen by the signal: when the
+ * source in force has been dead for fail_windows windows the output crossfades to a backup, and when a candidate of
+ * higher priority has been live for return_windows windows the output crossfades back.  It is the silence switcher in
+ * front of a stream that runs around the clock, in exact integers, decided where the samples are.  It belongs behind a
+ * low cut (a DC offset reads as live) and in front of the leveller.  The stage adds no delay.
+ *
+ * Shapes.  The input is S streams of C interleaved int16 channels (C in 1..16), the output O outputs of C channels in a
+ *   second array.  Slots, strides, alignment and overlap refusals are cmhip_agc_run's.  window_log2 = w in 6..14,
+ *   W = 2^w.  max_frames is per run and output, max_frames * C < 2^31.
+ * Sources.  Each output has an ordered list of K = 1..4 candidate input streams: candidate 0 is the main source, later
+ *   candidates are backups.  cmhip_failover_set_sources(m, output, n, streams) sets the list: COOLMIC_ERROR_INVAL for n
+ *   outside 1..4, a stream >= S, a stream named twice or an output out of range, COOLMIC_ERROR_FAULT for NULL; it resets
+ *   the output (below) and sets its `force` back to -1.  At creation output o has the one candidate min(o, S - 1): a
+ *   copy.  An input stream may be a candidate of many outputs; it is measured once per (output, candidate), on that
+ *   output's clock, so no two outputs ever have to agree on counts.  cmhip_failover_get_sources answers from the
+ *   mirror: *n and the first *n entries of streams[4].
+ * Parameters, per output, settable between runs (cmhip_failover_set, output -1: all outputs):
+ *     quiet[4]          0..32767, per candidate    a window of candidate i is LIVE iff m_i > quiet[i]^2
+ *     fail_windows      1..65535    consecutive non-live windows of the source in force before it is left
+ *     return_windows    1..65535    consecutive live windows of a higher-priority candidate before it is taken back
+ *     fade_log2 = phi   w..16       a changeover is a crossfade over 2^phi frames, that is 2^(phi - w) whole windows
+ *     force             -1..K-1     -1: automatic; i: go to candidate i and stay there
+ *   Defaults: quiet 33 (the leveller's gate, -60 dB), fail_windows = return_windows = 1, phi = w, force -1.  A refused
+ *   call changes nothing; with output -1 a force that one output's list is too short for refuses the whole call.
+ *
+ * Arithmetic, per output o.  Frames are counted since creation or the last reset: n, 64 bits.  Window k = n >> w,
+ *   j = n & (W - 1).
+ *   Level of candidate i in window k: E_i[k] = max over the channels c of the sum over the window's frames of
+ *     x_i[n][c]^2; m_i[k] = E_i[k] >> w: the leveller's E and shift, to the letter; m <= 2^30.
+ *     LIVE_i[k] iff m_i[k] > quiet[i]^2.
+ *     live_run_i[k] = LIVE ? min(live_run_i[k-1] + 1, 65535) : 0
+ *     dead_run_i[k] = LIVE ? 0 : min(dead_run_i[k-1] + 1, 65535)           both 0 before window 0
+ *   Plan of window k: (from, to, q).  A steady window has from = to and q = 0.  Window q of a fade covers the fade's
+ *     frames d = q W + j.
+ *     Window 0 is steady on candidate c0 = force if force >= 0, else 0.
+ *     When frame n = k W (k >= 1) is processed, first the counters are updated with window k - 1 (with the quiet in
+ *     force in that run).  Then:
+ *       1. If window k - 1 was fade window q and q + 1 < 2^(phi' - w), window k is fade window q + 1 of the same fade;
+ *          phi' is the phi in force when the fade began.  A fade keeps its length, and no decision is taken inside a
+ *          fade, `force` included.
+ *       2. Otherwise cur = `to` of window k - 1, and want = cmhip_failover_step(K, params, cur, live_run, dead_run):
+ *            if force >= 0: want = force
+ *            else let b be the smallest i with live_run_i >= return_windows; if b exists and b < cur: want = b
+ *            else if dead_run_cur >= fail_windows: want = the smallest i != cur with live_run_i >= 1, or cur if there
+ *              is none -- when everything is dead the output stays
+ *            else want = cur
+ *          If want != cur, window k is fade window 0 of (from = cur, to = want) and the output's `switches` counter
+ *          goes up by one; otherwise window k is steady on cur.
+ *     The parameters used are those in force in the run that processes frame k W.  The plan of window k depends only on
+ *     windows that ended before it began: the stage is causal and adds no delay.
+ *   Per frame and channel.  Steady: y = x_to, bit for bit.  Fade: p = (d << 15) >> phi' and
+ *     y = cmhip_delay_crossfade(x_from, x_to, p), the delay stage's rule.  d < 2^16, so the shift is exact in uint32 and
+ *     p < 32768; nothing saturates.  The fade's first frame is x_from; the window behind the fade's last is steady on
+ *     x_to (or the first of another fade from it).
+ *   Properties.  K = 1 is a copy.  A steady output is a copy of its source.  An output given 0 frames in a run keeps
+ *     everything.  Cuts: the concatenated output and the state do not depend on how an output is cut into runs, with
+ *     the sets at the same frames -- every sum is of integers.  Every candidate slot of output o must hold the run's
+ *     count[o] frames.
+ *   cmhip_failover_reset(m, output) (-1: all): the output's next frame is frame 0 again; the counters, the levels, the
+ *     sums of an open window and any fade are forgotten.  `switches`, parameters and lists stay.
+ * cmhip_failover_new: NULL for C outside 1..16, S = 0, O = 0 or O >= 2^29, window_log2 outside 6..14, max_frames = 0,
+ *   max_frames * C >= 2^31, or a failed allocation.
+ * cmhip_failover_run has cmhip_agc_run's contract with S input slots, O output slots and frames_per_output (host, O
+ *   entries, may be NULL): asynchronous on the object's stream; the counts are free on return; COOLMIC_ERROR_INVAL, with
+ *   nothing launched and nothing changed, when a base is not 16-byte aligned, a stride is not a multiple of 8 samples or
+ *   below frames * C, frames > max_frames, a count is above frames, either array would end past the address space, or
+ *   the two arrays share a byte; COOLMIC_ERROR_FAULT for NULL arrays.  Outputs past an output's count are not written.
+ * cmhip_failover_set, _set_sources and _reset touch the host mirror only: they need no host wait and no device memory,
+ *   and are ordered with the runs as the calls are.  cmhip_failover_get answers from the mirror.
+ * cmhip_failover_state: synchronous (it waits for the object's stream).  Any pointer may be NULL.  Per output, O entries
+ *   each, for the window the output's last frame lies in: from, to, fade_window (before the first frame: c0, c0, 0);
+ *   switches (uint64; clear != 0 zeroes the counters after reading them).  Per (output, candidate), [O][4]: live_run
+ *   and dead_run as the last window edge processed left them, level = m of the last complete window; 0 before the first
+ *   and for candidates the list does not have.
+ * cmhip_failover_check (host only): 0 for a valid window_log2, n_sources in 1..4 and parameter set (params may be NULL),
+ *   else COOLMIC_ERROR_INVAL.
+ * cmhip_failover_design (host only): parameters from a law in dB re 32768 and seconds:
+ *     quiet[i] = rint(32768 * 10^(quiet_db[i] / 20)) clamped to 0..32767;
+ *     fail_windows = max(1, rint(fail_s * rate / W)), return_windows likewise from return_s, clamped to 65535;
+ *     phi = clamp(rint(log2(fade_ms * rate / 1000)), w, 16) (w for fade_ms <= 0); force = -1.
+ *   COOLMIC_ERROR_INVAL for a non-finite input, a rate that is not positive, a window_log2 that is no integer in 6..14
+ *   or a negative time; COOLMIC_ERROR_FAULT for NULL.
+ * cmhip_failover_step (host only): the decision of rule 2 for one edge as a pure function -> want.  n_sources outside
+ *   1..4, cur >= n_sources, a force >= n_sources or NULL: cur is returned. */
+typedef struct cmhip_failover cmhip_failover_t;
+typedef struct cmhip_failover_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 input slots */
+    unsigned int outputs;         /* O >= 1 output slots */
+    unsigned int channels;        /* 1..16 */
+    unsigned int window_log2;     /* w in 6..14: a source is judged once per 2^w frames */
+    size_t       max_frames;      /* per run and output */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_failover_desc_t;
+typedef struct cmhip_failover_params {
+    uint16_t quiet[4];
+    uint16_t fail_windows, return_windows, fade_log2;
+    int16_t  force;
+} cmhip_failover_params_t;
+typedef struct cmhip_failover_law_desc {
+    double rate;                  /* frames per second */
+    double window_log2;           /* the object's w */
+    double quiet_db[4];           /* dB re 32768 */
+    double fail_s, return_s;      /* seconds, >= 0 */
+    double fade_ms;
+} cmhip_failover_law_desc_t;
+cmhip_failover_t *cmhip_failover_new(const cmhip_failover_desc_t *d);
+void     cmhip_failover_free(cmhip_failover_t *m);
+int      cmhip_failover_set_sources(cmhip_failover_t *m, unsigned int output, unsigned int n, const uint32_t *streams);
+int      cmhip_failover_get_sources(const cmhip_failover_t *m, unsigned int output, unsigned int *n,
+                                    uint32_t *streams /* [4] */);
+int      cmhip_failover_set(cmhip_failover_t *m, long output, const cmhip_failover_params_t *p);
+int      cmhip_failover_get(const cmhip_failover_t *m, unsigned int output, cmhip_failover_params_t *p);
+int      cmhip_failover_run(cmhip_failover_t *m, const void *in, size_t in_stride, size_t frames,
+                            const uint32_t *frames_per_output, void *out, size_t out_stride);
+int      cmhip_failover_reset(cmhip_failover_t *m, long output);
+int      cmhip_failover_state(cmhip_failover_t *m, uint32_t *from /* [O] */, uint32_t *to /* [O] */,
+                              uint32_t *fade_window /* [O] */, uint64_t *switches /* [O] */, int clear,
+                              uint32_t *live_run /* [O][4] */, uint32_t *dead_run /* [O][4] */,
+                              uint32_t *level /* [O][4] */);
+int      cmhip_failover_sync(cmhip_failover_t *m);
+void    *cmhip_failover_hip_stream(cmhip_failover_t *m);
+/* host only, no device needed */
+int      cmhip_failover_check(unsigned int window_log2, unsigned int n_sources, const cmhip_failover_params_t *p);
+int      cmhip_failover_design(const cmhip_failover_law_desc_t *law, cmhip_failover_params_t *p);
+uint32_t cmhip_failover_step(unsigned int n_sources, const cmhip_failover_params_t *p, uint32_t cur,
+                             const uint32_t *live_run /* [4] */, const uint32_t *dead_run /* [4] */);
+
 /* ---- filter: a biquad cascade in exact integers, an object of its own beside the batch -- */
 /* A filter runs each of S streams of C interleaved int16 channels (C in 1..16) through a cascade of N second-order
  * sections (N in 1..8), in exact integers: a low cut per microphone in front of a leveller, a gate or a bus, a

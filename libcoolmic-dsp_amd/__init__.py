@@ -238,6 +238,28 @@ class AutomixLawDesc(C.Structure):
                                           "release_ms")]
 
 
+class FailoverDesc(C.Structure):
+    """cmhip_failover_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("outputs", C.c_uint), ("channels", C.c_uint),
+                ("window_log2", C.c_uint), ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
+class FailoverParams(C.Structure):
+    """cmhip_failover_params_t (include/coolmic_hip.h)"""
+    _fields_ = [("quiet", C.c_uint16 * 4), ("fail_windows", C.c_uint16), ("return_windows", C.c_uint16),
+                ("fade_log2", C.c_uint16), ("force", C.c_int16)]
+
+    def as_dict(self):
+        return {"quiet": tuple(self.quiet), "fail_windows": self.fail_windows, "return_windows": self.return_windows,
+                "fade_log2": self.fade_log2, "force": self.force}
+
+
+class FailoverLawDesc(C.Structure):
+    """cmhip_failover_law_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("rate", C.c_double), ("window_log2", C.c_double), ("quiet_db", C.c_double * 4), ("fail_s", C.c_double),
+                ("return_s", C.c_double), ("fade_ms", C.c_double)]
+
+
 class IirDesc(C.Structure):
     """cmhip_iir_desc_t (include/coolmic_hip.h)"""
     _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("sections", C.c_uint),
@@ -448,6 +470,20 @@ SIGNATURES = {
     "cmhip_automix_hip_stream": (_vp, [_vp]),
     "cmhip_automix_check": (C.c_int, [C.c_uint, _P(AutomixParams)]),
     "cmhip_automix_design": (C.c_int, [_P(AutomixLawDesc), _P(AutomixParams)]),
+    "cmhip_failover_new": (_vp, [_P(FailoverDesc)]),
+    "cmhip_failover_free": (None, [_vp]),
+    "cmhip_failover_set_sources": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
+    "cmhip_failover_get_sources": (C.c_int, [_vp, C.c_uint, _P(C.c_uint), _vp]),
+    "cmhip_failover_set": (C.c_int, [_vp, C.c_long, _P(FailoverParams)]),
+    "cmhip_failover_get": (C.c_int, [_vp, C.c_uint, _P(FailoverParams)]),
+    "cmhip_failover_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_failover_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_failover_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "cmhip_failover_sync": (C.c_int, [_vp]),
+    "cmhip_failover_hip_stream": (_vp, [_vp]),
+    "cmhip_failover_check": (C.c_int, [C.c_uint, C.c_uint, _P(FailoverParams)]),
+    "cmhip_failover_design": (C.c_int, [_P(FailoverLawDesc), _P(FailoverParams)]),
+    "cmhip_failover_step": (C.c_uint32, [C.c_uint, _P(FailoverParams), C.c_uint32, _vp, _vp]),
     "cmhip_iir_new": (_vp, [_P(IirDesc)]),
     "cmhip_iir_free": (None, [_vp]),
     "cmhip_iir_set": (C.c_int, [_vp, C.c_long, C.c_uint, _P(IirSection)]),
@@ -1142,6 +1178,80 @@ def agc_design(rate, window_log2, target_db, gate_db, max_gain_db, min_gain_db, 
     p = AgcParams()
     _check("agc_design", lib.cmhip_agc_design(C.byref(law), C.byref(p)))
     return p
+
+
+if hasattr(lib, "cmhip_test_failover_new_dry"):  # (not in builds older than the failover switch)
+    lib.cmhip_test_failover_new_dry.restype = _vp
+    lib.cmhip_test_failover_new_dry.argtypes = [_P(FailoverDesc)]
+    lib.cmhip_test_failover_edge.restype = C.c_uint32
+    lib.cmhip_test_failover_edge.argtypes = [C.c_uint32, C.c_uint, _P(FailoverParams), C.c_uint, _vp, _vp, _vp,
+                                             _P(C.c_uint32)]
+    lib.cmhip_test_failover_first.restype = C.c_uint32
+    lib.cmhip_test_failover_first.argtypes = [_P(FailoverParams)]
+    lib.cmhip_test_failover_fade.restype = C.c_int32
+    lib.cmhip_test_failover_fade.argtypes = [C.c_int16, C.c_int16, C.c_uint32, C.c_uint32]
+    lib.cmhip_test_failover_run_events.restype = C.c_int
+    lib.cmhip_test_failover_run_events.argtypes = [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _P(C.c_void_p)]
+
+
+def failover_params(window_log2, **kw):
+    """a FailoverParams: the creation defaults of an object with this window_log2, with `kw` over them"""
+    f = dict(quiet=(33, 33, 33, 33), fail_windows=1, return_windows=1, fade_log2=window_log2, force=-1)
+    f.update(kw)
+    q = f.pop("quiet")
+    q = (q,) * 4 if np.isscalar(q) else tuple(q)
+    return FailoverParams((C.c_uint16 * 4)(*q), **f)
+
+
+def failover_check(window_log2, n_sources, params=None):
+    """cmhip_failover_check -> error number"""
+    return lib.cmhip_failover_check(window_log2, n_sources, C.byref(params) if params is not None else None)
+
+
+def failover_design(rate, window_log2, quiet_db=-60.0, fail_s=0.0, return_s=0.0, fade_ms=0.0):
+    """cmhip_failover_design -> FailoverParams (quiet_db: one value for every candidate, or four)"""
+    q = (quiet_db,) * 4 if np.isscalar(quiet_db) else tuple(quiet_db)
+    law = FailoverLawDesc(rate, window_log2, (C.c_double * 4)(*q), fail_s, return_s, fade_ms)
+    p = FailoverParams()
+    _check("failover_design", lib.cmhip_failover_design(C.byref(law), C.byref(p)))
+    return p
+
+
+def failover_step(n_sources, params, cur, live_run, dead_run):
+    """cmhip_failover_step: the candidate wanted at a window edge outside a fade, the specification as code"""
+    lv = np.ascontiguousarray(live_run, dtype=np.uint32)
+    dd = np.ascontiguousarray(dead_run, dtype=np.uint32)
+    assert lv.size == 4 and dd.size == 4
+    return lib.cmhip_failover_step(n_sources, C.byref(params), cur, lv.ctypes.data, dd.ctypes.data)
+
+
+def failover_edge(plan, n_sources, params, window_log2, level, live_run, dead_run):
+    """Test hook (cmhip_test_failover_edge): one window edge as k_failover_step takes it: the counters take `level`,
+    then the plan word moves on -> (plan word, live_run [4], dead_run [4], switched)"""
+    lv = np.array(live_run, dtype=np.uint32)
+    dd = np.array(dead_run, dtype=np.uint32)
+    m = np.ascontiguousarray(level, dtype=np.uint32)
+    assert lv.size == 4 and dd.size == 4 and m.size == 4
+    sw = C.c_uint32(0)
+    pl = lib.cmhip_test_failover_edge(plan, n_sources, C.byref(params), window_log2, m.ctypes.data, lv.ctypes.data,
+                                      dd.ctypes.data, C.byref(sw))
+    return pl, [int(v) for v in lv], [int(v) for v in dd], sw.value
+
+
+def failover_first(params):
+    """Test hook (cmhip_test_failover_first): the plan word of window 0"""
+    return lib.cmhip_test_failover_first(C.byref(params))
+
+
+def failover_fade(a, b, d, phi):
+    """Test hook (cmhip_test_failover_fade): frame d of a fade over 2^phi frames from sample a to sample b"""
+    return lib.cmhip_test_failover_fade(a, b, d, phi)
+
+
+def test_failover_without_device(streams, outputs, channels, window_log2, max_frames):
+    """Test hook (cmhip_test_failover_new_dry): a Failover with the host mirror and every check but no device behind
+    it"""
+    return Failover(streams, outputs, channels, window_log2, max_frames, _new=lib.cmhip_test_failover_new_dry)
 
 
 def automix_params(**kw):
@@ -1943,7 +2053,7 @@ class Batch:
 
 class _Stage:
     """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay,
-    Leveller, Filter, Automixer): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
+    Leveller, Filter, Automixer, Failover): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
     object's C functions: cmhip_<stem>_free, _sync, _hip_stream, _run, _reset.  The Mixer and the Bus have no state to
     reset and the library no cmhip_mix_reset or cmhip_bus_reset: their reset() raises AttributeError, as the lookup of
     any symbol the library lacks does."""
@@ -2196,6 +2306,68 @@ class Automixer(_Stage):
         sh = np.zeros(self.streams, dtype=np.uint32)
         _check("automix_state", lib.cmhip_automix_state(self.h, g.ctypes.data, pw.ctypes.data, sh.ctypes.data))
         return g, pw, sh
+
+
+class Failover(_Stage):
+    """cmhip_failover_t: a silence-triggered source changeover beside a batch: each of `outputs` outputs is a copy of one
+    of up to four candidate input streams, judged once per window of 2^window_log2 frames, with a crossfade at every
+    changeover.  Output o starts with the one candidate min(o, streams - 1).  `params` (a FailoverParams): set for every
+    output at creation.  Counts of a run are per OUTPUT."""
+
+    _stem = "failover"
+
+    def __init__(self, streams, outputs, channels, window_log2, max_frames, params=None, device=0, hip_stream=None,
+                 _new=None):
+        d = FailoverDesc(device, streams, outputs, channels, window_log2, max_frames, hip_stream)
+        self.h = (_new or lib.cmhip_failover_new)(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_failover_new", ERROR_INVAL)
+        self.inputs, self.outputs, self.channels, self.window_log2, self.max_frames = (streams, outputs, channels,
+                                                                                        window_log2, max_frames)
+        self.streams = outputs                       # (what _Stage._counts holds a run's counts against)
+        if params is not None:
+            self.set(-1, params)
+
+    def set_rc(self, output, params):
+        """cmhip_failover_set as it is -> error number"""
+        return lib.cmhip_failover_set(self.h, output, C.byref(params))
+
+    def set(self, output, params):
+        """the output's parameters from the next run on (output -1: every output)"""
+        _check("failover_set", self.set_rc(output, params))
+
+    def get(self, output):
+        p = FailoverParams()
+        _check("failover_get", lib.cmhip_failover_get(self.h, output, C.byref(p)))
+        return p
+
+    def set_sources_rc(self, output, streams):
+        """cmhip_failover_set_sources as it is -> error number"""
+        s = np.ascontiguousarray(streams, dtype=np.uint32)
+        return lib.cmhip_failover_set_sources(self.h, output, s.size, s.ctypes.data)
+
+    def set_sources(self, output, streams):
+        """the output's candidate list, main source first; the output starts afresh and is automatic again"""
+        _check("failover_set_sources", self.set_sources_rc(output, streams))
+
+    def get_sources(self, output):
+        n = C.c_uint(0)
+        s = np.zeros(4, dtype=np.uint32)
+        _check("failover_get_sources", lib.cmhip_failover_get_sources(self.h, output, C.byref(n), s.ctypes.data))
+        return [int(v) for v in s[:n.value]]
+
+    def state(self, clear=False):
+        """-> dict of from, to, fade_window (uint32 [O]), switches (uint64 [O]), live_run, dead_run, level (uint32
+        [O][4]); a synchronous round trip"""
+        O = self.outputs
+        r = {k: np.zeros(O, dtype=np.uint32) for k in ("from", "to", "fade_window")}
+        r["switches"] = np.zeros(O, dtype=np.uint64)
+        r.update({k: np.zeros((O, 4), dtype=np.uint32) for k in ("live_run", "dead_run", "level")})
+        _check("failover_state", lib.cmhip_failover_state(self.h, r["from"].ctypes.data, r["to"].ctypes.data,
+                                                          r["fade_window"].ctypes.data, r["switches"].ctypes.data,
+                                                          1 if clear else 0, r["live_run"].ctypes.data,
+                                                          r["dead_run"].ctypes.data, r["level"].ctypes.data))
+        return r
 
 
 class Filter(_Stage):

@@ -20,6 +20,7 @@
 //   cmhip_delay.hip    the delay line
 //   cmhip_agc.hip      the leveller: slow automatic gain control
 //   cmhip_automix.hip  the automixer: gain-sharing groups
+//   cmhip_failover.hip the failover switch: silence-triggered source changeover
 //   cmhip_iir.hip      the filter: a biquad cascade in exact integers
 #pragma once
 

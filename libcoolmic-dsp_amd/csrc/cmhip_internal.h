@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_failover.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -13,6 +13,7 @@
 #include "delay_plan.h"
 #include "agc_plan.h"
 #include "automix_plan.h"
+#include "failover_plan.h"
 #include "iir_plan.h"
 #include "iir_ramp.h"
 #include "spec_plan.h"
@@ -466,6 +467,28 @@ struct AutomixArgs {
     AutomixState  *state;          // [S]
 };
 
+// Failover switch (k_failover.hip; the arithmetic: include/coolmic_hip.h, the records, the plan word and the mirror:
+// csrc/failover_plan.h).  What an output carries from run to run, written by k_failover_step alone:
+struct FailoverState {
+    unsigned long long psum[4][16];    // the open window's sums of squares so far, per candidate and channel
+    uint32_t level[4];                 // m of the last complete window, per candidate
+    unsigned long long live, dead;     // the counters as the last edge processed left them, packed (failover_run)
+    uint32_t plan;                     // the plan word of the window the output's last frame lies in
+    uint32_t pad[3];
+};
+// a run of a failover switch: S input slots, O output slots
+struct FailoverArgs {
+    AgcArgs        energy;         // what the leveller's energy body reads: O * 4 rows, rec: the rows' records, in: the
+                                   // input array, table [O * 4][nw][C]; out, nodes, state and clips unused (nullptr)
+    int16_t       *out;            // int16 [O][out_stride]
+    const uint32_t *rec;           // [O][FO_REC] the outputs' records
+    uint32_t      *plan;           // [O][nw + 1] the run's plan words: window i of the run has entry i
+    FailoverState *state;          // [O]
+    unsigned long long *switches;  // [O] changeovers begun
+    uint64_t       out_stride;     // samples between output slots (a multiple of 8)
+    uint32_t       outputs;
+};
+
 // Filter (k_iir.hip; the arithmetic: include/coolmic_hip.h, the tiles: csrc/iir_plan.h): a run of a biquad cascade over
 // S stream slots
 struct IirArgs {
@@ -657,6 +680,9 @@ hipError_t launch_agc(const AgcArgs &a, uint64_t max_frames, uint32_t frames, hi
 // that order on `st`; the plan is the leveller's.  ev: nullptr, or five events around the four launches
 // (tools/bench_automix.py); the clearing of gsum lies between the first two.
 hipError_t launch_automix(const AutomixArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
+// Failover switch (k_failover.hip): k_failover_energy, k_failover_step and k_failover_apply, in that order.  ev (may be
+// nullptr): four events recorded in front of, between and behind the three launches (tools/bench_failover.py).
+hipError_t launch_failover(const FailoverArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
 // Filter (k_iir.hip): one launch, a workgroup per iir_plan's spw streams.  frames: the run's largest count.  ramp: some
 // section ramps at the run's start, a.coef is the ramp table (csrc/iir_ramp.h) and the kernels are k_iirramp.hip's.
 hipError_t launch_iir(const IirArgs &a, uint32_t frames, bool ramp, hipStream_t st);

@@ -1,6 +1,7 @@
 // k_agc.h -- the leveller's tile bodies (k_agc.hip has the decomposition): a tile's context from the run's record, the
 // energy pass and the apply pass.  k_agc.hip instantiates them for the leveller, k_automix.hip for the automixer, whose
 // record keeps the count and the position in the leveller's places and whose gain nodes have the leveller's form.
+// k_failover.hip instantiates the energy pass alone, with SLOTS: its rows' records name the input slot they read.
 #pragma once
 
 #include "cmhip_device.h"
@@ -15,7 +16,9 @@ struct AgcTileCtx {                                  // a tile (wave-uniform)
     u32 s;
 };
 
-// false: the workgroup has no frames (uniform)
+// false: the workgroup has no frames (uniform).  SLOTS (the failover switch's energy pass): row s of the records reads the
+// input slot its record names in AREC_SLOT; its table row is still row s.
+template <bool SLOTS = false>
 __device__ __forceinline__ bool agc_tile_ctx(const AgcArgs &a, u32 C, AgcTileCtx &c)
 {
     c.s = blockIdx.x / a.chunks;
@@ -26,7 +29,10 @@ __device__ __forceinline__ bool agc_tile_ctx(const AgcArgs &a, u32 C, AgcTileCtx
     if (c.tl.fa >= c.tl.fb)
         return false;
     c.sp = agc_tile_span(c.tl.fa, c.tl.fb, C);
-    c.ins = a.in + (u64)c.s * a.in_stride;
+    if constexpr (SLOTS)
+        c.ins = a.in + (u64)uniform(rec[AREC_SLOT]) * a.in_stride;
+    else
+        c.ins = a.in + (u64)c.s * a.in_stride;
     c.outs = a.out + (u64)c.s * a.out_stride;
     return true;
 }
@@ -36,12 +42,12 @@ __device__ __forceinline__ u64 agc_sq(int x) { return (u64)(u32)(x * x); }
 // ---------------------------------------------------------------------------
 // energy.  CT: the channel count of the fast forms, 0 for the any-channel-count form.  NT threads, NV vectors each.
 // lds (CT == 0 only): u64 [C][NT], a slot per thread and channel
-template <int CT, u32 NT, u32 NV>
+template <int CT, u32 NT, u32 NV, bool SLOTS = false>
 __device__ __forceinline__ void agc_energy_body(const AgcArgs &a, u64 *lds)
 {
     const u32 C = CT ? (u32)CT : a.channels;
     AgcTileCtx c;
-    if (!agc_tile_ctx(a, C, c))
+    if (!agc_tile_ctx<SLOTS>(a, C, c))
         return;
     const u32 tid = threadIdx.x;
     const AgcSpan sp = c.sp;
