@@ -1614,6 +1614,113 @@ int      cmhip_failover_design(const cmhip_failover_law_desc_t *law, cmhip_failo
 uint32_t cmhip_failover_step(unsigned int n_sources, const cmhip_failover_params_t *p, uint32_t cur,
                              const uint32_t *live_run /* [4] */, const uint32_t *dead_run /* [4] */);
 
+/* ---- clock-drift compensation: a variable-ratio resampler, an object of its own beside the batch -- */
+/* A drift stage resamples S streams of C = 1..16 interleaved int16 channels by a ratio close to 1 that the caller
+ * moves per stream between runs: what reconciles a source on its own clock (a second sound card, a network
+ * contribution, the backup behind a cmhip_failover_t) with the batch's.  Exact integers; the signal is the raw int16.
+ *
+ * Table.  H[P][T] of int16 coefficients in units of 2^-14, P = 2^phi phases with phi in 5..8, T even in 4..64.  Row p
+ *   is the filter for a fractional position of p / P input frames behind frame n.  A table is valid when H[0][0] = 0
+ *   and sum_k |H[p][k]| <= 65535 for every row; anything else is COOLMIC_ERROR_INVAL.  The library appends row P
+ *   itself: row 0 moved by one tap, H[P][k] = H[0][k+1] for k < T-1 and H[P][T-1] = 0 (a fraction of one whole frame
+ *   is the next frame at fraction 0; H[0][0] = 0 is what makes that lose nothing).
+ * Position.  Each stream has a position pos, a uint64 in units of 2^-32 input frames, measured from frame 0 of the
+ *   NEXT run; 0 at creation and after reset.  Each stream has a step of 2^32 + delta with |delta| <= 2^24
+ *   (+-3906 ppm); delta 0 at creation.
+ * Arithmetic.  Output m = 0, 1, .. of a run has t = pos + m * step and
+ *       n = t >> 32      f = t & (2^32 - 1)      p = f >> (32 - phi)      mu = (f >> (17 - phi)) & 32767
+ *   and per channel
+ *       a0  = sum_{k<T} H[p][k]   * x[n-k]            exact in int32
+ *       a1  = sum_{k<T} H[p+1][k] * x[n-k]            exact in int32
+ *       num = a0 * (32768 - mu) + a1 * mu             exact in int64
+ *       y   = saturate_int16((num + 2^28) >> 29)      arithmetic shift (floor), one rounding
+ *   x[i] for i < 0 is the stream's history, the last T-1 input frames: zero at creation and after reset.  With
+ *   sum |H| <= 65535, |a0|, |a1| <= 65535 * 32768 < 2^31 and |num| < 2^46.
+ * Counts.  Output m exists once input n exists: a run of F frames produces
+ *       K = ceil((F * 2^32 - pos) / step)   outputs,   K = 0 when pos >= F * 2^32
+ *   and leaves pos' = pos + K * step - F * 2^32 with 0 <= pos' < step: nothing grows with the stream's age.  With delta
+ *   unchanged the concatenated output does not depend on how a stream is cut into runs; a stream that gets 0 frames
+ *   keeps everything.  cmhip_drift_out_frames(pos, delta, F) is K on the host (0 for |delta| > 2^24);
+ *   cmhip_drift_max_out_frames(m) is K for pos = 0, delta = -2^24 and F = max_in_frames, the most a run can give.
+ * Control, each a change of the host's mirror alone (no device work, no wait; the position, the step and the count
+ *   travel to the device with each run, so a call takes effect with the first output of the next run queued behind
+ *   it):  cmhip_drift_set(m, stream, delta): stream -1 is every stream, |delta| > 2^24 is COOLMIC_ERROR_INVAL.
+ *   cmhip_drift_seek(m, stream, frac) sets pos = frac < 2^32 (COOLMIC_ERROR_INVAL otherwise); with delta = 0 and the
+ *   designed table the stage is then a fractional delay of T/2 - frac * 2^-32 frames.  cmhip_drift_reset(m, stream)
+ *   zeroes the history (that on the object's stream, in order with the runs), pos and the totals, delta stays.
+ *   cmhip_drift_get answers from the mirror, which advances by every run's counts: delta, pos, and the total input and
+ *   output frames since creation or reset (each pointer may be NULL).
+ *   cmhip_drift_ppm(ppm) = rint(ppm * 2^32 / 10^6) clamped to +-2^24 (0 for NaN): +ppm consumes more input per
+ *   output; cmhip_drift_to_ppm(delta) = delta * 10^6 / 2^32.
+ * cmhip_drift_run has cmhip_src_run's contract and refusals (alignment, strides, counts, in == out, NULL), with
+ *   max_in_frames for the input and the run's largest output count for the output stride --
+ *   cmhip_drift_max_out_frames() * C always suffices.  out_frames[] (host, S entries, may be NULL) is filled from the
+ *   mirror before the call returns.  Outputs past a stream's count are not written.
+ * The designed table (cmhip_drift_design(phase_log2, taps, h, cap), host only, double precision, in this order): with
+ *   P = 2^phase_log2, T = taps, fc = 0.92 * 0.5, for p < P and k < T with x = k + p/P - T/2:
+ *       w = I0(7.5 * sqrt(max(0, 1 - (x / (T/2))^2))) / I0(7.5)          g[p][k] = 2*fc * sinc(2*fc*x) * w
+ *   (sinc and I0 as cmhip_src_design's); g[0][0] is set to 0 (its window is 0 there already: x = -T/2) BEFORE row 0 is
+ *   normalised; every row is divided by its own sum, multiplied by 16384 and rounded with rint, and the difference
+ *   between 16384 and the row's integer sum is added to the row's first tap of largest magnitude.  Every row then
+ *   sums to exactly 16384, and so does row P: a constant input comes out as the same constant at every mu once the
+ *   history is full.  cap counts the entries of h; below P*T is COOLMIC_ERROR_INVAL with nothing written.
+ *   cmhip_drift_new designs phase_log2 = 7, taps = 32; cmhip_drift_new_table takes the caller's H[P][T].
+ *   max_in_frames * C and cmhip_drift_max_out_frames() * C may not pass 2^31 samples.  Both return NULL on failure.
+ * Where it sits: behind a source's elastic buffer and in front of whatever combines streams (failover switch,
+ *   automixer, bus): its out_frames[] are the frames_per_stream of what follows.
+ *
+ * Servo (host only): a PI controller in integers that turns the fill of the caller's elastic buffer, read once per
+ *   block, into the next delta.  State: target, kp_log2, ki_log2 (each 0..24), limit (1..2^24), integ (int64, 0 at
+ *   init and reset), delta, clamped.  cmhip_drift_servo_step(servo, fill_frames), with 0 <= fill_frames < 2^31
+ *   (anything else returns the last delta and changes nothing):
+ *       e    = fill_frames - target
+ *       raw  = e * 2^kp_log2 + (integ + e) * 2^ki_log2                     exact in int64
+ *       |raw| <= limit:  integ = integ + e,  delta = raw,  clamped = 0
+ *       otherwise:       delta = limit with raw's sign,  clamped = 1,  integ stays (the integrator is frozen)
+ *   A fill above the target gives a positive delta: more input is consumed per output.  cmhip_drift_servo_init
+ *   refuses (COOLMIC_ERROR_INVAL) a target above 2^31 - 1, a shift above 24 or a limit outside 1..2^24. */
+typedef struct cmhip_drift cmhip_drift_t;
+typedef struct cmhip_drift_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    size_t       max_in_frames;   /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_drift_desc_t;
+typedef struct cmhip_drift_servo {
+    int64_t      target;          /* frames */
+    int64_t      integ;           /* sum of e over the steps that were not clamped */
+    uint32_t     kp_log2, ki_log2;
+    int32_t      limit;
+    int32_t      delta;           /* the last step's answer */
+    uint32_t     clamped;
+} cmhip_drift_servo_t;
+#define CMHIP_DRIFT_DELTA_MAX (1 << 24)
+cmhip_drift_t *cmhip_drift_new(const cmhip_drift_desc_t *d);
+cmhip_drift_t *cmhip_drift_new_table(const cmhip_drift_desc_t *d, unsigned int phase_log2, unsigned int taps,
+                                     const int16_t *h /* [2^phase_log2][taps] */);
+void     cmhip_drift_free(cmhip_drift_t *m);
+int      cmhip_drift_geometry(const cmhip_drift_t *m, unsigned int *phase_log2, unsigned int *taps);
+size_t   cmhip_drift_max_out_frames(const cmhip_drift_t *m);
+int      cmhip_drift_set(cmhip_drift_t *m, long stream, int32_t delta);
+int      cmhip_drift_seek(cmhip_drift_t *m, long stream, uint64_t frac);
+int      cmhip_drift_reset(cmhip_drift_t *m, long stream);
+int      cmhip_drift_get(const cmhip_drift_t *m, unsigned int stream, int32_t *delta, uint64_t *pos, uint64_t *in_total,
+                         uint64_t *out_total);
+int      cmhip_drift_run(cmhip_drift_t *m, const void *in, size_t in_stride, size_t frames,
+                         const uint32_t *frames_per_stream, void *out, size_t out_stride, uint32_t *out_frames);
+int      cmhip_drift_sync(cmhip_drift_t *m);
+void    *cmhip_drift_hip_stream(cmhip_drift_t *m);
+/* host only, no device needed */
+int      cmhip_drift_design(unsigned int phase_log2, unsigned int taps, int16_t *h, size_t cap /* entries */);
+uint32_t cmhip_drift_out_frames(uint64_t pos, int32_t delta, uint32_t frames);
+int32_t  cmhip_drift_ppm(double ppm);
+double   cmhip_drift_to_ppm(int32_t delta);
+int      cmhip_drift_servo_init(cmhip_drift_servo_t *servo, uint32_t target_frames, unsigned int kp_log2,
+                                unsigned int ki_log2, int32_t limit);
+int32_t  cmhip_drift_servo_step(cmhip_drift_servo_t *servo, int64_t fill_frames);
+void     cmhip_drift_servo_reset(cmhip_drift_servo_t *servo);
+
 /* ---- filter: a biquad cascade in exact integers, an object of its own beside the batch -- */
 /* A filter runs each of S streams of C interleaved int16 channels (C in 1..16) through a cascade of N second-order
  * sections (N in 1..8), in exact integers: a low cut per microphone in front of a leveller, a gate or a bus, a

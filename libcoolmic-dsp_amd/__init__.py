@@ -156,6 +156,18 @@ class SrcDesc(C.Structure):
                 ("rate_out", C.c_uint), ("max_in_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
 
 
+class DriftDesc(C.Structure):
+    """cmhip_drift_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("max_in_frames", C.c_size_t),
+                ("hip_stream", C.c_void_p)]
+
+
+class DriftServo(C.Structure):
+    """cmhip_drift_servo_t (include/coolmic_hip.h)"""
+    _fields_ = [("target", C.c_int64), ("integ", C.c_int64), ("kp_log2", C.c_uint32), ("ki_log2", C.c_uint32),
+                ("limit", C.c_int32), ("delta", C.c_int32), ("clamped", C.c_uint32)]
+
+
 class MixDesc(C.Structure):
     """cmhip_mix_desc_t (include/coolmic_hip.h)"""
     _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels_in", C.c_uint), ("channels_out", C.c_uint),
@@ -470,6 +482,25 @@ SIGNATURES = {
     "cmhip_automix_hip_stream": (_vp, [_vp]),
     "cmhip_automix_check": (C.c_int, [C.c_uint, _P(AutomixParams)]),
     "cmhip_automix_design": (C.c_int, [_P(AutomixLawDesc), _P(AutomixParams)]),
+    "cmhip_drift_new": (_vp, [_P(DriftDesc)]),
+    "cmhip_drift_new_table": (_vp, [_P(DriftDesc), C.c_uint, C.c_uint, _vp]),
+    "cmhip_drift_free": (None, [_vp]),
+    "cmhip_drift_geometry": (C.c_int, [_vp, _P(C.c_uint), _P(C.c_uint)]),
+    "cmhip_drift_max_out_frames": (C.c_size_t, [_vp]),
+    "cmhip_drift_set": (C.c_int, [_vp, C.c_long, C.c_int32]),
+    "cmhip_drift_seek": (C.c_int, [_vp, C.c_long, C.c_uint64]),
+    "cmhip_drift_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_drift_get": (C.c_int, [_vp, C.c_uint, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "cmhip_drift_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "cmhip_drift_sync": (C.c_int, [_vp]),
+    "cmhip_drift_hip_stream": (_vp, [_vp]),
+    "cmhip_drift_design": (C.c_int, [C.c_uint, C.c_uint, _vp, C.c_size_t]),
+    "cmhip_drift_out_frames": (C.c_uint32, [C.c_uint64, C.c_int32, C.c_uint32]),
+    "cmhip_drift_ppm": (C.c_int32, [C.c_double]),
+    "cmhip_drift_to_ppm": (C.c_double, [C.c_int32]),
+    "cmhip_drift_servo_init": (C.c_int, [_P(DriftServo), C.c_uint32, C.c_uint, C.c_uint, C.c_int32]),
+    "cmhip_drift_servo_step": (C.c_int32, [_P(DriftServo), C.c_int64]),
+    "cmhip_drift_servo_reset": (None, [_P(DriftServo)]),
     "cmhip_failover_new": (_vp, [_P(FailoverDesc)]),
     "cmhip_failover_free": (None, [_vp]),
     "cmhip_failover_set_sources": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
@@ -1053,6 +1084,78 @@ def src_design(rate_in, rate_out):
 def src_out_frames(L, M, r, frames):
     """output frames of a run of `frames` input frames for a stream at position r = (frames so far) mod M"""
     return lib.cmhip_src_out_frames(L, M, r, frames)
+
+
+if hasattr(lib, "cmhip_test_drift_new_dry"):    # (not in builds older than the drift stage)
+    lib.cmhip_test_drift_new_dry.restype = _vp
+    lib.cmhip_test_drift_new_dry.argtypes = [_P(DriftDesc), C.c_uint, C.c_uint, _vp]
+    lib.cmhip_test_drift_advance.restype = C.c_int
+    lib.cmhip_test_drift_advance.argtypes = [_vp, C.c_size_t, _vp, _vp]
+    lib.cmhip_test_plan_drift.restype = None
+    lib.cmhip_test_plan_drift.argtypes = [C.c_uint32] * 5 + [C.c_void_p]
+
+DRIFT_DELTA_MAX = 1 << 24
+
+
+class DriftPlan(C.Structure):
+    """cmhip::DriftPlan (csrc/drift_plan.h): what the drift stage's launcher launches for a run"""
+    _fields_ = [("err", C.c_int)] + [(n, C.c_uint32) for n in ("fast", "grid", "block", "chunks", "tile_out", "tile_in",
+                                                               "row", "table_lds", "table_words", "lds_bytes")]
+
+
+def plan_drift(streams, channels, phase_log2, taps, out_frames):
+    """Test hook: the drift launcher's plan for a run that gives its longest stream out_frames frames (host logic,
+    needs no GPU)"""
+    p = DriftPlan()
+    lib.cmhip_test_plan_drift(streams, channels, phase_log2, taps, out_frames, C.addressof(p))
+    return p
+
+
+def drift_design_rc(phase_log2, taps, cap=None):
+    """cmhip_drift_design as it is -> (error number, int16 array of `cap` entries, default the table's)"""
+    h = np.zeros(max(1, (taps << phase_log2) if cap is None else cap), dtype=np.int16)
+    return lib.cmhip_drift_design(phase_log2, taps, h.ctypes.data, h.size if cap is None else cap), h
+
+
+def drift_design(phase_log2=7, taps=32):
+    """the designed drift table -> int16 array [2^phase_log2][taps]"""
+    rc, h = drift_design_rc(phase_log2, taps)
+    _check("drift_design", rc)
+    return h.reshape(1 << phase_log2, taps)
+
+
+def drift_out_frames(pos, delta, frames):
+    """output frames of a run of `frames` input frames for a stream at position pos with step 2^32 + delta"""
+    return lib.cmhip_drift_out_frames(pos, delta, frames)
+
+
+def drift_ppm(ppm):
+    """cmhip_drift_ppm: parts per million -> delta"""
+    return lib.cmhip_drift_ppm(ppm)
+
+
+def drift_to_ppm(delta):
+    """cmhip_drift_to_ppm: delta -> parts per million"""
+    return lib.cmhip_drift_to_ppm(delta)
+
+
+class Servo:
+    """cmhip_drift_servo_t: the PI controller that turns an elastic buffer's fill into the next delta"""
+
+    def __init__(self, target_frames, kp_log2, ki_log2, limit=DRIFT_DELTA_MAX):
+        self.s = DriftServo()
+        _check("drift_servo_init", lib.cmhip_drift_servo_init(C.byref(self.s), target_frames, kp_log2, ki_log2, limit))
+
+    def step(self, fill_frames):
+        return lib.cmhip_drift_servo_step(C.byref(self.s), fill_frames)
+
+    def reset(self):
+        lib.cmhip_drift_servo_reset(C.byref(self.s))
+
+
+def test_drift_without_device(streams, channels, max_in_frames, table=None):
+    """Test hook (cmhip_test_drift_new_dry): a Drift with the host mirror and every check but no device behind it"""
+    return Drift(streams, channels, max_in_frames, table=table, _dry=True)
 
 
 class SplitPlan(C.Structure):
@@ -2053,7 +2156,7 @@ class Batch:
 
 class _Stage:
     """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay,
-    Leveller, Filter, Automixer, Failover): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
+    Leveller, Filter, Automixer, Failover, Drift): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
     object's C functions: cmhip_<stem>_free, _sync, _hip_stream, _run, _reset.  The Mixer and the Bus have no state to
     reset and the library no cmhip_mix_reset or cmhip_bus_reset: their reset() raises AttributeError, as the lookup of
     any symbol the library lacks does."""
@@ -2137,6 +2240,80 @@ class Resampler(_Stage):
         """one run over device arrays (src, dst: device pointers) -> the streams' output counts"""
         rc, got = self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream)
         _check("src_run", rc)
+        return got
+
+
+class Drift(_Stage):
+    """cmhip_drift_t: clock-drift compensation of S streams beside a batch, a resampler whose step 2^32 + delta is set
+    per stream between runs.  Without `table` the library designs one (phase_log2 7, 32 taps); with it, table is the
+    int16 array [2^phase_log2][taps]."""
+
+    _stem = "drift"
+
+    def __init__(self, streams, channels, max_in_frames, table=None, device=0, hip_stream=None, _dry=False):
+        d = DriftDesc(device, streams, channels, max_in_frames, hip_stream)
+        if _dry or table is not None:
+            phi = taps = 0
+            if table is not None:
+                table = np.ascontiguousarray(table, dtype=np.int16)
+                assert table.ndim == 2
+                phi, taps = max(table.shape[0].bit_length() - 1, 0), table.shape[1]
+                assert table.shape[0] == 1 << phi
+        if _dry:
+            self.h = lib.cmhip_test_drift_new_dry(C.byref(d), phi, taps, table.ctypes.data if table is not None else None)
+        elif table is None:
+            self.h = lib.cmhip_drift_new(C.byref(d))
+        else:
+            self.h = lib.cmhip_drift_new_table(C.byref(d), phi, taps, table.ctypes.data)
+        if not self.h:
+            raise CoolmicError("cmhip_drift_new", ERROR_INVAL)
+        self.streams, self.channels, self.max_in_frames = streams, channels, max_in_frames
+
+    def geometry(self):
+        phi, taps = C.c_uint(), C.c_uint()
+        _check("drift_geometry", lib.cmhip_drift_geometry(self.h, C.byref(phi), C.byref(taps)))
+        return phi.value, taps.value
+
+    def max_out_frames(self):
+        return lib.cmhip_drift_max_out_frames(self.h)
+
+    def set_rc(self, stream, delta):
+        """cmhip_drift_set as it is -> error number"""
+        return lib.cmhip_drift_set(self.h, stream, delta)
+
+    def set(self, stream, delta):
+        _check("drift_set", self.set_rc(stream, delta))
+
+    def seek_rc(self, stream, frac):
+        """cmhip_drift_seek as it is -> error number"""
+        return lib.cmhip_drift_seek(self.h, stream, frac)
+
+    def seek(self, stream, frac):
+        _check("drift_seek", self.seek_rc(stream, frac))
+
+    def get(self, stream):
+        """-> (delta, pos, total input frames, total output frames) of the host's mirror"""
+        d, p, i, o = C.c_int32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check("drift_get", lib.cmhip_drift_get(self.h, stream, C.byref(d), C.byref(p), C.byref(i), C.byref(o)))
+        return d.value, p.value, i.value, o.value
+
+    def advance_rc(self, frames, frames_per_stream=None):
+        """Test hook (cmhip_test_drift_advance): the mirror's part of a run -> (error number, output counts)"""
+        got = np.zeros(self.streams, dtype=np.uint32)
+        rc = lib.cmhip_test_drift_advance(self.h, frames, self._counts(frames_per_stream), got.ctypes.data)
+        return rc, got
+
+    def run_rc(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """cmhip_drift_run as it is -> (error number, uint32 array of the streams' output counts)"""
+        got = np.zeros(self.streams, dtype=np.uint32)
+        rc = lib.cmhip_drift_run(self.h, src, in_stride, frames, self._counts(frames_per_stream), dst, out_stride,
+                                 got.ctypes.data)
+        return rc, got
+
+    def run(self, src, in_stride, frames, dst, out_stride, frames_per_stream=None):
+        """one run over device arrays (src, dst: device pointers) -> the streams' output counts"""
+        rc, got = self.run_rc(src, in_stride, frames, dst, out_stride, frames_per_stream)
+        _check("drift_run", rc)
         return got
 
 

@@ -21,6 +21,7 @@
 //   cmhip_agc.hip      the leveller: slow automatic gain control
 //   cmhip_automix.hip  the automixer: gain-sharing groups
 //   cmhip_failover.hip the failover switch: silence-triggered source changeover
+//   cmhip_drift.hip    the drift stage: a variable-ratio resampler against clock drift
 //   cmhip_iir.hip      the filter: a biquad cascade in exact integers
 #pragma once
 

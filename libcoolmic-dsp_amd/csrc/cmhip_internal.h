@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_failover.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_failover.hip, k_drift.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -14,6 +14,7 @@
 #include "agc_plan.h"
 #include "automix_plan.h"
 #include "failover_plan.h"
+#include "drift_plan.h"
 #include "iir_plan.h"
 #include "iir_ramp.h"
 #include "spec_plan.h"
@@ -489,6 +490,27 @@ struct FailoverArgs {
     uint32_t       outputs;
 };
 
+// Drift stage (k_drift.hip; the arithmetic: include/coolmic_hip.h, the table's form, the record and the plan:
+// csrc/drift_plan.h): a run over S stream slots.
+struct DriftArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *rec;           // [S][DRIFT_REC] the run's F, K, delta and pos per stream, from the host's mirror
+    const uint32_t *table;         // [P + 1][T/2 + 1] the table in the kernel's form (drift_compile)
+    int16_t       *hist;           // [2][S][C][T-1] the last T-1 input frames; the two slots of SrcArgs::hist
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       streams;
+    uint32_t       channels;
+    uint32_t       parity;
+    uint32_t       phi, T;
+    // (the launcher fills these in)
+    uint32_t       chunks;         // tiles per stream
+    uint32_t       tile_out;       // output frames per tile
+    uint32_t       row;            // samples between the planes of a tile in LDS
+    uint32_t       table_lds;      // the table is copied into LDS
+    uint32_t       table_words;    // its dwords
+};
+
 // Filter (k_iir.hip; the arithmetic: include/coolmic_hip.h, the tiles: csrc/iir_plan.h): a run of a biquad cascade over
 // S stream slots
 struct IirArgs {
@@ -683,6 +705,9 @@ hipError_t launch_automix(const AutomixArgs &a, uint64_t max_frames, uint32_t fr
 // Failover switch (k_failover.hip): k_failover_energy, k_failover_step and k_failover_apply, in that order.  ev (may be
 // nullptr): four events recorded in front of, between and behind the three launches (tools/bench_failover.py).
 hipError_t launch_failover(const FailoverArgs &a, uint64_t max_frames, uint32_t frames, hipStream_t st, hipEvent_t *ev = nullptr);
+// Drift stage (k_drift.hip): one workgroup of 256 threads per stream and tile of output frames; the plan is
+// csrc/drift_plan.h's.  out_frames: what the run gives its longest stream.
+hipError_t launch_drift(const DriftArgs &a, uint32_t out_frames, hipStream_t st);
 // Filter (k_iir.hip): one launch, a workgroup per iir_plan's spw streams.  frames: the run's largest count.  ramp: some
 // section ramps at the run's start, a.coef is the ramp table (csrc/iir_ramp.h) and the kernels are k_iirramp.hip's.
 hipError_t launch_iir(const IirArgs &a, uint32_t frames, bool ramp, hipStream_t st);

@@ -7,6 +7,7 @@
 // the host flips per run (HistoryPair, csrc/cmhip_stage.h; the positions follow its parity).  The host keeps a mirror of every r: it knows each
 // run's counts, so a run's output counts are known before the call returns, without a device wait.
 #include "cmhip_engine.h"
+#include "design_window.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -66,19 +67,6 @@ static int src_geometry(unsigned rate_in, unsigned rate_out, unsigned *L, unsign
     return COOLMIC_ERROR_NONE;
 }
 
-// I0 from its power series, summed until a term no longer changes the sum
-static double src_i0(double x)
-{
-    double sum = 1.0, t = 1.0;
-    for (unsigned k = 1;; k++) {
-        t = t * (x / 2.0) / (double)k;
-        const double next = sum + t * t;
-        if (next == sum)
-            return sum;
-        sum = next;
-    }
-}
-
 // (the body of cmhip_src_design: its vectors may throw)
 static int src_design(unsigned rate_in, unsigned rate_out, unsigned *L, unsigned *M, unsigned *T, int16_t *h, size_t cap)
 {
@@ -91,16 +79,11 @@ static int src_design(unsigned rate_in, unsigned rate_out, unsigned *L, unsigned
         if (cap < N)
             return fail(COOLMIC_ERROR_INVAL, "src_design: room for %zu entries, the table has %zu", cap, N);
         const double fc = 0.92 * 0.5 / (double)(l > m ? l : m);
-        const double i0b = src_i0(7.5);
+        const double i0b = design_i0(DESIGN_BETA);
         std::vector<double> proto(N);
         for (size_t i = 0; i < N; i++) {
             const double x = (double)i - ((double)N - 1.0) / 2.0;
-            const double u = x / ((double)N / 2.0);
-            const double arg = 1.0 - u * u;
-            const double w = src_i0(7.5 * sqrt(arg > 0.0 ? arg : 0.0)) / i0b;
-            const double ts = 2.0 * fc * x;
-            const double sinc = ts == 0.0 ? 1.0 : sin(M_PI * ts) / (M_PI * ts);
-            proto[i] = 2.0 * fc * sinc * w * (double)l;
+            proto[i] = design_tap(x, (double)N / 2.0, fc, i0b) * (double)l;      // (csrc/design_window.h)
         }
         std::vector<int16_t> tab(N);
         for (unsigned p = 0; p < l; p++) {

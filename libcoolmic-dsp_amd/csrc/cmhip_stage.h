@@ -1,5 +1,5 @@
-// cmhip_stage.h -- a stage object beside the batch, on the HIP side: what the eleven stages (resampler, mixer, bus, limiter,
-// dynamics, band split, delay, leveller, filter, automixer, failover switch) do alike, once.  Not part of the C ABI; cmhip_engine.h includes it
+// cmhip_stage.h -- a stage object beside the batch, on the HIP side: what the twelve stages (resampler, mixer, bus, limiter,
+// dynamics, band split, delay, leveller, filter, automixer, failover switch, drift stage) do alike, once.  Not part of the C ABI; cmhip_engine.h includes it
 // once fail and HIP_TRY exist.
 //   CountsRing        the pinned ring a run's counts travel through
 //   StageBase         the device, the stream (the caller's or its own), the counts, and every device array of the object
@@ -212,7 +212,8 @@ static inline M *stage_new(const char *who, Init &&init)
     return m;
 }
 
-// A history in two slots, int16 [2][S][per] (the resampler, the limiter, the dynamics stage, the band split): a run
+// A history in two slots, int16 [2][S][per] (the resampler, the limiter, the dynamics stage, the band split, the drift
+// stage, whose drift_history is src_history's twin): a run
 // reads slot `parity` and writes the other one, flip() after a successful launch makes that the slot the next run reads.
 // reset() zeroes the streams' part of the slot the next run reads and nothing else.  That is sufficient: k_src.hip's
 // src_history, k_split.hip's split_history, k_lim.h's lim_write_hist and k_dyn.h's dyn_write_hist each write every
