@@ -1867,6 +1867,128 @@ double   cmhip_iir_response_db(const cmhip_iir_section_t *sections, unsigned int
 void     cmhip_iir_ramp_section(const cmhip_iir_section_t *c0, const cmhip_iir_section_t *c1, uint32_t p,
                                 cmhip_iir_section_t *out);              /* c(p) */
 
+/* ---- noise suppressor: a spectral gate in exact integers, an object of its own beside the batch -- */
+/* A noise suppressor takes steady background noise -- room tone, fans, hiss -- out of each of S streams of C
+ * interleaved int16 channels (C in 1..16), per frequency bin and in exact integers: where a bin's power does not rise
+ * above the noise profile learned for it, the bin is turned down towards a floor.  It belongs in front of the leveller,
+ * which would otherwise lift the noise of quiet speakers.  It has cmhip_agc_t's shapes: slots, strides, alignment and
+ * refusals are cmhip_agc_run's.  Every channel of every stream is a row of its own, with its own profile and gains.
+ *
+ * Geometry, per object: fft_log2 = n in 8..12, N = 2^n frames per block, hop H = N / 2.  A row's frames are counted
+ *   since creation or the last cmhip_denoise_reset; block j covers its frames [j H, j H + N) and is computed in the run
+ *   in which its last frame arrives, as the spectrum meter's blocks are.  Frames before frame 0 are zero.
+ * Parameters, per stream, settable between runs (cmhip_denoise_set, stream -1: all streams); a block uses the
+ *   parameters of the last cmhip_denoise_set queued before the run that completes it:
+ *     floor                 0..32768    units of 2^-15: the smallest gain of a bin (32768: nothing is removed)
+ *     over (beta)           0..255      units of 2^-4: the profile is multiplied by it before the comparison
+ *     rise_shift, fall_shift  0..8      a bin's gain moves by 2^-shift of its distance to the target per block
+ *
+ * The subtractive form.  The stage computes the REMOVED part r and subtracts it from the delayed input:
+ *     y[m + D] = clamp16(x[m] - r[m]),  D = N - 1 (cmhip_denoise_delay),
+ *   and every sample the clamp changes increments the stream's `clips`.  With every gain at 32768 the removed spectrum
+ *   is zero, the inverse transform of zeros is zero, and the output is the input delayed by D, bit for bit, by
+ *   construction: the synthesis window need not sum to one exactly.  Output frames 0 .. D - 1 are 0 (x before frame 0).
+ *   Block 0 covers frames [0, N), so frames 0 .. H - 1 are covered by one block only: there the removal fades in with
+ *   the window's square.
+ *
+ * Arithmetic, per row and block j:
+ *   Window.  sw[i] = min(32767, rint(32768 sin(pi i / N))) for i <= N / 2, sw[N - i] = sw[i] (cmhip_denoise_window).
+ *     v[i] = x[j H + i] * sw[i], exact in int32.
+ *   Forward transform.  The spectrum meter's, to the bit (above, "spectrum"): the same twiddles, bit reversal, stages and
+ *     roundings, X = DFT(v) / N with every butterfly output (a 2^30 +- P + 2^30) >> 31.  |X| <= 2^30 per component.
+ *     p[k] = (uint64)(re^2 + im^2) >> 16, k = 0 .. N / 2.
+ *   Target gain.  Np[k]: the row's profile, uint64, at most 2^52.  t = (Np[k] * beta) >> 4 (below 2^60).
+ *     If p <= t: target = floor.  Otherwise sh = max(0, bitlength(p) - 34), ps = p >> sh, ts = t >> sh, and
+ *       target = max(floor, isqrt(((ps - ts) << 30) / ps))
+ *     an unsigned 64-bit division (ps < 2^34, ts <= ps: the numerator fits) and the exact integer root, at most 32768:
+ *     the Wiener-like gain sqrt((p - t) / p).  cmhip_denoise_gain(p, np, over, floor) is this rule as code.
+ *   Smoothing.  g[k] in 0..32768, 32768 at frame 0.  d = target - g; d > 0: g += max(1, d >> rise_shift); d < 0:
+ *     g -= max(1, (-d) >> fall_shift).  No dead band: g reaches every target; a shift of 0 is instant.
+ *   Learning (cmhip_denoise_learn, per stream).  A block completed while the stream learns, and while cnt < 65536, does
+ *     acc[k] = (cnt ? acc[k] : 0) + p[k], cnt += 1, Np[k] = acc[k] / cnt -- AFTER its own gains: a block's gains use
+ *     the profile in force before it.  Turning learning on from off sets cnt = 0 (so the sums start anew); later
+ *     learning blocks beyond cnt = 65536 are ignored.  p <= 2^45 (|X| <= 2^30 per component), so acc <= 65536 * 2^45 = 2^61 fits uint64.
+ *   Removed spectrum.  Z[k] = (X[k] * (32768 - g[k]) + 2^16) >> 17 on both components, arithmetic shift (int64 product):
+ *     two bits of headroom.  Im Z[0] = Im Z[N/2] = 0.  Z[N - k] = conj(Z[k]).
+ *   Inverse transform.  The same decimation in time over bit-reversed input, the twiddles conjugated (Wr, -Wi), no
+ *     halving: every butterfly output is sat32((a 2^30 +- P + 2^29) >> 30), the exact int64 sum (|a| <= 2^31,
+ *     |P| <= 2^61.5) shifted arithmetically and clamped to int32; every clamped component increments the stream's
+ *     `sat`.  The imaginary output is discarded; t[i] is the real one.  An implementation may arrange the work as it
+ *     likes but reproduces every stage's rounded and clamped values.
+ *   Synthesis and overlap-add.  c[i] = (t[i] * sw[i] + 2^14) >> 15, an int64 product, an int32 result.  Frame m sums the
+ *     c of the one or two blocks that cover it, in int64: r[m] = (sum + 2^12) >> 13.
+ *   Properties.  Cuts: the concatenated output, the counters, g, Np and the state do not depend on how a stream is cut
+ *     into runs, per-stream counts and counts of 0 included, with the calls at the same frames.  A row's output never
+ *     depends on another row.
+ * State per row: the last N - 1 inputs (they serve the next blocks and the delayed dry signal); the overlap-add of
+ *   the last completed block's span, N int32 -- its upper half are the not-yet-completed sums, its lower half holds the
+ *   finished r that the output, D frames behind, has not reached yet (at most H - 1 of them); g, Np, acc.  Per stream:
+ *   cnt, clips, sat.
+ * cmhip_denoise_new: NULL for C outside 1..16, S = 0, fft_log2 outside 8..12, max_frames = 0, max_frames * C >= 2^31,
+ *   S * C >= 2^31 or a failed allocation.  Every stream starts with floor 32768, over 16, both shifts 0, learning off
+ *   and a zero profile: a pure delay, until cmhip_denoise_set says otherwise.
+ * cmhip_denoise_run has cmhip_delay_run's contract (asynchronous on the object's stream, frames_per_stream free on
+ *   return, the same refusals).  Outputs past a stream's count are not written.
+ * cmhip_denoise_set, _learn and _reset are ordered with the runs as the calls are: they touch a host mirror that every
+ *   run hands to the device with its counts, need no host wait and touch no device memory.  COOLMIC_ERROR_INVAL for
+ *   parameters or a stream out of range; a refused call changes nothing.  cmhip_denoise_get answers from the mirror.
+ * cmhip_denoise_set_profile(m, stream, channel, np[N / 2 + 1]): the row's profile, copied from a staged copy in the
+ *   object's stream order (np is free on return); acc and cnt stay.  COOLMIC_ERROR_BUSY while the mirror says the stream
+ *   learns, COOLMIC_ERROR_INVAL for a value above 2^52 or indices out of range; a refused call changes nothing.
+ * cmhip_denoise_get_profile: synchronous.  np[N / 2 + 1] and gain[N / 2 + 1] of the row; either may be NULL.
+ * cmhip_denoise_reset (stream -1: all): the stream's next frame is frame 0 again: history and overlap are zero, g is
+ *   32768, learning ends.  The profile, the parameters, cnt and the counters stay.
+ * cmhip_denoise_state: synchronous.  Per stream, S entries each: clips, sat, learned_blocks = cnt; clear != 0 zeroes
+ *   clips and sat after reading them.  Any of the three pointers may be NULL.
+ * cmhip_denoise_check (host only): 0 for a valid fft_log2 and parameter set (params may be NULL), else INVAL.
+ * cmhip_denoise_design (host only): floor = rint(32768 * 10^(-reduction_db / 20)), over = min(255,
+ *   rint(16 * 10^(over_db / 10))), and for each of attack_ms (rise) and release_ms (fall) the nearest shift for the hop:
+ *   with h = ms * rate / 1000 / H hops, shift = 0 for h <= 1, else min(8, rint(log2(h))).  COOLMIC_ERROR_INVAL for a
+ *   non-finite input, a rate that is not positive, an fft_log2 that is no integer in 8..12, a negative reduction or time.
+ * cmhip_denoise_gain (host only): the target rule; 0 for np above 2^52, over above 255 or floor above 32768. */
+typedef struct cmhip_denoise cmhip_denoise_t;
+typedef struct cmhip_denoise_desc {
+    int          device;          /* HIP device ordinal */
+    unsigned int streams;         /* S >= 1 */
+    unsigned int channels;        /* 1..16 */
+    unsigned int fft_log2;        /* n in 8..12: blocks of 2^n frames, hop 2^(n-1) */
+    size_t       max_frames;      /* per run and stream */
+    void        *hip_stream;      /* hipStream_t to launch on, NULL: own stream */
+} cmhip_denoise_desc_t;
+typedef struct cmhip_denoise_params {
+    uint16_t floor;
+    uint8_t  over, rise_shift, fall_shift;
+} cmhip_denoise_params_t;
+typedef struct cmhip_denoise_law_desc {
+    double rate;                  /* frames per second */
+    double fft_log2;              /* the object's n */
+    double reduction_db;          /* >= 0: the most a bin is turned down */
+    double over_db;               /* over-subtraction: dB the profile is raised by before the comparison */
+    double attack_ms, release_ms; /* >= 0: how fast a bin's gain rises / falls */
+} cmhip_denoise_law_desc_t;
+cmhip_denoise_t *cmhip_denoise_new(const cmhip_denoise_desc_t *d);
+void     cmhip_denoise_free(cmhip_denoise_t *m);
+int      cmhip_denoise_set(cmhip_denoise_t *m, long stream, const cmhip_denoise_params_t *p);
+int      cmhip_denoise_get(const cmhip_denoise_t *m, unsigned int stream, cmhip_denoise_params_t *p);
+int      cmhip_denoise_learn(cmhip_denoise_t *m, long stream, int on);
+int      cmhip_denoise_set_profile(cmhip_denoise_t *m, unsigned int stream, unsigned int channel,
+                                   const uint64_t *np /* [N/2 + 1] */);
+int      cmhip_denoise_get_profile(cmhip_denoise_t *m, unsigned int stream, unsigned int channel,
+                                   uint64_t *np /* [N/2 + 1] */, uint32_t *gain /* [N/2 + 1] */);
+int      cmhip_denoise_run(cmhip_denoise_t *m, const void *in, size_t in_stride, size_t frames,
+                           const uint32_t *frames_per_stream, void *out, size_t out_stride);
+int      cmhip_denoise_reset(cmhip_denoise_t *m, long stream);
+int      cmhip_denoise_state(cmhip_denoise_t *m, uint64_t *clips /* [S] */, uint64_t *sat /* [S] */,
+                             uint32_t *learned_blocks /* [S] */, int clear);
+int      cmhip_denoise_sync(cmhip_denoise_t *m);
+void    *cmhip_denoise_hip_stream(cmhip_denoise_t *m);
+size_t   cmhip_denoise_delay(const cmhip_denoise_t *m);
+/* host only, no device needed */
+int      cmhip_denoise_check(unsigned int fft_log2, const cmhip_denoise_params_t *p);
+int      cmhip_denoise_window(unsigned int fft_log2, int16_t *win /* [N] */);
+int      cmhip_denoise_design(const cmhip_denoise_law_desc_t *law, cmhip_denoise_params_t *p);
+uint32_t cmhip_denoise_gain(uint64_t p, uint64_t np, unsigned int over, unsigned int floor);
+
 /* ---- node-global VU ---------------------------------- */
 /* Reduces this batch's current windows over its streams into one record of
  * CMHIP_NODE_WORDS int64 words written to device memory `dst` (asynchronous):

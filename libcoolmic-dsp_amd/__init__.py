@@ -228,6 +228,28 @@ class AgcLawDesc(C.Structure):
                                           "initial_gain_db", "rise_db_per_s", "fall_db_per_s")]
 
 
+class DenoiseDesc(C.Structure):
+    """cmhip_denoise_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [("device", C.c_int), ("streams", C.c_uint), ("channels", C.c_uint), ("fft_log2", C.c_uint),
+                ("max_frames", C.c_size_t), ("hip_stream", C.c_void_p)]
+
+
+DENOISE_PARAM_NAMES = ("floor", "over", "rise_shift", "fall_shift")
+
+
+class DenoiseParams(C.Structure):
+    """cmhip_denoise_params_t (include/coolmic_hip.h)"""
+    _fields_ = [("floor", C.c_uint16), ("over", C.c_uint8), ("rise_shift", C.c_uint8), ("fall_shift", C.c_uint8)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n in DENOISE_PARAM_NAMES}
+
+
+class DenoiseLawDesc(C.Structure):
+    """cmhip_denoise_law_desc_t (include/coolmic_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("rate", "fft_log2", "reduction_db", "over_db", "attack_ms", "release_ms")]
+
+
 class AutomixDesc(C.Structure):
     """cmhip_automix_desc_t (include/coolmic_hip.h)"""
     _fields_ = AgcDesc._fields_
@@ -530,6 +552,23 @@ SIGNATURES = {
     "cmhip_iir_check": (C.c_int, [_P(IirSection)]),
     "cmhip_iir_design": (C.c_int, [_P(IirDesignDesc), _P(IirSection)]),
     "cmhip_iir_response_db": (C.c_double, [_P(IirSection), C.c_uint, C.c_double, C.c_double]),
+    "cmhip_denoise_new": (_vp, [_P(DenoiseDesc)]),
+    "cmhip_denoise_free": (None, [_vp]),
+    "cmhip_denoise_set": (C.c_int, [_vp, C.c_long, _P(DenoiseParams)]),
+    "cmhip_denoise_get": (C.c_int, [_vp, C.c_uint, _P(DenoiseParams)]),
+    "cmhip_denoise_learn": (C.c_int, [_vp, C.c_long, C.c_int]),
+    "cmhip_denoise_set_profile": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp]),
+    "cmhip_denoise_get_profile": (C.c_int, [_vp, C.c_uint, C.c_uint, _vp, _vp]),
+    "cmhip_denoise_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t]),
+    "cmhip_denoise_reset": (C.c_int, [_vp, C.c_long]),
+    "cmhip_denoise_state": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "cmhip_denoise_sync": (C.c_int, [_vp]),
+    "cmhip_denoise_hip_stream": (_vp, [_vp]),
+    "cmhip_denoise_delay": (C.c_size_t, [_vp]),
+    "cmhip_denoise_check": (C.c_int, [C.c_uint, _P(DenoiseParams)]),
+    "cmhip_denoise_window": (C.c_int, [C.c_uint, _vp]),
+    "cmhip_denoise_design": (C.c_int, [_P(DenoiseLawDesc), _P(DenoiseParams)]),
+    "cmhip_denoise_gain": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint, C.c_uint]),
     "cmhip_mix_new": (_vp, [_P(MixDesc)]),
     "cmhip_mix_free": (None, [_vp]),
     "cmhip_mix_set_matrix": (C.c_int, [_vp, C.c_long, _vp]),
@@ -815,6 +854,9 @@ if hasattr(lib, "cmhip_test_plan_agc"):         # (not in builds older than the 
     lib.cmhip_test_agc_step.argtypes = [C.c_uint32, C.c_uint32, _P(AgcParams)]
     lib.cmhip_test_agc_run_events.restype = C.c_int
     lib.cmhip_test_agc_run_events.argtypes = [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, _P(C.c_void_p)]
+if hasattr(lib, "cmhip_test_denoise_new_dry"):  # (not in builds older than the noise suppressor)
+    lib.cmhip_test_denoise_new_dry.restype = _vp
+    lib.cmhip_test_denoise_new_dry.argtypes = [_P(DenoiseDesc)]
 if hasattr(lib, "cmhip_test_plan_iir"):         # (not in builds older than the filter)
     lib.cmhip_test_plan_iir.restype = None
     lib.cmhip_test_plan_iir.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
@@ -1481,6 +1523,44 @@ def test_iir_without_device(streams, channels, sections, max_frames):
     """Test hook (cmhip_test_iir_new_dry): a Filter with the host mirror and every check but no device behind it, for
     the refusals on a machine without a GPU"""
     return Filter(streams, channels, sections, max_frames, _new=lib.cmhip_test_iir_new_dry)
+
+
+def test_denoise_without_device(streams, channels, fft_log2, max_frames):
+    """Test hook (cmhip_test_denoise_new_dry): a Denoiser with the host mirror and every check but no device behind it,
+    for the refusals and the mirror's answers on a machine without a GPU"""
+    return Denoiser(streams, channels, fft_log2, max_frames, _new=lib.cmhip_test_denoise_new_dry)
+
+
+def denoise_params(**kw):
+    """a DenoiseParams: the creation defaults (a pure delay) with `kw` over them"""
+    f = dict(floor=32768, over=16, rise_shift=0, fall_shift=0)
+    f.update(kw)
+    return DenoiseParams(**f)
+
+
+def denoise_check(fft_log2, params=None):
+    """cmhip_denoise_check -> error number"""
+    return lib.cmhip_denoise_check(fft_log2, C.byref(params) if params is not None else None)
+
+
+def denoise_window(fft_log2):
+    """cmhip_denoise_window -> int16 [N]"""
+    w = np.zeros(1 << fft_log2, dtype=np.int16)
+    _check("denoise_window", lib.cmhip_denoise_window(fft_log2, w.ctypes.data))
+    return w
+
+
+def denoise_design(rate, fft_log2, reduction_db, over_db, attack_ms, release_ms):
+    """cmhip_denoise_design -> DenoiseParams"""
+    law = DenoiseLawDesc(rate, fft_log2, reduction_db, over_db, attack_ms, release_ms)
+    p = DenoiseParams()
+    _check("denoise_design", lib.cmhip_denoise_design(C.byref(law), C.byref(p)))
+    return p
+
+
+def denoise_gain(p, np_, over, floor):
+    """cmhip_denoise_gain: the target rule of a bin, the specification as code"""
+    return lib.cmhip_denoise_gain(p, np_, over, floor)
 
 
 def delay_ms(rate, ms):
@@ -2156,7 +2236,7 @@ class Batch:
 
 class _Stage:
     """What the stage objects beside a batch share (Resampler, Mixer, Bus, Dynamics, Limiter, BandSplit, Delay,
-    Leveller, Filter, Automixer, Failover, Drift): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
+    Leveller, Filter, Automixer, Failover, Drift, Denoiser): the end of the handle `h`, its stream, a run and its counts, and reset.  `_stem` names the
     object's C functions: cmhip_<stem>_free, _sync, _hip_stream, _run, _reset.  The Mixer and the Bus have no state to
     reset and the library no cmhip_mix_reset or cmhip_bus_reset: their reset() raises AttributeError, as the lookup of
     any symbol the library lacks does."""
@@ -2432,6 +2512,70 @@ class Leveller(_Stage):
         _check("agc_state", lib.cmhip_agc_state(self.h, g.ctypes.data, lv.ctypes.data, c.ctypes.data,
                                                 1 if clear_clips else 0))
         return g, lv, c
+
+
+class Denoiser(_Stage):
+    """cmhip_denoise_t: a noise suppressor of S streams beside a batch: a spectral gate over blocks of 2^fft_log2 frames
+    with a learned noise profile per (stream, channel).  `params` (a DenoiseParams): set for every stream at creation
+    (default: a pure delay of N - 1 frames)."""
+
+    _stem = "denoise"
+
+    def __init__(self, streams, channels, fft_log2, max_frames, params=None, device=0, hip_stream=None, _new=None):
+        d = DenoiseDesc(device, streams, channels, fft_log2, max_frames, hip_stream)
+        self.h = (_new or lib.cmhip_denoise_new)(C.byref(d))
+        if not self.h:
+            raise CoolmicError("cmhip_denoise_new", ERROR_INVAL)
+        self.streams, self.channels, self.fft_log2, self.max_frames = streams, channels, fft_log2, max_frames
+        self.bins = (1 << fft_log2) // 2 + 1
+        if params is not None:
+            self.set(-1, params)
+
+    def delay(self):
+        return lib.cmhip_denoise_delay(self.h)
+
+    def set_rc(self, stream, params):
+        """cmhip_denoise_set as it is -> error number"""
+        return lib.cmhip_denoise_set(self.h, stream, C.byref(params))
+
+    def set(self, stream, params):
+        """the stream's parameters from the next block completed on (stream -1: every stream)"""
+        _check("denoise_set", self.set_rc(stream, params))
+
+    def get(self, stream):
+        p = DenoiseParams()
+        _check("denoise_get", lib.cmhip_denoise_get(self.h, stream, C.byref(p)))
+        return p
+
+    def learn(self, stream, on):
+        """learning of the noise profile on or off (stream -1: every stream); ordered with the runs"""
+        _check("denoise_learn", lib.cmhip_denoise_learn(self.h, stream, 1 if on else 0))
+
+    def set_profile_rc(self, stream, channel, profile):
+        """cmhip_denoise_set_profile as it is -> error number"""
+        q = np.ascontiguousarray(profile, dtype=np.uint64)
+        assert q.shape == (self.bins,)
+        return lib.cmhip_denoise_set_profile(self.h, stream, channel, q.ctypes.data)
+
+    def set_profile(self, stream, channel, profile):
+        """the row's noise profile, uint64 [N/2 + 1]; ordered with the runs"""
+        _check("denoise_set_profile", self.set_profile_rc(stream, channel, profile))
+
+    def get_profile(self, stream, channel):
+        """-> (profile uint64 [N/2 + 1], gain uint32 [N/2 + 1]) of the row; a synchronous round trip"""
+        q = np.zeros(self.bins, dtype=np.uint64)
+        g = np.zeros(self.bins, dtype=np.uint32)
+        _check("denoise_get_profile", lib.cmhip_denoise_get_profile(self.h, stream, channel, q.ctypes.data, g.ctypes.data))
+        return q, g
+
+    def state(self, clear=False):
+        """-> (clips uint64 [S], sat uint64 [S], learned_blocks uint32 [S]); a synchronous round trip"""
+        c = np.zeros(self.streams, dtype=np.uint64)
+        t = np.zeros(self.streams, dtype=np.uint64)
+        b = np.zeros(self.streams, dtype=np.uint32)
+        _check("denoise_state", lib.cmhip_denoise_state(self.h, c.ctypes.data, t.ctypes.data, b.ctypes.data,
+                                                        1 if clear else 0))
+        return c, t, b
 
 
 class Automixer(_Stage):

@@ -23,6 +23,7 @@
 //   cmhip_failover.hip the failover switch: silence-triggered source changeover
 //   cmhip_drift.hip    the drift stage: a variable-ratio resampler against clock drift
 //   cmhip_iir.hip      the filter: a biquad cascade in exact integers
+//   cmhip_denoise.hip  the noise suppressor: a spectral gate in exact integers
 #pragma once
 
 #include "cmhip_internal.h"

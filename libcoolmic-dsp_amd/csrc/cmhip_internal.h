@@ -1,5 +1,5 @@
 // cmhip_internal.h -- device-side records and launcher prototypes shared by the gfx950 kernels (k_block.hip, k_eq.hip,
-// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_failover.hip, k_drift.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip) and the host code that
+// k_misc.hip, k_tpeak.hip, k_corr.hip, k_loud.hip, k_src.hip, k_mix.hip, k_mixramp.hip, k_bus.hip, k_busramp.hip, k_lim.hip, k_limtp.hip, k_limrel.hip, k_dyn.hip, k_split.hip, k_delay.hip, k_agc.hip, k_automix.hip, k_failover.hip, k_drift.hip, k_iir.hip, k_iirramp.hip, k_spec.hip, k_watch.hip, k_denoise.hip) and the host code that
 // launches them (cmhip_engine.h includes it).  Nothing host-only lives here.
 #pragma once
 
@@ -19,6 +19,7 @@
 #include "iir_ramp.h"
 #include "spec_plan.h"
 #include "watch_plan.h"
+#include "denoise_plan.h"
 
 namespace cmhip {
 
@@ -457,6 +458,28 @@ struct AutomixState {
     uint32_t pending;              // D of the last complete window: the node the next window edge brings in
     uint32_t pad;
 };
+// Noise suppressor (k_denoise.hip; the arithmetic: include/coolmic_hip.h, the block and the mirror:
+// csrc/denoise_plan.h).  A row is a (stream, channel); everything a row carries from run to run is written by the one
+// workgroup that owns the row.
+struct DenoiseArgs {
+    const int16_t *in;             // int16 [S][in_stride]
+    int16_t       *out;            // int16 [S][out_stride]
+    const uint32_t *rec;           // [S][DENOISE_REC] the run's records: count, back, flags, cnt, the parameters
+    const int32_t *table;          // Wr[N/2], Wi[N/2], sw[N]
+    int16_t       *hist;           // [2][S][C][N] the rows' last N - 1 inputs, oldest first (entry N - 1 unused); a run
+                                   // reads slot `parity` and writes the other one
+    int32_t       *tail;           // [S][C][N] the overlap-add of the last completed block's span (denoise_plan.h)
+    uint32_t      *gain;           // [S][C][N/2 + 1] g
+    unsigned long long *np;        // [S][C][N/2 + 1] the profile
+    unsigned long long *acc;       // [S][C][N/2 + 1] the learning sums
+    unsigned long long *clips;     // [S] clamped output samples
+    unsigned long long *sat;       // [S] clamped components of the inverse transform
+    uint64_t       in_stride, out_stride;    // samples between stream slots (multiples of 8)
+    uint32_t       streams, channels;
+    uint32_t       log2n;
+    uint32_t       parity;
+};
+
 // a run of an automixer over S stream slots
 struct AutomixArgs {
     AgcArgs        tile;           // what the leveller's tile bodies read (state: unused, nullptr); tile.rec: every stream's
@@ -593,6 +616,9 @@ struct SpecPlan {
 };
 SpecPlan plan_spec(const SpecArgs &a, uint32_t max_blocks);
 hipError_t launch_spec(const SpecArgs &a, uint32_t max_blocks, hipStream_t st);
+// Noise suppressor (k_denoise.hip): one workgroup of DENOISE_BLOCK threads per row, streams * channels of them (below
+// 2^31: the object's geometry says so).
+hipError_t launch_denoise(const DenoiseArgs &a, hipStream_t st);
 // Signal watch (k_watch.hip): the plan is csrc/watch_plan.h's, shared with the CPU tests.  launch_watch queues the
 // tile pass and the fold; a.scratch holds at least plan.scratch summaries.  ev: nullptr, or three events recorded
 // ahead of the tile pass, between the two kernels and behind the fold (the measurement of tools/bench_watch.py).

@@ -1,5 +1,5 @@
-// cmhip_stage.h -- a stage object beside the batch, on the HIP side: what the twelve stages (resampler, mixer, bus, limiter,
-// dynamics, band split, delay, leveller, filter, automixer, failover switch, drift stage) do alike, once.  Not part of the C ABI; cmhip_engine.h includes it
+// cmhip_stage.h -- a stage object beside the batch, on the HIP side: what the thirteen stages (resampler, mixer, bus, limiter,
+// dynamics, band split, delay, leveller, filter, automixer, failover switch, drift stage, noise suppressor) do alike, once.  Not part of the C ABI; cmhip_engine.h includes it
 // once fail and HIP_TRY exist.
 //   CountsRing        the pinned ring a run's counts travel through
 //   StageBase         the device, the stream (the caller's or its own), the counts, and every device array of the object
